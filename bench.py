@@ -74,9 +74,18 @@ def parse():
     ap.add_argument("--no-config3", action="store_true", help="N = 1: skip variants.config3_homogenization (44^3 periodic cell, 6 cell problems)")
     ap.add_argument("--ranks-per-gpu-ok", action="store_true",
                     help="N > visible GPUs: share the GPUs (ranks on one GPU talk through gloo, staged through the host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="N = 1, grid <= 60: after the timed steps, write the K the last step assembled as DIR/*.npy (float64, a fixed sample of "
+                         "whole block rows, at most 48 MiB) so that two builds can be compared output for output; all of K is copied to the host "
+                         "for it (about 22 GB at 60^3)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.grid <= 0:
         a.grid = 119 if (a.scaling == "strong" or (a.scaling is None and a.gpus > 1)) else 60
+    if a.dump_outputs and (a.gpus > 1 or a.leg or a.grid > 60):
+        ap.error("--dump-outputs belongs to the N = 1 line up to the 60^3 grid (no --leg, --gpus 1, no --scaling strong): "
+                 "it copies all of K to the host, over 100 GB at 119^3")
     return a
 
 
@@ -355,6 +364,26 @@ def forced_2_ranks_one_gpu(args, n=48, timeout_s=240):
     return res
 
 
+def dump_outputs(c, out_dir, seed=0, budget_bytes=48 << 20):
+    """--dump-outputs: what a caller of the timed step receives -- K in block-CSR, both triangles (mfh_export_bsr) -- on a sample of whole block
+    rows drawn with a fixed seed, as many as fit the budget: K_rows / K_cols (block coordinates) and K_values (the 3 x 3 blocks), all float64."""
+    rp, ci, vals = c.export_bsr()
+    order = np.random.default_rng(seed).permutation(len(rp) - 1)
+    per_block = vals[0].nbytes + 2 * 8
+    ends = np.cumsum((rp[order + 1] - rp[order]).astype(np.int64)) * per_block
+    rows = np.sort(order[:int(np.searchsorted(ends, budget_bytes, side="right"))])
+    lens = (rp[rows + 1] - rp[rows]).astype(np.int64)
+    idx = np.repeat(rp[rows].astype(np.int64) - np.cumsum(lens) + lens, lens) + np.arange(int(lens.sum()))
+    arrays = dict(K_rows=np.repeat(rows, lens).astype(np.float64), K_cols=ci[idx].astype(np.float64), K_values=vals[idx])
+    del rp, ci, vals
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return dict(dir=os.path.abspath(out_dir), files={k + ".npy": list(a.shape) for k, a in arrays.items()}, sampled_block_rows=len(rows),
+                seed=seed, note="K after the last timed step, whole block rows of a fixed random sample (both triangles, mfh_export_bsr); the default "
+                                "assembly adds in no fixed order, so two runs agree to rounding, not bit for bit (option deterministic does)")
+
+
 def one_shot_fresh_context(M, T, V, deg, rtol, maxit):
     """What a Simulate_cli caller pays end to end (VERDICT r5 item 4): a FRESH context, mesh_build -> boundary conditions -> Simulator::solve with
     the drivers' default preconditioner (symbolic phase, first assembly, multigrid hierarchy, PCG, download of u), wall clock around all of it,
@@ -428,6 +457,12 @@ def run_single(args):
     dt = time.perf_counter() - t0
     ms_step = dt / args.steps * 1e3
     value = nE * args.steps / dt
+    dumped = None
+    if args.dump_outputs:
+        try:
+            dumped = dump_outputs(c, args.dump_outputs)
+        except Exception as e:   # noqa: BLE001 -- never lose the line over the dump
+            dumped = dict(error="%s: %s" % (type(e).__name__, e))
     # dominant kernel alone, HIP events on the context's stream
     k_ms = c.time_assembly_kernel(M.ASSEMBLE_GATHER, max(3, args.steps))
     # Storage of K: automatic (option matrix_storage -1). Elasticity solves on the matrix-free operator, nothing multiplies by the stored K,
@@ -482,6 +517,8 @@ def run_single(args):
                           first_assembly_ms=(t_build + t_sym + t_first) * 1e3, first_assembly_elements_per_s=nE / (t_build + t_sym + t_first),
                           reservation="mfh_device_reserve(%.1f GB in two segments, asynchronous) at process start" % (reserve_main / 1e9) if reserve_main else "none",
                           **c.timing(), **c.symbolic_sizes()))
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     # comparison variant: element-major global-atomic scatter (north_star: "colored or atomic ... by evidence")
     try:
         a_ms = c.time_assembly_kernel(M.ASSEMBLE_ATOMIC, 3)
