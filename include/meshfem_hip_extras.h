@@ -42,6 +42,17 @@ mfh_status mfh_debug_arena_free(mfh_ctx* ctx, void* p);
 /* test hook (host only, no context): the row chunks of the assembly kernel -- greedy, whole rows, at most chunkSlots slots each, a chunk ends at
  * every row listed in breaks -- scanned by `threads` host threads over ranges of `grain` rows and stitched (threads = 1: the plain sequential
  * scan the result must equal). Writes the chunks' first rows + nRows to chunkRow (capacity cap); *nOut = entries (chunks + 1) */
+/* test hook: Y = K X for nr host vectors (rows of X and Y, dim * nDoF doubles each) through the operator of the batched PCG -- the batched
+ * kernels (k_mf_cluster_nr / k_mf_rows_nr / k_spmv_nr) for nr > 1, the single-vector ones for nr = 1; masked != 0 zeroes the fixed rows.
+ * Y's incoming contents are uploaded as y (a closed gate must leave them). flavour: 0 plain, dots[k] = the kernels' fused X[k] . Y[k];
+ * 1 classic-PCG bookkeeping with the gate open (nr = 1); 2 Chronopoulos-Gear bookkeeping with the gate open; 3 / 4 the same two gates
+ * closed. With 1 and 2, dots[k] is read from the scalar history where the PCG reads p . Ap (dots may be null). A batch size the kernels
+ * are not built for: MFH_ERR_UNSUPPORTED. Inside a PCG the direction is zero on the fixed rows; masked runs of flavours 1-4 assume it. */
+mfh_status mfh_debug_apply_operator(mfh_ctx* ctx, int32_t nr, int32_t masked, int32_t flavour, const double* X, double* Y, double* dots);
+/* test hook: Z = M^-1 R (rows, dim * nDoF doubles each) with the preconditioner the next mfh_solve uses (built if need be), ungated:
+ * nr = 1 the single-vector path (block-Jacobi / two-level / V-cycle), nr > 1 the batched one (two-level: k_tl_*_nr; multigrid on a
+ * quadratic mesh: the batched V-cycle). MFH_ERR_UNSUPPORTED where the preconditioner has no batched path or the batch size no kernels */
+mfh_status mfh_debug_apply_precond(mfh_ctx* ctx, int32_t nr, const double* R, double* Z);
 mfh_status mfh_debug_row_chunks(int64_t nRows, const int32_t* rowPtr, int32_t chunkSlots, int64_t nBreaks, const int64_t* breaks, int64_t grain,
                                 int32_t threads, int32_t* chunkRow, int64_t cap, int64_t* nOut);
 

@@ -277,6 +277,23 @@ class Context:
         self._ck(self.lib.mfh_debug_device_node_tables(self.h, ptr(en), ptr(pos)))
         return en, pos
 
+    def debug_apply_operator(self, X, masked=False, flavour=0, Y=None):
+        """(Y, dots) = the batched PCG's operator on the rows of X (test hook mfh_debug_apply_operator). Y: the incoming contents of
+        the output (default NaN: every row must be written), returned unchanged by a closed gate (flavours 3, 4)."""
+        X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float64)
+        nr = X.shape[0]
+        Y = np.full(X.shape, np.nan) if Y is None else np.array(np.broadcast_to(Y, X.shape), dtype=np.float64, order="C")
+        dots = np.zeros(nr)
+        self._ck(self.lib.mfh_debug_apply_operator(self.h, nr, int(bool(masked)), int(flavour), ptr(X), ptr(Y), ptr(dots)))
+        return Y, dots
+
+    def debug_apply_precond(self, R):
+        """Z = M^-1 R on the rows of R with the preconditioner of the next solve (test hook mfh_debug_apply_precond)."""
+        R = np.ascontiguousarray(np.atleast_2d(R), dtype=np.float64)
+        Z = np.empty_like(R)
+        self._ck(self.lib.mfh_debug_apply_precond(self.h, R.shape[0], ptr(R), ptr(Z)))
+        return Z
+
     def export_upper_triplets(self):
         n = C.c_uint64(0)
         self._ck(self.lib.mfh_export_upper_triplets(self.h, None, None, None, C.byref(n)))

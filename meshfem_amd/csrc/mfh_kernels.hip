@@ -2574,6 +2574,8 @@ void launch_mf_cluster_nr(const SpmvMfArgs &a, int NR, const double *x, double *
                           const int32_t *blockList, int64_t nList, hipStream_t s) {
     if (nList <= 0) return;
     if (NR == 1) { launch_mf_cluster_mode(a, a.pcgMode ? a.pcgMode : (ctl ? 2 : 0), x, y, dotOut, scal, it, ctl, blockList, nList, s); return; }
+    // only the instantiated batch sizes: any other NR would run a kernel built for a different vector stride
+    if (!op_batch_supported(a.dim, NR)) throw Error(MFH_ERR_UNSUPPORTED, "cluster operator: unsupported batch size " + std::to_string(NR));
     const int nrs = cluster_nrs(a.dim, NR);
     const size_t ldsC = ((size_t)2 * a.clMaxLocal * a.dim * nrs + 8) * sizeof(double);
     const int gridC = (int)std::min<int64_t>(nList, 256 * 64);
@@ -2585,7 +2587,7 @@ void launch_mf_cluster_nr(const SpmvMfArgs &a, int NR, const double *x, double *
 #define CALL(D, G, M)                                          \
     if (D == 3) {                                              \
         if (NR == 2) CALLN(3, G, M, 2, 2);                     \
-        else CALLN(3, G, M, 6, 2);                             \
+        else if (NR == 6) CALLN(3, G, M, 6, 2);                \
     } else {                                                   \
         CALLN(2, G, M, 3, 3);                                  \
     }
@@ -2598,12 +2600,13 @@ void launch_mf_cluster_nr(const SpmvMfArgs &a, int NR, const double *x, double *
 void launch_mf_rows_nr(const SpmvMfArgs &a, int NR, const double *x, double *y, double *dotOut, double *scal, int it, const double *ctl, hipStream_t s) {
     if (a.nChunk == 0) return;
     if (NR == 1) { launch_mf_rows_mode(a, a.pcgMode ? a.pcgMode : (ctl ? 2 : 0), x, y, dotOut, scal, it, ctl, s); return; }
+    if (!op_batch_supported(a.dim, NR)) throw Error(MFH_ERR_UNSUPPORTED, "cluster operator (interface rows): unsupported batch size " + std::to_string(NR));
     const int nrs = cluster_nrs(a.dim, NR);
     const size_t lds = ((size_t)a.maxRows * a.dim * nrs + 8) * sizeof(double);
     const int grid = persistent_grid(a.nChunk, 256 * 8);
 #define ROWS(D, N, NS) hipLaunchKernelGGL((k_mf_rows_nr<D, N, NS>), dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, ctl)
     if (a.dim == 3) {
-        if (NR == 2) ROWS(3, 2, 2); else ROWS(3, 6, 2);
+        if (NR == 2) ROWS(3, 2, 2); else if (NR == 6) ROWS(3, 6, 2);
     } else {
         ROWS(2, 3, 3);
     }
@@ -2615,6 +2618,7 @@ void launch_spmv_nr(const SpmvArgs &a, int NR, const double *x, double *y, doubl
                     const int32_t *chunkList, int64_t nList, hipStream_t s) {
     if (nList <= 0) return;
     if (NR == 1) { launch_spmv_mode(a, a.pcgMode ? a.pcgMode : (ctl ? 2 : 0), x, y, dotOut, scal, it, ctl, chunkList, nList, s); return; }
+    if (!op_batch_supported(a.dim, NR)) throw Error(MFH_ERR_UNSUPPORTED, "assembled SpMV: unsupported batch size " + std::to_string(NR));
     // the smoother of a multigrid level (FP32 copy of the matrix) takes all six vectors in ONE pass over the matrix: it is bound by the matrix bytes
     const bool onePass = a.dim == 3 && NR == 6 && a.vals32 && ((size_t)a.dim * 6 * a.chunkSlots + 8) * sizeof(double) <= 80 * 1024;
     const int nrs = onePass ? 6 : (a.dim == 1 ? (NR == 6 ? 3 : NR) : cluster_nrs(a.dim, NR));
@@ -2626,11 +2630,11 @@ void launch_spmv_nr(const SpmvArgs &a, int NR, const double *x, double *y, doubl
         hipLaunchKernelGGL((k_spmv_nr<D, N, NS>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, ctl, chunkList, nList);     \
     } while (0)
     if (a.dim == 3) {
-        if (NR == 2) SPMV(3, 2, 2); else if (onePass) SPMV(3, 6, 6); else SPMV(3, 6, 2);
+        if (NR == 2) SPMV(3, 2, 2); else if (onePass) SPMV(3, 6, 6); else if (NR == 6) SPMV(3, 6, 2);
     } else if (a.dim == 2) {
         SPMV(2, 3, 3);
     } else {
-        if (NR == 2) SPMV(1, 2, 2); else if (NR == 3) SPMV(1, 3, 3); else SPMV(1, 6, 3);
+        if (NR == 2) SPMV(1, 2, 2); else if (NR == 3) SPMV(1, 3, 3); else if (NR == 6) SPMV(1, 6, 3);
     }
 #undef SPMV
     CHECK_LAUNCH();

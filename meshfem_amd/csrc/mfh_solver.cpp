@@ -168,6 +168,7 @@ k::TLArgs tl_args(mfh_ctx *c);
 void ensure_fixed_uploaded(mfh_ctx *c);
 void solve_one_classic(mfh_ctx *c, const double *f, double *u, double rtol, int maxit, mfh_solve_info *info);
 void apply_operator(mfh_ctx *c, bool masked, const double *x, double *y, double *dotOut);
+void tl_precond(mfh_ctx *c, const double *r, double *z, double *scal, int it);
 
 namespace {
 
@@ -1391,6 +1392,100 @@ mfh_status mfh_dev_memcpy(mfh_ctx *c, void *dst, const void *src, int64_t bytes,
     const hipMemcpyKind kd = kind == 0 ? hipMemcpyHostToDevice : (kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
     MFH_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, kd, s));
     MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// ---------------------------------------------------------------- test hooks (meshfem_hip_extras.h)
+mfh_status mfh_debug_apply_operator(mfh_ctx *c, int32_t nr, int32_t masked, int32_t flavour, const double *X, double *Y, double *dots) {
+    MFH_TRY(c)
+    require(c && (c->haveMesh || c->external) && X && Y && nr > 0 && nr <= 8 && flavour >= 0 && flavour <= 4, MFH_ERR_INVALID,
+            "mfh_debug_apply_operator: arguments");
+    require(nr == 1 || (flavour != 1 && flavour != 3), MFH_ERR_INVALID, "mfh_debug_apply_operator: the classic-PCG gate belongs to one right-hand side");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    require(!dist_active(c), MFH_ERR_UNSUPPORTED, "mfh_debug_apply_operator: unpartitioned contexts only");
+    ensure_precond(c);          // what a solve prepares: the matrix, the fixed-variable mask on the device
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_STATE, "mfh_debug_apply_operator: all rows must be owned");
+    if (!cg_operator_supported(c)) throw Error(MFH_ERR_UNSUPPORTED, "mfh_debug_apply_operator: this matrix-free variant has no batched kernel");
+    const int d = c->bs();
+    const int64_t nRows = c->sym.nRows, n = nRows * d, nAll = n * nr;
+    hipStream_t s = c->stream;
+    DBuf<double> sep, xv, yv, sc, ctl;
+    sep.alloc((size_t)nAll); xv.alloc((size_t)nAll); yv.alloc((size_t)nAll);
+    // host rows (separate vectors) <-> the interleaved layout of the batched kernels; y starts from the caller's Y (a closed gate leaves it)
+    auto in = [&](const double *h, DBuf<double> &dst) {
+        MFH_HIP(hipMemcpyAsync(sep.p, h, (size_t)nAll * sizeof(double), hipMemcpyHostToDevice, s));
+        k::launch_interleave(nRows, nr, d, sep.p, dst.p, true, n, s);
+    };
+    in(X, xv);
+    in(Y, yv);
+    if (cluster_operator(c) && c->mfcDev.ifaceBuf.n < (size_t)std::max<int64_t>(c->mfc.nIface, 1) * d * nr)
+        c->mfcDev.ifaceBuf.alloc((size_t)std::max<int64_t>(c->mfc.nIface, 1) * d * nr);
+    // the scalar history of the PCG: iteration 0 with rr = 1 (gate open) or 0 (closed: rr <= threshold 0); control block all zero
+    // (classic layout: threshold ctl[0], base ctl[3]; Chronopoulos-Gear layout: base ctl[0], thresholds ctl[2 + k])
+    const size_t nScal = (size_t)4 * nr * 2;
+    std::vector<double> hs(nScal, 0.0), hc(16, 0.0);
+    const bool gate = flavour != 0, open = flavour == 1 || flavour == 2;
+    if (gate)
+        for (int q = 0; q < nr; ++q) hs[(size_t)q * 4 + 2] = open ? 1.0 : 0.0;
+    sc.upload(hs, s);
+    ctl.upload(hc, s);
+    DistLink L(c);
+    if (flavour == 0) apply_op_nr(c, L, nr, xv.p, yv.p, masked != 0, sc.p, nullptr, 0, nullptr);
+    else if (flavour == 1 || flavour == 3) apply_op_nr(c, L, 1, xv.p, yv.p, masked != 0, nullptr, sc.p, 0, ctl.p, 1);
+    else apply_op_nr(c, L, nr, xv.p, yv.p, masked != 0, nullptr, sc.p, 0, ctl.p);
+    k::launch_interleave(nRows, nr, d, yv.p, sep.p, false, n, s);
+    MFH_HIP(hipMemcpyAsync(Y, sep.p, (size_t)nAll * sizeof(double), hipMemcpyDeviceToHost, s));
+    sc.download(hs.data(), nScal, s);
+    if (dots)
+        for (int q = 0; q < nr; ++q)   // where the PCG reads p.Ap: dotOut[4 k] (plain), scal[1] (classic), scal[(NR + k) 4 + 1] (Chronopoulos-Gear)
+            dots[q] = flavour == 0 ? hs[(size_t)q * 4] : (flavour == 1 || flavour == 3) ? hs[1] : hs[((size_t)nr + q) * 4 + 1];
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_apply_precond(mfh_ctx *c, int32_t nr, const double *R, double *Z) {
+    MFH_TRY(c)
+    require(c && (c->haveMesh || c->external) && R && Z && nr > 0 && nr <= 8, MFH_ERR_INVALID, "mfh_debug_apply_precond: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    require(!dist_active(c), MFH_ERR_UNSUPPORTED, "mfh_debug_apply_precond: unpartitioned contexts only");
+    ensure_precond(c);
+    ensure_coarse_levels(c, nr);          // as mfh_solve does: the preconditioner its next solve uses
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_STATE, "mfh_debug_apply_precond: all rows must be owned");
+    // the choice of solve_one_classic / solve_cg
+    const bool useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
+    const bool useTL = !useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
+    const int d = c->bs();
+    const int64_t nRows = c->sym.nRows, n = nRows * d;
+    hipStream_t s = c->stream;
+    DBuf<double> r, z, sep;
+    if (nr == 1) {
+        r.upload(R, (size_t)n, s);
+        z.alloc((size_t)n);
+        if (useMG) mg_precond(c, r.p, z.p, nullptr, -1, nullptr);
+        else if (useTL) tl_precond(c, r.p, z.p, nullptr, -1);
+        else k::launch_precond(d, nRows, c->dDinv.p, r.p, z.p, s);
+        z.download(Z, (size_t)n, s);
+    } else if (useMG) {
+        // separate vectors vs apart, as solve_multigrid_batch lays them out
+        const int64_t vs = (n + 31) / 32 * 32;
+        r.alloc((size_t)vs * nr); z.alloc((size_t)vs * nr);
+        r.zero(s);
+        for (int q = 0; q < nr; ++q) MFH_HIP(hipMemcpyAsync(r.p + (size_t)q * vs, R + (size_t)q * n, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+        mg_precond_batch(c, nr, r.p, z.p, vs, nullptr, 0, -1, nullptr);
+        for (int q = 0; q < nr; ++q) MFH_HIP(hipMemcpyAsync(Z + (size_t)q * n, z.p + (size_t)q * vs, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+        MFH_HIP(hipStreamSynchronize(s));
+    } else if (useTL) {
+        if (!k::op_batch_supported(d, nr)) throw Error(MFH_ERR_UNSUPPORTED, "two-level preconditioner: unsupported batch size");
+        sep.upload(R, (size_t)n * nr, s);
+        r.alloc((size_t)n * nr); z.alloc((size_t)n * nr);
+        k::launch_interleave(nRows, nr, d, sep.p, r.p, true, n, s);
+        DistLink L(c);
+        tl_precond_nr(c, L, nr, r.p, z.p, nullptr, -1, nullptr);
+        k::launch_interleave(nRows, nr, d, z.p, sep.p, false, n, s);
+        sep.download(Z, (size_t)n * nr, s);
+    } else
+        throw Error(MFH_ERR_UNSUPPORTED, "mfh_debug_apply_precond: block-Jacobi has no batched application (the batched PCG folds it into its vector updates)");
     MFH_CATCH(c)
 }
 
