@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X-native MeshFEM hot path.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: the script launches its own N ranks)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: the script launches its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
 
-Metric (BASELINE.json): stiffness-assembly elements/s (+ PCG DOF/s), quadratic tets.
+Metric (BASELINE.json): stiffness-assembly elements/s, quadratic tets.
   * workload at N=1: BASELINE.json configs[2] -- synthetic 60^3 grid -> 5,184,000 P2 tets
     (22,292,283 DOF), isotropic E=200 nu=0.35, u=0 on x=0, traction (0,-1,0) on x=1.
   * a STEP = one numeric pass of the hot path over the whole mesh: element embedding (a1) +
@@ -14,13 +14,16 @@ Metric (BASELINE.json): stiffness-assembly elements/s (+ PCG DOF/s), quadratic t
   * `value` = elements * K / (wall time of the K timed steps), max over ranks.
   * N>1: weak scaling towards BASELINE configs[4] -- the global grid is n x n x (L N) with n ~ 60 N^(1/3) and
     L ~ 60^3 / n^2 hex layers per rank (N = 8: the 120^3 cube, 41.5 M P2 tets, 15-layer z-slabs), so every rank
-    keeps ~5.2 M elements (row/element partition, owner computes, no assembly communication); the PCG leg
+    keeps ~5.2 M elements (row/element partition, owner computes, no assembly communication); with --full the PCG leg
     runs the distributed solver (halo exchange + all-reduces over RCCL, global two-level preconditioner).
-Every N = 1 line also carries BASELINE configs[1] (`variants.config1_p1`), configs[3] (`variants.config3_homogenization`: six cell problems end to end, Ch
-checked in-line) and configs[4]'s cube in one context (`strong_scaling_n1`: run FIRST, in a process of its own -- `python bench.py --leg strong_n1` --, and
-again inside this process at the end as `warm_process`); `--leg config{1,2,3}|strong_n1` runs one workload alone (one rocprofv3 trace per workload).
-Extra objects on the JSON line: `roofline` (assembly kernel: the contract fraction on SURVEY's algorithmic bytes AND the
-fraction on the bytes the counters / the design actually move), `pcg` (solve to 1e-8 incl. its own roofline for the
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline, the workload and its setup
+phases. Its set-up starts with a short process that reserves and returns what the --full line's 119^3 leg takes, so that the K values are
+placed as they are in the --full line (return_what_the_leg_takes). Everything else is measured with --full only.
+With --full every N = 1 line also carries BASELINE configs[1] (`variants.config1_p1`), configs[3] (`variants.config3_homogenization`: six cell problems
+end to end, Ch checked in-line) and configs[4]'s cube in one context (`strong_scaling_n1`: run FIRST, in a process of its own -- `python bench.py --leg
+strong_n1` --, and again inside this process at the end as `warm_process`); `--leg config{1,2,3}|strong_n1` runs one workload alone (one rocprofv3 trace
+per workload). Extra objects on the --full line: `roofline` (assembly kernel: the contract fraction on SURVEY's algorithmic bytes AND the
+fraction on the bytes the counters / the design actually move), `hbm_measured`, `pcg` (solve to 1e-8 incl. its own roofline for the
 operator kernels), `cpu_baseline` (plain-C port of the reference loop structure timed on the host cores, bounded sample,
 plus a DIRECT SOLVE of a bounded sample next to the PCG at the same size), `variants` (atomic-scatter assembly).
 """
@@ -49,12 +52,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and kernel-alone times, the measured HBM rates, the PCG legs, the assembly "
+                         "variants, configs[1], configs[3], the one-shot sums, the 119^3 cube in one context, the forced two-rank line and the CPU "
+                         "baseline at N = 1; the solver leg and `weak_scaling` at N > 1. Without it the line carries the timed steps alone "
+                         "(the --no-* switches below only thin out a --full line)")
     ap.add_argument("--grid", type=int, default=0, help="hexes per side (0 = 60: configs[2] / the per-rank volume of the weak-scaling run; "
                                                         "119 with --scaling strong: configs[4])")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=os.environ.get("MFH_BENCH_SCALING") or None,
-                    help="default: N = 1 runs configs[2] (60^3) and adds the 119^3 cube in one context as `strong_scaling_n1`; N > 1 runs the "
+                    help="default: N = 1 runs configs[2] (60^3) (--full adds the 119^3 cube in one context as `strong_scaling_n1`); N > 1 runs the "
                          "STRONG-scaling line -- ONE grid^3 cube (119^3 = configs[4], 40.4 M P2 tets) dealt out over the N ranks (north_star: "
-                         ">= 6x at 8 GPUs) -- and adds the weak-scaling run (~60^3 hexes per rank; N = 8: the 120^3 cube) as `weak_scaling`. "
+                         ">= 6x at 8 GPUs) -- (--full adds the weak-scaling run (~60^3 hexes per rank; N = 8: the 120^3 cube) as `weak_scaling`). "
                          "--scaling weak: the weak line alone; --scaling strong with N = 1: the 119^3 cube as the line itself")
     ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the secondary weak-scaling object")
     ap.add_argument("--no-strong-n1", action="store_true", help="N = 1: skip the strong_scaling_n1 object (the 119^3 cube in one context)")
@@ -68,8 +76,8 @@ def parse():
     ap.add_argument("--no-orderings", action="store_true", help="skip the shuffled / Morton-ordered mesh variants")
     ap.add_argument("--cpu-grid", type=int, default=0, help="grid size of the CPU-baseline sample (0 = auto)")
     ap.add_argument("--cpu-solve-grid", type=int, default=0, help="grid size of the CPU direct-solve sample (0 = auto)")
-    ap.add_argument("--leg", default="", help="internal: run ONE leg of the N = 1 line in this (fresh) process and print its JSON object "
-                                              "(strong_n1: the 119^3 cube in one context, what a one-shot caller of that size sees)")
+    ap.add_argument("--leg", default="", help="internal: run ONE leg of the N = 1 --full line in this (fresh) process and print its JSON object "
+                                              "(strong_n1: the 119^3 cube in one context, what a one-shot caller of that size sees); --full does not apply")
     ap.add_argument("--no-forced-ranks", action="store_true", help="N = 1: skip variants.forced_2_ranks_one_gpu (48^3 cube over two processes on the one device)")
     ap.add_argument("--no-config3", action="store_true", help="N = 1: skip variants.config3_homogenization (44^3 periodic cell, 6 cell problems)")
     ap.add_argument("--ranks-per-gpu-ok", action="store_true",
@@ -321,8 +329,8 @@ def forced_2_ranks_one_gpu(args, n=48, timeout_s=240):
     import meshfem_amd as M
     from meshfem_amd import grid
     t0 = time.time()
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "2", "--ranks-per-gpu-ok", "--scaling", "strong", "--grid", str(n), "--no-cpu", "--no-weak",
-           "--steps", "5", "--warmup", "1", "--rtol", str(args.rtol)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "2", "--ranks-per-gpu-ok", "--scaling", "strong", "--grid", str(n), "--full", "--no-cpu",
+           "--no-weak", "--steps", "5", "--warmup", "1", "--rtol", str(args.rtol)]
     env = dict(os.environ)
     env.pop("MFH_BENCH_CHILD", None)
     env["MFH_DEVICE_SHARERS"] = "2"
@@ -420,9 +428,12 @@ def run_single(args):
     strong = args.scaling == "strong"
     # configs[4]'s cube in ONE context as a one-shot caller sees it: a process of its own, run BEFORE this one touches the device
     # (inside a process that had run the other legs the same code took 4.8 s instead of 0.6 s for the first assembly)
-    strong_first = None
+    strong_first, before = None, None
     if not strong and not args.no_strong_n1 and deg == 2:
-        strong_first = run_leg_subprocess(args, "strong_n1")
+        if args.full:
+            strong_first = run_leg_subprocess(args, "strong_n1")
+        else:
+            before = return_what_the_leg_takes(deg)
     # "reserve once", as in the strong_n1 leg: the memory of this leg (3.6 kB per quadratic tet) is asked for before anything else happens in
     # the process, on a thread of the library: what the driver has to clear first -- the process before this one returned 146 GB -- is cleared
     # while torch starts, the bandwidth probe runs and the mesh is generated (2.85 s inside the symbolic phase's hipMalloc otherwise,
@@ -431,7 +442,7 @@ def run_single(args):
     if not os.environ.get("MFH_BENCH_NO_RESERVE"):
         reserve_main = reserve_for(M, n, deg)
     torch.cuda.set_device(0)
-    hbm_measured = hbm_stream_probe(torch)
+    hbm_measured = hbm_stream_probe(torch) if args.full else None
     if strong:      # one 40 M-element context: no room (and no point) for the storage / ordering variants next to it
         args.no_orderings = True
     t0 = time.time()
@@ -463,44 +474,11 @@ def run_single(args):
             dumped = dump_outputs(c, args.dump_outputs)
         except Exception as e:   # noqa: BLE001 -- never lose the line over the dump
             dumped = dict(error="%s: %s" % (type(e).__name__, e))
-    # dominant kernel alone, HIP events on the context's stream
-    k_ms = c.time_assembly_kernel(M.ASSEMBLE_GATHER, max(3, args.steps))
     # Storage of K: automatic (option matrix_storage -1). Elasticity solves on the matrix-free operator, nothing multiplies by the stored K,
     # and the context stores / assembles the triangle the reference's TripletMatrix holds (SURVEY 8d's "upper-only variant, matches
     # reference storage", 4 316 B per P2 tet, 872 B per P1 tet); both triangles (7 736 / 1 328 B) with option matrix_free 0.
     upper, stored_blocks = c.matrix_storage()
-    bytes_per_element = ALG_BYTES_UPPER[(3, deg)] if upper else ALG_BYTES[(3, deg)]
-    alg = bytes_per_element * nE
-    tb, tsrc = pmc_traffic(PMC_KERNEL_KEY, n, deg, PMC_PROFILE_UPPER if upper else PMC_PROFILE)
     nr, nc, nnzb = c.matrix_info()
-    comp = compulsory_assembly_bytes(c, nE, stored_blocks)
-    roof = dict(bound="hbm", kernel="k_assemble_gather", achieved=alg / k_ms / 1e6, peak=HBM_PEAK_GBS, unit="GB/s",
-                frac=alg / k_ms / 1e6 / HBM_PEAK_GBS, traffic=None if tb is None else tb / k_ms / 1e6,
-                # the contract fraction above counts SURVEY 8(d)'s 100 Ke blocks per element, which an owner-computes kernel
-                # never moves; the two fractions below are on bytes that DO cross the HBM interface
-                frac_traffic=None if tb is None else tb / k_ms / 1e6 / HBM_PEAK_GBS,
-                compulsory_bytes=comp, frac_compulsory=comp / k_ms / 1e6 / HBM_PEAK_GBS,
-                traffic_bytes_per_launch_from_profile=tb, traffic_from_profile=tsrc, alg_bytes_per_launch=alg, kernel_ms=k_ms,
-                kernel_trace="profiles/r06_config2_kernel_stats.csv: rocprofv3 --kernel-trace --stats of `python bench.py --leg config2` (this workload alone: "
-                             "k_assemble_gather<3, 2, 0, true, false>, no deterministic and no 119^3 launches in the file)",
-                bytes_per_element=bytes_per_element,
-                matrix_storage="upper triangle (blocks (r, c >= r): what the reference assembles)" if upper else "both triangles",
-                note="frac = SURVEY 8(d) algorithmic bytes (the row of the storage in use) / time / 8 TB/s (contract); frac_traffic = "
-                     "rocprofv3 PMC bytes of the committed profile / time; frac_compulsory = bytes the design must move (stored K "
-                     "once + records + lists) / time")
-    # the committed trace's average of the same kernel (another box, another draw of where the driver put the K values): both on the line
-    if (n, deg) == (60, 2) and upper:
-        pavg, pcalls = profile_kernel_avg_ms(PROFILE_ROUND + "_config2_kernel_stats.csv", "k_assemble_gather<3, 2, 0, true, false>")
-        if pavg:
-            roof.update(kernel_ms_profile_avg=pavg, profile_launches=pcalls, frac_profile_avg=alg / pavg / 1e6 / HBM_PEAK_GBS,
-                        kernel_ms_spread="2.88-3.30 ms by process and box -- where the driver puts the K values (profiles/r06_config2_profile_spread.txt: five profiled "
-                                         "processes per box; the profile average and the process's own HIP events agree to 0.9 % inside every process)",
-                        frac_traffic_profile_avg=None if tb is None else tb / pavg / 1e6 / HBM_PEAK_GBS,
-                        frac_compulsory_profile_avg=comp / pavg / 1e6 / HBM_PEAK_GBS)
-    # context: the kernel's MEASURED traffic rate against the triad rate measured on this box a minute ago
-    if roof["traffic"] is not None:
-        roof["measured_triad_GBs"] = hbm_measured["triad_GBs"]
-        roof["traffic_frac_of_measured_triad"] = roof["traffic"] / hbm_measured["triad_GBs"]
     out = dict(metric="stiffness_assembly_elements_per_s", value=value, unit="elements/s", n_gpus=1, steps=args.steps,
                warmup=args.warmup, ms_per_step=ms_step, higher_is_better=True, scaling=args.scaling or "strong", vs_baseline=None,
                dtype="f64", data="synthetic",
@@ -509,16 +487,57 @@ def run_single(args):
                                        if strong else ("configs[2]" if (n, deg) == (60, 2) else "configs[2] generator at another size"), n, nE, deg),
                            elements=nE, nodes=c.n_node, dof=3 * c.n_dof, nnz_blocks=nnzb,
                            stored_blocks=stored_blocks, matrix_storage="upper" if upper else "full",
-                           parallelism="1 GPU", step="embed + Ke blocks + assembly into block-CSR (gather/owner-computes)"),
-               roofline=roof, hbm_measured=hbm_measured,
-               setup=dict(mesh_gen_s=t_gen, femmesh_build_s=t_build, symbolic_s=t_sym, first_assemble_call_s=t_first,
-                          # the timed step excludes what a one-shot caller pays once per mesh -- FEMMesh build (edge numbering,
-                          # boundary extraction, node table; includes the upload), symbolic phase (pattern + gather lists), first pass
-                          first_assembly_ms=(t_build + t_sym + t_first) * 1e3, first_assembly_elements_per_s=nE / (t_build + t_sym + t_first),
-                          reservation="mfh_device_reserve(%.1f GB in two segments, asynchronous) at process start" % (reserve_main / 1e9) if reserve_main else "none",
-                          **c.timing(), **c.symbolic_sizes()))
+                           parallelism="1 GPU", step="embed + Ke blocks + assembly into block-CSR (gather/owner-computes)"))
+    if args.full:
+        # dominant kernel alone, HIP events on the context's stream
+        k_ms = c.time_assembly_kernel(M.ASSEMBLE_GATHER, max(3, args.steps))
+        bytes_per_element = ALG_BYTES_UPPER[(3, deg)] if upper else ALG_BYTES[(3, deg)]
+        alg = bytes_per_element * nE
+        tb, tsrc = pmc_traffic(PMC_KERNEL_KEY, n, deg, PMC_PROFILE_UPPER if upper else PMC_PROFILE)
+        comp = compulsory_assembly_bytes(c, nE, stored_blocks)
+        roof = dict(bound="hbm", kernel="k_assemble_gather", achieved=alg / k_ms / 1e6, peak=HBM_PEAK_GBS, unit="GB/s",
+                    frac=alg / k_ms / 1e6 / HBM_PEAK_GBS, traffic=None if tb is None else tb / k_ms / 1e6,
+                    # the contract fraction above counts SURVEY 8(d)'s 100 Ke blocks per element, which an owner-computes kernel
+                    # never moves; the two fractions below are on bytes that DO cross the HBM interface
+                    frac_traffic=None if tb is None else tb / k_ms / 1e6 / HBM_PEAK_GBS,
+                    compulsory_bytes=comp, frac_compulsory=comp / k_ms / 1e6 / HBM_PEAK_GBS,
+                    traffic_bytes_per_launch_from_profile=tb, traffic_from_profile=tsrc, alg_bytes_per_launch=alg, kernel_ms=k_ms,
+                    kernel_trace="profiles/r06_config2_kernel_stats.csv: rocprofv3 --kernel-trace --stats of `python bench.py --leg config2` (this workload alone: "
+                                 "k_assemble_gather<3, 2, 0, true, false>, no deterministic and no 119^3 launches in the file)",
+                    bytes_per_element=bytes_per_element,
+                    matrix_storage="upper triangle (blocks (r, c >= r): what the reference assembles)" if upper else "both triangles",
+                    note="frac = SURVEY 8(d) algorithmic bytes (the row of the storage in use) / time / 8 TB/s (contract); frac_traffic = "
+                         "rocprofv3 PMC bytes of the committed profile / time; frac_compulsory = bytes the design must move (stored K "
+                         "once + records + lists) / time")
+        # the committed trace's average of the same kernel (another box, another draw of where the driver put the K values): both on the line
+        if (n, deg) == (60, 2) and upper:
+            pavg, pcalls = profile_kernel_avg_ms(PROFILE_ROUND + "_config2_kernel_stats.csv", "k_assemble_gather<3, 2, 0, true, false>")
+            if pavg:
+                roof.update(kernel_ms_profile_avg=pavg, profile_launches=pcalls, frac_profile_avg=alg / pavg / 1e6 / HBM_PEAK_GBS,
+                            kernel_ms_spread="2.88-3.30 ms by process and box -- where the driver puts the K values (profiles/r06_config2_profile_spread.txt: five profiled "
+                                             "processes per box; the profile average and the process's own HIP events agree to 0.9 % inside every process)",
+                            frac_traffic_profile_avg=None if tb is None else tb / pavg / 1e6 / HBM_PEAK_GBS,
+                            frac_compulsory_profile_avg=comp / pavg / 1e6 / HBM_PEAK_GBS)
+        # context: the kernel's MEASURED traffic rate against the triad rate measured on this box a minute ago
+        if roof["traffic"] is not None:
+            roof["measured_triad_GBs"] = hbm_measured["triad_GBs"]
+            roof["traffic_frac_of_measured_triad"] = roof["traffic"] / hbm_measured["triad_GBs"]
+        out.update(roofline=roof, hbm_measured=hbm_measured)
+    out["setup"] = dict(mesh_gen_s=t_gen, femmesh_build_s=t_build, symbolic_s=t_sym, first_assemble_call_s=t_first,
+                        # the timed step excludes what a one-shot caller pays once per mesh -- FEMMesh build (edge numbering,
+                        # boundary extraction, node table; includes the upload), symbolic phase (pattern + gather lists), first pass
+                        first_assembly_ms=(t_build + t_sym + t_first) * 1e3, first_assembly_elements_per_s=nE / (t_build + t_sym + t_first),
+                        reservation="mfh_device_reserve(%.1f GB in two segments, asynchronous) at process start" % (reserve_main / 1e9) if reserve_main else "none",
+                        **c.timing(), **c.symbolic_sizes())
+    if before is not None:
+        out["setup"]["device_memory_before"] = before
     if dumped is not None:
         out["dumped_outputs"] = dumped
+    if not args.full:
+        # the plain line ends here: the timed steps, the workload and its setup; what is measured after the steps belongs to --full
+        print(json.dumps(out), flush=True)
+        c.close()
+        return
     # comparison variant: element-major global-atomic scatter (north_star: "colored or atomic ... by evidence")
     try:
         a_ms = c.time_assembly_kernel(M.ASSEMBLE_ATOMIC, 3)
@@ -933,6 +952,24 @@ def config3_homogenization(args, n=44):
     return res
 
 
+def return_what_the_leg_takes(deg, n=119, timeout_s=120):
+    """The plain N = 1 line's stand-in for the strong_n1 leg that --full runs first: a process that reserves what that leg reserves and exits.
+    Where the driver puts the K values decides the timed step's time (docs/design/04_2_k_assemble_gather.md (xi)), and the line has always drawn
+    its placement right after the leg's process returned its memory. Measured on one box: without this step 20 plain lines of 21 drew 3.50 ms per
+    step; with it 4 of 6 drew 3.13-3.15 ms, like the --full line (3.13 ms in 4 processes of 5, 3.41 once). Other boxes have other levels."""
+    import subprocess
+    t0 = time.time()
+    code = "import meshfem_amd as M; print(M.device_reserve_for(3, %d, %d, wait=True))" % (deg, 24 * n ** 3)
+    try:
+        p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=timeout_s)
+    except subprocess.TimeoutExpired:
+        return dict(error="no answer within %d s" % timeout_s)
+    if p.returncode != 0:
+        return dict(error="exit code %d" % p.returncode, stderr_tail=p.stderr[-400:])
+    return dict(reserved_and_returned_GB=float(p.stdout.split()[-1]) / 1e9, wall_s=time.time() - t0,
+                note="a process of its own reserved what the --full line's strong_n1 leg reserves (the %d^3 cube) and exited" % n)
+
+
 def run_leg_subprocess(args, leg, timeout_s=900, extra=()):
     """One leg of the line in a FRESH process (a one-shot caller of that size is one): returns the leg's JSON object."""
     import subprocess
@@ -1095,6 +1132,8 @@ def run_multi(args):
     if shared and not (args.ranks_per_gpu_ok or os.environ.get("MFH_BENCH_SHARE_GPUS")):
         raise SystemExit("bench.py --gpus %d needs %d GPUs, %d visible (pass --ranks-per-gpu-ok to share them)" % (world, world, ndev))
     device = local % max(1, ndev)
+    if not args.full:           # the plain line: the timed steps alone (the solver leg and the weak-scaling object belong to --full)
+        args.no_solve, args.no_weak = True, True
     if shared:          # the ranks of a device bound their arenas to their share of it (mfh_pool.cpp)
         os.environ.setdefault("MFH_DEVICE_SHARERS", str((world + max(1, ndev) - 1) // max(1, ndev)))
     torch.cuda.set_device(device)

@@ -18,7 +18,7 @@ cp $R/gpurun_out/pmc/FETCH_SIZE_n60_counter_collection.csv $R/$O/r06_pmc_FETCH_S
 timeout 900 python $R/scripts/pmc_collect.py 60 > $R/$O/pmc_full.out 2>&1 < /dev/null
 cp $R/gpurun_out/pmc_traffic_n60.json $R/$O/r06_pmc_traffic_n60.json
 cd $R
-timeout 1200 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
-timeout 900 python bench.py --gpus 2 --ranks-per-gpu-ok --scaling strong --grid 48 --no-cpu --no-weak > $O/bench_n2_strong48.out 2> $O/bench_n2_strong48.err < /dev/null
-timeout 1500 python bench.py --gpus 8 --ranks-per-gpu-ok --no-cpu --no-weak > $O/bench_n8_forced.out 2> $O/bench_n8_forced.err < /dev/null
+timeout 1200 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
+timeout 900 python bench.py --full --gpus 2 --ranks-per-gpu-ok --scaling strong --grid 48 --no-cpu --no-weak > $O/bench_n2_strong48.out 2> $O/bench_n2_strong48.err < /dev/null
+timeout 1500 python bench.py --full --gpus 8 --ranks-per-gpu-ok --no-cpu --no-weak > $O/bench_n8_forced.out 2> $O/bench_n8_forced.err < /dev/null
 ls -la $O | head -40

@@ -14,5 +14,5 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_b
 f=$(find $R/$O/prof_batch -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $R/$O/batch_probe_kernel_stats.csv
 rm -rf $R/$O/prof_batch
 cd $R
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
 tail -c 600 $O/bench_n1.json

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_solver.py tests/test_gpu_arena.py -x
 tail -3 $O/tests_a.log
 timeout 1500 python scripts/r06/tile_probe.py > $O/tile_probe.txt 2>&1 < /dev/null
 cat $O/tile_probe.txt
-timeout 900 python bench.py --no-strong-n1 --no-cpu > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
+timeout 900 python bench.py --full --no-strong-n1 --no-cpu > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06d/bench_n1.json").read().strip().splitlines()[-1])

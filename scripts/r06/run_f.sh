@@ -6,7 +6,7 @@ cd $R
 timeout 900 python -m pytest tests/test_gpu_arena.py -x -q -m gpu > $O/tests_a.log 2>&1 < /dev/null
 tail -3 $O/tests_a.log
 timeout 600 python scripts/mg_setup_probe.py 60 2 > $O/mg_setup_60.log 2>&1 < /dev/null
-timeout 900 python bench.py --no-strong-n1 --no-cpu --no-config3 > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
+timeout 900 python bench.py --full --no-strong-n1 --no-cpu --no-config3 > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06f/bench_n1.json").read().strip().splitlines()[-1])

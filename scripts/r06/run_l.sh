@@ -2,7 +2,7 @@ O=gpurun_out/r06l
 mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd $R
-MFH_POOL_TRACE=1 timeout 1200 python bench.py --no-cpu > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
+MFH_POOL_TRACE=1 timeout 1200 python bench.py --full --no-cpu > $O/bench_n1.json 2> $O/bench_n1.err < /dev/null
 grep "arena" $O/bench_n1.err | tail -60
 python - <<'PY'
 import json
