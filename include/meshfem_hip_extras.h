@@ -55,6 +55,13 @@ mfh_status mfh_debug_apply_operator(mfh_ctx* ctx, int32_t nr, int32_t masked, in
 mfh_status mfh_debug_apply_precond(mfh_ctx* ctx, int32_t nr, const double* R, double* Z);
 mfh_status mfh_debug_row_chunks(int64_t nRows, const int32_t* rowPtr, int32_t chunkSlots, int64_t nBreaks, const int64_t* breaks, int64_t grain,
                                 int32_t threads, int32_t* chunkRow, int64_t cap, int64_t* nOut);
+/* test hook (host only, no context): the stopping rule of the PCG loops, fed a synthetic residual history of n records {rr[q] = r.r, pKp[q] = p.Kp,
+ * known[q] != 0: that p.Kp is known} in order. threshold: on r.r; window: iterations without a best r.r 10 % below the last one that are reported
+ * as stagnation (0: no such rule); lastComplete: the records after it are half-written (the end of a block of iterations: their p.Kp is not looked
+ * at). *convergedAt = the first record at or below the threshold, -1 if there is none. When the rule reports a breakdown instead, its status is
+ * returned and its message copied to msg (capacity msgCap; may be null) */
+mfh_status mfh_debug_pcg_watch(int64_t n, const double* rr, const double* pKp, const uint8_t* known, double threshold, int32_t window,
+                               int64_t lastComplete, int64_t* convergedAt, char* msg, int64_t msgCap);
 
 
 /* ---------------------------------------------------------------- device-pointer building blocks

@@ -174,6 +174,7 @@ PROTOTYPES = {
     "mfh_debug_arena_alloc": (_i32, [_P, _i64, C.POINTER(_P)]),
     "mfh_debug_arena_free": (_i32, [_P, _P]),
     "mfh_debug_row_chunks": (_i32, [_i64, _P, _i32, _i64, _P, _i64, _i32, _P, _i64, _P]),
+    "mfh_debug_pcg_watch": (_i32, [_i64, _P, _P, _P, _f64, _i32, _i64, _P, _P, _i64]),
     "mfh_debug_apply_operator": (_i32, [_P, _i32, _i32, _i32, _P, _P, _P]),
     "mfh_debug_apply_precond": (_i32, [_P, _i32, _P, _P]),
 }

@@ -318,7 +318,7 @@ struct mfh_ctx {
     }
 };
 
-namespace mfhi {   // internal helpers with external linkage (defined in mfh_api.cpp unless inline)
+namespace mfhi {   // internal helpers with external linkage (defined in mfh_api.cpp, the solver's in mfh_solver.cpp, unless inline)
 using namespace mfh;
 
 #define MFH_TRY(ctx) try {         \
@@ -424,6 +424,19 @@ void add_fixed(mfh_ctx *c, int64_t n, const int64_t *vars, const double *vals);
 void ensure_geometry(mfh_ctx *c, bool deferCheck = false);
 void finish_geometry(mfh_ctx *c);
 void ensure_mf_cluster(mfh_ctx *c);
+void upload_mesh(mfh_ctx *c, bool deviceTables);
+void ensure_fixed_uploaded(mfh_ctx *c);
+bool prepare_matrix_free(mfh_ctx *c);
+k::SpmvArgs spmv_args(mfh_ctx *c, bool masked);
+k::SpmvMfArgs spmv_mf_args(mfh_ctx *c, bool masked);
+k::SpmvMfArgs spmv_mf_cluster_args(mfh_ctx *c, bool masked);
+k::TLArgs tl_args(mfh_ctx *c);
+void apply_operator(mfh_ctx *c, bool masked, const double *x, double *y, double *dotOut);
+void apply_operator_smoother(mfh_ctx *c, bool masked, const double *x, double *y);
+void batch_apply(mfh_ctx *c, int NR, double *x, double *y, bool masked);            // y = K x for NR interleaved vectors (mfh_solver.cpp)
+void tl_precond(mfh_ctx *c, const double *r, double *z, double *scal, int it);
+bool dense_inverse_device(mfh_ctx *c, const double *Ac, int64_t mm, DBuf<double> &Ainv, int64_t &ldInv);
+double device_dot(mfh_ctx *c, int64_t n, const double *a, const double *b);
 void ensure_precond(mfh_ctx *c);
 bool ensure_twolevel(mfh_ctx *c);
 bool ensure_multigrid(mfh_ctx *c);
@@ -444,6 +457,7 @@ const int32_t *device_dof_map(mfh_ctx *c);
 void box_corners(mfh_ctx *c, const double *mn, const double *mx, int relative, double *omn, double *omx);
 void dirichlet_vars(mfh_ctx *c, std::vector<int64_t> &vars, std::vector<double> &vals);
 int64_t pin_node(const mfh_ctx *c);
+void solve_one_classic(mfh_ctx *c, const double *f, double *u, double rtol, int maxit, mfh_solve_info *info);
 void solve_one(mfh_ctx *c, const double *f, double *u, double rtol, int maxit, mfh_solve_info *info);
 void solve_many(mfh_ctx *c, int nrhs, const double *f, double *u, int64_t stride, double rtol, int maxit, mfh_solve_info *infos);
 // Device-resident ends of a multigrid batch (mfh_solve_cell_problems): the right-hand sides are constantStrainLoad vectors formed on the device

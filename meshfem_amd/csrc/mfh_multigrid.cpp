@@ -15,17 +15,6 @@
 
 namespace mfhi {
 
-k::TLArgs tl_args(mfh_ctx *c);
-void apply_operator(mfh_ctx *c, bool masked, const double *x, double *y, double *dotOut);
-bool prepare_matrix_free(mfh_ctx *c);
-void apply_operator_smoother(mfh_ctx *c, bool masked, const double *x, double *y);
-void batch_apply(mfh_ctx *c, int NR, double *x, double *y, bool masked);            // y = K x for NR interleaved vectors (mfh_solver.cpp)
-void ensure_fixed_uploaded(mfh_ctx *c);
-double device_dot(mfh_ctx *c, int64_t n, const double *a, const double *b);
-void upload_mesh(mfh_ctx *c, bool deviceTables);
-bool dense_inverse_device(mfh_ctx *c, const double *Ac, int64_t mm, DBuf<double> &Ainv, int64_t &ldInv);
-const int32_t *device_dof_map(mfh_ctx *c);
-
 namespace {
 
 // What a Chebyshev sweep needs of a level: y = A x, and the fused step  r' = rin - t; d = a d + b D^-1 r'; x (+)= d

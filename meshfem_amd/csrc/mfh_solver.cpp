@@ -161,15 +161,6 @@ void dist_detach(mfh_ctx *c) {
     c->dist.listKind = 0;
 }
 
-k::SpmvArgs spmv_args(mfh_ctx *c, bool masked);
-k::SpmvMfArgs spmv_mf_cluster_args(mfh_ctx *c, bool masked);
-bool prepare_matrix_free(mfh_ctx *c);
-k::TLArgs tl_args(mfh_ctx *c);
-void ensure_fixed_uploaded(mfh_ctx *c);
-void solve_one_classic(mfh_ctx *c, const double *f, double *u, double rtol, int maxit, mfh_solve_info *info);
-void apply_operator(mfh_ctx *c, bool masked, const double *x, double *y, double *dotOut);
-void tl_precond(mfh_ctx *c, const double *r, double *z, double *scal, int it);
-
 namespace {
 
 struct DistLink {   // stream / event plumbing of one solve on a partitioned context
@@ -565,6 +556,88 @@ void dist_agree(mfh_ctx *c) {
     }
 }
 
+// ---- what the four PCG loops below share: everything around their iteration bodies
+namespace {
+
+// Launch-bound regime (small meshes: a few tens of microseconds per kernel): one block of check_every iterations recorded on `s` and replayed;
+// the kernels find their iteration through a device-side base that the block's last node advances. Or nothing -- not wanted, or the capture
+// failed -- and the caller enqueues its iterations eagerly.
+struct IterationGraph {
+    hipGraphExec_t exec = nullptr;
+    template <class Record> IterationGraph(hipStream_t s, bool enabled, Record &&record) {
+        if (!enabled) return;
+        hipGraph_t graph = nullptr;
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
+            bool ok = true;
+            try { record(); } catch (...) { ok = false; }
+            if (hipStreamEndCapture(s, &graph) != hipSuccess || !ok || !graph) { graph = nullptr; (void)hipGetLastError(); }
+        } else (void)hipGetLastError();
+        if (graph) {
+            if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { exec = nullptr; (void)hipGetLastError(); }
+            (void)hipGraphDestroy(graph);
+        }
+    }
+    IterationGraph(const IterationGraph &) = delete;
+    ~IterationGraph() { if (exec) (void)hipGraphExecDestroy(exec); }      // also when the scan of the history throws
+    explicit operator bool() const { return exec != nullptr; }
+    void launch(hipStream_t s) { MFH_HIP(hipGraphLaunch(exec, s)); }
+};
+
+// The stopping rule of one right-hand side, fed the records {.., p.Kp, r.r, ..} of its residual history in order.
+struct ResidualWatch {
+    double threshold = 0;           // converged at the first r.r <= threshold
+    int stagnationWindow = 0;       // iterations without a new best r.r that are reported (stagnation_window); 0: no such rule
+    int itConv = -1;                // the iteration that met the threshold
+    double rrFinal = 0;             // r.r of the last record judged
+    double bestRR = 1e300;
+    int itBest = 0;
+    // true when record q meets the threshold. CHOLMOD reports "not positive definite" at once; the iterative counterpart: negative curvature
+    // p.Kp (curvatureKnown: not for the last record of a block, whose p.Kp is not written yet), or a residual whose best value has not improved
+    // by 10 % for thousands of iterations (a singular system with an inconsistent right-hand side: missing boundary conditions, unbalanced
+    // loads on a free body)
+    bool judge(int q, double rr, bool curvatureKnown, double pKp) {
+        if (rr <= threshold) { itConv = q; rrFinal = rr; return true; }
+        if (!(rr == rr)) throw Error(MFH_ERR_NOT_CONVERGED, "PCG breakdown (NaN residual): K is not SPD on the free variables");
+        if (curvatureKnown && pKp < 0.0)
+            throw Error(MFH_ERR_NOT_CONVERGED, "PCG breakdown (p.Kp = " + std::to_string(pKp) + " < 0 at iteration " + std::to_string(q) +
+                                                   ", residual^2 " + std::to_string(rr) + "): K is not positive definite on the free variables");
+        if (rr < 0.9 * bestRR) { bestRR = rr; itBest = q; }
+        else if (stagnationWindow > 0 && q - itBest > stagnationWindow)
+            throw Error(MFH_ERR_NOT_CONVERGED, "PCG stagnated (no progress of the residual for " + std::to_string(stagnationWindow) +
+                                                   " iterations): the system is singular with an inconsistent right-hand side "
+                                                   "(missing boundary conditions?) or too ill-conditioned for this preconditioner");
+        rrFinal = rr;
+        return false;
+    }
+};
+
+// (a plateau is not a stagnation: block-Jacobi PCG on a one-layer plate in bending, 59 k DOF, sits above its best residual for more than
+// 5 000 iterations and then converges at 5 913 -- CG owes its answer within about n iterations, so the window grows with n)
+int stagnation_window(const mfh_ctx *c) {
+    return (int)std::max<int64_t>(std::max(5000, 40 * c->checkEvery), std::min<int64_t>((int64_t)c->bs() * c->nDoF, 50000));
+}
+
+// What a batched loop reports: one mfh_solve_info per right-hand side (bb = |b|^2, tr = |f - K u|^2 on the free variables), then the
+// residual-gap check of each -- after every info has been written (norms are global: all ranks agree)
+void report_batch(int NR, const ResidualWatch *watch, const double *bb, const double *tr, int itRun, int maxit, double rtol, double solveMs,
+                  double setupMs, bool usedGraph, mfh_solve_info *infos) {
+    mfh_solve_info li[8] = {};
+    for (int k2 = 0; k2 < NR; ++k2) {
+        li[k2].converged = watch[k2].itConv >= 0 ? 1 : 0;
+        li[k2].iterations = watch[k2].itConv >= 0 ? watch[k2].itConv : std::min(itRun, maxit);
+        li[k2].rel_residual = bb[k2] > 0 ? std::sqrt(watch[k2].rrFinal / bb[k2]) : 0.0;
+        li[k2].true_rel_residual = bb[k2] > 0 ? std::sqrt(tr[k2] / bb[k2]) : 0.0;
+        li[k2].solve_ms = solveMs;               // the batch's device time (shared by its right-hand sides)
+        li[k2].setup_ms = setupMs;
+        li[k2].used_graph = usedGraph ? 1 : 0;
+        li[k2].reserved = NR;
+        if (infos) infos[k2] = li[k2];
+    }
+    for (int k2 = 0; k2 < NR; ++k2) check_residual_gap(li[k2], rtol);
+}
+
+}   // namespace
+
 // PCG on the free variables for NR right-hand sides at once. f / u: NR host vectors of bs * nRows doubles each (nRows = the
 // rows this context owns), fStride doubles apart.
 void solve_cg(mfh_ctx *c, int NR, const double *f, double *u, int64_t fStride, double rtol, int maxit, mfh_solve_info *infos) {
@@ -616,8 +689,8 @@ void solve_cg(mfh_ctx *c, int NR, const double *f, double *u, int64_t fStride, d
     c->scal.zero(s);
     c->cgX.zero(s); c->cgP.zero(s); c->cgS.zero(s);
     const double setupMs = tsetup.stop();
-    std::vector<int> itConv((size_t)NR, -1);
-    std::vector<double> rrFinal((size_t)NR, 0.0);
+    ResidualWatch watch[8];
+    for (int k2 = 0; k2 < NR; ++k2) { watch[k2].threshold = ctlHost[2 + k2]; watch[k2].stagnationWindow = stagnation_window(c); if (!(bb[k2] > 0)) watch[k2].itConv = 0; }
     double solveMs = 0;
     bool usedGraph = false;
     int itRun = 0;
@@ -637,35 +710,17 @@ void solve_cg(mfh_ctx *c, int NR, const double *f, double *u, int64_t fStride, d
             apply_op_nr(c, L, NR, c->cgU.p, c->cgW.p, masked, nullptr, scal, itLocal, ctl);
             L.allreduce(scal + (size_t)(itAbs + 1) * 4 * NR, 4 * NR);
         };
-        // launch-bound regime (small meshes): replay blocks of check_every iterations from a hipGraph; the kernels find their
-        // iteration through the device-side base ctl[0], which the last node advances. Not with a communicator.
-        hipGraphExec_t exec = nullptr;
-        if (c->useGraph && c->checkEvery > 1 && !L.active) {
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                bool ok = true;
-                try {
-                    for (int j = 0; j < c->checkEvery; ++j) enqueue(j, j);
-                    k::launch_add_scalar(c->cgCtl.p, (double)c->checkEvery, s);
-                } catch (...) { ok = false; }
-                if (hipStreamEndCapture(s, &graph) != hipSuccess || !ok || !graph) { graph = nullptr; (void)hipGetLastError(); }
-            } else (void)hipGetLastError();
-            if (graph) {
-                if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { exec = nullptr; (void)hipGetLastError(); }
-                (void)hipGraphDestroy(graph);
-            }
-        }
-        usedGraph = exec != nullptr;
+        // the iteration base is ctl[0]. Not with a communicator.
+        IterationGraph graph(s, c->useGraph && c->checkEvery > 1 && !L.active, [&] {
+            for (int j = 0; j < c->checkEvery; ++j) enqueue(j, j);
+            k::launch_add_scalar(c->cgCtl.p, (double)c->checkEvery, s);
+        });
+        usedGraph = (bool)graph;
         std::vector<double> hs;
         int it = 0, lastChecked = 0, nConv = 0;
-        for (int k2 = 0; k2 < NR; ++k2) if (!(bb[k2] > 0)) { itConv[k2] = 0; ++nConv; }
-        std::vector<double> bestRR((size_t)NR, 1e300);
-        std::vector<int> itBest((size_t)NR, 0);
-        // (a plateau is not a stagnation: block-Jacobi PCG on a one-layer plate in bending, 59 k DOF, sits above its best residual for more than
-        // 5 000 iterations and then converges at 5 913 -- CG owes its answer within about n iterations, so the window grows with n)
-        const int stagnationWindow = (int)std::max<int64_t>(std::max(5000, 40 * c->checkEvery), std::min<int64_t>((int64_t)d * c->nDoF, 50000));
+        for (int k2 = 0; k2 < NR; ++k2) nConv += watch[k2].itConv >= 0;
         while (nConv < NR && it < maxit) {
-            if (exec) { MFH_HIP(hipGraphLaunch(exec, s)); it += c->checkEvery; }
+            if (graph) { graph.launch(s); it += c->checkEvery; }
             else {
                 const int itEnd = std::min(maxit, it + c->checkEvery);
                 for (; it < itEnd; ++it) enqueue(it, it);
@@ -673,34 +728,16 @@ void solve_cg(mfh_ctx *c, int NR, const double *f, double *u, int64_t fStride, d
             hs.resize((size_t)(it - lastChecked + 1) * 4 * NR);
             MFH_HIP(hipMemcpyAsync(hs.data(), scal + (size_t)lastChecked * 4 * NR, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
             MFH_HIP(hipStreamSynchronize(s));
-            for (int k2 = 0; k2 < NR; ++k2) {
-                if (itConv[k2] >= 0) continue;
-                for (int q = lastChecked; q <= std::min(it, maxit); ++q) {
-                    const double *sc = &hs[((size_t)(q - lastChecked) * NR + k2) * 4];
-                    const double rr = sc[2];
-                    if (rr <= ctlHost[2 + k2]) { itConv[k2] = q; rrFinal[k2] = rr; ++nConv; break; }
-                    if (!(rr == rr)) throw Error(MFH_ERR_NOT_CONVERGED, "PCG breakdown (NaN residual): K is not SPD on the free variables");
-                    // CHOLMOD reports "not positive definite" at once; the iterative counterpart: negative curvature
-                    // (p.Kp = gamma / alpha < 0), or a residual that has not improved by 10 % for thousands of iterations (a
-                    // singular system with an inconsistent right-hand side: missing boundary conditions, unbalanced loads)
-                    if (q < it && sc[3] != 0.0 && sc[0] / sc[3] < 0.0)
-                        throw Error(MFH_ERR_NOT_CONVERGED, "PCG breakdown (p.Kp = " + std::to_string(sc[0] / sc[3]) + " < 0 at iteration " + std::to_string(q) +
-                                                               ", residual^2 " + std::to_string(rr) + "): K is not positive definite on the free variables");
-                    if (rr < 0.9 * bestRR[k2]) { bestRR[k2] = rr; itBest[k2] = q; }
-                    else if (q - itBest[k2] > stagnationWindow)
-                        throw Error(MFH_ERR_NOT_CONVERGED, "PCG stagnated (no progress of the residual for " + std::to_string(stagnationWindow) +
-                                                               " iterations): the system is singular with an inconsistent right-hand side "
-                                                               "(missing boundary conditions?) or too ill-conditioned for this preconditioner");
-                    rrFinal[k2] = rr;
+            for (int k2 = 0; k2 < NR; ++k2)
+                for (int q = lastChecked; watch[k2].itConv < 0 && q <= std::min(it, maxit); ++q) {
+                    const double *sc = &hs[((size_t)(q - lastChecked) * NR + k2) * 4];      // {gamma, delta, r.r, alpha}: p.Kp = gamma / alpha
+                    const bool known = q < it && sc[3] != 0.0;
+                    nConv += watch[k2].judge(q, sc[2], known, known ? sc[0] / sc[3] : 0.0);
                 }
-            }
             lastChecked = it;
         }
         itRun = it;
-        if (exec) (void)hipGraphExecDestroy(exec);
         solveMs = tsolve.stop();
-    } else {
-        for (int k2 = 0; k2 < NR; ++k2) itConv[k2] = 0;
     }
     // u = x + ubar  (SparseMatrices.hh:2592-2605)
     if (masked && !c->solveHomogeneous) k::launch_scatter_values_nr((int64_t)c->fixedVars.size(), NR, d, c->dFixedIdx.p, c->dFixedVal.p, c->cgX.p, nRows, s);   // owned rows only: x has no halo part
@@ -723,21 +760,7 @@ void solve_cg(mfh_ctx *c, int NR, const double *f, double *u, int64_t fStride, d
     for (int k2 = 0; k2 < NR; ++k2)
         MFH_HIP(hipMemcpyAsync(u + (size_t)k2 * fStride, c->cgS.p + (size_t)k2 * nRows * d, (size_t)nRows * d * sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
-    mfh_solve_info gap[8];
-    for (int k2 = 0; k2 < NR; ++k2) {
-        mfh_solve_info li{};
-        li.converged = itConv[k2] >= 0 ? 1 : 0;
-        li.iterations = itConv[k2] >= 0 ? itConv[k2] : std::min(itRun, maxit);
-        li.rel_residual = bb[k2] > 0 ? std::sqrt(rrFinal[k2] / bb[k2]) : 0.0;
-        li.true_rel_residual = bb[k2] > 0 ? std::sqrt(tr[k2] / bb[k2]) : 0.0;
-        li.solve_ms = solveMs;
-        li.setup_ms = setupMs;
-        li.used_graph = usedGraph ? 1 : 0;
-        li.reserved = NR;
-        if (infos) infos[k2] = li;
-        gap[k2] = li;
-    }
-    for (int k2 = 0; k2 < NR; ++k2) check_residual_gap(gap[k2], rtol);   // after every info has been written (norms are global: all ranks agree)
+    report_batch(NR, watch, bb, tr, itRun, maxit, rtol, solveMs, setupMs, usedGraph, infos);
 }
 
 // The CLASSIC PCG (two reduction points) on a row-partitioned context, one right-hand side: the same kernels as the
@@ -787,7 +810,7 @@ void solve_classic_partitioned(mfh_ctx *c, const double *f, double *u, double rt
     li.setup_ms = tsetup.stop();
     li.reserved = 1;
     int itDone = 0;
-    double rrFinal = 0;
+    ResidualWatch watch{stopv};         // (no stagnation rule in this loop)
     if (bb == 0.0) { c->wx.zero(s); li.converged = 1; }
     else {
         EventTimer tsolve(s);
@@ -837,21 +860,18 @@ void solve_classic_partitioned(mfh_ctx *c, const double *f, double *u, double rt
             hs.resize((size_t)(it - lastChecked + 1) * 4);
             MFH_HIP(hipMemcpyAsync(hs.data(), scal + (size_t)lastChecked * 4, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
             MFH_HIP(hipStreamSynchronize(s));
-            for (int k2 = lastChecked; k2 <= it; ++k2) {
-                const double rr = hs[(size_t)(k2 - lastChecked) * 4 + 2];
-                if (rr <= stopv) { done = true; itDone = k2; rrFinal = rr; break; }
-                if (!(rr == rr)) throw Error(MFH_ERR_NOT_CONVERGED, "PCG breakdown (NaN residual): K is not SPD on the free variables");
-                const double pAp = hs[(size_t)(k2 - lastChecked) * 4 + 1];
-                if (k2 < it && pAp < 0.0) throw Error(MFH_ERR_NOT_CONVERGED, "PCG breakdown (p.Kp < 0): K is not positive definite on the free variables");
+            for (int q = lastChecked; !done && q <= it; ++q) {
+                const double *sc = &hs[(size_t)(q - lastChecked) * 4];      // {r.z, p.Kp, r.r, -}
+                done = watch.judge(q, sc[2], q < it, sc[1]);
             }
-            if (!done) { itDone = it; rrFinal = hs[(size_t)(it - lastChecked) * 4 + 2]; }
+            itDone = done ? watch.itConv : it;
             lastChecked = it;
         }
         li.solve_ms = tsolve.stop();
         li.converged = done ? 1 : 0;
     }
     li.iterations = itDone;
-    li.rel_residual = bb > 0 ? std::sqrt(rrFinal / bb) : 0.0;
+    li.rel_residual = bb > 0 ? std::sqrt(watch.rrFinal / bb) : 0.0;
     if (masked && !c->solveHomogeneous) k::launch_scatter_values((int64_t)c->fixedVars.size(), c->dFixedIdx.p, c->dFixedVal.p, c->wx.p, nOwn, s);   // owned rows only
     if (bb > 0) {   // true residual on the free variables
         MFH_HIP(hipMemcpyAsync(p, c->wx.p, (size_t)nOwn * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -871,6 +891,294 @@ void solve_classic_partitioned(mfh_ctx *c, const double *f, double *u, double rt
     MFH_HIP(hipStreamSynchronize(s));
     if (info) *info = li;
     check_residual_gap(li, rtol);
+}
+
+double device_dot(mfh_ctx *c, int64_t n, const double *a, const double *b) {
+    c->stop.alloc(4);
+    MFH_HIP(hipMemsetAsync(c->stop.p + 1, 0, sizeof(double), c->stream));
+    k::launch_dot(n, a, b, c->stop.p + 1, c->stream);
+    double v = 0;
+    MFH_HIP(hipMemcpyAsync(&v, c->stop.p + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    return v;
+}
+
+// Classic PCG (two reduction points per iteration) on the free variables of K, one right-hand side: kept as option
+// "pcg_variant" 0 and for the operator variants without a batched kernel; the default solver is solve_cg above.
+void solve_one_classic(mfh_ctx *c, const double *f, double *u, double rtol, int maxit, mfh_solve_info *info) {
+    RoctxRange range("Elasticity Solve");
+    const int d = c->bs();
+    const int64_t n = (int64_t)d * c->nDoF;
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_STATE,
+            "mfh_solve needs all rows owned; use the mfh_dev_* building blocks for partitioned meshes");
+    hipStream_t s = c->stream;
+    c->wx.alloc(n); c->wr.alloc(n); c->wz.alloc(n); c->wp.alloc(n); c->wAp.alloc(n); c->wb.alloc(n); c->wf.alloc(n);
+    c->stop.alloc(4);
+    EventTimer tsetup(s);
+    prepare_matrix_free(c);   // gather lists of the operator: once per mesh / DoF map, part of the setup time
+    if (f) MFH_HIP(hipMemcpyAsync(c->wf.p, f, n * sizeof(double), hipMemcpyHostToDevice, s));      // (null: the caller has formed it in c->wf on the device)
+    // b = f - K ubar on the free variables (SparseMatrices.hh:2457-2470,2526-2535)
+    MFH_HIP(hipMemcpyAsync(c->wb.p, c->wf.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (c->anyFixedNonzero && !c->solveHomogeneous) {
+        c->wu0.alloc(n);
+        c->wu0.zero(s);
+        k::launch_scatter_values((int64_t)c->fixedVars.size(), c->dFixedIdx.p, c->dFixedVal.p, c->wu0.p, n, s);
+        apply_operator(c, false, c->wu0.p, c->wAp.p, nullptr);
+        k::launch_axpby(n, -1.0, c->wAp.p, 1.0, c->wb.p, s);
+    }
+    if (!c->fixedVars.empty()) k::launch_mask(n, c->dFixedMask.p, c->wb.p, s);
+    const double bb = device_dot(c, n, c->wb.p, c->wb.p);
+    mfh_solve_info li{};
+    // the graph path runs whole blocks of check_every iterations, so the history may run past maxit
+    const size_t scalN = ((size_t)maxit + (size_t)c->checkEvery + 2) * 4;
+    c->scal.alloc(scalN);
+    c->scal.zero(s);
+    const double stopv = rtol * rtol * bb;
+    MFH_HIP(hipMemsetAsync(c->stop.p, 0, 4 * sizeof(double), s));   // [0] threshold, [1] dot scratch, [3] iteration base
+    MFH_HIP(hipMemcpyAsync(c->stop.p, &stopv, sizeof(double), hipMemcpyHostToDevice, s));
+    li.setup_ms = tsetup.stop();
+    int itDone = 0;
+    ResidualWatch watch{stopv, stagnation_window(c)};
+    if (bb == 0.0) {
+        c->wx.zero(s);
+        li.converged = 1;
+    } else {
+        EventTimer tsolve(s);
+        const bool useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
+        const bool useTL = !useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
+        const uint8_t *maskPtr = c->fixedVars.empty() ? nullptr : c->dFixedMask.p;
+        k::launch_pcg_init(d, c->sym.nRows, c->dDinv.p, c->wb.p, c->wx.p, c->wr.p, c->wz.p, c->wp.p, c->scal.p, s);
+        if (useTL || useMG) {   // replace z, p and r.z of the block-Jacobi initialisation
+            MFH_HIP(hipMemsetAsync(c->scal.p, 0, sizeof(double), s));
+            if (useMG) {
+                mg_precond(c, c->wr.p, c->wz.p, nullptr, -1, nullptr);
+                k::launch_mg_rz(n, c->wr.p, c->wz.p, maskPtr, c->scal.p, -1, nullptr, nullptr, s);
+            } else
+                tl_precond(c, c->wr.p, c->wz.p, c->scal.p, -1);
+            MFH_HIP(hipMemcpyAsync(c->wp.p, c->wz.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+        const k::SpmvArgs sa = spmv_args(c, !c->fixedVars.empty());
+        const bool useMF = c->use_mf();
+        if (!useMF) require_full_storage(c, "the assembled SpMV of the PCG");
+        const bool useCluster = useMF && c->mfModeEff() == 4 && c->op == MFH_OP_ELASTICITY;
+        const k::SpmvMfArgs mfa = useCluster ? spmv_mf_cluster_args(c, !c->fixedVars.empty())
+                                             : (useMF ? spmv_mf_args(c, !c->fixedVars.empty()) : k::SpmvMfArgs{});
+        const double mgZs = useMG && c->mgFuse ? mg_fuse_scale(c) : 0.0;
+        const float *dinv32 = mgZs > 0 ? smoother_dinv32(c) : nullptr;
+        std::vector<double> hs;
+        int it = 0;
+        bool done = false;
+        int lastChecked = 0;
+        auto enqueue = [&](int itLocal) {   // one PCG iteration; `itLocal` is relative to the iteration base stop[3]
+            if (useCluster) k::launch_spmv_mf_cluster(mfa, c->wp.p, c->wAp.p, nullptr, c->scal.p, itLocal, c->stop.p, true, s);
+            else if (useMF && c->mfModeEff() >= 2 && c->op == MFH_OP_ELASTICITY) k::launch_spmv_mf2(mfa, c->wp.p, c->wAp.p, nullptr, c->scal.p, itLocal, c->stop.p, true, s);
+            else if (useMF) k::launch_spmv_mf(mfa, c->wp.p, c->wAp.p, nullptr, c->scal.p, itLocal, c->stop.p, true, s);
+            else k::launch_pcg_spmv(sa, c->wp.p, c->wAp.p, c->scal.p, itLocal, c->stop.p, s);
+            if (useMG && mgZs > 0) {
+                // the V-cycle's first and last vector kernels folded into the loop's own (MgFuse): r -= alpha Ap and z = Dinv r / theta in one
+                // pass, the last smoothing step and r.z in another -- three vector passes of 24.6 less per iteration
+                k::launch_pcg_update_presmooth(d, c->sym.nRows, c->dDinv.p, dinv32, c->wAp.p, c->wr.p, c->wz.p, mgZs, c->scal.p, itLocal, c->stop.p, s);
+                const MgFuse fz{true, c->scal.p, maskPtr};
+                mg_precond(c, c->wr.p, c->wz.p, c->scal.p, itLocal, c->stop.p, &fz);
+            } else if (useMG) {
+                k::launch_pcg_update_noz(d, c->sym.nRows, c->wAp.p, c->wr.p, c->scal.p, itLocal, c->stop.p, s);
+                mg_precond(c, c->wr.p, c->wz.p, c->scal.p, itLocal, c->stop.p);
+                k::launch_mg_rz(n, c->wr.p, c->wz.p, maskPtr, c->scal.p, itLocal, c->scal.p, c->stop.p, s);
+            } else if (useTL) {
+                k::launch_pcg_update_noz(d, c->sym.nRows, c->wAp.p, c->wr.p, c->scal.p, itLocal, c->stop.p, s);
+                tl_precond(c, c->wr.p, c->wz.p, c->scal.p, itLocal);
+            } else
+                k::launch_pcg_update(d, c->sym.nRows, c->dDinv.p, c->wAp.p, c->wr.p, c->wz.p, c->scal.p, itLocal, c->stop.p, s);
+            k::launch_pcg_direction(n, c->wz.p, c->wp.p, c->wx.p, c->scal.p, itLocal, c->stop.p, s);
+        };
+        // a multigrid iteration is tens of kernels and milliseconds long and only tens of them are needed: short blocks (the operator
+        // applications inside the V-cycle are not gated, so iterations past convergence would cost real time)
+        const int checkEvery = useMG ? std::min(c->checkEvery, 2) : c->checkEvery;
+        IterationGraph graph(s, c->useGraph && checkEvery > 1, [&] {      // the iteration base is stop[3]
+            for (int j = 0; j < checkEvery; ++j) enqueue(j);
+            k::launch_advance_base(c->stop.p, checkEvery, s);
+        });
+        li.used_graph = graph ? 1 : 0;
+        while (!done && it < maxit) {
+            if (graph) {
+                graph.launch(s);
+                it += checkEvery;
+            } else {
+                const int itEnd = std::min(maxit, it + checkEvery);
+                for (; it < itEnd; ++it) enqueue(it);
+            }
+            // scan the residual history of the iterations just enqueued
+            hs.resize((size_t)(it - lastChecked + 1) * 4);
+            MFH_HIP(hipMemcpyAsync(hs.data(), c->scal.p + (size_t)lastChecked * 4, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            MFH_HIP(hipStreamSynchronize(s));
+            for (int q = lastChecked; !done && q <= std::min(it, maxit); ++q) {
+                const double *sc = &hs[(size_t)(q - lastChecked) * 4];      // {r.z, p.Kp, r.r, -}
+                done = watch.judge(q, sc[2], q < it, sc[1]);
+            }
+            itDone = done ? watch.itConv : std::min(it, maxit);
+            lastChecked = it;
+        }
+        li.solve_ms = tsolve.stop();
+        li.converged = done ? 1 : 0;
+    }
+    li.iterations = itDone;
+    li.rel_residual = bb > 0 ? std::sqrt(watch.rrFinal / bb) : 0.0;
+    // u = x + ubar  (SparseMatrices.hh:2592-2605)
+    if (!c->fixedVars.empty() && !c->solveHomogeneous)
+        k::launch_scatter_values((int64_t)c->fixedVars.size(), c->dFixedIdx.p, c->dFixedVal.p, c->wx.p, n, s);
+    // true residual on the free variables: || mask(f - K u) || / ||b||
+    if (bb > 0) {
+        apply_operator(c, false, c->wx.p, c->wAp.p, nullptr);
+        k::launch_axpby(n, 1.0, c->wf.p, -1.0, c->wAp.p, s);
+        if (!c->fixedVars.empty()) k::launch_mask(n, c->dFixedMask.p, c->wAp.p, s);
+        li.true_rel_residual = std::sqrt(device_dot(c, n, c->wAp.p, c->wAp.p) / bb);
+    }
+    MFH_HIP(hipMemcpyAsync(u, c->wx.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    if (info) *info = li;
+    check_residual_gap(li, rtol);
+}
+
+// NR right-hand sides under the multigrid preconditioner of an unpartitioned quadratic context (solve_many, option "mg_batch"): NR classic PCG
+// loops advancing in lockstep -- loop k with vectors of its own (k vs apart), its own history scal + k scalStride and control block
+// stop + 4 k, hence its own convergence: a loop that has met its threshold is frozen by its gate like in solve_one_classic -- and ONE pass
+// through the linear / aggregate / dense levels of every V-cycle for all of them (mg_precond_batch). The quadratic level's kernels are the
+// single-vector ones at their single-vector cost; what the batch shares is everything below, which is bound by matrix bytes and launch latency.
+// The reference's counterpart: one factorisation, one back-substitution per right-hand side (SparseMatrices.hh:2106-2124).
+void solve_multigrid_batch(mfh_ctx *c, int NR, const double *f, double *u, int64_t hostStride, double rtol, int maxit, mfh_solve_info *infos, const BatchIO *io) {
+    RoctxRange range("Elasticity Solve");
+    const int d = c->bs();
+    const int64_t n = (int64_t)d * c->nDoF;
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_STATE, "batched multigrid solve needs all rows owned");
+    require(NR >= 2 && NR <= 6, MFH_ERR_INVALID, "batch size");
+    hipStream_t s = c->stream;
+    const int64_t vs = (n + 31) / 32 * 32;                   // doubles between the vectors of consecutive loops (256-byte aligned: the vector kernels use 16-byte accesses)
+    const size_t tot = (size_t)vs * NR;
+    c->wx.reserve(tot); c->wr.reserve(tot); c->wz.reserve(tot); c->wp.reserve(tot); c->wAp.reserve(tot); c->wb.reserve(tot); c->wf.reserve(tot);
+    EventTimer tsetup(s);
+    prepare_matrix_free(c);
+    const bool masked = !c->fixedVars.empty();
+    const uint8_t *maskPtr = masked ? c->dFixedMask.p : nullptr;
+    if (io && io->cstrains) {               // constantStrainLoad vectors, formed where they are needed
+        const int fl = c->dim() * (c->dim() + 1) / 2;
+        for (int k2 = 0; k2 < NR; ++k2)
+            if (!constant_strain_load_device(c, io->cstrains + (size_t)k2 * fl, c->wf.p + (size_t)k2 * vs)) throw Error(MFH_ERR_STATE, "constant-strain loads need the cluster operator");
+    } else
+        for (int k2 = 0; k2 < NR; ++k2)
+            MFH_HIP(hipMemcpyAsync(c->wf.p + (size_t)k2 * vs, f + (size_t)k2 * hostStride, n * sizeof(double), hipMemcpyHostToDevice, s));
+    MFH_HIP(hipMemcpyAsync(c->wb.p, c->wf.p, tot * sizeof(double), hipMemcpyDeviceToDevice, s));
+    // b = f - K ubar on the free variables (SparseMatrices.hh:2457-2470,2526-2535): the same lift for every right-hand side
+    if (c->anyFixedNonzero && !c->solveHomogeneous) {
+        c->wu0.alloc(n);
+        c->wu0.zero(s);
+        k::launch_scatter_values((int64_t)c->fixedVars.size(), c->dFixedIdx.p, c->dFixedVal.p, c->wu0.p, n, s);
+        apply_operator(c, false, c->wu0.p, c->wAp.p, nullptr);
+        for (int k2 = 0; k2 < NR; ++k2) k::launch_axpby(n, -1.0, c->wAp.p, 1.0, c->wb.p + (size_t)k2 * vs, s);
+    }
+    if (masked) for (int k2 = 0; k2 < NR; ++k2) k::launch_mask(n, c->dFixedMask.p, c->wb.p + (size_t)k2 * vs, s);
+    double bb[6] = {0, 0, 0, 0, 0, 0};
+    for (int k2 = 0; k2 < NR; ++k2) bb[k2] = device_dot(c, n, c->wb.p + (size_t)k2 * vs, c->wb.p + (size_t)k2 * vs);      // (uses c->stop: before the control blocks are set up)
+    const int checkEvery = std::min(c->checkEvery, 2);       // a V-cycle is milliseconds long and tens of them are needed: short blocks
+    const size_t scalStride = ((size_t)maxit + (size_t)checkEvery + 2) * 4;
+    c->scal.alloc(scalStride * NR);
+    c->scal.zero(s);
+    c->stop.alloc(4 * (size_t)NR);
+    double hstop[24] = {0};
+    bool anyWork = false;
+    for (int k2 = 0; k2 < NR; ++k2) { hstop[4 * k2] = rtol * rtol * bb[k2]; anyWork |= bb[k2] > 0; }
+    MFH_HIP(hipMemcpyAsync(c->stop.p, hstop, 4 * NR * sizeof(double), hipMemcpyHostToDevice, s));
+    const double setupMs = tsetup.stop();
+    ResidualWatch watch[8];             // (no stagnation rule in this loop)
+    for (int k2 = 0; k2 < NR; ++k2) { watch[k2].threshold = hstop[4 * k2]; if (!(bb[k2] > 0)) watch[k2].itConv = 0; }
+    double solveMs = 0;
+    bool usedGraph = false;
+    int itRun = 0;
+    auto vec = [&](DBuf<double> &b, int k2) { return b.p + (size_t)k2 * vs; };
+    auto sck = [&](int k2) { return c->scal.p + (size_t)k2 * scalStride; };
+    auto stk = [&](int k2) { return c->stop.p + 4 * (size_t)k2; };
+    if (!anyWork) MFH_HIP(hipMemsetAsync(c->wx.p, 0, tot * sizeof(double), s));
+    else {
+        EventTimer tsolve(s);
+        // x = 0, r = b, z = M^-1 r (one V-cycle for all), p = z; {r.z, -, r.r}_0 per loop. A zero right-hand side starts converged (0 <= 0).
+        for (int k2 = 0; k2 < NR; ++k2) {
+            k::launch_pcg_init(d, c->sym.nRows, c->dDinv.p, vec(c->wb, k2), vec(c->wx, k2), vec(c->wr, k2), vec(c->wz, k2), vec(c->wp, k2), sck(k2), s);
+            MFH_HIP(hipMemsetAsync(sck(k2), 0, sizeof(double), s));
+        }
+        mg_precond_batch(c, NR, c->wr.p, c->wz.p, vs, nullptr, 0, -1, nullptr);
+        for (int k2 = 0; k2 < NR; ++k2) {
+            k::launch_mg_rz(n, vec(c->wr, k2), vec(c->wz, k2), maskPtr, sck(k2), -1, nullptr, nullptr, s);
+            MFH_HIP(hipMemcpyAsync(vec(c->wp, k2), vec(c->wz, k2), n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+        const k::SpmvMfArgs mfa = spmv_mf_cluster_args(c, masked);
+        const double mgZs = c->mgFuse ? mg_fuse_scale(c) : 0.0;
+        const float *dinv32 = mgZs > 0 ? smoother_dinv32(c) : nullptr;
+        auto enqueue = [&](int itLocal) {   // one iteration of every loop; `itLocal` is relative to the iteration bases stop[4 k + 3]
+            for (int k2 = 0; k2 < NR; ++k2) {
+                k::launch_spmv_mf_cluster(mfa, vec(c->wp, k2), vec(c->wAp, k2), nullptr, sck(k2), itLocal, stk(k2), true, s);
+                if (mgZs > 0) k::launch_pcg_update_presmooth(d, c->sym.nRows, c->dDinv.p, dinv32, vec(c->wAp, k2), vec(c->wr, k2), vec(c->wz, k2), mgZs, sck(k2), itLocal, stk(k2), s);
+                else k::launch_pcg_update_noz(d, c->sym.nRows, vec(c->wAp, k2), vec(c->wr, k2), sck(k2), itLocal, stk(k2), s);
+            }
+            const MgFuse fz{mgZs > 0, mgZs > 0 ? c->scal.p : nullptr, maskPtr};      // (see solve_one_classic)
+            mg_precond_batch(c, NR, c->wr.p, c->wz.p, vs, c->scal.p, (int64_t)scalStride, itLocal, c->stop.p, &fz);
+            for (int k2 = 0; k2 < NR; ++k2) {
+                if (!(mgZs > 0)) k::launch_mg_rz(n, vec(c->wr, k2), vec(c->wz, k2), maskPtr, sck(k2), itLocal, sck(k2), stk(k2), s);
+                k::launch_pcg_direction(n, vec(c->wz, k2), vec(c->wp, k2), vec(c->wx, k2), sck(k2), itLocal, stk(k2), s);
+            }
+        };
+        IterationGraph graph(s, c->useGraph && checkEvery > 1, [&] {
+            for (int j = 0; j < checkEvery; ++j) enqueue(j);
+            for (int k2 = 0; k2 < NR; ++k2) k::launch_advance_base(stk(k2), checkEvery, s);
+        });
+        usedGraph = (bool)graph;
+        std::vector<double> hs;
+        int it = 0, lastChecked = 0, nConv = 0;
+        for (int k2 = 0; k2 < NR; ++k2) nConv += watch[k2].itConv >= 0;
+        while (nConv < NR && it < maxit) {
+            if (graph) { graph.launch(s); it += checkEvery; }
+            else {
+                const int itEnd = std::min(maxit, it + checkEvery);
+                for (; it < itEnd; ++it) enqueue(it);
+            }
+            const size_t per = (size_t)(it - lastChecked + 1) * 4;
+            hs.resize(per * NR);
+            for (int k2 = 0; k2 < NR; ++k2)
+                MFH_HIP(hipMemcpyAsync(hs.data() + per * k2, sck(k2) + (size_t)lastChecked * 4, per * sizeof(double), hipMemcpyDeviceToHost, s));
+            MFH_HIP(hipStreamSynchronize(s));
+            for (int k2 = 0; k2 < NR; ++k2)
+                for (int q = lastChecked; watch[k2].itConv < 0 && q <= std::min(it, maxit); ++q) {
+                    const double *sc = &hs[per * k2 + (size_t)(q - lastChecked) * 4];       // {r.z, p.Kp, r.r, -}
+                    nConv += watch[k2].judge(q, sc[2], q < it, sc[1]);
+                }
+            lastChecked = it;
+        }
+        itRun = it;
+        solveMs = tsolve.stop();
+    }
+    // u = x + ubar (SparseMatrices.hh:2592-2605); true residual on the free variables: || mask(f - K u) || / ||b||
+    double tr[6] = {0, 0, 0, 0, 0, 0};
+    for (int k2 = 0; k2 < NR; ++k2) {
+        if (masked && !c->solveHomogeneous) k::launch_scatter_values((int64_t)c->fixedVars.size(), c->dFixedIdx.p, c->dFixedVal.p, vec(c->wx, k2), n, s);
+        if (bb[k2] > 0) {
+            apply_operator(c, false, vec(c->wx, k2), c->wAp.p, nullptr);
+            k::launch_axpby(n, 1.0, vec(c->wf, k2), -1.0, c->wAp.p, s);
+            if (masked) k::launch_mask(n, c->dFixedMask.p, c->wAp.p, s);
+            tr[k2] = device_dot(c, n, c->wAp.p, c->wAp.p);
+        }
+        if (io && io->uNodes) {             // dofToNodeField (LinearElasticity.hh:664-677) on the device, then one download per nodal field
+            const int64_t nn = c->mesh.nNode * (int64_t)d;
+            const double *src = vec(c->wx, k2);
+            if (!c->dofForNode.empty()) {
+                c->wNodeField.reserve((size_t)nn * 2);
+                double *dst = c->wNodeField.p + (size_t)(k2 & 1) * nn;     // two halves: the gather of field k + 1 does not wait for the download of field k
+                k::launch_pack_rows(c->mesh.nNode, d, device_dof_map(c), src, dst, s);
+                src = dst;
+            }
+            MFH_HIP(hipMemcpyAsync(io->uNodes + (size_t)k2 * io->nodeStride, src, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, s));
+        } else
+            MFH_HIP(hipMemcpyAsync(u + (size_t)k2 * hostStride, vec(c->wx, k2), n * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    MFH_HIP(hipStreamSynchronize(s));
+    report_batch(NR, watch, bb, tr, itRun, maxit, rtol, solveMs, setupMs, usedGraph, infos);
 }
 
 // The right-hand side of solve_one may already lie on the device, in c->wf (f == nullptr; neumannLoad formed by a kernel, mfh_simulator.cpp): the
@@ -1487,6 +1795,23 @@ mfh_status mfh_debug_apply_precond(mfh_ctx *c, int32_t nr, const double *R, doub
     } else
         throw Error(MFH_ERR_UNSUPPORTED, "mfh_debug_apply_precond: block-Jacobi has no batched application (the batched PCG folds it into its vector updates)");
     MFH_CATCH(c)
+}
+
+// test hook: a synthetic residual history through the stopping rule of the loops above (no context: the message goes to the caller's buffer)
+mfh_status mfh_debug_pcg_watch(int64_t n, const double *rr, const double *pKp, const uint8_t *known, double threshold, int32_t window, int64_t lastComplete,
+                               int64_t *convergedAt, char *msg, int64_t msgCap) {
+    if (n < 0 || !rr || !pKp || !known || !convergedAt) return MFH_ERR_INVALID;
+    *convergedAt = -1;
+    if (msg && msgCap > 0) msg[0] = 0;
+    try {
+        ResidualWatch w{threshold, window};
+        for (int64_t q = 0; q < n && w.itConv < 0; ++q) w.judge((int)q, rr[q], known[q] && q <= lastComplete, pKp[q]);
+        *convergedAt = w.itConv;
+    } catch (const Error &e) {
+        if (msg && msgCap > 0) snprintf(msg, (size_t)msgCap, "%s", e.what());
+        return e.code;
+    }
+    return MFH_OK;
 }
 
 }   // extern "C"
