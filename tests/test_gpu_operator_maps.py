@@ -14,6 +14,7 @@ import scipy.sparse as sp
 import meshfem_amd as M
 from meshfem_amd import _lib as L
 from meshfem_amd import grid
+from element_integrals_util import MODES, material as _material, perturbed   # one copy, shared with test_gpu_element_integrals.py
 from oracle import c_oracle as CO
 from oracle import meshfem_oracle as O
 
@@ -23,7 +24,6 @@ Y_RTOL = 1e-12
 DOT_RTOL = 1e-12
 BATCHES = {3: (1, 2, 6), 2: (1, 3)}
 UNSUPPORTED = {3: (3, 4, 5), 2: (2, 6)}
-MODES = ("iso", "iso_field", "general", "ortho_field", "general_field", "ortho")   # material modes 0..5 of the context
 
 
 def _mesh(dim, small=False, seed=0):
@@ -33,42 +33,7 @@ def _mesh(dim, small=False, seed=0):
         V, T = grid.grid_tet_mesh(*((2, 2, 1) if small else (6, 5, 4)))
     else:
         V, T = grid.grid_tri_mesh(*((3, 2) if small else (20, 16)))
-    V = np.array(V, dtype=np.float64)
-    lo, hi = V.min(axis=0), V.max(axis=0)
-    inner = np.all((V > lo + 1e-9) & (V < hi - 1e-9), axis=1)
-    rng = np.random.default_rng(seed + dim)
-    V[inner] += 0.04 * rng.uniform(-1.0, 1.0, size=(inner.sum(), dim))
-    return V, np.asarray(T)
-
-
-def _spd(rng, fl):
-    A = rng.normal(size=(fl, fl))
-    return A @ A.T + fl * np.eye(fl)
-
-
-def _material(mode, dim, n_elem, seed=0):
-    """(setter of the context, D per element or one D for the oracle)."""
-    rng = np.random.default_rng(100 + seed)
-    fl = dim * (dim + 1) // 2
-    if mode == "iso":
-        return (lambda c: c.material_isotropic(200.0, 0.35)), O.ElasticityTensor.isotropic(dim, 200.0, 0.35).D
-    if mode == "iso_field":
-        E, nu = rng.uniform(50.0, 300.0, n_elem), rng.uniform(0.1, 0.4, n_elem)
-        return (lambda c: c.material_iso_field(E, nu)), np.stack([O.ElasticityTensor.isotropic(dim, a, b).D for a, b in zip(E, nu)])
-    if mode == "general":
-        D = _spd(rng, fl)
-        return (lambda c: c.material_const(D)), D
-    if mode == "general_field":
-        D = np.stack([_spd(rng, fl) for _ in range(n_elem)])
-        return (lambda c: c.material_tensor_field(D)), D
-    if mode == "ortho_field":
-        P = grid.synthetic_orthotropic_field(n_elem, dim, seed=seed)
-        mk = O.ElasticityTensor.orthotropic3d if dim == 3 else O.ElasticityTensor.orthotropic2d
-        return (lambda c: c.material_ortho_field(P)), np.stack([mk(*p).D for p in P])
-    assert mode == "ortho"
-    D = (O.ElasticityTensor.orthotropic3d(100.0, 150.0, 120.0, 0.2, 0.25, 0.3, 40.0, 50.0, 60.0) if dim == 3
-         else O.ElasticityTensor.orthotropic2d(100.0, 150.0, 0.25, 40.0)).D
-    return (lambda c: c.material_const(D)), D
+    return perturbed(V, 0.04, seed), np.asarray(T)
 
 
 def _context(V, T, deg, set_material, periodic, options=()):
