@@ -56,8 +56,17 @@ enum { MFH_NEUMANN_TRACTION = 0, MFH_NEUMANN_PRESSURE = 1, MFH_NEUMANN_FORCE = 2
  * (PoissonMesh::applyBoundaryConditions, Poisson.hh:57-89), `mfh_sim_solve(f = NULL)` solves with a zero
  * right-hand side (Poisson.hh:91-117).
  *   MFH_OP_LAPLACIAN  int grad phi_i . grad phi_j   (Laplacian::construct, Laplacian.hh:27-57; full degree)
- *   MFH_OP_MASS       int phi_i phi_j               (MassMatrix::construct, MassMatrix.hh:50-86; full degree, not lumped) */
-enum { MFH_OP_ELASTICITY = 0, MFH_OP_LAPLACIAN = 1, MFH_OP_MASS = 2 };
+ *   MFH_OP_MASS       int phi_i phi_j               (MassMatrix::construct, MassMatrix.hh:50-86; not lumped)
+ *   MFH_OP_MASS_VECTOR  the mass matrix on interleaved displacement vectors (MassMatrix::construct_vector_valued, MassMatrix.hh:131-147):
+ *                     dim variables per DoF like elasticity, block (i, j) = m_ij I_dim. ONE double per block is stored and assembled
+ *                     (pattern, gather lists and values are MFH_OP_MASS's); mfh_apply_K / mfh_dev_spmv / mfh_solve multiply through
+ *                     k_spmv_kron (8 bytes of matrix per block instead of 8 dim^2), Jacobi-preconditioned (the scalar diagonal for all
+ *                     components); mfh_export_upper_triplets gives the reference's entries (dim i + c, dim j + c, m_ij), c < dim -- the
+ *                     components do not couple, so this is NOT the dense triangle of the blocks. A request for the two-level or
+ *                     multigrid preconditioner falls back to Jacobi with a note (mfh_precond_info), as for the scalar operators; the
+ *                     matrix-free operator does not apply; row-partitioned contexts refuse the operator.
+ * The degree of the three scalar-valued operators follows mfh_set_operator_degree. */
+enum { MFH_OP_ELASTICITY = 0, MFH_OP_LAPLACIAN = 1, MFH_OP_MASS = 2, MFH_OP_MASS_VECTOR = 3 };
 
 /* preconditioners */
 enum {
@@ -368,8 +377,28 @@ mfh_status mfh_mutual_energy_differential(mfh_ctx* ctx, const double* w, double*
 /* Select the operator (default MFH_OP_ELASTICITY). Keeps mesh, DoF map, pattern and gather lists; drops the
  * assembled values and the fixed variables (their numbering depends on the block size). */
 mfh_status mfh_set_operator(mfh_ctx* ctx, int32_t op);
-/* PoissonMesh::gradUAverage (Poisson.hh:121-131): per-element average gradient of a scalar nodal field */
+/* PoissonMesh::gradUAverage (Poisson.hh:121-131): per-element average gradient of a scalar nodal field (any operator may be selected:
+ * this is the `gradient` of the reference's differential_operators module) */
 mfh_status mfh_average_gradient(mfh_ctx* ctx, const double* uNodes /* nNode */, double* grad /* nElem x dim */);
+/* Forced degree of MFH_OP_LAPLACIAN / MFH_OP_MASS / MFH_OP_MASS_VECTOR: 0 (default) the mesh's own, 1 = degree 1 on the vertices of a quadratic
+ * mesh (Laplacian::construct<1>, MassMatrix::construct<1>, NodeGetter<1,...> MassMatrix.hh:38-46; vertex node = vertex, FEMMesh.inl:17-37). The
+ * operators are then assembled from the corner nodes of every element on a P1 VIEW of the context: a pattern of its own on the vertex graph,
+ * the context's device vertex positions, the corner columns of its node table and its element records -- no second mesh build. While the
+ * view is in force mfh_symbolic / mfh_symbolic_sizes / mfh_assemble / mfh_matrix_info / mfh_matrix_storage / mfh_export_* / mfh_apply_K /
+ * mfh_dev_spmv / mfh_element_stiffness /
+ * mfh_fix_variables / mfh_clear_fixed / mfh_solve / mfh_solve_batch / mfh_mass_lumped work on it (nVert rows, vectors of nVert or dim nVert doubles);
+ * selecting MFH_OP_ELASTICITY is MFH_ERR_STATE. Back at 0 the full-degree pattern and values are as they were. A no-op on linear meshes;
+ * needs a mesh from mfh_mesh_build with the identity DoF map, all rows owned. */
+mfh_status mfh_set_operator_degree(mfh_ctx* ctx, int32_t degree /* 0 | 1 */);
+/* Lumped mass matrix (MassMatrix::construct(..., lumped = true), MassMatrix.hh:104-127): the row sums of the FULL symmetric mass matrix of the
+ * operator (MFH_OP_MASS: nNode values of the degree view; MFH_OP_MASS_VECTOR: dim times that, every row sum repeated dim times), summed on the
+ * device over the stored values (k_row_sums; with the upper-triangle storage an off-diagonal entry counts for both rows, :113-117).
+ * onDevice != 0: diagOut is a device pointer. */
+mfh_status mfh_mass_lumped(mfh_ctx* ctx, double* diagOut, int32_t onDevice);
+/* `divergence` of the reference's differential_operators module (differential_operators.cc:79-88): out[n] = sum over the elements e that
+ * contain node n of v_e . int_e grad phi_n, for a per-element vector field [nElem x dim]. Linear meshes only, like the reference
+ * (MFH_ERR_UNSUPPORTED on quadratic ones). Gather form on the device, no atomics (k_divergence). */
+mfh_status mfh_divergence(mfh_ctx* ctx, const double* elemVectors /* nElem x dim */, double* out /* nNode */);
 
 /* ---------------------------------------------------------------- multi-GPU solve (one process per GPU)
  * The reference is single-process (TBB, Parallelism.hh:31-43): these entry points have no counterpart to cite beyond the

@@ -12,7 +12,7 @@ OK, ERR_INVALID, ERR_STATE, ERR_HIP, ERR_NOT_CONVERGED, ERR_UNSUPPORTED = range(
 ASSEMBLE_GATHER, ASSEMBLE_ATOMIC = 0, 1
 NEUMANN_TRACTION, NEUMANN_PRESSURE, NEUMANN_FORCE = 0, 1, 2
 PRECOND_BLOCK_JACOBI, PRECOND_JACOBI, PRECOND_NONE, PRECOND_TWO_LEVEL, PRECOND_MULTIGRID, PRECOND_AUTO = 0, 1, 2, 3, 4, 5
-OP_ELASTICITY, OP_LAPLACIAN, OP_MASS = 0, 1, 2
+OP_ELASTICITY, OP_LAPLACIAN, OP_MASS, OP_MASS_VECTOR = 0, 1, 2, 3
 SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED = 1, 2, 4
 
 
@@ -124,6 +124,9 @@ PROTOTYPES = {
     "mfh_set_operator": (_i32, [_P, _i32]),
     "mfh_matrix_set_upper_triplets": (_i32, [_P, _i64, _i64, _P, _P, _P]),
     "mfh_average_gradient": (_i32, [_P, _P, _P]),
+    "mfh_set_operator_degree": (_i32, [_P, _i32]),
+    "mfh_mass_lumped": (_i32, [_P, _P, _i32]),
+    "mfh_divergence": (_i32, [_P, _P, _P]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),

@@ -24,6 +24,7 @@ class Context:
         self.host_only = device == -1
         self.dim = self.deg = None
         self.op = L.OP_ELASTICITY
+        self.op_degree = 0
         self.external = False
         # experiments: MFH_OPTIONS="name=value,name=value" presets mfh_set_option on every new context (A/B runs of the
         # measurement scripts without editing them); unset in normal use
@@ -70,6 +71,7 @@ class Context:
         self.npe, self.npbe = a.value, b.value
         self.n_dof = self.n_node
         self.external = False
+        self.op_degree = 0
 
     def elem_nodes(self):
         out = np.empty((self.n_elem, self.npe), dtype=np.int32)
@@ -216,9 +218,9 @@ class Context:
 
     @property
     def bs(self):
-        """Variables per DoF = block edge of K: dim for elasticity, 1 for the scalar operators and for
-        caller-supplied matrices."""
-        return self.dim if (self.op == L.OP_ELASTICITY and not self.external) else 1
+        """Variables per DoF = block edge of K: dim for elasticity and the vector-valued mass operator, 1 for
+        the scalar operators and for caller-supplied matrices."""
+        return self.dim if (self.op in (L.OP_ELASTICITY, L.OP_MASS_VECTOR) and not self.external) else 1
 
     def matrix_set_upper_triplets(self, n, i, j, v):
         """SPSDSystem(K) for a caller-supplied SPD matrix (upper-triangle triplets, repeats summed)."""
@@ -231,10 +233,43 @@ class Context:
         self.dim = 1
 
     def set_operator(self, op):
-        """OP_ELASTICITY (default) | OP_LAPLACIAN | OP_MASS: same mesh, pattern and kernels, 1x1 blocks
-        for the scalar operators (Laplacian.hh, MassMatrix.hh, Poisson.hh)."""
+        """OP_ELASTICITY (default) | OP_LAPLACIAN | OP_MASS | OP_MASS_VECTOR: same mesh, pattern and kernels, 1x1
+        blocks for the scalar operators (Laplacian.hh, MassMatrix.hh, Poisson.hh); OP_MASS_VECTOR is the mass matrix
+        on interleaved displacement vectors (MassMatrix::construct_vector_valued), one stored value per block."""
         self._ck(self.lib.mfh_set_operator(self.h, int(op)))
         self.op = int(op)
+
+    def set_operator_degree(self, degree):
+        """0: the operators have the mesh's degree (default). 1: OP_LAPLACIAN / OP_MASS / OP_MASS_VECTOR on a quadratic
+        mesh are the degree-1 operators on its vertices (Laplacian::construct<1>, MassMatrix::construct<1>); matrix_info,
+        the exports, apply_K, fix_variables, solve and mass_lumped then work on n_vert rows. No effect on linear meshes."""
+        self._ck(self.lib.mfh_set_operator_degree(self.h, int(degree)))
+        if self.deg == 2:
+            if int(degree) == 1 and self.op_degree != 1:
+                self._n_dof_full = self.n_dof
+                self.n_dof = self.n_vert
+            elif int(degree) == 0 and self.op_degree == 1:
+                self.n_dof = self._n_dof_full
+            self.op_degree = int(degree)
+
+    def mass_lumped(self):
+        """Row sums of the full symmetric mass matrix of OP_MASS (n_dof values) or OP_MASS_VECTOR (every row sum
+        repeated dim times), summed on the device over the stored values (mfh_mass_lumped)."""
+        if not self._assembled_info():
+            self.assemble()
+        out = np.empty(self.bs * self.matrix_info()[0])              # rows of the degree view in force, as the library counts them
+        self._ck(self.lib.mfh_mass_lumped(self.h, ptr(out), 0))
+        return out
+
+    def divergence(self, elem_vectors):
+        """out[n] = sum over the elements e containing node n of v_e . int_e grad phi_n (the reference's
+        differential_operators.divergence); linear meshes only."""
+        v = as_f64(elem_vectors)
+        if v.shape != (self.n_elem, self.dim):
+            raise ValueError("expected one %d-vector per element" % self.dim)
+        out = np.empty(self.n_node)
+        self._ck(self.lib.mfh_divergence(self.h, ptr(v), ptr(out)))
+        return out
 
     def precond_choice(self):
         """(kind, chosen automatically?, stretch of the mesh the choice looked at): mfh_precond_choice. With PRECOND_AUTO the choice is made now."""
@@ -303,7 +338,8 @@ class Context:
 
     def element_stiffness(self, first=0, count=None):
         count = self.n_elem - first if count is None else count
-        ks = self.npe * self.bs
+        npe = self.dim + 1 if self.op_degree == 1 else self.npe       # the forced-degree-1 view has the corner nodes only
+        ks = npe * (1 if self.op == L.OP_MASS_VECTOR else self.bs)    # (OP_MASS_VECTOR: the scalar element mass matrices it is assembled from)
         out = np.empty((count, ks, ks))
         self._ck(self.lib.mfh_element_stiffness(self.h, int(first), int(count), ptr(out)))
         return out

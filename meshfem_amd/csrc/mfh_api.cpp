@@ -101,6 +101,9 @@ void clear_fixed(mfh_ctx *c) {
 void upload_mesh(mfh_ctx *c, bool deviceTables) {
     double t0 = now_ms();
     c->autoStretch = -1.0;           // MFH_PRECOND_AUTO looks at the new vertices
+    drop_p1_view(c);                 // a forced-degree-1 view belongs to the previous mesh
+    c->opDegree = 0;
+    c->nodePairsValid = false;
     if (!c->hostOnly && !deviceTables) {      // (deviceTables: the device topology has written both from the vertices)
         require_device(c);
         MFH_HIP(hipSetDevice(c->device));
@@ -132,6 +135,29 @@ void set_isotropic(mfh_ctx *c, double E, double nu) {
     c->geoValid = false;
     c->hGeoValid = false;
     invalidate_matrix(c);
+}
+
+// ---- forced-degree-1 view (mfh_ctx::p1)
+void drop_p1_view(mfh_ctx *c) {
+    if (c->p1) { mfh_destroy(c->p1); c->p1 = nullptr; }
+    c->p1GeoGen = -1;
+}
+
+// The view in force, ready for use: it reads the parent's element records (k_geometry's output does not depend on the degree: gradients of the
+// barycentric coordinates and the volume come from the corner nodes) and vertex positions where they lie; matrices assembled from records
+// that have been rewritten since (new vertices) are dropped.
+mfh_ctx *p1_view(mfh_ctx *c) {
+    if (!c || c->opDegree != 1 || !c->p1) return nullptr;
+    mfh_ctx *v = c->p1;
+    if (!c->hostOnly) {
+        ensure_geometry(c);
+        v->dGeo.borrow(c->dGeo.p, c->dGeo.n);
+        v->geoStride = c->geoStride;
+        v->geoValid = true;
+        if (v->dVertPos.borrowed || !v->dVertPos.p) v->dVertPos.borrow(c->dVertPos.p, (size_t)v->mesh.nNode * v->mesh.dim);
+        if (c->p1GeoGen != c->geoGen) { invalidate_matrix(v); c->p1GeoGen = c->geoGen; }
+    }
+    return v;
 }
 
 void ensure_pass_events(mfh_ctx *c) {
@@ -190,6 +216,7 @@ void finish_geometry(mfh_ctx *c) {
                                          (c->matMode == 1 ? "need E > 0 and -1 < nu < 1/2, nu < 1 in plane stress" : "compliance matrix not positive definite") + ").");
     c->geoValid = true;
     c->hGeoValid = false;
+    ++c->geoGen;
 }
 
 const std::vector<double> &host_geo(mfh_ctx *c) {
@@ -411,6 +438,7 @@ k::SpmvArgs spmv_args(mfh_ctx *c, bool masked) {
     a.colIdx = c->dColIdx.p; a.vals = c->dVals.p; a.chunkSlots = c->sym.spmvChunkSlots;
     a.fixedMask = masked ? c->dFixedMask.p : nullptr;
     a.xcd = c->xcdSwizzle == 1;
+    a.kron = c->kron() ? 1 : 0;
     return a;
 }
 
@@ -528,6 +556,7 @@ void apply_operator(mfh_ctx *c, bool masked, const double *x, double *y, double 
         else if (c->mfModeEff() >= 2 && c->op == MFH_OP_ELASTICITY) k::launch_spmv_mf2(spmv_mf_args(c, masked), x, y, dotOut, nullptr, 0, nullptr, false, c->stream);
         else k::launch_spmv_mf(spmv_mf_args(c, masked), x, y, dotOut, nullptr, 0, nullptr, false, c->stream);
     } else if (c->upperOnly) {
+        require(!c->kron(), MFH_ERR_UNSUPPORTED, "the product with the vector-valued mass matrix (k_spmv_kron) needs both triangles of M: set option matrix_storage to 0");
         // the stored triangle serves both halves of the product (k_spmv_sym: transposed parts added with global atomics; measured slower than
         // k_spmv on both triangles, DESIGN 4.4: the PCG keeps asking for the full storage, this serves mfh_apply_K / mfh_dev_spmv)
         // k_spmv_sym adds in arrival order: not run-to-run reproducible, which option "deterministic" promises for every operator
@@ -616,7 +645,8 @@ void ensure_precond(mfh_ctx *c) {
     const int d = c->bs();
     c->dDinv.alloc((size_t)c->sym.nRows * (d * (d + 1) / 2));   // symmetric-packed inverse diagonal blocks
     k::launch_extract_diag_inv(d, c->sym.nRows, c->dRowPtr.p, c->dColIdx.p, c->dVals.p, c->dFixedMask.p,
-                               (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? MFH_PRECOND_BLOCK_JACOBI : c->precond, c->dDinv.p, c->stream);
+                               (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? MFH_PRECOND_BLOCK_JACOBI : c->precond, c->dDinv.p, c->stream,
+                               c->kron());
     c->dinvValid = true;
     c->dinv32Valid = false;
 }
@@ -684,7 +714,8 @@ bool ensure_twolevel(mfh_ctx *c) {
     if (c->tl.valid) return true;
     c->precondNote.clear();
     if (c->op != MFH_OP_ELASTICITY || c->external) {
-        c->precondNote = "two-level preconditioner is built on rigid-body modes (elasticity only): using Jacobi";
+        c->precondNote = c->kron() ? "two-level preconditioner is built on rigid-body modes (elasticity only; refused for the vector-valued mass operator): using Jacobi"
+                                   : "two-level preconditioner is built on rigid-body modes (elasticity only): using Jacobi";
         return false;
     }
     const HostMesh &m = c->mesh;
@@ -1016,6 +1047,17 @@ void elem_D(const mfh_ctx *c, const double *g, double *D) {
 using namespace mfhi;
 
 // =================================================================================================
+// An entry point that follows the forced-degree-1 view: when the view is in force the call is made on it and its error message becomes the caller's
+template <class F> static bool follow_view(mfh_ctx *c, mfh_status &st, F &&call) {
+    if (!c || c->opDegree != 1 || !c->p1) return false;
+    mfh_ctx *v = nullptr;
+    try { mfh::PoolScope poolScope(c->stream, c->dist.commStream, c->hostOnly ? 0 : 1); v = mfhi::p1_view(c); }
+    catch (const mfh::Error &e) { c->err = e.what(); st = e.code; return true; }
+    st = call(v);
+    if (st != MFH_OK) c->err = v->err;
+    return true;
+}
+
 extern "C" {
 
 const char *mfh_version(void) { return "meshfem_hip 0.1 (gfx950)"; }
@@ -1074,6 +1116,7 @@ void mfh_destroy(mfh_ctx *c) {
         for (auto &e : c->passEv) if (e) (void)hipEventDestroy(e);
         dist_detach(c);
         destroy_multigrid(c);
+        drop_p1_view(c);
         for (auto &e : c->dist.ev) if (e) (void)hipEventDestroy(e);
         for (auto &P : c->dist.prof) for (auto &e : P.ev) if (e) (void)hipEventDestroy(e);
         if (c->dist.commStream && !c->dist.commStreamBorrowed) (void)hipStreamDestroy(c->dist.commStream);
@@ -1376,6 +1419,7 @@ mfh_status mfh_material_get(mfh_ctx *c, int64_t elem, double *D) {
 // ---------------------------------------------------------------- DoF map
 mfh_status mfh_dof_map(mfh_ctx *c, const int32_t *dofForNode, int64_t nDoF) {
     MFH_TRY(c)
+    require(!(c && c->opDegree == 1 && c->p1), MFH_ERR_STATE, "a forced-degree-1 view is in force (mfh_set_operator_degree): it is defined for the identity DoF map");
     require(c && c->haveMesh, MFH_ERR_STATE, "no mesh set");
     c->nOwnedDoFSet = -1;
     if (!dofForNode) {
@@ -1441,6 +1485,7 @@ mfh_status mfh_get_dof_map(const mfh_ctx *c, int32_t *dofForNode, int64_t *nDoF)
 
 // ---------------------------------------------------------------- assembly
 mfh_status mfh_symbolic(mfh_ctx *c, int32_t withScatterMap) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_symbolic(v, withScatterMap); })) return st; }
     MFH_TRY(c)
     require(c && c->haveMesh, MFH_ERR_STATE, "no mesh set");
     ensure_symbolic(c, withScatterMap != 0);
@@ -1448,6 +1493,7 @@ mfh_status mfh_symbolic(mfh_ctx *c, int32_t withScatterMap) {
 }
 
 mfh_status mfh_symbolic_sizes(const mfh_ctx *c, int64_t *nChunk, int64_t *nContrib, int32_t *chunkSlots, int32_t *maxRowLen) {
+    if (c && c->opDegree == 1 && c->p1) return mfh_symbolic_sizes(c->p1, nChunk, nContrib, chunkSlots, maxRowLen);
     if (!c || !c->symValid) return MFH_ERR_STATE;
     if (nChunk) *nChunk = c->sym.nChunk();
     if (nContrib) *nContrib = c->sym.contribPtr.empty() ? 0 : c->sym.contribPtr.back();
@@ -1458,6 +1504,7 @@ mfh_status mfh_symbolic_sizes(const mfh_ctx *c, int64_t *nChunk, int64_t *nContr
 
 mfh_status mfh_symbolic_get(const mfh_ctx *c, int32_t *rowPtr, int32_t *colIdx, int32_t *chunkRow, int64_t *contribPtr,
                             uint32_t *contribCode, uint16_t *contribSlot, int32_t *scatterSlot) {
+    if (c && c->opDegree == 1 && c->p1) return mfh_symbolic_get(c->p1, rowPtr, colIdx, chunkRow, contribPtr, contribCode, contribSlot, scatterSlot);
     if (!c || !c->symValid) return MFH_ERR_STATE;
     const Symbolic &S = c->sym;
     if (rowPtr) std::copy(S.rowPtr.begin(), S.rowPtr.end(), rowPtr);
@@ -1477,6 +1524,7 @@ mfh_status mfh_symbolic_get(const mfh_ctx *c, int32_t *rowPtr, int32_t *colIdx, 
 }
 
 mfh_status mfh_assemble(mfh_ctx *c, int32_t mode) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_assemble(v, mode); })) return st; }
     MFH_TRY(c)
     require(c && c->haveMesh, MFH_ERR_STATE, "no mesh set");
     require(mode == MFH_ASSEMBLE_GATHER || mode == MFH_ASSEMBLE_ATOMIC, MFH_ERR_INVALID, "bad assembly mode");
@@ -1503,6 +1551,7 @@ mfh_status mfh_assemble(mfh_ctx *c, int32_t mode) {
 }
 
 mfh_status mfh_matrix_info(const mfh_ctx *c, int64_t *nBlockRows, int64_t *nBlockCols, int64_t *nnzBlocks) {
+    if (c && c->opDegree == 1 && c->p1) return mfh_matrix_info(c->p1, nBlockRows, nBlockCols, nnzBlocks);
     if (!c || !c->symValid) return MFH_ERR_STATE;
     if (nBlockRows) *nBlockRows = c->sym.nRows;
     if (nBlockCols) *nBlockCols = c->sym.nCols;
@@ -1511,6 +1560,7 @@ mfh_status mfh_matrix_info(const mfh_ctx *c, int64_t *nBlockRows, int64_t *nBloc
 }
 
 mfh_status mfh_matrix_storage(const mfh_ctx *c, int32_t *upperOnly, int64_t *storedBlocks) {
+    if (c && c->opDegree == 1 && c->p1) return mfh_matrix_storage(c->p1, upperOnly, storedBlocks);
     if (!c || !c->symValid) return MFH_ERR_STATE;
     if (upperOnly) *upperOnly = c->upperOnly ? 1 : 0;
     if (storedBlocks) *storedBlocks = c->sym.nnzb;
@@ -1590,7 +1640,23 @@ mfh_status mfh_matrix_set_upper_triplets(mfh_ctx *c, int64_t n, int64_t nnz, con
     MFH_CATCH(c)
 }
 
+// the stored blocks as dense bs x bs row-major blocks on the host (MFH_OP_MASS_VECTOR: m I expanded from the one stored value)
+static void fetch_dense_blocks(mfh_ctx *c, double *out) {
+    const Symbolic &S = c->sym;
+    const int d = c->bs(), nb = d * d, vb = c->vbs();
+    DBuf<double> aos;
+    aos.alloc((size_t)S.nnzb * vb * vb);
+    k::launch_untile_vals(vb, S.nnzb, c->dVals.p, aos.p, c->stream);
+    if (vb == d) { aos.download(out, (size_t)S.nnzb * nb, c->stream); return; }
+    std::vector<double> mv((size_t)S.nnzb);
+    aos.download(mv.data(), mv.size(), c->stream);
+    std::fill(out, out + (size_t)S.nnzb * nb, 0.0);
+    for (int64_t q = 0; q < S.nnzb; ++q)
+        for (int a2 = 0; a2 < d; ++a2) out[(size_t)q * nb + a2 * d + a2] = mv[(size_t)q];
+}
+
 mfh_status mfh_export_bsr(mfh_ctx *c, int32_t *rowPtr, int32_t *colIdx, double *vals) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_export_bsr(v, rowPtr, colIdx, vals); })) return st; }
     MFH_TRY(c)
     require(c && c->assembled, MFH_ERR_STATE, "matrix not assembled");
     ensure_host_colidx(c);
@@ -1598,13 +1664,7 @@ mfh_status mfh_export_bsr(mfh_ctx *c, int32_t *rowPtr, int32_t *colIdx, double *
     if (!c->upperOnly) {
         if (rowPtr) std::copy(S.rowPtr.begin(), S.rowPtr.end(), rowPtr);
         if (colIdx) std::copy(S.colIdx.begin(), S.colIdx.end(), colIdx);
-        if (vals && S.nnzb) {
-            const int nb = c->bs() * c->bs();
-            DBuf<double> aos;
-            aos.alloc((size_t)S.nnzb * nb);
-            k::launch_untile_vals(c->bs(), S.nnzb, c->dVals.p, aos.p, c->stream);
-            aos.download(vals, (size_t)S.nnzb * nb, c->stream);
-        }
+        if (vals && S.nnzb) fetch_dense_blocks(c, vals);
     } else {
         // upper-triangle storage: the export is K all the same. Row r = the transposes of the stored blocks (q, r), q < r, in
         // ascending q (= ascending column), then the stored blocks (r, c >= r).
@@ -1625,10 +1685,7 @@ mfh_status mfh_export_bsr(mfh_ctx *c, int32_t *rowPtr, int32_t *colIdx, double *
         std::vector<double> sv;
         if (vals && S.nnzb) {
             sv.resize((size_t)S.nnzb * nb);
-            DBuf<double> aos;
-            aos.alloc(sv.size());
-            k::launch_untile_vals(d, S.nnzb, c->dVals.p, aos.p, c->stream);
-            aos.download(sv.data(), sv.size(), c->stream);
+            fetch_dense_blocks(c, sv.data());
         }
         if (colIdx || vals) {
             std::vector<int64_t> cur(full.begin(), full.end() - 1);
@@ -1654,12 +1711,53 @@ mfh_status mfh_export_bsr(mfh_ctx *c, int32_t *rowPtr, int32_t *colIdx, double *
 }
 
 mfh_status mfh_export_upper_triplets(mfh_ctx *c, uint64_t *oi, uint64_t *oj, double *ov, uint64_t *nnz) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_export_upper_triplets(v, oi, oj, ov, nnz); })) return st; }
     MFH_TRY(c)
     require(c && c->assembled && nnz, MFH_ERR_STATE, "matrix not assembled");
     require(c->sym.nRows == c->sym.nCols, MFH_ERR_STATE, "triplet export needs a square matrix");
     ensure_host_colidx(c);
     const Symbolic &S = c->sym;
     const int d = c->bs(), nb = d * d;
+    if (c->kron()) {
+        // MassMatrix::construct_vector_valued (MassMatrix.hh:142-144): every scalar upper entry (i, j, v) becomes (d i + a, d j + a, v), a < d --
+        // the components do not couple, so no entry (d i + a, d j + b), a != b, exists. Column-major order as below: a column d j + a receives
+        // the rows d i + a in ascending i.
+        if (!(oi && oj && ov)) {
+            uint64_t cap = 0;
+            for (int64_t r = 0; r < S.nRows; ++r)
+                for (int32_t q = S.rowPtr[r]; q < S.rowPtr[r + 1]; ++q) cap += S.colIdx[q] >= r ? (uint64_t)d : 0;
+            *nnz = cap;
+            return MFH_OK;
+        }
+        std::vector<double> mv((size_t)S.nnzb);
+        {
+            DBuf<double> aos;
+            aos.alloc(mv.size());
+            k::launch_untile_vals(1, S.nnzb, c->dVals.p, aos.p, c->stream);
+            aos.download(mv.data(), mv.size(), c->stream);
+        }
+        const int64_t n = (int64_t)S.nRows * d;
+        std::vector<uint64_t> colPtr((size_t)n + 1, 0);
+        for (int64_t r = 0; r < S.nRows; ++r)
+            for (int32_t q = S.rowPtr[r]; q < S.rowPtr[r + 1]; ++q) {
+                const int64_t col = S.colIdx[q];
+                if (col < r || mv[(size_t)q] == 0.0) continue;      // pruneTol = 0, as below
+                for (int a2 = 0; a2 < d; ++a2) ++colPtr[(size_t)(col * d + a2) + 1];
+            }
+        for (int64_t j2 = 0; j2 < n; ++j2) colPtr[(size_t)j2 + 1] += colPtr[(size_t)j2];
+        require(*nnz >= colPtr[(size_t)n], MFH_ERR_INVALID, "triplet buffers too small");
+        *nnz = colPtr[(size_t)n];
+        for (int64_t r = 0; r < S.nRows; ++r)
+            for (int32_t q = S.rowPtr[r]; q < S.rowPtr[r + 1]; ++q) {
+                const int64_t col = S.colIdx[q];
+                if (col < r || mv[(size_t)q] == 0.0) continue;      // pruneTol = 0, as below
+                for (int a2 = 0; a2 < d; ++a2) {
+                    const uint64_t at = colPtr[(size_t)(col * d + a2)]++;
+                    oi[at] = (uint64_t)r * d + a2; oj[at] = (uint64_t)col * d + a2; ov[at] = mv[(size_t)q];
+                }
+            }
+        return MFH_OK;
+    }
     if (!(oi && oj && ov)) {
         // capacity query: the structural entries of the upper triangle (an upper bound of the count: exact zeros are pruned below)
         uint64_t cap = 0;
@@ -1711,11 +1809,12 @@ mfh_status mfh_export_upper_triplets(mfh_ctx *c, uint64_t *oi, uint64_t *oj, dou
 }
 
 mfh_status mfh_element_stiffness(mfh_ctx *c, int64_t first, int64_t count, double *Ke) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_element_stiffness(v, first, count, Ke); })) return st; }
     MFH_TRY(c)
     require(c && c->haveMesh && Ke, MFH_ERR_STATE, "no mesh set");
     require(first >= 0 && count > 0 && first + count <= c->mesh.nElem, MFH_ERR_INVALID, "bad element range");
     ensure_geometry(c);
-    const size_t ks = (size_t)c->mesh.npe * c->bs();
+    const size_t ks = (size_t)c->mesh.npe * c->vbs();      // (MFH_OP_MASS_VECTOR: the scalar element mass matrices it is assembled from)
     DBuf<double> out;
     out.alloc((size_t)count * ks * ks);
     k::AsmArgs a = asm_args(c);
@@ -1726,6 +1825,7 @@ mfh_status mfh_element_stiffness(mfh_ctx *c, int64_t first, int64_t count, doubl
 
 // ---------------------------------------------------------------- constrained solve
 mfh_status mfh_clear_fixed(mfh_ctx *c) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_clear_fixed(v); })) return st; }
     MFH_TRY(c)
     require(c && (c->haveMesh || c->external), MFH_ERR_STATE, "no mesh set");
     clear_fixed(c);
@@ -1733,6 +1833,7 @@ mfh_status mfh_clear_fixed(mfh_ctx *c) {
 }
 
 mfh_status mfh_fix_variables(mfh_ctx *c, int64_t n, const int64_t *vars, const double *vals) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_fix_variables(v, n, vars, vals); })) return st; }
     MFH_TRY(c)
     require(c && (c->haveMesh || c->external), MFH_ERR_STATE, "no mesh set");
     if (n == 0) return MFH_OK;
@@ -1747,6 +1848,7 @@ mfh_status mfh_set_preconditioner(mfh_ctx *c, int32_t kind) {
     c->autoStretch = -1.0;
     c->precond = c->precondAuto ? MFH_PRECOND_MULTIGRID : kind;      // (AUTO: the choice is made for the mesh in hand when the next solve prepares itself)
     c->dinvValid = false;
+    if (c->p1) (void)mfh_set_preconditioner(c->p1, kind);
     return MFH_OK;
 }
 
@@ -1807,6 +1909,7 @@ mfh_status mfh_multigrid_level_info(const mfh_ctx *c, int32_t cap, int64_t *out7
 }
 
 mfh_status mfh_solve(mfh_ctx *c, int32_t nrhs, const double *f, double *u, double rtol, int32_t maxit, mfh_solve_info *info) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_solve(v, nrhs, f, u, rtol, maxit, info); })) return st; }
     MFH_TRY(c)
     require(c && (c->haveMesh || c->external) && f && u && nrhs > 0 && maxit > 0 && rtol > 0, MFH_ERR_INVALID, "bad solve arguments");
     require_device(c);
@@ -1826,6 +1929,7 @@ mfh_status mfh_solve(mfh_ctx *c, int32_t nrhs, const double *f, double *u, doubl
 }
 
 mfh_status mfh_solve_batch(mfh_ctx *c, int32_t nrhs, const double *f, double *u, double rtol, int32_t maxit, mfh_solve_info *info) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_solve_batch(v, nrhs, f, u, rtol, maxit, info); })) return st; }
     MFH_TRY(c)
     require(c && (c->haveMesh || c->external) && f && u && nrhs > 0 && maxit > 0 && rtol > 0, MFH_ERR_INVALID, "bad solve arguments");
     require_device(c);
@@ -1844,6 +1948,7 @@ mfh_status mfh_solve_batch(mfh_ctx *c, int32_t nrhs, const double *f, double *u,
 }
 
 mfh_status mfh_apply_K(mfh_ctx *c, const double *u, double *Ku) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_apply_K(v, u, Ku); })) return st; }
     MFH_TRY(c)
     require(c && (c->haveMesh || c->external) && u && Ku, MFH_ERR_INVALID, "null argument");
     require_device(c);
@@ -1862,6 +1967,7 @@ mfh_status mfh_apply_K(mfh_ctx *c, const double *u, double *Ku) {
 
 // ---------------------------------------------------------------- device-pointer building blocks
 mfh_status mfh_dev_spmv(mfh_ctx *c, const double *x_dev, double *y_dev) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_dev_spmv(v, x_dev, y_dev); })) return st; }
     MFH_TRY(c)
     require(c && x_dev && y_dev, MFH_ERR_INVALID, "null argument");
     require_device(c);
@@ -2032,6 +2138,7 @@ mfh_status mfh_time_assembly_kernel(mfh_ctx *c, int32_t mode, int32_t reps, doub
 }
 
 mfh_status mfh_time_spmv_kernel(mfh_ctx *c, int32_t reps, double *avg_ms) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_time_spmv_kernel(v, reps, avg_ms); })) return st; }
     MFH_TRY(c)
     require(c && c->haveMesh && avg_ms && reps > 0, MFH_ERR_INVALID, "bad arguments");
     require_device(c);
@@ -2133,6 +2240,8 @@ mfh_status mfh_set_option(mfh_ctx *c, const char *key, double value) {
     MFH_TRY(c)
     require(c && key, MFH_ERR_INVALID, "null argument");
     const std::string k2(key);
+    // A new option that assembly, the assembled product or the classic PCG reads: a forced-degree-1 view made LATER starts from the copies in
+    // mfh_set_operator_degree -- add the member there too (a view that exists already gets the call forwarded at the end of this function).
     if (k2 == "asm_chunk_order") { c->asmChunkOrder = (int)value; }
     else if (k2 == "mg_steps_fine") c->mgSteps0 = std::max(1, (int)value);
     else if (k2 == "mg_steps_coarse") c->mgSteps1 = std::max(1, (int)value);
@@ -2207,6 +2316,92 @@ mfh_status mfh_set_option(mfh_ctx *c, const char *key, double value) {
     else if (k2 == "tl_host_inverse") { c->tlHostInverse = value != 0; c->tl.valid = false; }
     else throw Error(MFH_ERR_INVALID, "unknown option " + k2);
     refresh_storage_rule(c);   // matrix_storage, matrix_free, tl_probe, tl_rap_agg decide the storage of K
+    if (c->p1 && k2 != "matrix_free") {          // the forced-degree-1 view follows its context's options (it always multiplies by its assembled matrix)
+        const mfh_status st = mfh_set_option(c->p1, key, value);
+        if (st != MFH_OK) throw Error(st, c->p1->err);
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_set_operator_degree(mfh_ctx *c, int32_t degree) {
+    MFH_TRY(c)
+    require(c && (degree == 0 || degree == 1), MFH_ERR_INVALID, "operator degree must be 0 (the mesh's own) or 1");
+    require(c->haveMesh, MFH_ERR_STATE, "no mesh set");
+    if (c->mesh.deg == 1) return MFH_OK;                 // linear mesh: degree 1 is its own
+    if (degree == 0) { c->opDegree = 0; return MFH_OK; }  // the full-degree pattern and values were never touched; the view is kept for the next time
+    require(c->op != MFH_OP_ELASTICITY, MFH_ERR_STATE, "forced degree 1 is defined for the Laplacian and mass operators: select one with mfh_set_operator first");
+    require(c->mesh.hasTopology && c->dofForNode.empty() && c->mesh.nOwned == c->mesh.nNode && !dist_active(c), MFH_ERR_UNSUPPORTED,
+            "forced degree 1 needs a mesh from mfh_mesh_build (vertex nodes first) with the identity DoF map and all rows owned");
+    if (!c->p1) {
+        if (!c->hostOnly) { require_device(c); MFH_HIP(hipSetDevice(c->device)); }
+        mfh_ctx *v = make_linear_context(c, c->mesh.nVert, nullptr, true);
+        c->p1 = v;
+        c->p1GeoGen = -1;
+        v->matrixFree = 0;                               // the view multiplies by its assembled matrix
+        v->matrixStorage = c->matrixStorage; v->chunkSlots = c->chunkSlots; v->contribOrder = c->contribOrder; v->keepHostSymbolic = c->keepHostSymbolic || c->hostOnly;
+        v->asmPackedCodes = c->asmPackedCodes; v->checkEvery = c->checkEvery; v->useGraph = c->useGraph; v->refine = c->refine; v->pcgVariant = c->pcgVariant;
+        v->precond = c->precond; v->precondAuto = c->precondAuto; v->asmChunkOrder = c->asmChunkOrder;
+        if (c->deterministic) {                          // scratch of its own for the reproducible sums of the calls made on it
+            v->deterministic = false;
+            const mfh_status st = mfh_set_option(v, "deterministic", 1.0);
+            if (st != MFH_OK) throw Error(st, v->err);
+        }
+    }
+    const mfh_status st = mfh_set_operator(c->p1, c->op);
+    if (st != MFH_OK) throw Error(st, c->p1->err);
+    c->opDegree = 1;
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_mass_lumped(mfh_ctx *c, double *diagOut, int32_t onDevice) {
+    { mfh_status st; if (follow_view(c, st, [&](mfh_ctx *v) { return mfh_mass_lumped(v, diagOut, onDevice); })) return st; }
+    MFH_TRY(c)
+    require(c && c->haveMesh && diagOut, MFH_ERR_INVALID, "null argument");
+    require(c->op == MFH_OP_MASS || c->op == MFH_OP_MASS_VECTOR, MFH_ERR_STATE, "the lumped mass matrix is defined for MFH_OP_MASS and MFH_OP_MASS_VECTOR");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_assembled(c);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_mass_lumped needs all rows owned");
+    require(!(c->deterministic && c->upperOnly), MFH_ERR_UNSUPPORTED, "deterministic 1: the row sums of an upper-triangle matrix (matrix_storage 1) add the mirrored halves with global atomics in arrival order; use matrix_storage 0");
+    const int rep = c->kron() ? c->mesh.dim : 1;
+    const size_t n = (size_t)rep * (size_t)c->sym.nRows;
+    DBuf<double> tmp;
+    double *out = diagOut;
+    if (!onDevice) { tmp.alloc(n); out = tmp.p; }
+    if (c->upperOnly) MFH_HIP(hipMemsetAsync(out, 0, n * sizeof(double), c->stream));
+    k::launch_row_sums(c->sym.nRows, c->dRowPtr.p, c->dColIdx.p, c->dVals.p, rep, c->upperOnly, out, c->stream);
+    if (!onDevice) tmp.download(diagOut, n, c->stream);
+    else MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_divergence(mfh_ctx *c, const double *elemVectors, double *out) {
+    MFH_TRY(c)
+    require(c && c->haveMesh && elemVectors && out, MFH_ERR_INVALID, "null argument");
+    require(c->mesh.deg == 1, MFH_ERR_UNSUPPORTED, "Divergence only implemented for degree 1");     // as the reference's binding throws
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_geometry(c);
+    const HostMesh &m = c->mesh;
+    const int npe = m.npe;
+    if (!c->nodePairsValid) {
+        // the (element, local node) pairs of every node, ascending by element: a counting sort of the node table (connectivity only: kept
+        // until the next mesh)
+        std::vector<int32_t> ptr((size_t)m.nNode + 1, 0), pairs((size_t)m.nElem * npe);
+        require((int64_t)pairs.size() <= 2147483647LL, MFH_ERR_UNSUPPORTED, "mfh_divergence: more than 2^31 (element, node) pairs");
+        for (size_t k2 = 0; k2 < pairs.size(); ++k2) ++ptr[(size_t)m.elemNodes[k2] + 1];
+        for (int64_t n = 0; n < m.nNode; ++n) ptr[(size_t)n + 1] += ptr[(size_t)n];
+        std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
+        for (size_t k2 = 0; k2 < pairs.size(); ++k2) pairs[(size_t)cur[(size_t)m.elemNodes[k2]]++] = (int32_t)k2;
+        c->dNodePtr.upload(ptr, c->stream);
+        c->dNodePair.upload(pairs, c->stream);
+        c->nodePairsValid = true;
+    }
+    DBuf<double> v, res;
+    v.upload(elemVectors, (size_t)m.nElem * m.dim, c->stream);
+    res.alloc((size_t)m.nNode);
+    k::launch_divergence(m.dim, m.nNode, c->dNodePtr.p, c->dNodePair.p, c->dGeo.p, c->geoStride, v.p, res.p, c->stream);
+    res.download(out, res.n, c->stream);
     MFH_CATCH(c)
 }
 

@@ -47,7 +47,16 @@ struct mfh_ctx {
     // ---- material
     int matMode = 0;                  // see k_geometry
     int matKind = MAT_ISO;
-    int op = MFH_OP_ELASTICITY;       // operator assembled into K: elasticity (dim x dim blocks) or scalar Laplacian / mass
+    int op = MFH_OP_ELASTICITY;       // operator assembled into K: elasticity (dim x dim blocks), scalar Laplacian / mass, or the mass matrix on
+                                      // displacement vectors (MFH_OP_MASS_VECTOR: dim variables per DoF, ONE stored value per block)
+    // Forced degree 1 on a quadratic mesh (mfh_set_operator_degree; Laplacian::construct<1>, MassMatrix::construct<1>): the scalar operators live on
+    // the vertices. The view is a context of its own on the linear mesh -- the construction of the multigrid's linear level (make_linear_context,
+    // mfh_multigrid.cpp) -- that borrows this context's vertex positions and element records; the entry points that follow the view forward to it.
+    int opDegree = 0;                 // 0 = the mesh's degree, 1 = forced degree 1
+    mfh_ctx *p1 = nullptr;            // owned: the view (null until degree 1 is first asked for on a quadratic mesh)
+    int64_t geoGen = 0, p1GeoGen = -1;   // element records (re)written / the generation the view's matrices were assembled from
+    DBuf<int32_t> dNodePtr, dNodePair;   // mfh_divergence: (element, local node) pairs grouped by node
+    bool nodePairsValid = false;
     std::vector<double> matParams;    // host copy in the layout k_geometry expects
     DBuf<double> dMatParams;
     const double *dMatBorrowed = nullptr;   // linear level of a multigrid hierarchy: the parent's per-element table on the device (the child lives no longer than it)
@@ -94,7 +103,7 @@ struct mfh_ctx {
     int matrixFree = -1;              // option "matrix_free": 1 on, 0 off, -1 auto = on for elasticity (quadratic: 6x faster than the assembled SpMV; linear, since
                                       // the blocks of the cluster operator hold 512-1024 elements: 0.15 against 0.27 ms at 6.3 M tets, 0.033 against 0.040 at 1 M)
     bool use_mf() const {
-        if (external || !haveMesh || hostOnly) return false;
+        if (external || !haveMesh || hostOnly || kron()) return false;
         return matrixFree == 1 || (matrixFree < 0 && op == MFH_OP_ELASTICITY);
     }
     DBuf<int32_t> dMfChunkRow;
@@ -307,7 +316,9 @@ struct mfh_ctx {
     mfh_timing timing{0, 0, 0, 0};
 
     int dim() const { return mesh.dim; }
-    int bs() const { return (op == MFH_OP_ELASTICITY && !external) ? mesh.dim : 1; }   // variables per DoF = block edge of K
+    bool kron() const { return op == MFH_OP_MASS_VECTOR && !external; }                 // K = M (x) I_dim, one stored value per block
+    int bs() const { return ((op == MFH_OP_ELASTICITY || op == MFH_OP_MASS_VECTOR) && !external) ? mesh.dim : 1; }   // variables per DoF = block edge of K
+    int vbs() const { return kron() ? 1 : bs(); }                                        // edge of a STORED block
     int asmMat() const { return op == MFH_OP_ELASTICITY ? matKind : (op == MFH_OP_LAPLACIAN ? (int)MAT_LAPLACE : (int)MAT_MASS); }
     int64_t nOwnedDoFSet = -1;        // mfh_dof_map_partitioned: the first nOwnedDoFSet DoFs are this rank's rows (-1: not set)
     int64_t nOwnedDoF() const {
@@ -442,6 +453,13 @@ bool ensure_twolevel(mfh_ctx *c);
 bool ensure_multigrid(mfh_ctx *c);
 void ensure_coarse_levels(mfh_ctx *c, int nrhs);
 void destroy_multigrid(mfh_ctx *c);
+// The linear mesh on the corner nodes of a quadratic context as a context of its own (same device and stream): host tables, device tables (taken
+// from the parent's where the mesh is in the library's own numbering), shape tables. coarseNode[n] = the linear node of parent node n or -1
+// (null: the library's own numbering, the vertices are the nodes [0, nCN)).
+// Shared by the multigrid's linear level and the forced-degree-1 view; borrowPositions: the child reads the parent's position array in place.
+mfh_ctx *make_linear_context(mfh_ctx *c, int64_t nCN, const int32_t *coarseNode, bool borrowPositions);
+mfh_ctx *p1_view(mfh_ctx *c);                 // the forced-degree-1 view in force (synchronised with the parent's element records), or null
+void drop_p1_view(mfh_ctx *c);
 // What the PCG loop around the V-cycle takes over from it / hands to it when the first level's smoother is ONE step (mg_fuse_scale > 0):
 //   presmoothed: z already holds zs Dinv r (k_pcg_update's ZS flavour wrote it with the residual update) -- the cycle starts at its residual;
 //   rzScal:      the cycle's last kernel also forms r.z into the iteration's history (k_mg_cheb_rz; rzMask: the fixed-variable mask, may be null)

@@ -109,19 +109,25 @@ struct DBuf {
     DBuf(const DBuf &) = delete;
     DBuf &operator=(const DBuf &) = delete;
     ~DBuf() { release(); }
+    bool borrowed = false;              // p belongs to another buffer that outlives this one (borrow): never freed here
     void release() {
-        if (p) device_free(p);
+        if (p && !borrowed) device_free(p);
         p = nullptr;
         n = 0;
+        borrowed = false;
+    }
+    void borrow(T *q, size_t count) {
+        if (!borrowed) release();
+        p = q; n = count; borrowed = q != nullptr;
     }
     void alloc(size_t count) {
-        if (count == n && p) return;
+        if (count == n && p && !borrowed) return;       // (a borrowed range is never written through alloc / upload: the borrow ends here)
         release();
         if (count == 0) return;
         p = (T *)device_alloc(count * sizeof(T));
         n = count;
     }
-    void swap(DBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
+    void swap(DBuf &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(borrowed, o.borrowed); }
     // grow-only: work vectors whose size alternates between calls (batch widths 2, 1, 2, ...) are not reallocated every time
     void reserve(size_t count) {
         if (count > n || !p) alloc(count);
@@ -465,6 +471,7 @@ struct SpmvArgs {
     const uint8_t *fixedMask;           // per scalar row, may be null
     int xcd;                            // 1: XCD-contiguous chunk ranges (xcd_span)
     int pcgMode;                        // launch_spmv_nr with one vector: 0 = by ctl (none / Chronopoulos-Gear), 1 = classic PCG bookkeeping
+    int kron;                           // 1: K = M (x) I_dim with ONE stored value per block (MFH_OP_MASS_VECTOR): k_spmv_kron
     DetBuf det;                         // filled by the launcher (t_det)
 };
 // Matrix-free operator: y = K x without reading the assembled K. One lane per (element, local node i) pair:
@@ -527,7 +534,13 @@ void launch_spmv_sym(const SpmvArgs &a, int64_t nRows, const double *x, double *
 
 void launch_untile_vals(int dim, int64_t nnzb, const double *tiled, double *aos, hipStream_t s);
 void launch_extract_diag_inv(int dim, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *vals,
-                             const uint8_t *fixedMask, int precondKind, double *dinv, hipStream_t s);
+                             const uint8_t *fixedMask, int precondKind, double *dinv, hipStream_t s, bool kron = false);
+// rows sums of a matrix with one value per block (scalar operators, MFH_OP_MASS_VECTOR): out[rep r + c] = sum_j m_rj for c < rep; upperOnly: the stored
+// triangle serves both rows of an off-diagonal entry (out must then be zeroed by the caller: the mirrored halves are added atomically)
+void launch_row_sums(int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *vals, int rep, bool upperOnly, double *out, hipStream_t s);
+// out[n] = sum over the (element, local node) pairs of node n of vol_e v_e . grad lambda_i (linear elements; pairs: e (dim + 1) + i, grouped by node)
+void launch_divergence(int dim, int64_t nNode, const int32_t *nodePtr, const int32_t *nodePair, const double *geo, int geoStride, const double *elemVec,
+                       double *out, hipStream_t s);
 void launch_precond(int dim, int64_t nRows, const double *dinv, const double *r, double *z, hipStream_t s);
 
 // PCG step kernels. scal: device array of per-iteration reductions, 4 doubles per iteration

@@ -25,7 +25,8 @@ template <int DIM> DEV void invert_block(const double *A, double *Inv) {
 
 // Inverse of the diagonal blocks of the constrained operator P K P + (I-P): rows/cols of fixed
 // components are replaced by identity before inversion. kind: 0 block-Jacobi, 1 Jacobi, 2 identity.
-template <int DIM>
+// KRON: K = M (x) I_DIM stored as one value per block (MFH_OP_MASS_VECTOR): the scalar diagonal entry, broadcast to the DIM components.
+template <int DIM, bool KRON = false>
 __global__ void __launch_bounds__(256) k_diag_inv(int64_t nRows, const int32_t *__restrict__ rowPtr,
                                                   const int32_t *__restrict__ colIdx, const double *__restrict__ vals,
                                                   const uint8_t *__restrict__ fixedMask, int kind, double *__restrict__ dinv) {
@@ -40,8 +41,14 @@ __global__ void __launch_bounds__(256) k_diag_inv(int64_t nRows, const int32_t *
         const int mid = lo + ((hi - lo) >> 1);   // (lo + hi) overflows int beyond 2^30 blocks (found at 31.9 M P2 tets: 1.24e9 blocks)
         const int cv = colIdx[mid];
         if (cv == r) {
+            if (KRON) {
+                const double mrr = vals[tiled_index(mid, 0, 1)];
 #pragma unroll
-            for (int c = 0; c < NB; ++c) A[c] = vals[tiled_index(mid, c, NB)];
+                for (int c = 0; c < DIM; ++c) A[c * DIM + c] = mrr;
+            } else {
+#pragma unroll
+                for (int c = 0; c < NB; ++c) A[c] = vals[tiled_index(mid, c, NB)];
+            }
             break;
         }
         if (cv < r) lo = mid + 1; else hi = mid;
@@ -1985,9 +1992,11 @@ void launch_untile_vals(int dim, int64_t nnzb, const double *tiled, double *aos,
 }
 
 void launch_extract_diag_inv(int dim, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *vals,
-                             const uint8_t *fixedMask, int kind, double *dinv, hipStream_t s) {
+                             const uint8_t *fixedMask, int kind, double *dinv, hipStream_t s, bool kron) {
     const int grid = (int)((nRows + 255) / 256);
-    if (dim == 1) hipLaunchKernelGGL(k_diag_inv<1>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
+    if (kron && dim == 3) hipLaunchKernelGGL((k_diag_inv<3, true>), dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
+    else if (kron) hipLaunchKernelGGL((k_diag_inv<2, true>), dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
+    else if (dim == 1) hipLaunchKernelGGL(k_diag_inv<1>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
     else if (dim == 3) hipLaunchKernelGGL(k_diag_inv<3>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
     else hipLaunchKernelGGL(k_diag_inv<2>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
     CHECK_LAUNCH();

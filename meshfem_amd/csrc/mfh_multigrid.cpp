@@ -643,6 +643,54 @@ void destroy_multigrid(mfh_ctx *c) {
     if (G.coarse) { mfh_destroy(G.coarse); G.coarse = nullptr; }
 }
 
+// The linear mesh on the corner nodes of a quadratic context, as a context of its own sharing device and stream (see mfh_ctx.hh). The caller owns it.
+mfh_ctx *make_linear_context(mfh_ctx *c, int64_t nCN, const int32_t *coarseNode, bool borrowPositions) {
+    const HostMesh &m = c->mesh;
+    const bool ownNumbering = coarseNode == nullptr;
+    auto coarse_node = [&](int64_t n) -> int32_t { return ownNumbering ? (n < nCN ? (int32_t)n : -1) : coarseNode[(size_t)n]; };
+    const int d = m.dim, nv = d + 1, npe = m.npe;
+    hipStream_t s = c->stream;
+    std::unique_ptr<mfh_ctx> holder(new mfh_ctx());
+    mfh_ctx *c1 = holder.get();
+    c1->hierarchyLevel = true;        // (its K values are an ordinary large buffer for the arena: only a caller's context gets the values' segment class)
+    c1->device = c->device; c1->stream = c->stream; c1->ownStream = false; c1->nCU = c->nCU;
+    c1->hostOnly = c->hostOnly;
+    c1->deterministic = c->deterministic;     // its assembly orders the waves too; its launches use the calling thread's scratch (the parent's: k::t_det)
+    c1->symbolicDevice = c->symbolicDevice; c1->topologyDevice = c->topologyDevice;
+    HostMesh &m1 = c1->mesh;
+    m1 = HostMesh();
+    m1.dim = d; m1.deg = 1; m1.npe = nv; m1.npbe = nodes_per_bdry_elem(d, 1);
+    m1.nElem = m.nElem; m1.nNode = nCN; m1.nVert = nCN; m1.nOwned = nCN;
+    m1.elemNodes.resize((size_t)m.nElem * nv);
+    parallel_ranges(m.nElem, [&](int64_t eb, int64_t ee, int) {
+        for (int64_t e = eb; e < ee; ++e)
+            for (int k2 = 0; k2 < nv; ++k2) m1.elemNodes[(size_t)e * nv + k2] = coarse_node(m.elemNodes[(size_t)e * npe + k2]);
+    });
+    m1.nodePos.resize((size_t)nCN * d);
+    parallel_ranges(m.nNode, [&](int64_t nb, int64_t ne, int) {
+        for (int64_t n = nb; n < ne; ++n)
+            if (coarse_node(n) >= 0)
+                for (int a = 0; a < d; ++a) m1.nodePos[(size_t)coarse_node(n) * d + a] = m.nodePos[(size_t)n * d + a];
+    });
+    m1.vertPos = m1.nodePos;
+    m1.isBdryNode.assign((size_t)nCN, 0);
+    // the library's own numbering: the vertices are the first nodes, so the device copies of the child are the corner columns of the parent's
+    // node table and the head of its position array -- copied where they lie instead of uploaded again (0.69 GB at 119^3)
+    const bool childTablesOnDevice = !c->hostOnly && ownNumbering && c->dElemNodes.p && c->dVertPos.p && c->dElemNodes.n == (size_t)m.nElem * npe && c->dVertPos.n >= (size_t)nCN * d;
+    if (childTablesOnDevice) {
+        MFH_HIP(hipSetDevice(c->device));
+        c1->dElemNodes.alloc((size_t)m.nElem * nv);
+        k::launch_take_columns_i32(m.nElem, npe, nv, c->dElemNodes.p, c1->dElemNodes.p, s);
+        if (borrowPositions) c1->dVertPos.borrow(c->dVertPos.p, (size_t)nCN * d);
+        else {
+            c1->dVertPos.alloc((size_t)nCN * d);
+            MFH_HIP(hipMemcpyAsync(c1->dVertPos.p, c->dVertPos.p, (size_t)nCN * d * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    upload_mesh(c1, childTablesOnDevice);
+    return holder.release();
+}
+
 // Builds (or rebuilds) the hierarchy. false (with a note in precondNote) when it does not apply; the caller then falls back.
 bool ensure_multigrid(mfh_ctx *c) {
     auto &G = c->mg;
@@ -789,16 +837,9 @@ bool ensure_multigrid(mfh_ctx *c) {
     auto coarse_node = [&](int64_t n) -> int32_t { return ownNumbering ? (n < m.nVert ? (int32_t)n : -1) : coarseNode[(size_t)n]; };
     auto coarse_dof = [&](int64_t f) -> int32_t { return ownNumbering ? (f < m.nVert ? (int32_t)f : -1) : coarseDofOfFine[(size_t)f]; };
     // ---- level 1: a context of its own on the vertices (degree 1), sharing device and stream
-    mfh_ctx *c1 = new mfh_ctx();
+    mfh_ctx *c1 = make_linear_context(c, nCN, ownNumbering ? nullptr : coarseNode.data(), false);
     G.coarse = c1;
-    c1->hierarchyLevel = true;        // (its K values are an ordinary large buffer for the arena: only a caller's context gets the values' segment class)
-    c1->device = c->device; c1->stream = c->stream; c1->ownStream = false; c1->nCU = c->nCU;
-    c1->deterministic = c->deterministic;     // its assembly orders the waves too; its launches use the calling thread's scratch (the parent's: k::t_det)
-    c1->symbolicDevice = c->symbolicDevice; c1->topologyDevice = c->topologyDevice;
     HostMesh &m1 = c1->mesh;
-    m1 = HostMesh();
-    m1.dim = d; m1.deg = 1; m1.npe = nv; m1.npbe = nodes_per_bdry_elem(d, 1);
-    m1.nElem = m.nElem; m1.nNode = nCN; m1.nVert = nCN; m1.nOwned = nCN;
     int64_t nOwnedCoarseDoF = -1;
     if (distributed && c->dofForNode.empty()) {
         // the vertices this rank owns come first in the parent's numbering, hence in the child's: the child is partitioned the same way
@@ -809,30 +850,6 @@ bool ensure_multigrid(mfh_ctx *c) {
         nOwnedCoarseDoF = 0;                    // rows are DoFs: the coarse DoFs among the fine DoFs this rank owns
         for (int64_t f = 0; f < c->nOwnedDoF(); ++f) nOwnedCoarseDoF += coarse_dof(f) >= 0;
     }
-    m1.elemNodes.resize((size_t)m.nElem * nv);
-    parallel_ranges(m.nElem, [&](int64_t eb, int64_t ee, int) {
-        for (int64_t e = eb; e < ee; ++e)
-            for (int k2 = 0; k2 < nv; ++k2) m1.elemNodes[(size_t)e * nv + k2] = coarse_node(m.elemNodes[(size_t)e * npe + k2]);
-    });
-    m1.nodePos.resize((size_t)nCN * d);
-    parallel_ranges(m.nNode, [&](int64_t nb, int64_t ne, int) {
-        for (int64_t n = nb; n < ne; ++n)
-            if (coarse_node(n) >= 0)
-                for (int a = 0; a < d; ++a) m1.nodePos[(size_t)coarse_node(n) * d + a] = m.nodePos[(size_t)n * d + a];
-    });
-    m1.vertPos = m1.nodePos;
-    m1.isBdryNode.assign((size_t)nCN, 0);
-    // the library's own numbering: the vertices are the first nodes, so the device copies of the child are the corner columns of the parent's
-    // node table and the head of its position array -- copied where they lie instead of uploaded again (0.69 GB at 119^3)
-    const bool childTablesOnDevice = ownNumbering && c->dElemNodes.p && c->dVertPos.p && c->dElemNodes.n == (size_t)m.nElem * npe && c->dVertPos.n >= (size_t)nCN * d;
-    if (childTablesOnDevice) {
-        MFH_HIP(hipSetDevice(c->device));
-        c1->dElemNodes.alloc((size_t)m.nElem * nv);
-        k::launch_take_columns_i32(m.nElem, npe, nv, c->dElemNodes.p, c1->dElemNodes.p, s);
-        c1->dVertPos.alloc((size_t)nCN * d);
-        MFH_HIP(hipMemcpyAsync(c1->dVertPos.p, c->dVertPos.p, (size_t)nCN * d * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    upload_mesh(c1, childTablesOnDevice);
     lap("linear mesh + upload");
     // material: the same per-element parameters (k_geometry rebuilds the records of the linear elements from them)
     c1->matMode = c->matMode; c1->matKind = c->matKind;

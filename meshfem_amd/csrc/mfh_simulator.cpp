@@ -914,7 +914,14 @@ mfh_status mfh_delta_average_strain(mfh_ctx *c, const double *uNodes, const doub
 
 mfh_status mfh_set_operator(mfh_ctx *c, int32_t op) {
     MFH_TRY(c)
-    require(c && (op == MFH_OP_ELASTICITY || op == MFH_OP_LAPLACIAN || op == MFH_OP_MASS), MFH_ERR_INVALID, "unknown operator");
+    require(c && (op == MFH_OP_ELASTICITY || op == MFH_OP_LAPLACIAN || op == MFH_OP_MASS || op == MFH_OP_MASS_VECTOR), MFH_ERR_INVALID, "unknown operator");
+    require(!(op == MFH_OP_ELASTICITY && c->opDegree == 1 && c->haveMesh && c->mesh.deg == 2), MFH_ERR_STATE,
+            "forced degree 1 is defined for the Laplacian and mass operators: call mfh_set_operator_degree(ctx, 0) before selecting elasticity");
+    require(!(op == MFH_OP_MASS_VECTOR && dist_active(c)), MFH_ERR_UNSUPPORTED, "the vector-valued mass operator (MFH_OP_MASS_VECTOR) is not available on row-partitioned contexts");
+    if (c->p1) {                       // the forced-degree-1 view carries the same operator (elasticity excepted: it has none)
+        const mfh_status st = op == MFH_OP_ELASTICITY ? MFH_OK : mfh_set_operator(c->p1, op);
+        if (st != MFH_OK) throw Error(st, c->p1->err);
+    }
     if (op != c->op) {
         c->op = op;
         invalidate_matrix(c);          // pattern and gather lists are shared by all operators; only the values change

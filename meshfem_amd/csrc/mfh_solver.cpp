@@ -501,6 +501,7 @@ void dist_profile_collect(mfh_ctx *c) {
 
 bool cg_operator_supported(mfh_ctx *c) {
     // the batched operators: the cluster variant of the matrix-free operator and the assembled SpMV
+    if (c->kron()) return false;          // one value per block: k_spmv_kron serves the plain product and the classic loop
     if (!c->use_mf()) return true;
     prepare_matrix_free(c);
     return cluster_operator(c);
@@ -1572,6 +1573,8 @@ mfh_status mfh_dist_setup(mfh_ctx *c, mfh_comm *cm, int32_t nPeers, const int32_
                           const int64_t *recvPtr) {
     MFH_TRY(c)
     require(c && c->haveMesh && cm && nPeers >= 0 && (nPeers == 0 || (peers && sendPtr && recvPtr)), MFH_ERR_INVALID, "bad distributed setup arguments");
+    require(!c->kron(), MFH_ERR_UNSUPPORTED, "the vector-valued mass operator (MFH_OP_MASS_VECTOR) is not available on row-partitioned contexts");
+    require(!(c->opDegree == 1 && c->mesh.deg == 2), MFH_ERR_UNSUPPORTED, "forced-degree-1 operators are not available on row-partitioned contexts");
     require(c->dofForNode.empty() || c->nOwnedDoFSet >= 0, MFH_ERR_UNSUPPORTED,
             "a row-partitioned context with a DoF map needs mfh_dof_map_partitioned (which DoFs are this rank's rows)");
     require_device(c);

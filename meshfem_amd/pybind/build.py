@@ -1,4 +1,4 @@
-"""Build the compiled pybind11 modules `mesh`, `tensors`, `sparse_matrices`, `periodic_homogenization` (the names of the
+"""Build the compiled pybind11 modules `mesh`, `tensors`, `sparse_matrices`, `periodic_homogenization`, `differential_operators` (the names of the
 reference's extension modules, src/python_bindings/CMakeLists.txt:10-33) in-tree, linked against ../libmeshfem_hip.so.
     import sys, meshfem_amd.pybind; sys.path.insert(0, meshfem_amd.pybind.PATH); import mesh, tensors, ..."""
 import os
@@ -8,7 +8,7 @@ import sysconfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "src")
-MODULES = ["tensors", "mesh", "sparse_matrices", "periodic_homogenization"]
+MODULES = ["tensors", "mesh", "sparse_matrices", "periodic_homogenization", "differential_operators"]
 SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
 
@@ -18,7 +18,8 @@ def target(name):
 
 def needs_build():
     deps = [os.path.join(SRC, "common.hh"), os.path.join(HERE, "..", "..", "include", "MeshFEMHip", "LinearElasticity.hh"),
-            os.path.join(HERE, "..", "..", "include", "MeshFEMHip", "PeriodicHomogenization.hh"), os.path.join(HERE, "..", "..", "include", "meshfem_hip.h")]
+            os.path.join(HERE, "..", "..", "include", "MeshFEMHip", "PeriodicHomogenization.hh"),
+            os.path.join(HERE, "..", "..", "include", "MeshFEMHip", "DifferentialOperators.hh"), os.path.join(HERE, "..", "..", "include", "meshfem_hip.h")]
     for n in MODULES:
         t = target(n)
         if not os.path.exists(t):

@@ -2,8 +2,11 @@
 (Laplacian.hh:97-104), `MassMatrix::construct` (MassMatrix.hh:103-128) and `PoissonMesh`
 (Poisson.hh:55-132). They run on the kernels of the elasticity path with 1x1 blocks
 (`Context.set_operator`): same mesh topology, pattern, gather lists, assembly kernel, SpMV and PCG.
-Only the full-degree operators are provided (the reference's forced-degree-1 variants on a
-quadratic mesh are not)."""
+`forceP1=True` gives the reference's forced-degree-1 variants on a quadratic mesh
+(`Laplacian::construct<1>`, `MassMatrix::construct<1>`): a degree-1 view of the same context on its
+vertices (`Context.set_operator_degree`), no second mesh. `mass_elasticity` is
+`MassMatrix::construct_vector_valued` (one stored value per block on the device), `gradient` /
+`divergence` the two remaining functions of the reference's `differential_operators` module."""
 import numpy as np
 
 from . import _lib as L
@@ -36,27 +39,70 @@ class _Triplets:
         return A
 
 
-def laplacian(elements, vertices, degree=1, device=0, ctx=None):
-    """== Laplacian::construct: upper triangle of the (positive semi-definite) FEM Laplacian."""
+def _select(c, op, forceP1):
+    """Operator and degree view of a context (the degree is left as the caller finds it: see _assembled)."""
+    if c.op == L.OP_ELASTICITY and c.op_degree == 0 and forceP1:
+        c.set_operator(op)                                 # elasticity has no degree-1 view: leave it first
+    c.set_operator_degree(1 if forceP1 else 0)
+    c.set_operator(op)
+
+
+def _assembled(c, op, forceP1, lumped=False):
+    """Triplets of `op` on `c`; a caller's context gets its degree view back afterwards."""
+    before = c.op_degree
+    _select(c, op, forceP1)
+    try:
+        c.assemble()
+        n = c.bs * c.matrix_info()[0]                      # rows of the degree view in force, as the library counts them
+        if lumped:
+            diag = c.mass_lumped()                         # row sums of the full symmetric matrix, summed on the device
+            r = np.arange(n, dtype=np.uint64)
+            return _Triplets(n, r, r.copy(), diag)
+        i, j, v = c.export_upper_triplets()
+        return _Triplets(n, i, j, v)
+    finally:
+        c.set_operator_degree(before)
+
+
+def laplacian(elements, vertices, degree=1, device=0, ctx=None, forceP1=False):
+    """== Laplacian::construct: upper triangle of the (positive semi-definite) FEM Laplacian; `forceP1`:
+    Laplacian::construct<1> on the vertices of a quadratic mesh."""
     c = ctx or _context_for(elements, vertices, degree, device, L.OP_LAPLACIAN)
-    c.set_operator(L.OP_LAPLACIAN)
-    c.assemble()
-    i, j, v = c.export_upper_triplets()
-    return _Triplets(c.n_dof, i, j, v)
+    return _assembled(c, L.OP_LAPLACIAN, forceP1)
 
 
-def mass_matrix(elements, vertices, degree=1, lumped=False, device=0, ctx=None):
+def mass_matrix(elements, vertices, degree=1, lumped=False, device=0, ctx=None, forceP1=False):
     """== MassMatrix::construct: upper triangle of the mass matrix; `lumped` puts the row sums of the
-    full matrix on the diagonal (MassMatrix.hh:110-124)."""
+    full matrix on the diagonal (MassMatrix.hh:110-124); `forceP1`: MassMatrix::construct<1>."""
     c = ctx or _context_for(elements, vertices, degree, device, L.OP_MASS)
-    c.set_operator(L.OP_MASS)
-    c.assemble()
-    if lumped:
-        diag = c.apply_K(np.ones(c.n_dof))                 # row sums of the full symmetric matrix = M 1, on the device
-        r = np.arange(c.n_dof, dtype=np.uint64)
-        return _Triplets(c.n_dof, r, r.copy(), diag)
-    i, j, v = c.export_upper_triplets()
-    return _Triplets(c.n_dof, i, j, v)
+    return _assembled(c, L.OP_MASS, forceP1, lumped)
+
+
+def mass_elasticity(elements, vertices, degree, lumped=False, forceP1=False, ctx=None, device=0):
+    """== MassMatrix::construct_vector_valued (MassMatrix.hh:131-147): the mass matrix on interleaved
+    displacement vectors, entries (dim i + c, dim j + c, m_ij)."""
+    c = ctx or _context_for(elements, vertices, degree, device, L.OP_MASS_VECTOR)
+    return _assembled(c, L.OP_MASS_VECTOR, forceP1, lumped)
+
+
+def _as_context(ctx_or_mesh, device=0):
+    if isinstance(ctx_or_mesh, Context):
+        return ctx_or_mesh
+    if hasattr(ctx_or_mesh, "ctx"):                        # PoissonMesh, Simulator
+        return ctx_or_mesh.ctx
+    elements, vertices, degree = ctx_or_mesh               # (elements, vertices, degree)
+    return _context_for(elements, vertices, degree, device, L.OP_LAPLACIAN)
+
+
+def gradient(ctx_or_mesh, scalarField):
+    """Per-element average gradient of a scalar nodal field (differential_operators.gradient; PoissonMesh::gradUAverage)."""
+    return _as_context(ctx_or_mesh).average_gradient(scalarField)
+
+
+def divergence(ctx_or_mesh, vectorField):
+    """out[n] = sum_{e containing n} v_e . int_e grad phi_n for a per-element vector field
+    (differential_operators.divergence); linear meshes only, like the reference."""
+    return _as_context(ctx_or_mesh).divergence(vectorField)
 
 
 class PoissonMesh:
