@@ -348,6 +348,36 @@ mfh_status mfh_strain_field(mfh_ctx* ctx, const double* uNodes, int32_t wantStre
  * :226-288): values of the parent element's strain at the boundary element's corners, in the boundary element's vertex
  * order. out: [nBE][1 | dim][flatLen]. */
 mfh_status mfh_boundary_strain_field(mfh_ctx* ctx, const double* uNodes, int32_t wantStress, double* out);
+/* ---- stress measures on the device (VonMises.hh vonMises; SymmetricMatrix.hh eigenvalues / eigenDecomposition;
+ * FieldPostProcessing.hh vertexAveragedField). Symmetric matrices are flattened as the strain fields above: flatLen entries, TENSOR shear.
+ * `what` is a mask of MFH_MEASURE_*; an output that is not requested may be NULL, a requested one that is NULL is MFH_ERR_INVALID:
+ *   vonMises      one scalar per matrix: sqrt of the squared Frobenius norm of vonMisesExtractor<N>() : s, i.e. sqrt(3/2 dev s : dev s) in 3D
+ *                 and the plane-stress value sqrt(s00^2 + s11^2 - s00 s11 + 3 s01^2) in 2D (VonMises.hh:10-46)
+ *   eigenvalues   dim per matrix, ascending (the order of Eigen's SelfAdjointEigenSolver)
+ *   eigenvectors  dim x dim per matrix, row-major, the unit eigenvector of eigenvalue k in COLUMN k (sign unspecified)
+ * No atomics anywhere: every call returns the same bits. onDevice != 0 (as for the lumped mass above): every array argument is a device
+ * pointer, and the call returns after the context's stream has been synchronised.
+ *   mfh_sym_measures       a caller's field of n matrices [n][flatLen]; needs the context for its device and stream only (no mesh)
+ *   mfh_stress_measures    the strain (wantStress: stress) of uNodes at the corners the strain field above is given at, fused: the
+ *                          tensor is never stored. Outputs [nElem][NQ], [nElem][NQ][dim], [nElem][NQ][dim][dim], NQ = 1 | dim+1.
+ *                          Preconditions and error codes of the strain field.
+ *   mfh_vertex_average     C0 volume-weighted average of per-element corner values at the mesh vertices: out[v] = sum_e vol_e f(e, v) /
+ *                          sum_e vol_e over the elements around v, accumulated in element order. field: [nElem][NQ][nComp] with NQ = dim+1
+ *                          (perCorner != 0) or 1 (a per-element constant every corner takes); any nComp >= 1; out: [nVert][nComp]. The
+ *                          vertex of a single element takes that element's value unchanged. MFH_ERR_UNSUPPORTED on a row-partitioned
+ *                          context (nOwned < nNode): the elements of other ranks are missing at the interface vertices.
+ *   mfh_vertex_averaged_strain  the same average of the strain / stress field of uNodes ([nVert][flatLen]); the field stays on the device
+ *   mfh_peak_von_mises     max and argmax of the von Mises value over all corners, reduced on the device in two stages without writing a
+ *                          field (uNodes, value, cornerIndex: host pointers). cornerIndex = element NQ + corner; ties go to the lowest
+ *                          index; a NaN anywhere gives NaN with the index of the first NaN. */
+enum { MFH_MEASURE_VON_MISES = 1, MFH_MEASURE_EIGENVALUES = 2, MFH_MEASURE_EIGENVECTORS = 4 };
+mfh_status mfh_sym_measures(mfh_ctx* ctx, int32_t dim, int64_t n, const double* field, int32_t what, double* vonMises,
+                            double* eigenvalues, double* eigenvectors, int32_t onDevice);
+mfh_status mfh_stress_measures(mfh_ctx* ctx, const double* uNodes, int32_t wantStress, int32_t what, double* vonMises,
+                               double* eigenvalues, double* eigenvectors, int32_t onDevice);
+mfh_status mfh_vertex_average(mfh_ctx* ctx, const double* field, int32_t perCorner, int32_t nComp, double* out, int32_t onDevice);
+mfh_status mfh_vertex_averaged_strain(mfh_ctx* ctx, const double* uNodes, int32_t wantStress, double* out, int32_t onDevice);
+mfh_status mfh_peak_von_mises(mfh_ctx* ctx, const double* uNodes, int32_t wantStress, double* value, int64_t* cornerIndex);
 
 /* ---- discrete shape derivatives, forward mode (LinearElasticity.hh:234-330 at element level; Simulator level
  * :1297-1374). deltaP is a per-vertex perturbation field [nVert x dim] (indexed by the node id of the element corners:

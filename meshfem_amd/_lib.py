@@ -14,6 +14,7 @@ NEUMANN_TRACTION, NEUMANN_PRESSURE, NEUMANN_FORCE = 0, 1, 2
 PRECOND_BLOCK_JACOBI, PRECOND_JACOBI, PRECOND_NONE, PRECOND_TWO_LEVEL, PRECOND_MULTIGRID, PRECOND_AUTO = 0, 1, 2, 3, 4, 5
 OP_ELASTICITY, OP_LAPLACIAN, OP_MASS, OP_MASS_VECTOR = 0, 1, 2, 3
 SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED = 1, 2, 4
+MEASURE_VON_MISES, MEASURE_EIGENVALUES, MEASURE_EIGENVECTORS = 1, 2, 4
 
 
 class SolveInfo(C.Structure):
@@ -114,6 +115,11 @@ PROTOTYPES = {
     "mfh_integrated_stress": (_i32, [_P, _P, _P, _P]),
     "mfh_strain_field": (_i32, [_P, _P, _i32, _P]),
     "mfh_boundary_strain_field": (_i32, [_P, _P, _i32, _P]),
+    "mfh_sym_measures": (_i32, [_P, _i32, _i64, _P, _i32, _P, _P, _P, _i32]),
+    "mfh_stress_measures": (_i32, [_P, _P, _i32, _i32, _P, _P, _P, _i32]),
+    "mfh_vertex_average": (_i32, [_P, _P, _i32, _i32, _P, _i32]),
+    "mfh_vertex_averaged_strain": (_i32, [_P, _P, _i32, _P, _i32]),
+    "mfh_peak_von_mises": (_i32, [_P, _P, _i32, C.POINTER(_f64), _pi64]),
     "mfh_mesh_get_boundary_elem_parents": (_i32, [_P, _P]),
     "mfh_mesh_get_boundary_elem_internal": (_i32, [_P, _P]),
     "mfh_mesh_update_vertices": (_i32, [_P, _P]),

@@ -546,6 +546,68 @@ class Context:
         self._ck(self.lib.mfh_boundary_strain_field(self.h, ptr(u), int(bool(stress)), ptr(out)))
         return out
 
+    # ---------------------------------------------------------------- stress measures (VonMises.hh, SymmetricMatrix.hh, FieldPostProcessing.hh)
+    def _nq(self):
+        return 1 if self.deg == 1 else self.dim + 1
+
+    def stress_measures(self, u_nodes, what, stress=True):
+        """The requested measures (mask of MEASURE_*) of the stress (strain) of u at the corners of strain_field, fused on the device:
+        (von Mises [nElem, NQ], eigenvalues [nElem, NQ, dim] ascending, eigenvectors [nElem, NQ, dim, dim] in columns); None where not requested."""
+        u = as_f64(u_nodes)
+        n, d = (self.n_elem, self._nq()), self.dim
+        vm = np.empty(n) if what & L.MEASURE_VON_MISES else None
+        ev = np.empty(n + (d,)) if what & L.MEASURE_EIGENVALUES else None
+        vec = np.empty(n + (d, d)) if what & L.MEASURE_EIGENVECTORS else None
+        self._ck(self.lib.mfh_stress_measures(self.h, ptr(u), int(bool(stress)), int(what), ptr(vm), ptr(ev), ptr(vec), 0))
+        return vm, ev, vec
+
+    def von_mises(self, u_nodes, stress=True):
+        """von Mises value of the stress (strain) of u per element corner: [nElem, 1 | dim+1]"""
+        return self.stress_measures(u_nodes, L.MEASURE_VON_MISES, stress)[0]
+
+    def principal_values(self, u_nodes, stress=True, vectors=False):
+        """Ascending principal stresses (strains) per element corner [nElem, NQ, dim]; with vectors=True also the principal directions
+        [nElem, NQ, dim, dim], direction k in column k."""
+        _, ev, vec = self.stress_measures(u_nodes, L.MEASURE_EIGENVALUES | (L.MEASURE_EIGENVECTORS if vectors else 0), stress)
+        return (ev, vec) if vectors else ev
+
+    def vertex_averaged_field(self, field):
+        """C0 volume-weighted vertex average (vertexAveragedField) of element values laid out like strain_field's result: [nElem, NQ, ...]
+        with the corner axis NQ = dim+1, or NQ = 1 for a per-element constant that every corner takes ([nElem] is read as [nElem, 1]).
+        Any trailing shape (scalar, vector, flattened symmetric, full tensor); returns [nVert, ...]."""
+        f = as_f64(field)
+        if f.ndim == 1:
+            f = f[:, None]
+        if f.shape[0] != self.n_elem or f.shape[1] not in (1, self.dim + 1):
+            raise ValueError("expected [nElem, 1 | dim+1, ...]")
+        per_corner = f.shape[1] == self.dim + 1
+        tail = f.shape[2:]
+        ncomp = int(np.prod(tail)) if tail else 1
+        out = np.empty((self.n_vert,) + tuple(tail))
+        self._ck(self.lib.mfh_vertex_average(self.h, ptr(f), int(per_corner), ncomp, ptr(out), 0))
+        return out
+
+    def _vertex_averaged_strain(self, u_nodes, stress):
+        u = as_f64(u_nodes)
+        out = np.empty((self.n_vert, flat_len(self.dim)))
+        self._ck(self.lib.mfh_vertex_averaged_strain(self.h, ptr(u), int(stress), ptr(out), 0))
+        return out
+
+    def vertex_averaged_stress(self, u_nodes):
+        """vertex_averaged_field(strain_field(u, stress=True)) with the corner field kept on the device: [nVert, flatLen]"""
+        return self._vertex_averaged_strain(u_nodes, 1)
+
+    def vertex_averaged_strain(self, u_nodes):
+        return self._vertex_averaged_strain(u_nodes, 0)
+
+    def peak_von_mises(self, u_nodes, stress=True):
+        """(max von Mises value over all element corners, flat corner index element * NQ + corner), reduced on the device. Ties: the
+        lowest index; a NaN anywhere: NaN and the index of the first one."""
+        u = as_f64(u_nodes)
+        v, i = C.c_double(), C.c_int64()
+        self._ck(self.lib.mfh_peak_von_mises(self.h, ptr(u), int(bool(stress)), C.byref(v), C.byref(i)))
+        return v.value, i.value
+
     def average_stress(self, u_nodes):
         u = as_f64(u_nodes)
         out = np.empty((self.n_elem, flat_len(self.dim)))
@@ -719,6 +781,44 @@ class Context:
 
     def set_option(self, key, value):
         self._ck(self.lib.mfh_set_option(self.h, key.encode(), float(value)))
+
+
+def sym_measures(field, what, ctx=None):
+    """Measures (mask of MEASURE_*) of a field of flattened symmetric matrices [..., flatLen] (tensor shear; flatLen 3: 2D, 6: 3D) on the
+    device of `ctx` (default: a context of its own on device 0): (von Mises [...], eigenvalues [..., dim], eigenvectors [..., dim, dim])."""
+    f = as_f64(field)
+    dim = {3: 2, 6: 3}.get(f.shape[-1] if f.ndim else 0)
+    if dim is None:
+        raise ValueError("the last axis must hold 3 (2D) or 6 (3D) flattened entries")
+    own = ctx is None
+    c = Context(0) if own else ctx
+    try:
+        lead = f.shape[:-1]
+        n = int(np.prod(lead)) if lead else 1
+        vm = np.empty(lead) if what & L.MEASURE_VON_MISES else None
+        ev = np.empty(lead + (dim,)) if what & L.MEASURE_EIGENVALUES else None
+        vec = np.empty(lead + (dim, dim)) if what & L.MEASURE_EIGENVECTORS else None
+        c._ck(c.lib.mfh_sym_measures(c.h, dim, n, ptr(f), int(what), ptr(vm), ptr(ev), ptr(vec), 0))
+    finally:
+        if own:
+            c.close()
+    return vm, ev, vec
+
+
+def von_mises(field, ctx=None):
+    """vonMises(field) of the reference as the scalar per matrix (VonMises.hh)"""
+    return sym_measures(field, L.MEASURE_VON_MISES, ctx)[0]
+
+
+def principal_values(field, vectors=False, ctx=None):
+    """eigenvalues (ascending) and, with vectors=True, eigenvectors in columns (SymmetricMatrix.hh eigenDecomposition)"""
+    _, ev, vec = sym_measures(field, L.MEASURE_EIGENVALUES | (L.MEASURE_EIGENVECTORS if vectors else 0), ctx)
+    return (ev, vec) if vectors else ev
+
+
+def vertex_averaged_field(ctx, field):
+    """vertexAveragedField(mesh, f) on the mesh of `ctx`"""
+    return ctx.vertex_averaged_field(field)
 
 
 def device_cache_trim():

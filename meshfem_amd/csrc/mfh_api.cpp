@@ -329,6 +329,23 @@ void pack_gather_codes(mfh_ctx *c) {
     c->codesPacked = k::launch_pack_codes(c->sym.nChunk(), c->dContribPtr.p, c->dContribCode.p, c->mesh.npe, c->dChunkElemBase.p, flag.p, c->stream);
 }
 
+// the (element, local node) pairs of every node (code e npe + j), grouped by node and ascending by element: a counting sort of the node
+// table (connectivity only: kept until the next mesh). The gather list of mfh_divergence and of the vertex averages.
+void ensure_node_pairs(mfh_ctx *c) {
+    if (c->nodePairsValid) return;
+    const HostMesh &m = c->mesh;
+    const int npe = m.npe;
+    std::vector<int32_t> ptr((size_t)m.nNode + 1, 0), pairs((size_t)m.nElem * npe);
+    require((int64_t)pairs.size() <= 2147483647LL, MFH_ERR_UNSUPPORTED, "more than 2^31 (element, node) pairs");
+    for (size_t k2 = 0; k2 < pairs.size(); ++k2) ++ptr[(size_t)m.elemNodes[k2] + 1];
+    for (int64_t n = 0; n < m.nNode; ++n) ptr[(size_t)n + 1] += ptr[(size_t)n];
+    std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
+    for (size_t k2 = 0; k2 < pairs.size(); ++k2) pairs[(size_t)cur[(size_t)m.elemNodes[k2]]++] = (int32_t)k2;
+    c->dNodePtr.upload(ptr, c->stream);
+    c->dNodePair.upload(pairs, c->stream);
+    c->nodePairsValid = true;
+}
+
 k::AsmArgs asm_args(mfh_ctx *c) {
     const HostMesh &m = c->mesh;
     k::AsmArgs a{};
@@ -2383,20 +2400,7 @@ mfh_status mfh_divergence(mfh_ctx *c, const double *elemVectors, double *out) {
     MFH_HIP(hipSetDevice(c->device));
     ensure_geometry(c);
     const HostMesh &m = c->mesh;
-    const int npe = m.npe;
-    if (!c->nodePairsValid) {
-        // the (element, local node) pairs of every node, ascending by element: a counting sort of the node table (connectivity only: kept
-        // until the next mesh)
-        std::vector<int32_t> ptr((size_t)m.nNode + 1, 0), pairs((size_t)m.nElem * npe);
-        require((int64_t)pairs.size() <= 2147483647LL, MFH_ERR_UNSUPPORTED, "mfh_divergence: more than 2^31 (element, node) pairs");
-        for (size_t k2 = 0; k2 < pairs.size(); ++k2) ++ptr[(size_t)m.elemNodes[k2] + 1];
-        for (int64_t n = 0; n < m.nNode; ++n) ptr[(size_t)n + 1] += ptr[(size_t)n];
-        std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
-        for (size_t k2 = 0; k2 < pairs.size(); ++k2) pairs[(size_t)cur[(size_t)m.elemNodes[k2]]++] = (int32_t)k2;
-        c->dNodePtr.upload(ptr, c->stream);
-        c->dNodePair.upload(pairs, c->stream);
-        c->nodePairsValid = true;
-    }
+    ensure_node_pairs(c);
     DBuf<double> v, res;
     v.upload(elemVectors, (size_t)m.nElem * m.dim, c->stream);
     res.alloc((size_t)m.nNode);

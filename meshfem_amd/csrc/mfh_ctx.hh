@@ -55,7 +55,7 @@ struct mfh_ctx {
     int opDegree = 0;                 // 0 = the mesh's degree, 1 = forced degree 1
     mfh_ctx *p1 = nullptr;            // owned: the view (null until degree 1 is first asked for on a quadratic mesh)
     int64_t geoGen = 0, p1GeoGen = -1;   // element records (re)written / the generation the view's matrices were assembled from
-    DBuf<int32_t> dNodePtr, dNodePair;   // mfh_divergence: (element, local node) pairs grouped by node
+    DBuf<int32_t> dNodePtr, dNodePair;   // ensure_node_pairs: (element, local node) pairs grouped by node
     bool nodePairsValid = false;
     std::vector<double> matParams;    // host copy in the layout k_geometry expects
     DBuf<double> dMatParams;
@@ -434,6 +434,7 @@ void clear_fixed(mfh_ctx *c);
 void add_fixed(mfh_ctx *c, int64_t n, const int64_t *vars, const double *vals);
 void ensure_geometry(mfh_ctx *c, bool deferCheck = false);
 void finish_geometry(mfh_ctx *c);
+void ensure_node_pairs(mfh_ctx *c);    // dNodePtr / dNodePair of the current mesh
 void ensure_mf_cluster(mfh_ctx *c);
 void upload_mesh(mfh_ctx *c, bool deviceTables);
 void ensure_fixed_uploaded(mfh_ctx *c);

@@ -452,6 +452,21 @@ void launch_boundary_strain_field(const AsmArgs &a, const int32_t *elemNodes, co
                                   int wantStress, double *out, hipStream_t s);
 void launch_strain_field(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, int wantStress,
                          double *out, hipStream_t s);
+// Stress measures. what: bit mask 1 von Mises | 2 eigenvalues (ascending) | 4 eigenvectors (row-major, eigenvector k in column k); outputs that
+// are not requested may be null. launch_sym_measures: a field of n flattened symmetric matrices (tensor shear); launch_stress_measures: the
+// strain / stress of uNodes at the corners launch_strain_field evaluates, the tensor itself never written ([nElem][NQ] ...).
+void launch_sym_measures(int dim, int64_t n, const double *field, int what, double *vm, double *eval, double *evec, hipStream_t s);
+void launch_stress_measures(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, int wantStress, int what,
+                            double *vm, double *eval, double *evec, hipStream_t s);
+// max / argmax of the von Mises value over all corners in two stages (ties: lowest flat corner index; a NaN wins, the first one);
+// partV / partI: scratch of PEAK_GRID_CAP entries, outV / outI: one entry each
+constexpr int PEAK_GRID_CAP = 1024;
+void launch_peak_von_mises(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, int wantStress,
+                           double *partV, int64_t *partI, double *outV, int64_t *outI, hipStream_t s);
+// out[v][c] = sum vol_e field[e][corner | 0][c] / sum vol_e over the (element, corner) pairs of vertex v (node-pair list of launch_divergence,
+// code = e npe + j); field: [nElem][nq = 1 | dim + 1][nComp]
+void launch_vertex_average(int dim, int npe, int64_t nVert, const int32_t *nodePtr, const int32_t *nodePair, const double *geo, int geoStride,
+                           const double *field, int nq, int nComp, double *out, hipStream_t s);
 // out[pair(ij<=kl)][nVert][dim] += d(mutual energy)/d(vertex position)
 void launch_mutual_energy_differential(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *w,
                                        int64_t nNode, int64_t nVert, double *out, hipStream_t s);

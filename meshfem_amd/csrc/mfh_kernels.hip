@@ -1440,6 +1440,47 @@ DEV void sym_grad_u_at(const double (&xl)[(DIM == 3) ? (DEG == 1 ? 4 : 10) : (DE
         for (int r = p; r < DIM; ++r) ef[flat_idx<DIM>(p, r)] = 0.5 * (G[p][r] + G[r][p]);
 }
 
+// element prologue of k_strain_field and the stress-measure kernels: the element's barycentric gradients and its nodal values of uNodes
+template <int DIM, int DEG>
+DEV void load_elem_field(const LoadArgs &a, int64_t e, const double *__restrict__ uNodes, double (&gl)[DIM + 1][DIM],
+                         double (&xl)[(DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6)][DIM]) {
+    constexpr int NV = DIM + 1;
+    constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
+    const double *g = a.geo + e * a.geoStride;
+    const int32_t *en = a.elemNodes + e * NPE;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) gl[k][d] = g[k * DIM + d];
+#pragma unroll
+    for (int j = 0; j < NPE; ++j) {
+        const int64_t node = en[j];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) xl[j][d] = uNodes[node * DIM + d];
+    }
+}
+
+// flattened (tensor-shear) strain of the element's field at corner q, or the stress C : strain of the element record g
+template <int DIM, int DEG, int MAT>
+DEV void corner_tensor(const double *__restrict__ g, const double (&xl)[(DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6)][DIM],
+                       const double (&gl)[DIM + 1][DIM], int q, int wantStress, double (&ef)[DIM * (DIM + 1) / 2]) {
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    double G[DIM][DIM];
+    grad_u_at<DIM, DEG, true>(xl, gl, q, G);
+#pragma unroll
+    for (int p = 0; p < DIM; ++p)
+#pragma unroll
+        for (int r = p; r < DIM; ++r) ef[flat_idx<DIM>(p, r)] = 0.5 * (G[p][r] + G[r][p]);
+    if (wantStress) {
+        double sd[FL], sg[FL];
+#pragma unroll
+        for (int c = 0; c < FL; ++c) sd[c] = ef[c] * (c < DIM ? 1.0 : 2.0);
+        elem_D_apply<DIM, MAT>(g, sd, sg);
+#pragma unroll
+        for (int c = 0; c < FL; ++c) ef[c] = sg[c];
+    }
+}
+
 // Strain (or stress) field as per-element interpolants (Simulator::strainField / stressField, LinearElasticity.hh:511-526;
 // Element::strain :99-117): the nodal values of the degree-(DEG-1) interpolant, i.e. one value per element for P1 and the
 // values at the NV corners for P2. out: [nElem][NQ][flatLen].
@@ -1451,36 +1492,270 @@ __global__ void __launch_bounds__(256) k_strain_field(LoadArgs a, const double *
     constexpr int NQ = DEG == 1 ? 1 : NV;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.nElem; e += (int64_t)gridDim.x * 256) {
         const double *g = a.geo + e * a.geoStride;
-        const int32_t *en = a.elemNodes + e * NPE;
         double gl[NV][DIM], xl[NPE][DIM];
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-#pragma unroll
-            for (int d = 0; d < DIM; ++d) gl[k][d] = g[k * DIM + d];
-#pragma unroll
-        for (int j = 0; j < NPE; ++j) {
-            const int64_t node = en[j];
-#pragma unroll
-            for (int d = 0; d < DIM; ++d) xl[j][d] = uNodes[node * DIM + d];
-        }
+        load_elem_field<DIM, DEG>(a, e, uNodes, gl, xl);
         for (int q = 0; q < NQ; ++q) {
-            double G[DIM][DIM], ef[FL];
-            grad_u_at<DIM, DEG, true>(xl, gl, q, G);
-#pragma unroll
-            for (int p = 0; p < DIM; ++p)
-#pragma unroll
-                for (int r = p; r < DIM; ++r) ef[flat_idx<DIM>(p, r)] = 0.5 * (G[p][r] + G[r][p]);
-            if (wantStress) {
-                double sd[FL], sg[FL];
-#pragma unroll
-                for (int c = 0; c < FL; ++c) sd[c] = ef[c] * (c < DIM ? 1.0 : 2.0);
-                elem_D_apply<DIM, MAT>(g, sd, sg);
-#pragma unroll
-                for (int c = 0; c < FL; ++c) ef[c] = sg[c];
-            }
+            double ef[FL];
+            corner_tensor<DIM, DEG, MAT>(g, xl, gl, q, wantStress, ef);
 #pragma unroll
             for (int c = 0; c < FL; ++c) out[(e * NQ + q) * FL + c] = ef[c];
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stress measures (VonMises.hh, SymmetricMatrix.hh eigenvalues / eigenDecomposition, FieldPostProcessing.hh vertexAveragedField).
+// Everything per tensor lives in registers: every array below is indexed by unrolled compile-time constants only.
+// ------------------------------------------------------------------------------------------------
+constexpr int SM_VON_MISES = 1, SM_EIGENVALUES = 2, SM_EIGENVECTORS = 4;   // MFH_MEASURE_* of the C ABI
+
+// One Jacobi rotation in the (p, q) plane of a symmetric 3x3 matrix, annihilating a_pq; r is the third index. The columns p, q of the
+// accumulated rotations (v_kp, v_kq) follow when VEC. |theta| = inf (a_pq denormal against the diagonal gap) gives t = 0: the identity.
+template <bool VEC>
+DEV void jacobi_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p, double &v0q, double &v1p, double &v1q,
+                       double &v2p, double &v2q) {
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0.0;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp; arq = rq;
+    if (VEC) {
+        const double w0p = c * v0p - s * v0q, w0q = s * v0p + c * v0q;
+        const double w1p = c * v1p - s * v1q, w1q = s * v1p + c * v1q;
+        const double w2p = c * v2p - s * v2q, w2q = s * v2p + c * v2q;
+        v0p = w0p; v0q = w0q; v1p = w1p; v1q = w1q; v2p = w2p; v2q = w2q;
+    }
+}
+
+// order (la, column a) before (lb, column b)
+template <bool VEC>
+DEV void eig_cswap(double &la, double &lb, double &v0a, double &v0b, double &v1a, double &v1b, double &v2a, double &v2b) {
+    if (lb < la) {
+        double t = la; la = lb; lb = t;
+        if (VEC) {
+            t = v0a; v0a = v0b; v0b = t;
+            t = v1a; v1a = v1b; v1b = t;
+            t = v2a; v2a = v2b; v2b = t;
+        }
+    }
+}
+
+// s: flattened symmetric matrix in flat_idx order, TENSOR shear entries (what k_strain_field writes).
+//   vm   the von Mises scalar sqrt(|vonMisesExtractor<N>() : s|_F^2): 3D sqrt(3/2 dev s : dev s); 2D the plane-stress value
+//        sqrt(s00^2 + s11^2 - s00 s11 + 3 s01^2) (VonMises.hh:10-46), written as half a sum of squares so that nothing cancels
+//   lam  eigenvalues, ascending (SelfAdjointEigenSolver's order); V[i][k] = component i of the unit eigenvector of lam[k]
+// The matrix is divided by its largest |entry| first (entries near 1e+-150 neither overflow nor flush in the squares); a NaN entry makes
+// every output NaN. 3D: cyclic Jacobi on named scalars, pairs (0,1) (0,2) (1,2) per sweep, until the off-diagonal part is below 1e-20 of
+// the largest entry (quadratic convergence: a handful of sweeps; the closed trigonometric form loses digits near repeated eigenvalues).
+// 2D: mean -+ hypot(half difference, shear).
+template <int DIM, bool EIG, bool VEC>
+DEV void sym_measures(const double (&s)[DIM * (DIM + 1) / 2], double &vm, double (&lam)[DIM], double (&V)[DIM][DIM]) {
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    double m = 0.0;
+#pragma unroll
+    for (int c = 0; c < FL; ++c) m = fmax(m, fabs(s[c]));
+    if (!(m > 0.0)) m = 1.0;            // the zero matrix (fmax skips NaN entries: they pass through the division below)
+    double a[FL];
+#pragma unroll
+    for (int c = 0; c < FL; ++c) a[c] = s[c] / m;
+    if constexpr (DIM == 3) {
+        const double d01 = a[0] - a[1], d12 = a[1] - a[2], d20 = a[2] - a[0];
+        vm = m * sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3.0 * (a[3] * a[3] + a[4] * a[4] + a[5] * a[5]));
+        if (!EIG) return;
+        double a00 = a[0], a11 = a[1], a22 = a[2], a12 = a[3], a02 = a[4], a01 = a[5];
+        double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
+        for (int sweep = 0; sweep < 16; ++sweep) {
+            if (fabs(a01) + fabs(a02) + fabs(a12) <= 1e-20) break;      // (a NaN never passes: it spreads to every output)
+            jacobi_rotate<VEC>(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+            jacobi_rotate<VEC>(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+            jacobi_rotate<VEC>(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+        }
+        eig_cswap<VEC>(a00, a11, v00, v01, v10, v11, v20, v21);
+        eig_cswap<VEC>(a11, a22, v01, v02, v11, v12, v21, v22);
+        eig_cswap<VEC>(a00, a11, v00, v01, v10, v11, v20, v21);
+        lam[0] = m * a00; lam[1] = m * a11; lam[2] = m * a22;
+        if (VEC) {
+            V[0][0] = v00; V[0][1] = v01; V[0][2] = v02;
+            V[1][0] = v10; V[1][1] = v11; V[1][2] = v12;
+            V[2][0] = v20; V[2][1] = v21; V[2][2] = v22;
+        }
+    } else {
+        const double dd = a[0] - a[1];
+        vm = m * sqrt(0.5 * (dd * dd + a[0] * a[0] + a[1] * a[1]) + 3.0 * a[2] * a[2]);
+        if (!EIG) return;
+        const double mean = 0.5 * a[0] + 0.5 * a[1], d = 0.5 * dd, r = hypot(d, a[2]);
+        lam[0] = m * (mean - r);
+        lam[1] = m * (mean + r);
+        if (VEC) {
+            // (A - lam1 I) v = 0 from the row with the larger pivot: v = (d + r, s01) for d >= 0, (s01, r - d) otherwise
+            double x = d >= 0.0 ? d + r : a[2], y = d >= 0.0 ? a[2] : r - d;
+            const double n = hypot(x, y);
+            if (n > 0.0) { x /= n; y /= n; } else if (n == 0.0) { x = 0.0; y = 1.0; }
+            V[0][1] = x; V[1][1] = y;
+            V[0][0] = y; V[1][0] = -x;
+        }
+    }
+}
+
+// the requested measures of tensor i: vm[i], eval[i][DIM], evec[i][DIM][DIM] (row-major, eigenvector k in column k)
+template <int DIM>
+DEV void store_measures(const double (&s)[DIM * (DIM + 1) / 2], int what, int64_t i, double *__restrict__ vm, double *__restrict__ eval,
+                        double *__restrict__ evec) {
+    double v, lam[DIM], V[DIM][DIM];
+    if (what & SM_EIGENVECTORS) sym_measures<DIM, true, true>(s, v, lam, V);
+    else if (what & SM_EIGENVALUES) sym_measures<DIM, true, false>(s, v, lam, V);
+    else sym_measures<DIM, false, false>(s, v, lam, V);
+    if (what & SM_VON_MISES) vm[i] = v;
+    if (what & SM_EIGENVALUES) {
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) eval[i * DIM + k] = lam[k];
+    }
+    if (what & SM_EIGENVECTORS) {
+#pragma unroll
+        for (int r = 0; r < DIM; ++r)
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) evec[(i * DIM + r) * DIM + k] = V[r][k];
+    }
+}
+
+// measures of a caller's field of n flattened symmetric matrices: [n][flatLen]
+template <int DIM>
+__global__ void __launch_bounds__(256) k_sym_measures(int64_t n, const double *__restrict__ field, int what, double *__restrict__ vm,
+                                                     double *__restrict__ eval, double *__restrict__ evec) {
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double s[FL];
+#pragma unroll
+        for (int c = 0; c < FL; ++c) s[c] = field[i * FL + c];
+        store_measures<DIM>(s, what, i, vm, eval, evec);
+    }
+}
+
+// the same measures of the strain (stress) of the nodal displacements uNodes at the corners k_strain_field evaluates, fused: the tensor
+// is never written. vm: [nElem][NQ], eval: [nElem][NQ][DIM], evec: [nElem][NQ][DIM][DIM].
+template <int DIM, int DEG, int MAT>
+__global__ void __launch_bounds__(256) k_stress_measures(LoadArgs a, const double *__restrict__ uNodes, int wantStress, int what,
+                                                        double *__restrict__ vm, double *__restrict__ eval, double *__restrict__ evec) {
+    constexpr int NV = DIM + 1;
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
+    constexpr int NQ = DEG == 1 ? 1 : NV;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.nElem; e += (int64_t)gridDim.x * 256) {
+        const double *g = a.geo + e * a.geoStride;
+        double gl[NV][DIM], xl[NPE][DIM];
+        load_elem_field<DIM, DEG>(a, e, uNodes, gl, xl);
+        for (int q = 0; q < NQ; ++q) {
+            double ef[FL];
+            corner_tensor<DIM, DEG, MAT>(g, xl, gl, q, wantStress, ef);
+            store_measures<DIM>(ef, what, e * NQ + q, vm, eval, evec);
+        }
+    }
+}
+
+// Peak von Mises value over all corners with its flat corner index. The order is total, so the reduction gives the same pair in any
+// grouping: a NaN comes before every number, then the larger value, and among equals the lower index.
+DEV bool peak_before(double va, int64_t ia, double vb, int64_t ib) {
+    const bool na = va != va, nb = vb != vb;
+    if (na || nb) return na && (!nb || ia < ib);
+    return va > vb || (va == vb && ia < ib);
+}
+// workgroup-wide (256 lanes) reduction of (v, i) pairs; the result is valid in thread 0. lds: 4 values + 4 indices
+DEV void peak_block_reduce(double &v, int64_t &i, double *ldsV, long long *ldsI) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_down(v, off, 64);
+        const long long oi = __shfl_down((long long)i, off, 64);
+        if (peak_before(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { ldsV[w] = v; ldsI[w] = i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (peak_before(ldsV[k], ldsI[k], v, i)) { v = ldsV[k]; i = ldsI[k]; }
+    }
+}
+constexpr long long PEAK_NO_INDEX = 0x7fffffffffffffffLL;
+
+// first stage: one (value, index) pair per workgroup, partV / partI: [gridDim.x]
+template <int DIM, int DEG, int MAT>
+__global__ void __launch_bounds__(256) k_peak_von_mises(LoadArgs a, const double *__restrict__ uNodes, int wantStress, double *__restrict__ partV,
+                                                       long long *__restrict__ partI) {
+    constexpr int NV = DIM + 1;
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
+    constexpr int NQ = DEG == 1 ? 1 : NV;
+    __shared__ double ldsV[4];
+    __shared__ long long ldsI[4];
+    double best = -HUGE_VAL;
+    int64_t bestI = PEAK_NO_INDEX;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.nElem; e += (int64_t)gridDim.x * 256) {
+        const double *g = a.geo + e * a.geoStride;
+        double gl[NV][DIM], xl[NPE][DIM];
+        load_elem_field<DIM, DEG>(a, e, uNodes, gl, xl);
+        for (int q = 0; q < NQ; ++q) {
+            double ef[FL], v, lam[DIM], V[DIM][DIM];
+            corner_tensor<DIM, DEG, MAT>(g, xl, gl, q, wantStress, ef);
+            sym_measures<DIM, false, false>(ef, v, lam, V);
+            if (peak_before(v, e * NQ + q, best, bestI)) { best = v; bestI = e * NQ + q; }
+        }
+    }
+    peak_block_reduce(best, bestI, ldsV, ldsI);
+    if (threadIdx.x == 0) { partV[blockIdx.x] = best; partI[blockIdx.x] = bestI; }
+}
+
+// second stage: one workgroup over the partials
+__global__ void __launch_bounds__(256) k_peak_finish(int nPart, const double *__restrict__ partV, const long long *__restrict__ partI,
+                                                    double *__restrict__ outV, long long *__restrict__ outI) {
+    __shared__ double ldsV[4];
+    __shared__ long long ldsI[4];
+    double best = -HUGE_VAL;
+    int64_t bestI = PEAK_NO_INDEX;
+    for (int k = threadIdx.x; k < nPart; k += 256)
+        if (peak_before(partV[k], partI[k], best, bestI)) { best = partV[k]; bestI = partI[k]; }
+    peak_block_reduce(best, bestI, ldsV, ldsI);
+    if (threadIdx.x == 0) { outV[0] = best; outI[0] = bestI; }
+}
+
+// C0 volume-weighted vertex average of per-element corner values (vertexAveragedField, FieldPostProcessing.hh:24-47): one lane per
+// vertex walks the vertex's (element, local node) pairs of the node-pair list (ascending by element, code = e npe + j) and accumulates
+// vol_e value and vol_e in that order; nothing is added atomically. field: [nElem][nq][C] with nq = 1 (every corner takes the element's
+// value) or NV; this launch averages the CB components [c0, c0 + CB). A vertex of a single element takes that element's value as it is;
+// pairs with j >= NV (a caller-numbered quadratic mesh, where every node counts as a vertex) are no corners: such a node gets 0.
+template <int CB>
+__global__ void __launch_bounds__(256) k_vertex_average(int64_t nVert, const int32_t *__restrict__ nodePtr, const int32_t *__restrict__ nodePair,
+                                                       int npe, int NV, const double *__restrict__ geo, int geoStride,
+                                                       const double *__restrict__ field, int nq, int C, int c0, double *__restrict__ out) {
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < nVert; n += (int64_t)gridDim.x * 256) {
+        const int first = nodePtr[n], last = nodePtr[n + 1];
+        double acc[CB], w = 0.0;
+#pragma unroll
+        for (int k = 0; k < CB; ++k) acc[k] = 0.0;
+        int corners = 0;
+        for (int p = first; p < last; ++p) {
+            const int64_t code = nodePair[p], e = code / npe;
+            const int j = (int)(code - e * npe);
+            if (j >= NV) continue;
+            const double *f = field + (e * nq + (nq == 1 ? 0 : j)) * C + c0;
+            if (last - first == 1) {
+#pragma unroll
+                for (int k = 0; k < CB; ++k) acc[k] = f[k];
+                w = 1.0;
+            } else {
+                const double vol = geo[e * geoStride + 12];
+#pragma unroll
+                for (int k = 0; k < CB; ++k) acc[k] += vol * f[k];
+                w += vol;
+            }
+            ++corners;
+        }
+#pragma unroll
+        for (int k = 0; k < CB; ++k) out[n * C + c0 + k] = corners == 0 ? 0.0 : (last - first == 1 ? acc[k] : acc[k] / w);
     }
 }
 
@@ -2479,6 +2754,59 @@ void launch_strain_field(const AsmArgs &a, const int32_t *elemNodes, const doubl
 #define CALL(D, G, M) hipLaunchKernelGGL((k_strain_field<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, out)
     MFH_DISPATCH(a, CALL);
 #undef CALL
+    CHECK_LAUNCH();
+}
+
+void launch_sym_measures(int dim, int64_t n, const double *field, int what, double *vm, double *eval, double *evec, hipStream_t s) {
+    if (n <= 0) return;
+    const int grid = grid_for(n, 8192);
+    if (dim == 3) hipLaunchKernelGGL((k_sym_measures<3>), dim3(grid), dim3(256), 0, s, n, field, what, vm, eval, evec);
+    else hipLaunchKernelGGL((k_sym_measures<2>), dim3(grid), dim3(256), 0, s, n, field, what, vm, eval, evec);
+    CHECK_LAUNCH();
+}
+
+void launch_stress_measures(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, int wantStress, int what,
+                            double *vm, double *eval, double *evec, hipStream_t s) {
+    const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
+    const int grid = grid_for(a.nElem, 8192);
+#define CALL(D, G, M) hipLaunchKernelGGL((k_stress_measures<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, what, vm, eval, evec)
+    MFH_DISPATCH(a, CALL);
+#undef CALL
+    CHECK_LAUNCH();
+}
+
+void launch_peak_von_mises(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, int wantStress,
+                           double *partV, int64_t *partI, double *outV, int64_t *outI, hipStream_t s) {
+    const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
+    const int grid = grid_for(a.nElem, PEAK_GRID_CAP);
+    long long *pI = reinterpret_cast<long long *>(partI), *oI = reinterpret_cast<long long *>(outI);
+#define CALL(D, G, M) hipLaunchKernelGGL((k_peak_von_mises<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, partV, pI)
+    MFH_DISPATCH(a, CALL);
+#undef CALL
+    hipLaunchKernelGGL(k_peak_finish, dim3(1), dim3(256), 0, s, grid, (const double *)partV, (const long long *)pI, outV, oI);
+    CHECK_LAUNCH();
+}
+
+void launch_vertex_average(int dim, int npe, int64_t nVert, const int32_t *nodePtr, const int32_t *nodePair, const double *geo, int geoStride,
+                           const double *field, int nq, int nComp, double *out, hipStream_t s) {
+    if (nVert <= 0) return;
+    const int grid = grid_for(nVert);
+    for (int c0 = 0; c0 < nComp; c0 += 9) {          // components in register blocks of at most 9 (a full dim x dim tensor in 3D)
+        const int cb = std::min(9, nComp - c0);
+#define VA(CB) hipLaunchKernelGGL((k_vertex_average<CB>), dim3(grid), dim3(256), 0, s, nVert, nodePtr, nodePair, npe, dim + 1, geo, geoStride, field, nq, nComp, c0, out)
+        switch (cb) {
+        case 1: VA(1); break;
+        case 2: VA(2); break;
+        case 3: VA(3); break;
+        case 4: VA(4); break;
+        case 5: VA(5); break;
+        case 6: VA(6); break;
+        case 7: VA(7); break;
+        case 8: VA(8); break;
+        default: VA(9); break;
+        }
+#undef VA
+    }
     CHECK_LAUNCH();
 }
 

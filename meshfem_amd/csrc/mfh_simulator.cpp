@@ -863,6 +863,147 @@ mfh_status mfh_boundary_strain_field(mfh_ctx *c, const double *uNodes, int32_t w
     MFH_CATCH(c)
 }
 
+// ---- stress measures: von Mises, principal values, vertex averages, peak (docs/design/04_10_stress_measures.md)
+namespace {
+// an input array as the kernels read it: the caller's device pointer, or a device copy of its host array
+struct DevInput {
+    DBuf<double> buf;
+    const double *p = nullptr;
+    DevInput(const double *src, size_t n, bool onDevice, hipStream_t s) {
+        if (onDevice) { p = src; return; }
+        buf.alloc(n);
+        if (n) MFH_HIP(hipMemcpyAsync(buf.p, src, n * sizeof(double), hipMemcpyHostToDevice, s));
+        p = buf.p;
+    }
+};
+// an output array: the caller's device pointer, or a device buffer downloaded by finish() (null when not requested)
+struct DevOutput {
+    DBuf<double> buf;
+    double *p = nullptr, *host = nullptr;
+    DevOutput(double *dst, size_t n, bool wanted, bool onDevice) {
+        if (!wanted) return;
+        if (onDevice) { p = dst; return; }
+        buf.alloc(n);
+        p = buf.p; host = dst;
+    }
+    void finish(hipStream_t s) { if (host) buf.download(host, buf.n, s); }
+};
+void require_measure_outputs(int32_t what, const double *vm, const double *eval, const double *evec) {
+    require(what > 0 && what < 8, MFH_ERR_INVALID, "what: a mask of MFH_MEASURE_VON_MISES | MFH_MEASURE_EIGENVALUES | MFH_MEASURE_EIGENVECTORS");
+    require(!(what & MFH_MEASURE_VON_MISES) || vm, MFH_ERR_INVALID, "the von Mises output was requested but its pointer is null");
+    require(!(what & MFH_MEASURE_EIGENVALUES) || eval, MFH_ERR_INVALID, "the eigenvalues were requested but their pointer is null");
+    require(!(what & MFH_MEASURE_EIGENVECTORS) || evec, MFH_ERR_INVALID, "the eigenvectors were requested but their pointer is null");
+}
+// the preconditions of mfh_strain_field
+void require_strain_context(mfh_ctx *c) {
+    require(c->op == MFH_OP_ELASTICITY, MFH_ERR_STATE, "strain / stress fields are defined for the elasticity operator");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_geometry(c);
+}
+void vertex_average_device(mfh_ctx *c, const double *dField, int nq, int nComp, double *dOut) {
+    const HostMesh &m = c->mesh;
+    ensure_node_pairs(c);
+    k::launch_vertex_average(m.dim, m.npe, m.nVert, c->dNodePtr.p, c->dNodePair.p, c->dGeo.p, c->geoStride, dField, nq, nComp, dOut, c->stream);
+}
+void require_vertex_average_context(mfh_ctx *c) {
+    require(c->mesh.nOwned == c->mesh.nNode, MFH_ERR_UNSUPPORTED,
+            "vertex averages need all rows owned: the elements of other ranks are missing at the interface vertices of a row-partitioned context");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_geometry(c);
+}
+} // namespace
+
+mfh_status mfh_sym_measures(mfh_ctx *c, int32_t dim, int64_t n, const double *field, int32_t what, double *vonMises, double *eigenvalues,
+                            double *eigenvectors, int32_t onDevice) {
+    MFH_TRY(c)
+    require(c && field && n >= 0 && (dim == 2 || dim == 3), MFH_ERR_INVALID, "bad arguments");
+    require_measure_outputs(what, vonMises, eigenvalues, eigenvectors);
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    const size_t N = (size_t)n, d = (size_t)dim;
+    DevInput in(field, N * flat_len(dim), onDevice != 0, c->stream);
+    DevOutput vm(vonMises, N, what & MFH_MEASURE_VON_MISES, onDevice != 0), ev(eigenvalues, N * d, what & MFH_MEASURE_EIGENVALUES, onDevice != 0),
+        vec(eigenvectors, N * d * d, what & MFH_MEASURE_EIGENVECTORS, onDevice != 0);
+    k::launch_sym_measures(dim, n, in.p, what, vm.p, ev.p, vec.p, c->stream);
+    vm.finish(c->stream); ev.finish(c->stream); vec.finish(c->stream);
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_stress_measures(mfh_ctx *c, const double *uNodes, int32_t wantStress, int32_t what, double *vonMises, double *eigenvalues,
+                               double *eigenvectors, int32_t onDevice) {
+    MFH_TRY(c)
+    require(c && c->haveMesh && uNodes, MFH_ERR_STATE, "no mesh set");
+    require_measure_outputs(what, vonMises, eigenvalues, eigenvectors);
+    require_strain_context(c);
+    const HostMesh &m = c->mesh;
+    const size_t d = (size_t)m.dim, N = (size_t)m.nElem * (m.deg == 1 ? 1 : d + 1);
+    DevInput u(uNodes, (size_t)m.nNode * d, onDevice != 0, c->stream);
+    DevOutput vm(vonMises, N, what & MFH_MEASURE_VON_MISES, onDevice != 0), ev(eigenvalues, N * d, what & MFH_MEASURE_EIGENVALUES, onDevice != 0),
+        vec(eigenvectors, N * d * d, what & MFH_MEASURE_EIGENVECTORS, onDevice != 0);
+    k::launch_stress_measures(asm_args(c), c->dElemNodes.p, c->tables.intGrad.data(), u.p, wantStress, what, vm.p, ev.p, vec.p, c->stream);
+    vm.finish(c->stream); ev.finish(c->stream); vec.finish(c->stream);
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_vertex_average(mfh_ctx *c, const double *field, int32_t perCorner, int32_t nComp, double *out, int32_t onDevice) {
+    MFH_TRY(c)
+    require(c && c->haveMesh, MFH_ERR_STATE, "no mesh set");
+    require(field && out && nComp >= 1, MFH_ERR_INVALID, "bad arguments");
+    require_vertex_average_context(c);
+    const HostMesh &m = c->mesh;
+    const int nq = perCorner ? m.dim + 1 : 1;
+    DevInput in(field, (size_t)m.nElem * nq * nComp, onDevice != 0, c->stream);
+    DevOutput res(out, (size_t)m.nVert * nComp, true, onDevice != 0);
+    vertex_average_device(c, in.p, nq, nComp, res.p);
+    res.finish(c->stream);
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_vertex_averaged_strain(mfh_ctx *c, const double *uNodes, int32_t wantStress, double *out, int32_t onDevice) {
+    MFH_TRY(c)
+    require(c && c->haveMesh && uNodes && out, MFH_ERR_STATE, "no mesh set");
+    require_strain_context(c);
+    require_vertex_average_context(c);
+    const HostMesh &m = c->mesh;
+    const int d = m.dim, fl = flat_len(d), nq = m.deg == 1 ? 1 : d + 1;
+    DevInput u(uNodes, (size_t)m.nNode * d, onDevice != 0, c->stream);
+    DBuf<double> field;
+    field.alloc((size_t)m.nElem * nq * fl);
+    k::launch_strain_field(asm_args(c), c->dElemNodes.p, c->tables.intGrad.data(), u.p, wantStress, field.p, c->stream);
+    DevOutput res(out, (size_t)m.nVert * fl, true, onDevice != 0);
+    vertex_average_device(c, field.p, nq, fl, res.p);
+    res.finish(c->stream);
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_peak_von_mises(mfh_ctx *c, const double *uNodes, int32_t wantStress, double *value, int64_t *cornerIndex) {
+    MFH_TRY(c)
+    require(c && c->haveMesh && uNodes, MFH_ERR_STATE, "no mesh set");
+    require(value || cornerIndex, MFH_ERR_INVALID, "null outputs");
+    require_strain_context(c);
+    const HostMesh &m = c->mesh;
+    require(m.nElem > 0, MFH_ERR_INVALID, "the mesh has no elements");
+    DevInput u(uNodes, (size_t)m.nNode * m.dim, false, c->stream);
+    DBuf<double> partV, outV;
+    DBuf<int64_t> partI, outI;
+    partV.alloc(k::PEAK_GRID_CAP); partI.alloc(k::PEAK_GRID_CAP);
+    outV.alloc(1); outI.alloc(1);
+    k::launch_peak_von_mises(asm_args(c), c->dElemNodes.p, c->tables.intGrad.data(), u.p, wantStress, partV.p, partI.p, outV.p, outI.p, c->stream);
+    double v = 0;
+    int64_t i = 0;
+    outV.download(&v, 1, c->stream);
+    outI.download(&i, 1, c->stream);
+    if (value) *value = v;
+    if (cornerIndex) *cornerIndex = i;
+    MFH_CATCH(c)
+}
+
 mfh_status mfh_mutual_energy_differential(mfh_ctx *c, const double *w, double *out) {
     MFH_TRY(c)
     require(c && c->haveMesh && w && out, MFH_ERR_STATE, "no mesh set");
