@@ -378,6 +378,41 @@ mfh_status mfh_stress_measures(mfh_ctx* ctx, const double* uNodes, int32_t wantS
 mfh_status mfh_vertex_average(mfh_ctx* ctx, const double* field, int32_t perCorner, int32_t nComp, double* out, int32_t onDevice);
 mfh_status mfh_vertex_averaged_strain(mfh_ctx* ctx, const double* uNodes, int32_t wantStress, double* out, int32_t onDevice);
 mfh_status mfh_peak_von_mises(mfh_ctx* ctx, const double* uNodes, int32_t wantStress, double* value, int64_t* cornerIndex);
+/* ---- field sampler on the device (FieldSampler.hh: closestElementAndPoint, closestElementAndBaryCoords, closestNodeAndSqDist, contains,
+ * sample; docs/design/04_11_field_sampler.md). Query points P: [nP][dim]. The index -- a uniform cell grid over the elements, sorted on the
+ * device, and a second one over the boundary elements for the points outside the mesh -- is built on first use (or by mfh_sampler_build) and
+ * dropped by mfh_mesh_build, mfh_mesh_set, mfh_mesh_update_vertices and option "sampler_cell_scale" (factor on the cell sizes, default 1).
+ *   mfh_locate         elem[i]: the LOWEST-index element with min lambda >= -1e-12 at P[i] (contains(p, lambda, 1e-12)); bary: its barycentric
+ *                      coordinates [nP][dim+1]; closest = P[i], sqDist = 0. A point no element contains: the closest point C of the boundary
+ *                      under the total order (squared distance, boundary element index); elem = that boundary element's parent, bary = the
+ *                      coordinates of C in it, closest = C, sqDist = |P[i] - C|^2. A point with a NaN or infinite coordinate, and a point
+ *                      outside a mesh that has no boundary elements (mfh_mesh_set): elem -1 and NaN. Any output may be NULL.
+ *   mfh_sample_field   the field at (elem, bary) (MeshFieldSampler::sample): field has nComp >= 1 interleaved components per row and one row per
+ *                      vertex (sum_k B_k f(v_k)), per element (f(elem)) or per node (the degree's shape functions at bary); out: [nP][nComp];
+ *                      NaN rows where elem = -1. (elem, bary) stay on the device between the two kernels.
+ *   mfh_closest_node   the node of elem whose shape function is largest at bary (lowest local index on ties) and its squared distance to P[i];
+ *                      node -1 and NaN where elem = -1. Either output may be NULL.
+ * No floating-point atomics: the same call on the same context returns the same bits. onDevice as for mfh_mass_lumped: every array is a
+ * device pointer and the call returns after the context's stream has been synchronised. nP = 0 is valid.
+ * MFH_ERR_STATE: no mesh (or a matrix from mfh_matrix_set_upper_triplets); MFH_ERR_UNSUPPORTED: a row-partitioned context (nOwned < nNode);
+ * MFH_ERR_INVALID: a kind that is not one of MFH_FIELD_*, nComp < 1, a NULL array that is needed. */
+enum { MFH_FIELD_PER_VERTEX = 0, MFH_FIELD_PER_ELEMENT = 1, MFH_FIELD_PER_NODE = 2 };
+typedef struct mfh_sampler_grid_info {
+    int32_t built;                 /* 0: this grid has not been needed yet (every other member is 0) */
+    int32_t cells[3];              /* cells per axis (1 along z in 2D) */
+    int64_t items;                 /* elements / boundary elements */
+    int64_t pairs;                 /* (cell, item) entries */
+    int64_t max_cell_population;
+    double build_ms;               /* host clock around the build, synchronised */
+    double host_ms;                /* the part of build_ms spent in the host passes (bounding box, mean item extents) */
+} mfh_sampler_grid_info;
+typedef struct mfh_sampler_stats { mfh_sampler_grid_info elements, boundary; } mfh_sampler_stats;
+mfh_status mfh_sampler_build(mfh_ctx* ctx);
+mfh_status mfh_sampler_info(const mfh_ctx* ctx, mfh_sampler_stats* out);
+mfh_status mfh_locate(mfh_ctx* ctx, int64_t nP, const double* P, int32_t* elem, double* bary, double* closest, double* sqDist, int32_t onDevice);
+mfh_status mfh_sample_field(mfh_ctx* ctx, int64_t nP, const double* P, int32_t kind, const double* field, int32_t nComp, double* out,
+                            int32_t onDevice);
+mfh_status mfh_closest_node(mfh_ctx* ctx, int64_t nP, const double* P, int32_t* node, double* sqDist, int32_t onDevice);
 
 /* ---- discrete shape derivatives, forward mode (LinearElasticity.hh:234-330 at element level; Simulator level
  * :1297-1374). deltaP is a per-vertex perturbation field [nVert x dim] (indexed by the node id of the element corners:

@@ -15,6 +15,16 @@ PRECOND_BLOCK_JACOBI, PRECOND_JACOBI, PRECOND_NONE, PRECOND_TWO_LEVEL, PRECOND_M
 OP_ELASTICITY, OP_LAPLACIAN, OP_MASS, OP_MASS_VECTOR = 0, 1, 2, 3
 SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED = 1, 2, 4
 MEASURE_VON_MISES, MEASURE_EIGENVALUES, MEASURE_EIGENVECTORS = 1, 2, 4
+FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE = 0, 1, 2
+
+
+class SamplerGridInfo(C.Structure):
+    _fields_ = [("built", C.c_int32), ("cells", C.c_int32 * 3), ("items", C.c_int64), ("pairs", C.c_int64),
+                ("max_cell_population", C.c_int64), ("build_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+class SamplerStats(C.Structure):
+    _fields_ = [("elements", SamplerGridInfo), ("boundary", SamplerGridInfo)]
 
 
 class SolveInfo(C.Structure):
@@ -120,6 +130,11 @@ PROTOTYPES = {
     "mfh_vertex_average": (_i32, [_P, _P, _i32, _i32, _P, _i32]),
     "mfh_vertex_averaged_strain": (_i32, [_P, _P, _i32, _P, _i32]),
     "mfh_peak_von_mises": (_i32, [_P, _P, _i32, C.POINTER(_f64), _pi64]),
+    "mfh_sampler_build": (_i32, [_P]),
+    "mfh_sampler_info": (_i32, [_P, C.POINTER(SamplerStats)]),
+    "mfh_locate": (_i32, [_P, _i64, _P, _P, _P, _P, _P, _i32]),
+    "mfh_sample_field": (_i32, [_P, _i64, _P, _i32, _P, _i32, _P, _i32]),
+    "mfh_closest_node": (_i32, [_P, _i64, _P, _P, _P, _i32]),
     "mfh_mesh_get_boundary_elem_parents": (_i32, [_P, _P]),
     "mfh_mesh_get_boundary_elem_internal": (_i32, [_P, _P]),
     "mfh_mesh_update_vertices": (_i32, [_P, _P]),

@@ -608,6 +608,70 @@ class Context:
         self._ck(self.lib.mfh_peak_von_mises(self.h, ptr(u), int(bool(stress)), C.byref(v), C.byref(i)))
         return v.value, i.value
 
+    # ---------------------------------------------------------------- field sampler (FieldSampler.hh)
+    def _points(self, P):
+        P = as_f64(P)
+        if P.ndim != 2 or P.shape[1] != self.dim:
+            raise ValueError("expected query points [nP, dim]")
+        return P
+
+    def sampler_build(self):
+        """Build the element grid of the field sampler now (it is otherwise built by the first query)."""
+        self._ck(self.lib.mfh_sampler_build(self.h))
+
+    def sampler_info(self):
+        """{"elements": {...}, "boundary": {...}} with built, cells (per axis), items, pairs, max_cell_population, build_ms, host_ms of each grid."""
+        st = L.SamplerStats()
+        self._ck(self.lib.mfh_sampler_info(self.h, C.byref(st)))
+        return {name: {"built": bool(g.built), "cells": [int(x) for x in g.cells], "items": int(g.items), "pairs": int(g.pairs),
+                       "max_cell_population": int(g.max_cell_population), "build_ms": float(g.build_ms), "host_ms": float(g.host_ms)}
+                for name, g in (("elements", st.elements), ("boundary", st.boundary))}
+
+    def locate(self, P):
+        """(I [nP] int32, B [nP, dim+1], C [nP, dim], sqDist [nP]) of the query points P [nP, dim]: the lowest-index element containing the point
+        (min lambda >= -1e-12) with its barycentric coordinates, C = P and sqDist = 0; for a point outside the mesh the parent element of the
+        closest boundary element, the coordinates of the closest point C in it and |P - C|^2. NaN / infinite points: I = -1 and NaN."""
+        P = self._points(P)
+        n = len(P)
+        I, B, Cl, d2 = np.empty(n, dtype=np.int32), np.empty((n, self.dim + 1)), np.empty((n, self.dim)), np.empty(n)
+        self._ck(self.lib.mfh_locate(self.h, n, ptr(P), ptr(I), ptr(B), ptr(Cl), ptr(d2), 0))
+        return I, B, Cl, d2
+
+    def contains(self, P, eps=1e-10):
+        """FieldSampler::contains: squared distance to the mesh <= eps^2"""
+        P = self._points(P)
+        d2 = np.empty(len(P))
+        self._ck(self.lib.mfh_locate(self.h, len(P), ptr(P), None, None, None, ptr(d2), 0))
+        return d2 <= eps * eps
+
+    def sample(self, P, field_values):
+        """The field at the points P (at their closest points of the mesh where they lie outside). field_values has one row per vertex, per
+        element or per node -- detected from the row count in that order, like the reference -- and any number of components per row."""
+        P = self._points(P)
+        f = as_f64(field_values)
+        rows = f.shape[0] if f.ndim else 0
+        if rows == self.n_vert:
+            kind = L.FIELD_PER_VERTEX
+        elif rows == self.n_elem:
+            kind = L.FIELD_PER_ELEMENT
+        elif rows == self.n_node:
+            kind = L.FIELD_PER_NODE
+        else:
+            raise ValueError("Invalid fieldValues size")
+        tail = f.shape[1:]
+        ncomp = int(np.prod(tail)) if tail else 1
+        out = np.empty((len(P),) + tuple(tail))
+        self._ck(self.lib.mfh_sample_field(self.h, len(P), ptr(P), kind, ptr(f), ncomp, ptr(out), 0))
+        return out
+
+    def closest_node(self, P):
+        """(NI [nP] int32, sqDist [nP]): the node of the located element whose shape function is largest at the point, and its squared
+        distance to the query point (closestNodeAndSqDist)"""
+        P = self._points(P)
+        NI, d2 = np.empty(len(P), dtype=np.int32), np.empty(len(P))
+        self._ck(self.lib.mfh_closest_node(self.h, len(P), ptr(P), ptr(NI), ptr(d2), 0))
+        return NI, d2
+
     def average_stress(self, u_nodes):
         u = as_f64(u_nodes)
         out = np.empty((self.n_elem, flat_len(self.dim)))

@@ -104,6 +104,7 @@ void upload_mesh(mfh_ctx *c, bool deviceTables) {
     drop_p1_view(c);                 // a forced-degree-1 view belongs to the previous mesh
     c->opDegree = 0;
     c->nodePairsValid = false;
+    sampler_drop(c);
     if (!c->hostOnly && !deviceTables) {      // (deviceTables: the device topology has written both from the vertices)
         require_device(c);
         MFH_HIP(hipSetDevice(c->device));
@@ -1294,6 +1295,7 @@ mfh_status mfh_mesh_update_vertices(mfh_ctx *c, const double *vertPos) {
     c->autoStretch = -1.0;
     c->geoValid = false;
     c->hGeoValid = false;
+    sampler_drop(c);                 // the cell grids hold the old positions
     invalidate_matrix(c);
     MFH_CATCH(c)
 }
@@ -2292,6 +2294,11 @@ mfh_status mfh_set_option(mfh_ctx *c, const char *key, double value) {
         c->matrixStorage = (int)value;
     }
     else if (k2 == "symbolic_device") { c->symbolicDevice = value != 0; invalidate_symbolic(c); }
+    else if (k2 == "sampler_cell_scale") {
+        require(value > 0 && std::isfinite(value), MFH_ERR_INVALID, "sampler_cell_scale must be positive and finite");
+        c->samplerCellScale = value;
+        sampler_drop(c);
+    }
     else if (k2 == "xcd_swizzle") c->xcdSwizzle = std::max(0, (int)value);   // 1: contiguous eighths; G > 1: runs of G items per XCD
     else if (k2 == "pcg_graph") c->useGraph = value != 0;
     else if (k2 == "refine") c->refine = value != 0;

@@ -57,6 +57,25 @@ struct mfh_ctx {
     int64_t geoGen = 0, p1GeoGen = -1;   // element records (re)written / the generation the view's matrices were assembled from
     DBuf<int32_t> dNodePtr, dNodePair;   // ensure_node_pairs: (element, local node) pairs grouped by node
     bool nodePairsValid = false;
+    // Field sampler (mfh_sampler.hip, docs/design/04_11_field_sampler.md): uniform cell grids over the elements and over the boundary elements,
+    // built on first use and dropped with the mesh or its vertex positions (sampler_drop). A grid lists every item in each cell its inflated
+    // bounding box overlaps; the list of a cell is ascending in item index.
+    struct SamplerGrid {
+        bool valid = false;
+        int nc[3] = {1, 1, 1};            // cells per axis
+        double org[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, cs[3] = {1, 1, 1};   // the inflated bounding box [org, hi] and the cell sizes (org + nc cs >= hi)
+        int64_t nItems = 0, nPairs = 0, maxPop = 0;
+        double buildMs = 0, hostMs = 0;   // whole build / its host passes (bounding box, mean extents)
+        DBuf<int32_t> cellStart, items;   // [nCells + 1], [nPairs]
+        void reset() { valid = false; nItems = nPairs = maxPop = 0; buildMs = hostMs = 0; cellStart.release(); items.release(); }
+    };
+    struct Sampler {
+        SamplerGrid elem, bdry;
+        double pad = 0;                   // 1e-9 of the bounding-box diagonal
+        double bbMin[3] = {0, 0, 0}, bbMax[3] = {0, 0, 0};   // the mesh's bounding box (set with the element grid)
+        DBuf<int32_t> bdryVerts, bdryParent;   // [nBE][dim] vertex ids, [nBE] parent element
+    } sampler;
+    double samplerCellScale = 1.0;    // option "sampler_cell_scale": factor on the cell sizes (mean element bounding-box extent per axis)
     std::vector<double> matParams;    // host copy in the layout k_geometry expects
     DBuf<double> dMatParams;
     const double *dMatBorrowed = nullptr;   // linear level of a multigrid hierarchy: the parent's per-element table on the device (the child lives no longer than it)
@@ -435,6 +454,7 @@ void add_fixed(mfh_ctx *c, int64_t n, const int64_t *vars, const double *vals);
 void ensure_geometry(mfh_ctx *c, bool deferCheck = false);
 void finish_geometry(mfh_ctx *c);
 void ensure_node_pairs(mfh_ctx *c);    // dNodePtr / dNodePair of the current mesh
+void sampler_drop(mfh_ctx *c);         // the field sampler's grids describe the previous mesh / vertex positions (mfh_sampler.hip)
 void ensure_mf_cluster(mfh_ctx *c);
 void upload_mesh(mfh_ctx *c, bool deviceTables);
 void ensure_fixed_uploaded(mfh_ctx *c);

@@ -1,5 +1,5 @@
 """Compiled pybind11 modules named like the reference's extension modules (src/python_bindings/CMakeLists.txt:10-33):
-`mesh`, `tensors`, `sparse_matrices`, `periodic_homogenization`, over the C ABI / the C++ facade of libmeshfem_hip.
+`mesh`, `tensors`, `sparse_matrices`, `periodic_homogenization`, `differential_operators`, `field_sampler`, over the C ABI / the C++ facade of libmeshfem_hip.
 
     import sys, meshfem_amd.pybind; sys.path.insert(0, meshfem_amd.pybind.PATH)
     import mesh, tensors, sparse_matrices, periodic_homogenization

@@ -1,4 +1,4 @@
-"""Build the compiled pybind11 modules `mesh`, `tensors`, `sparse_matrices`, `periodic_homogenization`, `differential_operators` (the names of the
+"""Build the compiled pybind11 modules `mesh`, `tensors`, `sparse_matrices`, `periodic_homogenization`, `differential_operators`, `field_sampler` (the names of the
 reference's extension modules, src/python_bindings/CMakeLists.txt:10-33) in-tree, linked against ../libmeshfem_hip.so.
     import sys, meshfem_amd.pybind; sys.path.insert(0, meshfem_amd.pybind.PATH); import mesh, tensors, ..."""
 import os
@@ -8,7 +8,7 @@ import sysconfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "src")
-MODULES = ["tensors", "mesh", "sparse_matrices", "periodic_homogenization", "differential_operators"]
+MODULES = ["tensors", "mesh", "sparse_matrices", "periodic_homogenization", "differential_operators", "field_sampler"]
 SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
 
