@@ -465,6 +465,34 @@ mfh_status mfh_mass_lumped(mfh_ctx* ctx, double* diagOut, int32_t onDevice);
  * (MFH_ERR_UNSUPPORTED on quadratic ones). Gather form on the device, no atomics (k_divergence). */
 mfh_status mfh_divergence(mfh_ctx* ctx, const double* elemVectors /* nElem x dim */, double* out /* nNode */);
 
+/* ---------------------------------------------------------------- vibrational modes
+ * The nev smallest eigenpairs of K x = lambda M x (1 <= nev <= 20): K the elasticity operator of the context, M = density (> 0) times the consistent
+ * vector-valued mass matrix of the mesh's own degree (MassMatrix::construct_vector_valued) -- the reference's
+ * smallestNonzeroGenEigenpairsPSDKnownKernel (Eigensolver.hh; shift-invert Lanczos over CHOLMOD there). Here: LOBPCG on the device with the
+ * context's preconditioner (docs/design/04_12_modes.md). lambda ascending; the rows of X are M-orthonormal, each with its entry of largest
+ * modulus positive.
+ *   flags == 0 (clamped): the fixed variables of the context (mfh_fix_variables; their values are taken as 0) are removed from the pencil and
+ *     X is 0 there. They must leave no rigid motion free (MFH_ERR_UNSUPPORTED otherwise). Any DoF map mfh_solve accepts.
+ *   MFH_MODES_FREE: no fixed variables and the identity DoF map (MFH_ERR_UNSUPPORTED otherwise). The 6 (3D) / 3 (2D) rigid-body modes are a known
+ *     kernel: the iteration runs in their M-orthogonal complement and returns the smallest NON-ZERO eigenvalues. The preconditioner is the one
+ *     the rigid-motion-constrained solve uses on its singular K (multigrid with the dense level pinned; block-Jacobi in place of two-level:
+ *     info->note says so).
+ * A mode counts as converged at ||K x - lambda M x||_2 / (lambda ||M x||_2) <= rtol (written to residuals, may be null). maxit reached:
+ * MFH_ERR_NOT_CONVERGED with the outputs filled, like mfh_solve_batch. K and M are resident together (the mass values live in a buffer of their own
+ * beside K's; mfh_set_operator is not involved). The product with M needs both triangles of the pattern: on a context that stores the upper one
+ * (quadratic elasticity by default) the call re-runs the symbolic phase with both for its own duration -- info->note says so, option
+ * "matrix_storage" is not changed and the next call of any other entry point sees the storage it would have seen. Unpartitioned contexts,
+ * elasticity, not under the forced-degree-1 view (MFH_ERR_UNSUPPORTED). */
+enum { MFH_MODES_FREE = 1 };
+typedef struct mfh_modes_info {
+    int32_t converged, iterations, nLocked, precondUsed, blockSize, restarts;   /* precondUsed: the MFH_PRECOND_* that was applied */
+    double  maxResidual, solve_ms, setup_ms;
+    const char* note;                                                            /* owned by the context, valid until its next call */
+} mfh_modes_info;
+mfh_status mfh_modes(mfh_ctx* ctx, int32_t nev, double density, int32_t flags, double rtol, int32_t maxit,
+                     double* lambda /* nev */, double* X /* nev x dim*nDoF, row per mode */, double* residuals /* nev or NULL */,
+                     mfh_modes_info* info);
+
 /* ---------------------------------------------------------------- multi-GPU solve (one process per GPU)
  * The reference is single-process (TBB, Parallelism.hh:31-43): these entry points have no counterpart to cite beyond the
  * serial path they parallelise (Simulator::solve, LinearElasticity.hh:479-487; SPSDSystem::solve, SparseMatrices.hh:2515-2606).

@@ -14,6 +14,10 @@ extern "C" {
 mfh_status mfh_time_assembly_kernel(mfh_ctx* ctx, int32_t mode, int32_t reps, double* avg_ms);
 /* the same for one application of the operator the PCG uses (see "matrix_free") on internal scratch vectors */
 mfh_status mfh_time_spmv_kernel(mfh_ctx* ctx, int32_t reps, double* avg_ms);
+/* average device time (ms) of `reps` back-to-back k_block_gram calls (both stages) on hashed n x p and n x q blocks, and of `reps` device-to-device
+ * copies of the same n (p + q) doubles in the same process: the kernel is bound by reading those bytes (the copy also writes them) --
+ * scripts/probe_modes.py's roofline */
+mfh_status mfh_time_block_gram(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, int32_t reps, double* gram_ms, double* copy_ms);
 /* matrix-free operator in use? (see option "matrix_free"); for the cluster variant (mode 4): number of element blocks,
  * of (block, row) accumulators, of interface partial sums kept in HBM, and the largest block (LDS accumulators) */
 mfh_status mfh_matrix_free_info(mfh_ctx* ctx, int32_t* active, int32_t* mode, int64_t* nBlocks, int64_t* nBlockRows,
@@ -62,6 +66,15 @@ mfh_status mfh_debug_row_chunks(int64_t nRows, const int32_t* rowPtr, int32_t ch
  * returned and its message copied to msg (capacity msgCap; may be null) */
 mfh_status mfh_debug_pcg_watch(int64_t n, const double* rr, const double* pKp, const uint8_t* known, double threshold, int32_t window,
                                int64_t lastComplete, int64_t* convergedAt, char* msg, int64_t msgCap);
+/* test hook (host only, no context): the Rayleigh-Ritz step of mfh_modes -- all eigenpairs of the dense symmetric-definite pencil A v = w B v
+ * (row-major n x n, n <= 72; the stored upper triangles are read) by Cholesky reduction to standard form and cyclic Jacobi. w ascending, column k
+ * of V (row-major n x n) the eigenvector of w[k], V^T B V = I. MFH_ERR_INVALID: B not positive definite */
+mfh_status mfh_debug_sym_gen_eig(int64_t n, const double* A, const double* B, double* w, double* V);
+/* test hooks: the tall-skinny block kernels of mfh_modes on host arrays. A: n x p, B: n x q, column-major (column j at A + j n);
+ * G = A^T B (p x q row-major) through k_block_gram and its fixed-order second stage. p, q in [1, 24] */
+mfh_status mfh_debug_block_gram(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, const double* A, const double* B, double* G);
+/* Y = A C through k_block_update: A n x p and Y n x q column-major, C p x q row-major */
+mfh_status mfh_debug_block_update(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, const double* A, const double* C, double* Y);
 
 
 /* ---------------------------------------------------------------- device-pointer building blocks

@@ -16,6 +16,7 @@ OP_ELASTICITY, OP_LAPLACIAN, OP_MASS, OP_MASS_VECTOR = 0, 1, 2, 3
 SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED = 1, 2, 4
 MEASURE_VON_MISES, MEASURE_EIGENVALUES, MEASURE_EIGENVECTORS = 1, 2, 4
 FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE = 0, 1, 2
+MODES_FREE = 1
 
 
 class SamplerGridInfo(C.Structure):
@@ -34,6 +35,17 @@ class SolveInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ModesInfo(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("nLocked", C.c_int32), ("precondUsed", C.c_int32),
+                ("blockSize", C.c_int32), ("restarts", C.c_int32), ("maxResidual", C.c_double), ("solve_ms", C.c_double),
+                ("setup_ms", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
 
 
 class DistStats(C.Structure):
@@ -148,6 +160,7 @@ PROTOTYPES = {
     "mfh_set_operator_degree": (_i32, [_P, _i32]),
     "mfh_mass_lumped": (_i32, [_P, _P, _i32]),
     "mfh_divergence": (_i32, [_P, _P, _P]),
+    "mfh_modes": (_i32, [_P, _i32, _f64, _i32, _f64, _i32, _P, _P, _P, C.POINTER(ModesInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -190,6 +203,7 @@ PROTOTYPES = {
     "mfh_get_timing": (_i32, [_P, C.POINTER(Timing)]),
     "mfh_time_assembly_kernel": (_i32, [_P, _i32, _i32, C.POINTER(_f64)]),
     "mfh_time_spmv_kernel": (_i32, [_P, _i32, C.POINTER(_f64)]),
+    "mfh_time_block_gram": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_set_option": (_i32, [_P, C.c_char_p, _f64]),
     "mfh_debug_spd_inverse": (_i32, [_i64, _P]),
     "mfh_debug_spd_inverse_device": (_i32, [_P, _i64, _P]),
@@ -201,6 +215,9 @@ PROTOTYPES = {
     "mfh_debug_pcg_watch": (_i32, [_i64, _P, _P, _P, _f64, _i32, _i64, _P, _P, _i64]),
     "mfh_debug_apply_operator": (_i32, [_P, _i32, _i32, _i32, _P, _P, _P]),
     "mfh_debug_apply_precond": (_i32, [_P, _i32, _P, _P]),
+    "mfh_debug_sym_gen_eig": (_i32, [_i64, _P, _P, _P, _P]),
+    "mfh_debug_block_gram": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
+    "mfh_debug_block_update": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
 }
 
 # callback types of mfh_comm_create_callbacks

@@ -408,6 +408,47 @@ class Context:
         self._ck(st)
         return u, self.last_infos
 
+    def modes(self, nev, density=1.0, free=False, rtol=1e-6, maxit=500):
+        """(lam, X, info): the nev smallest eigenpairs of K x = lam M x (mfh_modes), M = density x the consistent vector-valued mass matrix.
+        free=False: clamped at the context's fixed variables; free=True: the free body, rigid-body modes excluded. X: [nev, dim * n_dof],
+        rows M-orthonormal. info["residuals"] holds ||K x - lam M x|| / (lam ||M x||) per mode. Raises on MFH_ERR_NOT_CONVERGED like solve();
+        what was reached is then in self.last_modes = (lam, X, info)."""
+        nev = int(nev)
+        n = self.bs * self.n_dof
+        lam, X, res = np.zeros(max(nev, 0)), np.zeros((max(nev, 0), n)), np.zeros(max(nev, 0))
+        info = L.ModesInfo()
+        st = self.lib.mfh_modes(self.h, nev, float(density), L.MODES_FREE if free else 0, float(rtol), int(maxit), ptr(lam), ptr(X), ptr(res),
+                                C.byref(info))
+        d = info.as_dict()
+        d["residuals"] = res
+        self.last_modes = (lam, X, d)
+        self._ck(st)
+        return lam, X, d
+
+    def debug_sym_gen_eig(self, A, B):
+        """(w, V) of the dense pencil A v = w B v by the Rayleigh-Ritz routine of mfh_modes (test hook mfh_debug_sym_gen_eig)."""
+        A, B = as_f64(A), as_f64(B)
+        n = A.shape[0]
+        w, V = np.empty(n), np.empty((n, n))
+        self._ck(self.lib.mfh_debug_sym_gen_eig(n, ptr(A), ptr(B), ptr(w), ptr(V)))
+        return w, V
+
+    def debug_block_gram(self, A, B):
+        """A^T B for A [n, p], B [n, q] through k_block_gram (test hook mfh_debug_block_gram)."""
+        A, B = np.asfortranarray(A, dtype=np.float64), np.asfortranarray(B, dtype=np.float64)
+        n, p, q = A.shape[0], A.shape[1], B.shape[1]
+        G = np.empty((p, q))
+        self._ck(self.lib.mfh_debug_block_gram(self.h, n, p, q, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), ptr(G)))
+        return G
+
+    def debug_block_update(self, A, Cm):
+        """A C for A [n, p], C [p, q] through k_block_update (test hook mfh_debug_block_update)."""
+        A, Cm = np.asfortranarray(A, dtype=np.float64), as_f64(Cm)
+        n, p, q = A.shape[0], A.shape[1], Cm.shape[1]
+        Y = np.empty((n, q), order="F")
+        self._ck(self.lib.mfh_debug_block_update(self.h, n, p, q, A.ctypes.data_as(C.c_void_p), ptr(Cm), Y.ctypes.data_as(C.c_void_p)))
+        return Y
+
     def apply_K(self, u):
         u = as_f64(u)
         nr, nc, _ = self.matrix_info() if self._assembled_info() else (self.n_dof, self.n_dof, 0)
@@ -842,6 +883,12 @@ class Context:
         v = C.c_double()
         self._ck(self.lib.mfh_time_spmv_kernel(self.h, int(reps), C.byref(v)))
         return v.value
+
+    def time_block_gram(self, n, p, q, reps=10):
+        """(gram_ms, copy_ms): k_block_gram on n x p, n x q blocks against a device-to-device copy of the same bytes (mfh_time_block_gram)."""
+        g, cp = C.c_double(), C.c_double()
+        self._ck(self.lib.mfh_time_block_gram(self.h, int(n), int(p), int(q), int(reps), C.byref(g), C.byref(cp)))
+        return g.value, cp.value
 
     def set_option(self, key, value):
         self._ck(self.lib.mfh_set_option(self.h, key.encode(), float(value)))

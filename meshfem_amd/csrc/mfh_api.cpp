@@ -46,7 +46,13 @@ void invalidate_matrix(mfh_ctx *c) {
     c->tl.valid = false;
     c->mg.valid = false;
 }
+void drop_mass(mfh_ctx *c) {
+    c->dMassVals.release();
+    c->massValid = false;
+    c->massGeoGen = -1;
+}
 void invalidate_symbolic(mfh_ctx *c) {
+    drop_mass(c);
     ++c->listsGen;                  // overlap lists of a partitioned solve (Dist::opList) are stale from here on
     c->symValid = false;
     c->mfValid = false;
@@ -244,7 +250,7 @@ void ensure_host_colidx(mfh_ctx *c) {
 
 // an option / operator change may have changed the storage the matrix should have: drop the K pattern (the operator lists stay)
 void refresh_storage_rule(mfh_ctx *c) {
-    if (c->symValid && resolve_upper_storage(c) != c->upperOnly) { c->symValid = false; invalidate_matrix(c); }
+    if (c->symValid && resolve_upper_storage(c) != c->upperOnly) { c->symValid = false; invalidate_matrix(c); drop_mass(c); }
 }
 
 void ensure_symbolic(mfh_ctx *c, bool wantScatter) {
@@ -252,6 +258,7 @@ void ensure_symbolic(mfh_ctx *c, bool wantScatter) {
     refresh_storage_rule(c);
     if (c->symValid && (!wantScatter || c->symHasScatter)) return;
     c->upperOnly = resolve_upper_storage(c);
+    drop_mass(c);
     RoctxRange range("Compress Matrix");   // sumRepeated's sort / merge, hoisted into the once-per-mesh symbolic phase
     double t0 = now_ms();
     if (!c->hostOnly && c->symbolicDevice && c->contribOrder == 1) {
@@ -457,6 +464,33 @@ k::SpmvArgs spmv_args(mfh_ctx *c, bool masked) {
     a.fixedMask = masked ? c->dFixedMask.p : nullptr;
     a.xcd = c->xcdSwizzle == 1;
     a.kron = c->kron() ? 1 : 0;
+    return a;
+}
+
+// The mass matrix beside K: the gather assembly with MAT_MASS into a value buffer of its own (one double per block), on the pattern and gather
+// lists K is assembled with. The pattern must hold both triangles (k_spmv_kron multiplies by the stored values).
+void ensure_mass(mfh_ctx *c) {
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the resident mass matrix needs a mesh on a device");
+    ensure_geometry(c);
+    ensure_symbolic(c, false);
+    require_full_storage(c, "the resident mass matrix (k_spmv_kron)");
+    if (c->massValid && c->massGeoGen == c->geoGen && c->dMassVals.p) return;
+    c->dMassVals.alloc(tiled_count(c->sym.nnzb, 1));
+    c->dMassVals.zero(c->stream);      // (the padding of the last tile)
+    k::AsmArgs a = asm_args(c);
+    a.mat = MAT_MASS;
+    a.vals = c->dMassVals.p;
+    k::launch_assemble_gather(a, c->stream);
+    c->massValid = true;
+    c->massGeoGen = c->geoGen;
+}
+
+k::SpmvArgs mass_spmv_args(mfh_ctx *c, bool masked) {
+    k::SpmvArgs a = spmv_args(c, masked);
+    a.dim = c->mesh.dim;
+    a.vals = c->dMassVals.p;
+    a.vals32 = nullptr;
+    a.kron = 1;
     return a;
 }
 
@@ -1296,6 +1330,7 @@ mfh_status mfh_mesh_update_vertices(mfh_ctx *c, const double *vertPos) {
     c->geoValid = false;
     c->hGeoValid = false;
     sampler_drop(c);                 // the cell grids hold the old positions
+    drop_mass(c);
     invalidate_matrix(c);
     MFH_CATCH(c)
 }

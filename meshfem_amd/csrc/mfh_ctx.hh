@@ -160,6 +160,16 @@ struct mfh_ctx {
     std::string placementNote;        // why the trials stopped early (empty: they did not)
     DBuf<float> dVals32;              // FP32 copy of dVals for the smoother of a multigrid linear level (built by ensure_multigrid, dropped whenever dVals is rewritten)
     bool assembled = false;
+    // The consistent mass matrix resident BESIDE K (mfh_modes, mfh_modes.hip): one double per stored block of the pattern, both triangles, density 1
+    // (the caller of the product scales). Written by k_assemble_gather<DIM, DEG, MAT_MASS> into this buffer, multiplied by k_spmv_kron from it;
+    // neither touches dVals, and mfh_set_operator does not touch this. Derived from the pattern and the element records: dropped with either
+    // (drop_mass; massGeoGen = the geoGen it was assembled from).
+    DBuf<double> dMassVals;
+    bool massValid = false;
+    int64_t massGeoGen = -1;
+    bool modesWide = false;           // mfh_modes in progress on a context whose storage rule says "upper triangle": the symbolic phase builds both
+                                      // (resolve_upper_storage) until the call returns; option matrix_storage itself is not changed
+    std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
 
     // ---- constraints (SPSDSystem state)
     std::vector<int64_t> fixedVars;
@@ -421,6 +431,7 @@ inline void check_residual_gap(const mfh_solve_info &li, double rtol) {
 
 // the storage the next symbolic phase will build (see mfh_ctx::matrixStorage)
 inline bool resolve_upper_storage(const mfh_ctx *c) {
+    if (c->modesWide) return false;
     if (c->matrixStorage >= 0) return c->matrixStorage == 1;
     return c->haveMesh && !c->hostOnly && !c->external && c->op == MFH_OP_ELASTICITY && c->use_mf() && !c->tlProbe && c->tlRapAgg;
 }
@@ -433,6 +444,10 @@ inline void require_full_storage(const mfh_ctx *c, const char *what) {
 
 inline int32_t dof_of(const mfh_ctx *c, int64_t node) { return c->dofForNode.empty() ? (int32_t)node : c->dofForNode[node]; }
 void invalidate_matrix(mfh_ctx *c);
+void drop_mass(mfh_ctx *c);            // the resident mass buffer describes the previous pattern / vertex positions
+void ensure_mass(mfh_ctx *c);          // dMassVals of the current pattern and element records (both triangles required)
+k::SpmvArgs mass_spmv_args(mfh_ctx *c, bool masked);   // k_spmv_kron on dMassVals
+void ensure_symbolic(mfh_ctx *c, bool wantScatter);
 void ensure_dirichlet_tables(mfh_ctx *c);
 void dist_detach(mfh_ctx *c);
 bool dist_active(const mfh_ctx *c);

@@ -1,0 +1,987 @@
+// Vibrational modes (mfh_modes, include/meshfem_hip.h; docs/design/04_12_modes.md): the smallest eigenpairs of K x = lambda M x by LOBPCG -- a host
+// loop over device kernels. The reference's counterpart is smallestNonzeroGenEigenpairsPSDKnownKernel (Eigensolver.hh: shift-invert Lanczos over
+// CHOLMOD); here K is never factored, the context's preconditioner (block-Jacobi / two-level / multigrid V-cycle) plays the part of the inverse.
+//   block vectors   n x <= 24, the columns stored apart, ld = n rounded up to 32 doubles (the layout mg_precond_batch takes)
+//   k_block_gram    G = A^T B: one wave per 6 x 8 tile of column pairs, the lanes take the 64 rows of a slab, tiles in registers, rows summed by
+//                   wave reductions, one partial per workgroup; k_block_partial_sum adds the partials in workgroup order. No atomics.
+//   k_block_update  Y1 = [A1 A2 A3] C1, Y2 = [A1 A2 A3] C2 (row-local, so outputs may be inputs): the lanes take rows, the coefficients are
+//                   wave-uniform scalar loads. One launch serves the vectors and their K- and M-images (blockIdx.y).
+//   k_block_residual  R = KX - MX diag(lambda) with the column norms of R and MX through the same two stages
+//   host            Cholesky-QR coefficients, Rayleigh-Ritz (sym_gen_eig: Cholesky reduction + cyclic Jacobi, <= 72 x 72), locking, the loop
+// FP64 throughout; two calls on one context with option "deterministic" return the same bits.
+#include "mfh_ctx.hh"
+#include "mfh_device.hh"
+#include <deque>
+
+namespace mfh { namespace k {
+
+namespace {
+
+constexpr int BLK_MAXC = 24;            // columns of a block vector
+constexpr int GRAM_TP = 6, GRAM_TQ = 8; // column-pair tile of one wave
+constexpr int GRAM_GRID_CAP = 512;      // workgroups of k_block_gram (= partials the second stage adds per entry)
+constexpr int UPD_GRID_CAP = 2048;
+
+// the columns col[0 .. nc) of a block: column j at base + col[j] ld
+struct BlockRef {
+    const double *base;
+    int64_t ld;
+    int nc;
+    unsigned char col[BLK_MAXC];
+};
+
+// partials[(blockIdx.x p + i) q + j] = sum over the rows of this workgroup's slabs of A_i B_j. Wave w of the workgroup owns the tile (w / ntq, w % ntq);
+// the waves of a workgroup read the same slab at about the same time, so a column comes from HBM once and from the CU's L1 for the other tiles.
+// Columns past the block's end are clamped to its last one (their sums are not written): the loop carries no branch.
+__global__ void __launch_bounds__(768) k_block_gram(int64_t n, BlockRef A, BlockRef B, double *__restrict__ partials) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ntq = (B.nc + GRAM_TQ - 1) / GRAM_TQ;
+    const int tp = wave / ntq, tq = wave - tp * ntq;
+    const double *pa[GRAM_TP], *pb[GRAM_TQ];
+#pragma unroll
+    for (int i = 0; i < GRAM_TP; ++i) pa[i] = A.base + (int64_t)A.col[min(tp * GRAM_TP + i, A.nc - 1)] * A.ld;
+#pragma unroll
+    for (int j = 0; j < GRAM_TQ; ++j) pb[j] = B.base + (int64_t)B.col[min(tq * GRAM_TQ + j, B.nc - 1)] * B.ld;
+    double acc[GRAM_TP][GRAM_TQ];
+#pragma unroll
+    for (int i = 0; i < GRAM_TP; ++i)
+#pragma unroll
+        for (int j = 0; j < GRAM_TQ; ++j) acc[i][j] = 0.0;
+    const int64_t nSlab = (n + 63) >> 6;
+    for (int64_t sl = blockIdx.x; sl < nSlab; sl += gridDim.x) {
+        const int64_t row = (sl << 6) + lane;
+        const bool ok = row < n;
+        const int64_t r = ok ? row : 0;
+        double a[GRAM_TP], b[GRAM_TQ];
+#pragma unroll
+        for (int i = 0; i < GRAM_TP; ++i) a[i] = pa[i][r];
+#pragma unroll
+        for (int j = 0; j < GRAM_TQ; ++j) b[j] = pb[j][r];
+#pragma unroll
+        for (int i = 0; i < GRAM_TP; ++i) a[i] = ok ? a[i] : 0.0;
+#pragma unroll
+        for (int j = 0; j < GRAM_TQ; ++j) b[j] = ok ? b[j] : 0.0;
+#pragma unroll
+        for (int i = 0; i < GRAM_TP; ++i)
+#pragma unroll
+            for (int j = 0; j < GRAM_TQ; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+    }
+    double *out = partials + (int64_t)blockIdx.x * A.nc * B.nc;
+#pragma unroll
+    for (int i = 0; i < GRAM_TP; ++i)
+#pragma unroll
+        for (int j = 0; j < GRAM_TQ; ++j) {
+            const double v = wave_sum(acc[i][j]);
+            const int gi = tp * GRAM_TP + i, gj = tq * GRAM_TQ + j;
+            if (lane == 0 && gi < A.nc && gj < B.nc) out[gi * B.nc + gj] = v;
+        }
+}
+
+// out[e] = partials[0][e] + partials[1][e] + ... in that order (count entries per workgroup of the first stage)
+__global__ void __launch_bounds__(256) k_block_partial_sum(int nPart, int count, const double *__restrict__ partials, double *__restrict__ out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    double v = 0.0;
+    for (int b = 0; b < nPart; ++b) v += partials[(int64_t)b * count + e];
+    out[e] = v;
+}
+
+// One family of block vectors (the vectors themselves, their K-images or their M-images): three input blocks, two output blocks
+struct UpdFamily {
+    const double *in[3];
+    double *out[2];
+};
+struct UpdArgs {
+    int64_t n, ld;
+    int nIn[3], nOut[2];
+    int skip2;                            // output 2 takes the inputs from (flattened) index skip2 on
+    int nFam;
+    unsigned char colIn[3][BLK_MAXC], colOut[2][BLK_MAXC];
+    UpdFamily fam[3];
+};
+
+// out1 = [in0 in1 in2] C1, out2 = [in0 in1 in2](skip2 ...) C2(skip2 ...) for the family blockIdx.y. C1 / C2: row-major, one row of BLK_MAXC doubles per
+// input column (zero-padded): wave-uniform, read-only -> scalar loads, the products take them as scalar operands. A lane reads every input of its row
+// before it writes any output, and rows do not interact: outputs may be inputs.
+__global__ void __launch_bounds__(256) k_block_update(UpdArgs a, const double *__restrict__ C1, const double *__restrict__ C2) {
+    const UpdFamily &F = a.fam[blockIdx.y];
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < a.n; row += (int64_t)gridDim.x * 256) {
+        double y1[BLK_MAXC], y2[BLK_MAXC];
+#pragma unroll
+        for (int q = 0; q < BLK_MAXC; ++q) { y1[q] = 0.0; y2[q] = 0.0; }
+        int jj = 0;
+        for (int b = 0; b < 3; ++b) {
+            const double *base = F.in[b];
+            for (int j = 0; j < a.nIn[b]; ++j, ++jj) {
+                const double v = base[(int64_t)a.colIn[b][j] * a.ld + row];
+                const double *c1 = C1 + jj * BLK_MAXC;
+#pragma unroll
+                for (int q = 0; q < BLK_MAXC; ++q) y1[q] = fma(v, c1[q], y1[q]);
+                if (C2 && jj >= a.skip2) {
+                    const double *c2 = C2 + jj * BLK_MAXC;
+#pragma unroll
+                    for (int q = 0; q < BLK_MAXC; ++q) y2[q] = fma(v, c2[q], y2[q]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BLK_MAXC; ++q)
+            if (q < a.nOut[0]) F.out[0][(int64_t)a.colOut[0][q] * a.ld + row] = y1[q];
+        if (C2) {
+#pragma unroll
+            for (int q = 0; q < BLK_MAXC; ++q)
+                if (q < a.nOut[1]) F.out[1][(int64_t)a.colOut[1][q] * a.ld + row] = y2[q];
+        }
+    }
+}
+
+struct ResArgs {
+    int64_t n, ld;
+    int nc;
+    unsigned char col[BLK_MAXC];
+    double lam[BLK_MAXC];
+    const double *KX, *MX;
+    double *R;
+};
+// R_j = KX_j - lam_j MX_j for the listed columns; partials[blockIdx.x][2 j] = sum R_j^2, [2 j + 1] = sum MX_j^2 over the rows of the workgroup
+// (wave reductions, the four waves added in wave order): the second stage is k_block_partial_sum
+__global__ void __launch_bounds__(256) k_block_residual(ResArgs a, double *__restrict__ partials) {
+    __shared__ double red[4][2 * BLK_MAXC];
+    double rr[BLK_MAXC], mm[BLK_MAXC];
+#pragma unroll
+    for (int j = 0; j < BLK_MAXC; ++j) { rr[j] = 0.0; mm[j] = 0.0; }
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < a.n; row += (int64_t)gridDim.x * 256) {
+#pragma unroll
+        for (int j = 0; j < BLK_MAXC; ++j)
+            if (j < a.nc) {
+                const int64_t at = (int64_t)a.col[j] * a.ld + row;
+                const double mx = a.MX[at], r = fma(-a.lam[j], mx, a.KX[at]);
+                a.R[at] = r;
+                rr[j] = fma(r, r, rr[j]);
+                mm[j] = fma(mx, mx, mm[j]);
+            }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int j = 0; j < BLK_MAXC; ++j) {
+        const double vr = wave_sum(rr[j]), vm = wave_sum(mm[j]);
+        if (lane == 0) { red[wave][2 * j] = vr; red[wave][2 * j + 1] = vm; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * BLK_MAXC)
+        partials[(int64_t)blockIdx.x * 2 * BLK_MAXC + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+int gram_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, GRAM_GRID_CAP)); }
+
+// G (device, p x q row-major) = A^T B; partials: scratch of GRAM_GRID_CAP * 576 doubles
+void launch_block_gram(int64_t n, const BlockRef &A, const BlockRef &B, double *partials, double *G, hipStream_t s) {
+    const int waves = ((A.nc + GRAM_TP - 1) / GRAM_TP) * ((B.nc + GRAM_TQ - 1) / GRAM_TQ);
+    const int grid = gram_grid(n), count = A.nc * B.nc;
+    hipLaunchKernelGGL(k_block_gram, dim3(grid), dim3(64 * waves), 0, s, n, A, B, partials);
+    hipLaunchKernelGGL(k_block_partial_sum, dim3((count + 255) / 256), dim3(256), 0, s, grid, count, (const double *)partials, G);
+    CHECK_LAUNCH();
+}
+
+void launch_block_update(const UpdArgs &a, const double *C1, const double *C2, hipStream_t s) {
+    hipLaunchKernelGGL(k_block_update, dim3(grid_for(a.n, UPD_GRID_CAP), a.nFam), dim3(256), 0, s, a, C1, C2);
+    CHECK_LAUNCH();
+}
+
+// norms (device, 2 BLK_MAXC doubles): [2 j] = ||R_j||^2, [2 j + 1] = ||MX_j||^2; partials: scratch of UPD_GRID_CAP * 48 doubles
+void launch_block_residual(const ResArgs &a, double *partials, double *norms, hipStream_t s) {
+    const int grid = grid_for(a.n, UPD_GRID_CAP);
+    hipLaunchKernelGGL(k_block_residual, dim3(grid), dim3(256), 0, s, a, partials);
+    hipLaunchKernelGGL(k_block_partial_sum, dim3(1), dim3(256), 0, s, grid, 2 * BLK_MAXC, (const double *)partials, norms);
+    CHECK_LAUNCH();
+}
+
+}   // namespace
+}}   // namespace mfh::k
+
+using namespace mfh;
+using namespace mfhi;
+using k::BlockRef;
+using k::BLK_MAXC;
+
+namespace {
+
+constexpr int RR_MAX = 72;              // largest Rayleigh-Ritz problem: three blocks of 24
+
+// All eigenpairs of A v = w B v, A symmetric, B symmetric positive definite (null: the identity), n x n row-major, upper triangles read. Cholesky
+// B = L L^T, C = L^-1 A L^-T, cyclic Jacobi on C (rotations of Rutishauser's form), V = L^-T Q. w ascending. false: B not positive definite.
+bool sym_gen_eig(int n, const double *A, const double *B, double *w, double *V) {
+    const size_t N = (size_t)n;
+    std::vector<double> L(N * N, 0.0), Cm(N * N), Q(N * N, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) Cm[i * N + j] = i <= j ? A[i * N + j] : A[j * N + i];
+    if (B) {
+        for (int j = 0; j < n; ++j) {
+            double d = B[j * N + j];
+            for (int q = 0; q < j; ++q) d -= L[j * N + q] * L[j * N + q];
+            if (!(d > 0.0)) return false;
+            const double ljj = std::sqrt(d);
+            L[j * N + j] = ljj;
+            for (int i = j + 1; i < n; ++i) {
+                double v = B[j * N + i];
+                for (int q = 0; q < j; ++q) v -= L[i * N + q] * L[j * N + q];
+                L[i * N + j] = v / ljj;
+            }
+        }
+        // T = L^-1 A (columns by forward substitution), then C = L^-1 T^T
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int c = 0; c < n; ++c)
+                for (int i = 0; i < n; ++i) {
+                    double v = Cm[i * N + c];
+                    for (int q = 0; q < i; ++q) v -= L[i * N + q] * Cm[q * N + c];
+                    Cm[i * N + c] = v / L[i * N + i];
+                }
+            for (int i = 0; i < n; ++i)
+                for (int j = i + 1; j < n; ++j) std::swap(Cm[i * N + j], Cm[j * N + i]);
+        }
+        for (int i = 0; i < n; ++i)
+            for (int j = i + 1; j < n; ++j) Cm[i * N + j] = Cm[j * N + i] = 0.5 * (Cm[i * N + j] + Cm[j * N + i]);
+    }
+    for (int i = 0; i < n; ++i) Q[i * N + i] = 1.0;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < n; ++i) {
+            diag += Cm[i * N + i] * Cm[i * N + i];
+            for (int j = i + 1; j < n; ++j) off += Cm[i * N + j] * Cm[i * N + j];
+        }
+        if (off == 0.0 || off <= 1e-34 * diag) break;
+        for (int p = 0; p < n; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = Cm[p * N + q];
+                if (apq == 0.0) continue;
+                const double app = Cm[p * N + p], aqq = Cm[q * N + q];
+                if (std::fabs(apq) <= 1e-300 || (sweep > 3 && std::fabs(apq) <= 2.2e-16 * 1e-4 * std::min(std::fabs(app), std::fabs(aqq)))) {
+                    if (sweep > 3) { Cm[p * N + q] = Cm[q * N + p] = 0.0; }
+                    continue;
+                }
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs, tau = sn / (1.0 + cs);
+                Cm[p * N + p] = app - t * apq;
+                Cm[q * N + q] = aqq + t * apq;
+                Cm[p * N + q] = Cm[q * N + p] = 0.0;
+                for (int r = 0; r < n; ++r) {
+                    if (r != p && r != q) {
+                        const double arp = Cm[r * N + p], arq = Cm[r * N + q];
+                        Cm[r * N + p] = Cm[p * N + r] = arp - sn * (arq + tau * arp);
+                        Cm[r * N + q] = Cm[q * N + r] = arq + sn * (arp - tau * arq);
+                    }
+                    const double vrp = Q[r * N + p], vrq = Q[r * N + q];
+                    Q[r * N + p] = vrp - sn * (vrq + tau * vrp);
+                    Q[r * N + q] = vrq + sn * (vrp - tau * vrq);
+                }
+            }
+    }
+    std::vector<int> order(N);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Cm[x * N + x] < Cm[y * N + y]; });
+    for (int k2 = 0; k2 < n; ++k2) {
+        const int src = order[k2];
+        w[k2] = Cm[src * N + src];
+        // column k2 of V = L^-T q (back substitution)
+        for (int i = n - 1; i >= 0; --i) {
+            double v = Q[i * N + src];
+            if (B) {
+                for (int q = i + 1; q < n; ++q) v -= L[q * N + i] * V[q * N + k2];
+                v /= L[i * N + i];
+            }
+            V[i * N + k2] = v;
+        }
+    }
+    return true;
+}
+
+// Upper-triangular U with (S U)^T M (S U) = I from the Gram matrix G = S^T M S (k x k row-major, symmetric): Cholesky of D^-1/2 G D^-1/2 with
+// D = diag G, U = D^-1/2 L^-T. A pivot of the scaled matrix at or below `floor` (or a non-positive diagonal entry) fails: its index is returned
+// (-1: success). U row-major k x k.
+int chol_qr_factor(int k, const std::vector<double> &G, double floor, std::vector<double> &U) {
+    const size_t K = (size_t)k;
+    std::vector<double> L(K * K, 0.0), sc(K);
+    for (int i = 0; i < k; ++i) {
+        if (!(G[i * K + i] > 0.0) || !std::isfinite(G[i * K + i])) return i;
+        sc[i] = 1.0 / std::sqrt(G[i * K + i]);
+    }
+    for (int j = 0; j < k; ++j) {
+        double d = 1.0;
+        for (int q = 0; q < j; ++q) d -= L[j * K + q] * L[j * K + q];
+        if (!(d > floor)) return j;
+        const double ljj = std::sqrt(d);
+        L[j * K + j] = ljj;
+        for (int i = j + 1; i < k; ++i) {
+            double v = 0.5 * (G[i * K + j] + G[j * K + i]) * sc[i] * sc[j];
+            for (int q = 0; q < j; ++q) v -= L[i * K + q] * L[j * K + q];
+            L[i * K + j] = v / ljj;
+        }
+    }
+    // U = D^-1/2 L^-T: column c of L^-T by back substitution on L^T
+    U.assign(K * K, 0.0);
+    for (int c = 0; c < k; ++c) {
+        for (int i = c; i >= 0; --i) {
+            double v = i == c ? 1.0 : 0.0;
+            for (int q = i + 1; q <= c; ++q) v -= L[q * K + i] * U[q * K + c];
+            U[i * K + c] = v / L[i * K + i];
+        }
+    }
+    for (int i = 0; i < k; ++i)
+        for (int c = i; c < k; ++c) U[i * K + c] *= sc[i];
+    return -1;
+}
+
+// Rigid motions that the fixed variables leave free: the candidates (translations; rotations unless a DoF map identifies nodes) restricted to the
+// fixed variables, as the constrained solve counts them (sim_solve_impl)
+int free_rigid_motions(const mfh_ctx *c) {
+    const HostMesh &m = c->mesh;
+    const int d = m.dim;
+    const bool periodic = !c->dofForNode.empty();
+    const int nc = periodic ? d : (d == 3 ? 6 : 3);
+    if (c->fixedVars.empty()) return nc;
+    std::vector<int32_t> nodeOfDof;
+    if (periodic) {
+        nodeOfDof.assign((size_t)c->nDoF, -1);
+        for (int64_t nd = m.nNode - 1; nd >= 0; --nd) nodeOfDof[(size_t)c->dofForNode[(size_t)nd]] = (int32_t)nd;
+    }
+    double cen[3] = {0, 0, 0}, ext = 0;
+    {
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        for (int64_t nd = 0; nd < m.nNode; ++nd)
+            for (int a = 0; a < d; ++a) { lo[a] = std::min(lo[a], m.nodePos[(size_t)nd * d + a]); hi[a] = std::max(hi[a], m.nodePos[(size_t)nd * d + a]); }
+        for (int a = 0; a < d; ++a) { cen[a] = 0.5 * (lo[a] + hi[a]); ext = std::max(ext, hi[a] - lo[a]); }
+        if (!(ext > 0)) ext = 1.0;
+    }
+    std::vector<double> G((size_t)nc * nc, 0.0);
+    for (int64_t fv : c->fixedVars) {
+        const int64_t dof = fv / d;
+        const int comp = (int)(fv % d);
+        const int64_t nd = periodic ? nodeOfDof[(size_t)dof] : dof;
+        double x[3] = {0, 0, 0};
+        for (int a = 0; a < d; ++a) x[a] = (m.nodePos[(size_t)nd * d + a] - cen[a]) / ext;
+        double z[6] = {0, 0, 0, 0, 0, 0};
+        z[comp] = 1.0;
+        if (!periodic) {
+            if (d == 3) {
+                const double rot[3][3] = {{0, -x[2], x[1]}, {x[2], 0, -x[0]}, {-x[1], x[0], 0}};
+                for (int r = 0; r < 3; ++r) z[3 + r] = rot[r][comp];
+            } else
+                z[2] = comp == 0 ? -x[1] : x[0];
+        }
+        for (int a = 0; a < nc; ++a)
+            for (int b = 0; b < nc; ++b) G[(size_t)a * nc + b] += z[a] * z[b];
+    }
+    std::vector<double> w((size_t)nc), V((size_t)nc * nc);
+    sym_gen_eig(nc, G.data(), nullptr, w.data(), V.data());
+    int q = 0;
+    for (int e = 0; e < nc; ++e)
+        if (w[e] <= 1e-12 * std::max(w[nc - 1], 1e-300)) ++q;
+    return q;
+}
+
+struct ModesWork {
+    mfh_ctx *c;
+    hipStream_t s;
+    int d, m;                          // variables per DoF, block size
+    int64_t n, ld;
+    double density;
+    bool masked;
+    DBuf<double> vec, zvec, gramPart, resPart, small, coef;
+    double *X, *W, *P, *KX, *KW, *KP, *MX, *MW, *MP, *R;
+    double *Z = nullptr, *KZ = nullptr, *MZ = nullptr;
+    int nz = 0;
+    size_t smallUsed = 0, coefUsed = 0;
+    std::deque<std::vector<double>> staged;    // host sources of asynchronous uploads, alive until the next synchronisation
+    bool useMG = false, useTL = false;
+    // per-phase device time (scripts/probe_modes.py: env MFH_MODES_TIMING=1 puts a synchronisation at every phase boundary)
+    bool timing = false;
+    double tPhase[7] = {0, 0, 0, 0, 0, 0, 0};   // K products, M products, preconditioner, Gram, update, residual, host Rayleigh-Ritz incl. its synchronisation
+    double tMark = 0;
+
+    void lap(int phase) {
+        if (!timing) return;
+        MFH_HIP(hipStreamSynchronize(s));
+        const double t = now_ms();
+        if (phase >= 0) tPhase[phase] += t - tMark;
+        tMark = t;
+    }
+    BlockRef ref(const double *base, const std::vector<int> &cols) const {
+        BlockRef r{};
+        r.base = base; r.ld = ld; r.nc = (int)cols.size();
+        for (size_t j = 0; j < cols.size(); ++j) r.col[j] = (unsigned char)cols[j];
+        return r;
+    }
+    void sync() {
+        MFH_HIP(hipStreamSynchronize(s));
+        staged.clear();
+        smallUsed = 0;
+        coefUsed = 0;
+    }
+    double *small_slot(size_t count) {
+        require(smallUsed + count <= small.n, MFH_ERR_STATE, "mfh_modes: Gram staging overflow");
+        double *p = small.p + smallUsed;
+        smallUsed += count;
+        return p;
+    }
+    // device G slot = A^T B
+    double *gram(const BlockRef &A, const BlockRef &B) {
+        double *G = small_slot((size_t)A.nc * B.nc);
+        k::launch_block_gram(n, A, B, gramPart.p, G, s);
+        return G;
+    }
+    const double *upload_coef(std::vector<double> &&h) {
+        require(coefUsed + h.size() <= coef.n, MFH_ERR_STATE, "mfh_modes: coefficient staging overflow");
+        staged.push_back(std::move(h));
+        double *p = coef.p + coefUsed;
+        coefUsed += staged.back().size();
+        MFH_HIP(hipMemcpyAsync(p, staged.back().data(), staged.back().size() * sizeof(double), hipMemcpyHostToDevice, s));
+        return p;
+    }
+    void apply_K(const double *x, double *y) { apply_operator(c, masked, x, y, nullptr); }
+    void apply_M(const double *x, double *y) {
+        k::launch_spmv(mass_spmv_args(c, masked), x, y, nullptr, s);
+        if (density != 1.0) k::launch_axpby(n, 0.0, y, density, y, s);      // the buffer holds density 1
+    }
+    void precond(const double *r, double *z) {
+        if (useMG) mg_precond(c, r, z, nullptr, -1, nullptr);
+        else if (useTL) tl_precond(c, r, z, nullptr, -1);
+        else k::launch_precond(d, c->sym.nRows, c->dDinv.p, r, z, s);
+        if (masked) k::launch_mask(n, c->dFixedMask.p, z, s);
+    }
+    double *col(double *base, int j) const { return base + (size_t)j * (size_t)ld; }
+};
+
+// Y (columns colsOut of outBase families) = sum over the input blocks: generic wrapper around launch_block_update.
+// C1: rows = all input columns in order, q1 columns (row-major, dense); padded to BLK_MAXC here.
+struct UpdCall {
+    k::UpdArgs a{};
+    std::vector<double> c1, c2;
+    int nInTot = 0;
+    void inputs(int b, const std::vector<int> &cols) {
+        a.nIn[b] = (int)cols.size();
+        for (size_t j = 0; j < cols.size(); ++j) a.colIn[b][j] = (unsigned char)cols[j];
+    }
+    void outputs(int o, const std::vector<int> &cols) {
+        a.nOut[o] = (int)cols.size();
+        for (size_t j = 0; j < cols.size(); ++j) a.colOut[o][j] = (unsigned char)cols[j];
+    }
+    void finish() {
+        nInTot = a.nIn[0] + a.nIn[1] + a.nIn[2];
+        c1.assign((size_t)nInTot * BLK_MAXC, 0.0);
+        c2.assign((size_t)nInTot * BLK_MAXC, 0.0);
+    }
+};
+
+void run_update(ModesWork &w, UpdCall &u, bool two) {
+    u.a.n = w.n; u.a.ld = w.ld;
+    const double *c1 = w.upload_coef(std::move(u.c1));
+    const double *c2 = two ? w.upload_coef(std::move(u.c2)) : nullptr;
+    k::launch_block_update(u.a, c1, c2, w.s);
+}
+
+// M-orthonormalise the columns `cols` of the block V (images MV kept, and KV if non-null) by Cholesky-QR, twice; the Gram matrices come from the
+// images. Used for the start block, the rigid modes and the returned columns. false: the Gram matrix is not positive definite.
+bool chol_qr_block(ModesWork &w, double *V, double *KV, double *MV, const std::vector<int> &cols) {
+    const int k2 = (int)cols.size();
+    for (int pass = 0; pass < 2; ++pass) {
+        w.lap(-1);
+        double *G = w.gram(w.ref(V, cols), w.ref(MV, cols));
+        std::vector<double> hG((size_t)k2 * k2), U;
+        MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, w.s));
+        w.sync();
+        w.lap(3);
+        if (chol_qr_factor(k2, hG, 1e-13, U) >= 0) return false;
+        UpdCall u;
+        u.inputs(0, cols); u.outputs(0, cols);
+        u.finish();
+        for (int i = 0; i < k2; ++i)
+            for (int j = 0; j < k2; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * k2 + j];
+        int f = 0;
+        u.a.fam[f].in[0] = V; u.a.fam[f].out[0] = V; ++f;
+        u.a.fam[f].in[0] = MV; u.a.fam[f].out[0] = MV; ++f;
+        if (KV) { u.a.fam[f].in[0] = KV; u.a.fam[f].out[0] = KV; ++f; }
+        u.a.nFam = f;
+        run_update(w, u, false);
+        w.lap(4);
+    }
+    return true;
+}
+
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_debug_sym_gen_eig(int64_t n, const double *A, const double *B, double *w, double *V) {
+    if (n < 1 || n > RR_MAX || !A || !B || !w || !V) return MFH_ERR_INVALID;
+    try {
+        return sym_gen_eig((int)n, A, B, w, V) ? MFH_OK : MFH_ERR_INVALID;
+    } catch (const std::exception &) { return MFH_ERR_INVALID; }
+}
+
+mfh_status mfh_debug_block_gram(mfh_ctx *c, int64_t n, int32_t p, int32_t q, const double *A, const double *B, double *G) {
+    MFH_TRY(c)
+    require(c && A && B && G && n >= 1 && p >= 1 && p <= BLK_MAXC && q >= 1 && q <= BLK_MAXC, MFH_ERR_INVALID, "mfh_debug_block_gram: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    DBuf<double> a, b, part, g;
+    a.alloc((size_t)ld * p); b.alloc((size_t)ld * q); part.alloc((size_t)k::GRAM_GRID_CAP * BLK_MAXC * BLK_MAXC); g.alloc((size_t)p * q);
+    MFH_HIP(hipMemcpy2DAsync(a.p, (size_t)ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)p, hipMemcpyHostToDevice, s));
+    MFH_HIP(hipMemcpy2DAsync(b.p, (size_t)ld * sizeof(double), B, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)q, hipMemcpyHostToDevice, s));
+    BlockRef ra{}, rb{};
+    ra.base = a.p; ra.ld = ld; ra.nc = p;
+    rb.base = b.p; rb.ld = ld; rb.nc = q;
+    for (int j = 0; j < BLK_MAXC; ++j) ra.col[j] = rb.col[j] = (unsigned char)j;
+    k::launch_block_gram(n, ra, rb, part.p, g.p, s);
+    g.download(G, (size_t)p * q, s);
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_time_block_gram(mfh_ctx *c, int64_t n, int32_t p, int32_t q, int32_t reps, double *gram_ms, double *copy_ms) {
+    MFH_TRY(c)
+    require(c && gram_ms && copy_ms && n >= 1 && reps >= 1 && p >= 1 && p <= BLK_MAXC && q >= 1 && q <= BLK_MAXC, MFH_ERR_INVALID, "mfh_time_block_gram: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    DBuf<double> ab, dst, part, g;
+    ab.alloc((size_t)ld * (p + q)); dst.alloc((size_t)ld * (p + q)); part.alloc((size_t)k::GRAM_GRID_CAP * BLK_MAXC * BLK_MAXC); g.alloc((size_t)p * q);
+    k::launch_fill_hash(ld * (p + q), ab.p, s);
+    BlockRef ra{}, rb{};
+    ra.base = ab.p; ra.ld = ld; ra.nc = p;
+    rb.base = ab.p + (size_t)ld * p; rb.ld = ld; rb.nc = q;
+    for (int j = 0; j < BLK_MAXC; ++j) ra.col[j] = rb.col[j] = (unsigned char)j;
+    for (int r = 0; r < 2; ++r) {      // warm-up of both
+        k::launch_block_gram(n, ra, rb, part.p, g.p, s);
+        MFH_HIP(hipMemcpyAsync(dst.p, ab.p, (size_t)ld * (p + q) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    MFH_HIP(hipStreamSynchronize(s));
+    {
+        EventTimer t(s);
+        for (int r = 0; r < reps; ++r) k::launch_block_gram(n, ra, rb, part.p, g.p, s);
+        *gram_ms = t.stop() / reps;
+    }
+    {
+        EventTimer t(s);
+        for (int r = 0; r < reps; ++r) MFH_HIP(hipMemcpyAsync(dst.p, ab.p, (size_t)ld * (p + q) * sizeof(double), hipMemcpyDeviceToDevice, s));
+        *copy_ms = t.stop() / reps;
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_block_update(mfh_ctx *c, int64_t n, int32_t p, int32_t q, const double *A, const double *C, double *Y) {
+    MFH_TRY(c)
+    require(c && A && C && Y && n >= 1 && p >= 1 && p <= BLK_MAXC && q >= 1 && q <= BLK_MAXC, MFH_ERR_INVALID, "mfh_debug_block_update: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    DBuf<double> a, y, coef;
+    a.alloc((size_t)ld * p); y.alloc((size_t)ld * q);
+    MFH_HIP(hipMemcpy2DAsync(a.p, (size_t)ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)p, hipMemcpyHostToDevice, s));
+    std::vector<double> hc((size_t)p * BLK_MAXC, 0.0);
+    for (int i = 0; i < p; ++i)
+        for (int j = 0; j < q; ++j) hc[(size_t)i * BLK_MAXC + j] = C[(size_t)i * q + j];
+    coef.upload(hc, s);
+    k::UpdArgs u{};
+    u.n = n; u.ld = ld; u.nIn[0] = p; u.nOut[0] = q; u.nFam = 1;
+    for (int j = 0; j < BLK_MAXC; ++j) u.colIn[0][j] = u.colOut[0][j] = (unsigned char)j;
+    u.fam[0].in[0] = a.p; u.fam[0].out[0] = y.p;
+    k::launch_block_update(u, coef.p, nullptr, s);
+    MFH_HIP(hipMemcpy2DAsync(Y, (size_t)n * sizeof(double), y.p, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)q, hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, double rtol, int32_t maxit, double *lambda, double *Xout, double *residuals,
+                     mfh_modes_info *info) {
+    if (info) { *info = mfh_modes_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c && nev >= 1 && nev <= 20 && density > 0.0 && std::isfinite(density) && lambda && Xout && rtol > 0.0 && maxit > 0 && (flags & ~MFH_MODES_FREE) == 0,
+            MFH_ERR_INVALID, "mfh_modes: 1 <= nev <= 20, density > 0, rtol > 0, maxit > 0, lambda and X not null");
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "mfh_modes: no mesh set");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    const bool freeBody = (flags & MFH_MODES_FREE) != 0;
+    require(c->op == MFH_OP_ELASTICITY && c->opDegree != 1, MFH_ERR_UNSUPPORTED, "mfh_modes: the pencil is (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
+    require(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
+    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "mfh_modes: 2D / 3D meshes");
+    if (freeBody) require(c->fixedVars.empty() && c->dofForNode.empty(), MFH_ERR_UNSUPPORTED, "mfh_modes: the free-free case takes no fixed variables and the identity DoF map");
+    else {
+        const int q = free_rigid_motions(c);
+        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables, or ask for MFH_MODES_FREE)");
+    }
+    hipStream_t s = c->stream;
+    c->modesNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
+    // the storage of the pattern for the duration of the call (see mfh_ctx::modesWide); the guard also restores the solver's singular-system switch
+    struct Guard {
+        mfh_ctx *c;
+        ~Guard() {
+            c->tlSuppress = false;
+            if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
+        }
+    } guard{c};
+    if (resolve_upper_storage(c)) {
+        c->modesWide = true;
+        note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    }
+    EventTimer tsetup(s);
+    // ---- preconditioner: what the next solve of this kind would use
+    c->tlSuppress = freeBody;
+    ensure_precond(c);
+    if (freeBody) {
+        c->precondNote.clear();
+        if (c->precond == MFH_PRECOND_MULTIGRID && ensure_multigrid(c)) note("multigrid preconditioner on the singular K of the free body: dense level pinned");
+        else if (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) note("two-level / multigrid preconditioner unavailable on the singular K of the free body: using block-Jacobi");
+    } else
+        ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes");
+
+    ModesWork w;
+    w.c = c; w.s = s; w.d = c->bs();
+    w.n = (int64_t)w.d * c->nDoF; w.ld = (w.n + 31) / 32 * 32;
+    w.density = density;
+    w.masked = !c->fixedVars.empty();
+    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
+    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
+    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
+    if (!freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
+    const int64_t nEff = w.n - (int64_t)c->fixedVars.size() - w.nz;        // dimension of the space the iteration lives in
+    require(nev <= nEff, MFH_ERR_INVALID, "mfh_modes: more modes asked for than the pencil has");
+    const int m = (int)std::min<int64_t>(std::min(nev + std::max(2, (nev + 3) / 4), BLK_MAXC), nEff);
+    w.m = m;
+    const size_t L = (size_t)w.ld;
+    w.vec.alloc(L * (size_t)m * 10);
+    w.vec.zero(s);
+    double *b0 = w.vec.p;
+    w.X = b0; w.W = b0 + L * m; w.P = b0 + 2 * L * m; w.KX = b0 + 3 * L * m; w.KW = b0 + 4 * L * m; w.KP = b0 + 5 * L * m;
+    w.MX = b0 + 6 * L * m; w.MW = b0 + 7 * L * m; w.MP = b0 + 8 * L * m; w.R = b0 + 9 * L * m;
+    w.gramPart.alloc((size_t)k::GRAM_GRID_CAP * BLK_MAXC * BLK_MAXC);
+    w.resPart.alloc((size_t)k::UPD_GRID_CAP * 2 * BLK_MAXC);
+    w.small.alloc((size_t)4 * RR_MAX * RR_MAX);
+    c->stop.alloc(4);                  // (control block the preconditioner kernels are handed; no gate here)
+    c->stop.zero(s);
+    w.coef.alloc((size_t)8 * RR_MAX * BLK_MAXC);
+    std::vector<int> all((size_t)m);
+    for (int j = 0; j < m; ++j) all[(size_t)j] = j;
+
+    // ---- the known kernel of the free body: translations and infinitesimal rotations about the centre, M-orthonormalised
+    std::vector<int> zall;
+    if (freeBody) {
+        const HostMesh &hm = c->mesh;
+        const int d = w.d, nz = w.nz;
+        for (int j = 0; j < nz; ++j) zall.push_back(j);
+        w.zvec.alloc(L * (size_t)nz * 3);
+        w.zvec.zero(s);
+        w.Z = w.zvec.p; w.KZ = w.zvec.p + L * nz; w.MZ = w.zvec.p + 2 * L * nz;
+        std::vector<double> hz(L * (size_t)nz, 0.0);
+        double cen[3] = {0, 0, 0};
+        for (int64_t nd = 0; nd < hm.nNode; ++nd)
+            for (int a = 0; a < d; ++a) cen[a] += hm.nodePos[(size_t)nd * d + a] / (double)hm.nNode;
+        for (int64_t nd = 0; nd < hm.nNode; ++nd) {
+            double x[3] = {0, 0, 0};
+            for (int a = 0; a < d; ++a) x[a] = hm.nodePos[(size_t)nd * d + a] - cen[a];
+            for (int a = 0; a < d; ++a) hz[(size_t)a * L + (size_t)nd * d + a] = 1.0;
+            if (d == 3) {
+                hz[3 * L + (size_t)nd * 3 + 1] = -x[2]; hz[3 * L + (size_t)nd * 3 + 2] = x[1];
+                hz[4 * L + (size_t)nd * 3 + 0] = x[2];  hz[4 * L + (size_t)nd * 3 + 2] = -x[0];
+                hz[5 * L + (size_t)nd * 3 + 0] = -x[1]; hz[5 * L + (size_t)nd * 3 + 1] = x[0];
+            } else {
+                hz[2 * L + (size_t)nd * 2 + 0] = -x[1]; hz[2 * L + (size_t)nd * 2 + 1] = x[0];
+            }
+        }
+        MFH_HIP(hipMemcpyAsync(w.Z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        MFH_HIP(hipStreamSynchronize(s));
+        for (int j = 0; j < nz; ++j) w.apply_M(w.col(w.Z, j), w.col(w.MZ, j));
+        if (!chol_qr_block(w, w.Z, nullptr, w.MZ, zall)) throw Error(MFH_ERR_STATE, "mfh_modes: the rigid-body modes of the mesh are linearly dependent");
+        // (KZ stays zero: K Z = 0 up to rounding, and the updates below want a K-image of every input block)
+    }
+    // W -= Z (MZ^T W) on the listed columns of a block (and of its M-image if given)
+    auto project_out_Z = [&](double *V, double *MV, const std::vector<int> &cols) {
+        if (!freeBody || cols.empty()) return;
+        const int nz = w.nz, k2 = (int)cols.size();
+        w.lap(-1);
+        double *G = w.gram(w.ref(w.MZ, zall), w.ref(V, cols));
+        std::vector<double> hG((size_t)nz * k2);
+        MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        w.sync();
+        w.lap(3);
+        UpdCall u;
+        u.inputs(0, zall); u.inputs(1, cols); u.outputs(0, cols);
+        u.finish();
+        for (int i = 0; i < nz; ++i)
+            for (int j = 0; j < k2; ++j) u.c1[(size_t)i * BLK_MAXC + j] = -hG[(size_t)i * k2 + j];
+        for (int j = 0; j < k2; ++j) u.c1[(size_t)(nz + j) * BLK_MAXC + j] = 1.0;
+        int f = 0;
+        u.a.fam[f].in[0] = w.Z; u.a.fam[f].in[1] = V; u.a.fam[f].out[0] = V; ++f;
+        if (MV) { u.a.fam[f].in[0] = w.MZ; u.a.fam[f].in[1] = MV; u.a.fam[f].out[0] = MV; ++f; }
+        u.a.nFam = f;
+        run_update(w, u, false);
+        w.lap(4);
+    };
+
+    // ---- start block: hashed values, smoothed once by the preconditioner, in the complement of Z, M-orthonormal; then Rayleigh-Ritz on it
+    k::launch_fill_hash((int64_t)L * m, w.W, s);
+    for (int j = 0; j < m; ++j) {
+        if (w.masked) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.W, j), s);
+        w.precond(w.col(w.W, j), w.col(w.X, j));
+    }
+    project_out_Z(w.X, nullptr, all);
+    for (int j = 0; j < m; ++j) w.apply_M(w.col(w.X, j), w.col(w.MX, j));
+    if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw Error(MFH_ERR_STATE, "mfh_modes: the start block is rank deficient");
+    for (int j = 0; j < m; ++j) { w.apply_K(w.col(w.X, j), w.col(w.KX, j)); w.apply_M(w.col(w.X, j), w.col(w.MX, j)); }
+    std::vector<double> lam((size_t)m, 0.0);
+    {
+        double *GK = w.gram(w.ref(w.X, all), w.ref(w.KX, all));
+        double *GM = w.gram(w.ref(w.X, all), w.ref(w.MX, all));
+        std::vector<double> hK((size_t)m * m), hM((size_t)m * m), ev((size_t)m), V((size_t)m * m);
+        MFH_HIP(hipMemcpyAsync(hK.data(), GK, hK.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        MFH_HIP(hipMemcpyAsync(hM.data(), GM, hM.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        w.sync();
+        if (!sym_gen_eig(m, hK.data(), hM.data(), ev.data(), V.data())) throw Error(MFH_ERR_STATE, "mfh_modes: the start block lost its M-orthonormality");
+        UpdCall u;
+        u.inputs(0, all); u.outputs(0, all);
+        u.finish();
+        for (int i = 0; i < m; ++i)
+            for (int j = 0; j < m; ++j) u.c1[(size_t)i * BLK_MAXC + j] = V[(size_t)i * m + j];
+        u.a.fam[0].in[0] = w.X; u.a.fam[0].out[0] = w.X;
+        u.a.fam[1].in[0] = w.KX; u.a.fam[1].out[0] = w.KX;
+        u.a.fam[2].in[0] = w.MX; u.a.fam[2].out[0] = w.MX;
+        u.a.nFam = 3;
+        run_update(w, u, false);
+        lam = ev;
+    }
+    MFH_HIP(hipStreamSynchronize(s));
+    const double setupMs = tsetup.stop();
+
+    // ---- the iteration
+    EventTimer tsolve(s);
+    std::vector<double> res((size_t)m, 0.0);
+    std::vector<uint8_t> conv((size_t)m, 0);
+    bool haveP = false, done = false;
+    int it = 0, restarts = 0;
+    w.lap(-1);
+    for (;; ++it) {
+        // residuals of all columns (R, ||R||, ||MX||): one download
+        {
+            k::ResArgs ra{};
+            ra.n = w.n; ra.ld = w.ld; ra.nc = m; ra.KX = w.KX; ra.MX = w.MX; ra.R = w.R;
+            for (int j = 0; j < m; ++j) { ra.col[j] = (unsigned char)j; ra.lam[j] = lam[(size_t)j]; }
+            double *norms = w.small_slot(2 * BLK_MAXC);
+            k::launch_block_residual(ra, w.resPart.p, norms, s);
+            double hn[2 * BLK_MAXC];
+            MFH_HIP(hipMemcpyAsync(hn, norms, sizeof(hn), hipMemcpyDeviceToHost, s));
+            w.sync();
+            w.lap(5);
+            for (int j = 0; j < m; ++j) {
+                const double den = std::fabs(lam[(size_t)j]) * std::sqrt(hn[2 * j + 1]);
+                res[(size_t)j] = den > 0 ? std::sqrt(hn[2 * j]) / den : (hn[2 * j] == 0.0 ? 0.0 : 1e300);
+                if (!std::isfinite(res[(size_t)j])) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (a residual is not finite)");
+                conv[(size_t)j] = res[(size_t)j] <= rtol;
+            }
+        }
+        done = true;
+        for (int j = 0; j < nev; ++j) done = done && conv[(size_t)j];
+        if (done || it >= maxit) break;
+        // soft locking: converged columns stay in X, their W and P columns leave the basis
+        std::vector<int> act;
+        for (int j = 0; j < m; ++j)
+            if (!conv[(size_t)j]) act.push_back(j);
+        for (int j : act) w.precond(w.col(w.R, j), w.col(w.W, j));
+        w.lap(2);
+        project_out_Z(w.W, nullptr, act);
+        for (int j : act) w.apply_K(w.col(w.W, j), w.col(w.KW, j));
+        w.lap(0);
+        for (int j : act) w.apply_M(w.col(w.W, j), w.col(w.MW, j));
+        w.lap(1);
+        std::vector<int> pact = haveP ? act : std::vector<int>();
+        // Cholesky-QR of the basis S = [X W P], twice: Gram-Schmidt in that order, so W leaves M-orthogonal to X
+        std::vector<int> wact = act;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int attempt = 0;; ++attempt) {
+                require(attempt < 2 * BLK_MAXC + 2, MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (the basis cannot be orthonormalised)");
+                const int nx = m, nw = (int)wact.size(), np = (int)pact.size(), kb = nx + nw + np;
+                const double *blk[3] = {w.X, w.W, w.P}, *mblk[3] = {w.MX, w.MW, w.MP};
+                const std::vector<int> *cl[3] = {&all, &wact, &pact};
+                const int off[4] = {0, nx, nx + nw, kb};
+                double *dG[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+                for (int bi = 0; bi < 3; ++bi)
+                    for (int bj = bi; bj < 3; ++bj)
+                        if (!cl[bi]->empty() && !cl[bj]->empty()) dG[bi][bj] = w.gram(w.ref(blk[bi], *cl[bi]), w.ref(mblk[bj], *cl[bj]));
+                std::vector<double> G((size_t)kb * kb, 0.0);
+                std::vector<std::vector<double>> parts;
+                parts.reserve(6);          // (asynchronous downloads point into the elements: no reallocation)
+                for (int bi = 0; bi < 3; ++bi)
+                    for (int bj = bi; bj < 3; ++bj)
+                        if (dG[bi][bj]) {
+                            parts.emplace_back(cl[bi]->size() * cl[bj]->size());
+                            MFH_HIP(hipMemcpyAsync(parts.back().data(), dG[bi][bj], parts.back().size() * sizeof(double), hipMemcpyDeviceToHost, s));
+                        }
+                w.sync();
+                w.lap(3);
+                size_t pi = 0;
+                for (int bi = 0; bi < 3; ++bi)
+                    for (int bj = bi; bj < 3; ++bj)
+                        if (dG[bi][bj]) {
+                            const std::vector<double> &pp = parts[pi++];
+                            const int ni = (int)cl[bi]->size(), nj = (int)cl[bj]->size();
+                            for (int i = 0; i < ni; ++i)
+                                for (int j = 0; j < nj; ++j) {
+                                    G[(size_t)(off[bi] + i) * kb + off[bj] + j] = pp[(size_t)i * nj + j];
+                                    if (bi != bj) G[(size_t)(off[bj] + j) * kb + off[bi] + i] = pp[(size_t)i * nj + j];
+                                }
+                        }
+                std::vector<double> U;
+                const int bad = chol_qr_factor(kb, G, 1e-12, U);
+                if (bad >= 0) {
+                    if (bad >= off[2]) { pact.clear(); haveP = false; ++restarts; continue; }       // restart: P leaves the basis for this iteration
+                    if (bad >= off[1]) { wact.erase(wact.begin() + (bad - off[1])); if (!pact.empty()) { pact.clear(); haveP = false; ++restarts; } continue; }
+                    throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (the Ritz block lost its rank)");
+                }
+                // S <- S U, images alike: first W and P (they read the old X), then X
+                const double *kblk[3] = {w.KX, w.KW, w.KP};
+                {
+                    UpdCall u;
+                    u.inputs(0, all); u.inputs(1, wact); u.inputs(2, pact);
+                    u.outputs(0, wact); u.outputs(1, pact);
+                    u.finish();
+                    for (int i = 0; i < kb; ++i) {
+                        for (int j = 0; j < nw; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + off[1] + j];
+                        for (int j = 0; j < np; ++j) u.c2[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + off[2] + j];
+                    }
+                    u.a.skip2 = 0;
+                    for (int f = 0; f < 3; ++f) {
+                        const double *const *src = f == 0 ? blk : (f == 1 ? kblk : mblk);
+                        for (int b = 0; b < 3; ++b) u.a.fam[f].in[b] = src[b];
+                        u.a.fam[f].out[0] = const_cast<double *>(src[1]);
+                        u.a.fam[f].out[1] = const_cast<double *>(src[2]);
+                    }
+                    u.a.nFam = 3;
+                    if (nw + np > 0) run_update(w, u, np > 0);
+                }
+                {
+                    UpdCall u;
+                    u.inputs(0, all); u.outputs(0, all);
+                    u.finish();
+                    for (int i = 0; i < nx; ++i)
+                        for (int j = 0; j < nx; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + j];
+                    for (int f = 0; f < 3; ++f) {
+                        const double *const *src = f == 0 ? blk : (f == 1 ? kblk : mblk);
+                        u.a.fam[f].in[0] = src[0];
+                        u.a.fam[f].out[0] = const_cast<double *>(src[0]);
+                    }
+                    u.a.nFam = 3;
+                    run_update(w, u, false);
+                }
+                w.lap(4);
+                break;
+            }
+        }
+        // Rayleigh-Ritz on the M-orthonormal basis: S^T K S, standard problem
+        {
+            const int nx = m, nw = (int)wact.size(), np = (int)pact.size(), kb = nx + nw + np;
+            const double *blk[3] = {w.X, w.W, w.P}, *kblk[3] = {w.KX, w.KW, w.KP}, *mblk[3] = {w.MX, w.MW, w.MP};
+            const std::vector<int> *cl[3] = {&all, &wact, &pact};
+            const int off[4] = {0, nx, nx + nw, kb};
+            std::vector<double> G((size_t)kb * kb, 0.0);
+            std::vector<std::vector<double>> parts;
+            parts.reserve(6);
+            std::vector<std::array<int, 2>> which;
+            for (int bi = 0; bi < 3; ++bi)
+                for (int bj = bi; bj < 3; ++bj)
+                    if (!cl[bi]->empty() && !cl[bj]->empty()) {
+                        double *dG = w.gram(w.ref(blk[bi], *cl[bi]), w.ref(kblk[bj], *cl[bj]));
+                        parts.emplace_back(cl[bi]->size() * cl[bj]->size());
+                        which.push_back({bi, bj});
+                        MFH_HIP(hipMemcpyAsync(parts.back().data(), dG, parts.back().size() * sizeof(double), hipMemcpyDeviceToHost, s));
+                    }
+            w.lap(3);
+            w.sync();
+            for (size_t pi = 0; pi < parts.size(); ++pi) {
+                const int bi = which[pi][0], bj = which[pi][1];
+                const int ni = (int)cl[bi]->size(), nj = (int)cl[bj]->size();
+                for (int i = 0; i < ni; ++i)
+                    for (int j = 0; j < nj; ++j) {
+                        G[(size_t)(off[bi] + i) * kb + off[bj] + j] = parts[pi][(size_t)i * nj + j];
+                        if (bi != bj) G[(size_t)(off[bj] + j) * kb + off[bi] + i] = parts[pi][(size_t)i * nj + j];
+                    }
+            }
+            for (int i = 0; i < kb; ++i)
+                for (int j = i + 1; j < kb; ++j) G[(size_t)i * kb + j] = G[(size_t)j * kb + i] = 0.5 * (G[(size_t)i * kb + j] + G[(size_t)j * kb + i]);
+            std::vector<double> ev((size_t)kb), V((size_t)kb * kb);
+            sym_gen_eig(kb, G.data(), nullptr, ev.data(), V.data());
+            w.lap(6);
+            // X+ = S C, P+ = [W P] C' (C' = the W and P rows of C), and the same combinations of the K- and M-images
+            UpdCall u;
+            u.inputs(0, all); u.inputs(1, wact); u.inputs(2, pact);
+            u.outputs(0, all); u.outputs(1, all);
+            u.finish();
+            for (int i = 0; i < kb; ++i)
+                for (int j = 0; j < m; ++j) {
+                    u.c1[(size_t)i * BLK_MAXC + j] = V[(size_t)i * kb + j];
+                    if (i >= nx) u.c2[(size_t)i * BLK_MAXC + j] = V[(size_t)i * kb + j];
+                }
+            u.a.skip2 = nx;
+            for (int f = 0; f < 3; ++f) {
+                const double *const *src = f == 0 ? blk : (f == 1 ? kblk : mblk);
+                for (int b = 0; b < 3; ++b) u.a.fam[f].in[b] = src[b];
+                u.a.fam[f].out[0] = const_cast<double *>(src[0]);
+                u.a.fam[f].out[1] = const_cast<double *>(src[2]);
+            }
+            u.a.nFam = 3;
+            run_update(w, u, true);
+            w.lap(4);
+            for (int j = 0; j < m; ++j) lam[(size_t)j] = ev[(size_t)j];
+            haveP = nw > 0;
+        }
+    }
+    // ---- the returned columns: one final M-orthonormalisation, sign rule, download
+    std::vector<int> ret;
+    for (int j = 0; j < nev; ++j) ret.push_back(j);
+    if (!chol_qr_block(w, w.X, nullptr, w.MX, ret)) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (the returned modes lost their rank)");
+    MFH_HIP(hipMemcpy2DAsync(Xout, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nev, hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    const double solveMs = tsolve.stop();
+    for (int j = 0; j < nev; ++j) {
+        double *x = Xout + (size_t)j * (size_t)w.n;
+        int64_t at = 0;
+        for (int64_t i = 1; i < w.n; ++i)
+            if (std::fabs(x[i]) > std::fabs(x[at])) at = i;
+        if (x[at] < 0)
+            for (int64_t i = 0; i < w.n; ++i) x[i] = -x[i];
+        if (w.masked)
+            for (int64_t fv : c->fixedVars) x[(size_t)fv] = 0.0;       // (exactly +0.0: the iteration keeps them at +-0.0)
+        lambda[j] = lam[(size_t)j];
+        if (residuals) residuals[j] = res[(size_t)j];
+    }
+    if (w.timing)
+        fprintf(stderr, "[mfh_modes] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f\n",
+                (long long)w.n, m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6]);
+    if (info) {
+        info->converged = done ? 1 : 0;
+        info->iterations = it;
+        int locked = 0;
+        double mr = 0;
+        for (int j = 0; j < m; ++j) locked += conv[(size_t)j] ? 1 : 0;
+        for (int j = 0; j < nev; ++j) mr = std::max(mr, res[(size_t)j]);
+        info->nLocked = locked;
+        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
+        info->blockSize = m;
+        info->restarts = restarts;
+        info->maxResidual = mr;
+        info->solve_ms = solveMs;
+        info->setup_ms = setupMs;
+        info->note = c->modesNote.c_str();
+    }
+    if (!done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    MFH_CATCH(c)
+}
+
+}   // extern "C"

@@ -136,6 +136,25 @@ class Simulator:
         self.info = dict(infos[-1])
         return [w[k] for k in range(len(w))]
 
+    def vibrational_modes(self, nev, density=1.0, free=None, rtol=1e-6, maxit=500):
+        """(frequencies, modes): the nev lowest natural frequencies sqrt(lam) / 2 pi of K x = lam M x (M = density x the consistent mass matrix)
+        and the mode shapes as nodal fields [nev, nNode, N] -- the reference's smallestNonzeroGenEigenpairsPSDKnownKernel (Eigensolver.hh)
+        on the device (mfh_modes). The Dirichlet variables of the applied boundary conditions are the clamp (their values play no part);
+        free=None means "free body exactly when no Dirichlet condition is present". self.modes_info holds the solver's record."""
+        v, _ = self.ctx.bc_dirichlet_vars()
+        if free is None:
+            free = len(v) == 0
+        self.ctx.clear_fixed()
+        if not free and len(v):
+            self.ctx.fix_variables(v)
+        lam, X, info = self.ctx.modes(nev, density=density, free=free, rtol=rtol, maxit=maxit)
+        self.modes_info = info
+        X = X.reshape(len(lam), self.ctx.n_dof, self.N)
+        if self.ctx.n_dof != self.ctx.n_node:               # a DoF map (periodic conditions): every node takes its DoF's value
+            dof, _ = self.ctx.get_dof_map()
+            X = X[:, dof, :]
+        return np.sqrt(lam) / (2.0 * np.pi), X
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 
