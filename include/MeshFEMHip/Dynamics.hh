@@ -1,0 +1,97 @@
+// Transient dynamics on the MI355X path: implicit Newmark time stepping over the C ABI (include/meshfem_hip.h, "transient dynamics"). The reference has
+// no time integrator, so there is no counterpart to cite; the layout follows Eigensolver.hh.
+//   transient(sim, dt, nSteps, opt)   M u'' + C u' + K u = g(t) f with K = the Simulator's stiffness matrix, M = opt.density x the consistent vector-valued
+//                                     mass matrix, C = opt.rayleighMass M + opt.rayleighStiff K, f = the Simulator's neumannLoad(), g = opt.amplitude (steps
+//                                     0 .. nSteps; empty: 1). The Dirichlet variables of the boundary conditions applied to the Simulator are the clamp,
+//                                     held at zero. opt.u0 / v0 / a0: the state at step 0, one N-vector per DoF (empty: rest; a0 empty: from the equation
+//                                     of motion at step 0 -- pass the a of an earlier result to continue that run).
+// Returns the state after the last step, the probe histories, the snapshots (one field per snapshot step) and, if asked for, the energies
+// {kinetic, strain, g f.u} per step. PCG on the device with the Simulator's preconditioner (mfh_set_preconditioner); throws std::runtime_error where the C
+// call fails, a step whose PCG does not reach opt.rtol within opt.maxit iterations included.
+#pragma once
+
+#include <utility>
+
+#include "LinearElasticity.hh"
+
+namespace MeshFEMHip {
+
+template <class VField>
+struct TransientOptions {
+    Real density = 1.0, rayleighMass = 0.0, rayleighStiff = 0.0;
+    Real beta = 0.25, gamma = 0.5;
+    Real rtol = 1e-8;       // ||r||_2 <= rtol ||b||_2 in every step's solve
+    int maxit = 10000;
+    std::vector<Real> amplitude;                          // nSteps + 1 values, or empty (= 1)
+    VField u0, v0, a0;                                    // one N-vector per DoF, or empty
+    std::vector<std::pair<size_t, int>> probes;           // (DoF, component) pairs recorded at every step
+    int snapshotStride = 0;                               // > 0: the displacement at the steps 0, stride, 2 stride, ...
+    bool energies = false;
+};
+
+template <class VField>
+struct TransientResult {
+    VField u, v, a;                                       // the state after the last step
+    std::vector<std::vector<Real>> probes;                // [nSteps + 1][number of probes]
+    std::vector<VField> snapshots;
+    std::vector<std::array<Real, 3>> energies;            // [nSteps + 1]: kinetic, strain, g f.u
+    mfh_newmark_info info{};
+};
+
+template <class Sim>
+TransientResult<typename Sim::VField> transient(const Sim &sim, Real dt, int nSteps,
+                                                const TransientOptions<typename Sim::VField> &opt = TransientOptions<typename Sim::VField>()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    mfh_ctx *c = sim.ctx();
+    check(c, mfh_clear_fixed(c));
+    int64_t nv = 0;
+    check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
+    if (nv > 0) {
+        std::vector<int64_t> vars((size_t)nv);
+        std::vector<Real> vals((size_t)nv);
+        check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
+        check(c, mfh_fix_variables(c, nv, vars.data(), nullptr));
+    }
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N, rows = (size_t)(nSteps > 0 ? nSteps : 0) + 1;
+    auto state = [&](const VField &x, const char *name) {
+        VField y(nDoF);
+        if (!x.empty()) {
+            if (x.size() != nDoF) throw std::runtime_error(std::string("transient: ") + name + " needs one entry per DoF");
+            y = x;
+        } else
+            for (auto &e : y) e.fill(0.0);
+        return y;
+    };
+    TransientResult<VField> r;
+    r.u = state(opt.u0, "u0"); r.v = state(opt.v0, "v0"); r.a = state(opt.a0, "a0");
+    if (!opt.amplitude.empty() && opt.amplitude.size() != rows) throw std::runtime_error("transient: amplitude needs nSteps + 1 values");
+    const VField f = sim.neumannLoad();
+    bool loaded = false;
+    for (const auto &e : f)
+        for (size_t a = 0; a < N; ++a) loaded = loaded || e[a] != 0.0;
+    std::vector<int64_t> probeVars;
+    for (const auto &p : opt.probes) probeVars.push_back((int64_t)(p.first * N) + p.second);
+    std::vector<Real> probeOut(rows * probeVars.size()), snaps, en;
+    const size_t nSnap = opt.snapshotStride > 0 ? (rows - 1) / (size_t)opt.snapshotStride + 1 : 0;
+    snaps.resize(nSnap * n);
+    if (opt.energies) en.resize(rows * 3);
+    mfh_newmark_params prm{};
+    prm.dt = dt; prm.beta = opt.beta; prm.gamma = opt.gamma; prm.density = opt.density;
+    prm.rayleighMass = opt.rayleighMass; prm.rayleighStiff = opt.rayleighStiff; prm.rtol = opt.rtol;
+    prm.nSteps = nSteps; prm.maxit = opt.maxit; prm.snapshotStride = nSnap ? opt.snapshotStride : 0;
+    prm.flags = (opt.a0.empty() ? 0 : MFH_DYN_HAVE_ACCEL) | (opt.energies ? MFH_DYN_ENERGIES : 0);
+    check(c, mfh_newmark(c, &prm, &r.u[0][0], &r.v[0][0], &r.a[0][0], loaded ? &f[0][0] : nullptr, opt.amplitude.empty() ? nullptr : opt.amplitude.data(),
+                         probeVars.empty() ? nullptr : probeVars.data(), (int32_t)probeVars.size(), probeVars.empty() ? nullptr : probeOut.data(),
+                         nSnap ? snaps.data() : nullptr, opt.energies ? en.data() : nullptr, &r.info));
+    r.probes.assign(rows, std::vector<Real>(probeVars.size()));
+    for (size_t k = 0; k < rows; ++k)
+        for (size_t j = 0; j < probeVars.size(); ++j) r.probes[k][j] = probeOut[k * probeVars.size() + j];
+    r.snapshots.assign(nSnap, VField(nDoF));
+    for (size_t k = 0; k < nSnap; ++k) std::copy(snaps.begin() + k * n, snaps.begin() + (k + 1) * n, &r.snapshots[k][0][0]);
+    r.energies.resize(opt.energies ? rows : 0);
+    for (size_t k = 0; k < r.energies.size(); ++k) r.energies[k] = {en[3 * k], en[3 * k + 1], en[3 * k + 2]};
+    return r;
+}
+
+} // namespace MeshFEMHip

@@ -493,6 +493,45 @@ mfh_status mfh_modes(mfh_ctx* ctx, int32_t nev, double density, int32_t flags, d
                      double* lambda /* nev */, double* X /* nev x dim*nDoF, row per mode */, double* residuals /* nev or NULL */,
                      mfh_modes_info* info);
 
+/* ---------------------------------------------------------------- transient dynamics
+ * Implicit Newmark time stepping of M u'' + C u' + K u = g(t) f on the device (docs/design/04_13_dynamics.md): K the elasticity operator of the
+ * context, M = density times the consistent vector-valued mass matrix of the mesh's own degree, C = rayleighMass M + rayleighStiff K, the fixed
+ * variables of the context (mfh_fix_variables; their values are taken as 0) held at zero -- their set may be empty. The reference has no time
+ * integrator. With beta > 0, gamma >= 1/2 every step solves
+ *     (cK K + cM M) u+ = g+ f + M (u~ / (beta dt^2)) + C (gamma / (beta dt) u~ - v~),    u~ = u + dt v + dt^2 (1/2 - beta) a,  v~ = v + dt (1 - gamma) a
+ *     a+ = (u+ - u~) / (beta dt^2),   v+ = v~ + gamma dt a+,    cK = 1 + gamma rayleighStiff / (beta dt),  cM = density (1 / (beta dt^2) + gamma rayleighMass / (beta dt))
+ * by PCG from the start vector u~ to ||r||_2 <= rtol ||b||_2 (the rule of mfh_solve) with the context's preconditioner: block-Jacobi on the diagonal
+ * blocks of cK K + cM M itself; two-level / multigrid on K's hierarchy (cond <= 1 + cM / (cK lambda_1)); block-Jacobi of the sum in their place when
+ * there are no fixed variables (K singular, the sum not) -- info->note says which. 2 beta < gamma is accepted (conditionally stable: info->note).
+ *   u, v, a      dim*nDoF each: the state at step 0 in, the state after the last completed step out. Without MFH_DYN_HAVE_ACCEL a is not read:
+ *                a0 comes from M a0 = g0 f - C v0 - K u0. Two calls chained through (u, v, a) with MFH_DYN_HAVE_ACCEL continue a run.
+ *   f            the load shape (NULL: none); amplitude: g at the steps 0 .. nSteps (NULL: 1)
+ *   probeVars    nProbe variables whose displacement is recorded at every step: probeOut[(nSteps+1) x nProbe]
+ *   snapshots    the displacement at the steps 0, stride, 2 stride, ...: (nSteps/stride + 1) x dim*nDoF (NULL: none)
+ *   energies     with MFH_DYN_ENERGIES, per step {1/2 v.Mv, 1/2 u.Ku, g f.u}: one more product with M and with K per step
+ * A step whose PCG reaches maxit: MFH_ERR_NOT_CONVERGED, info->stepsDone and the outputs of the steps completed (a failure in the solve for a0
+ * writes nothing). MFH_ERR_INVALID before any device work: dt <= 0, beta <= 0, gamma < 1/2, density <= 0, a negative Rayleigh coefficient, a
+ * probe variable out of range, energies without its flag. Like mfh_modes the call holds both triangles of the pattern for its own duration
+ * (info->note); elasticity, the mesh's own degree, unpartitioned contexts (MFH_ERR_UNSUPPORTED). */
+enum { MFH_DYN_HAVE_ACCEL = 1, MFH_DYN_ENERGIES = 2 };
+typedef struct mfh_newmark_params {
+    double dt, beta, gamma, density, rayleighMass, rayleighStiff, rtol;
+    int32_t nSteps, maxit, snapshotStride, flags;
+} mfh_newmark_params;
+typedef struct mfh_newmark_info {
+    int32_t stepsDone, iterationsTotal, iterationsMax, iterationsInit, precondUsed;   /* PCG iterations of the steps / of the worst step / of the solve for a0 */
+    double cK, cM, solve_ms, setup_ms;
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_newmark_info;
+mfh_status mfh_newmark(mfh_ctx* ctx, const mfh_newmark_params* params,
+                       double* u, double* v, double* a,          /* dim*nDoF each; state in, state after the last completed step out */
+                       const double* f,                          /* dim*nDoF or NULL */
+                       const double* amplitude,                  /* nSteps+1 or NULL (= 1) */
+                       const int64_t* probeVars, int32_t nProbe, double* probeOut,  /* (nSteps+1) x nProbe */
+                       double* snapshots,                        /* (nSteps/stride + 1) x dim*nDoF or NULL */
+                       double* energies,                         /* (nSteps+1) x 3: kinetic, strain, g_n f.u_n; needs MFH_DYN_ENERGIES */
+                       mfh_newmark_info* info);
+
 /* ---------------------------------------------------------------- multi-GPU solve (one process per GPU)
  * The reference is single-process (TBB, Parallelism.hh:31-43): these entry points have no counterpart to cite beyond the
  * serial path they parallelise (Simulator::solve, LinearElasticity.hh:479-487; SPSDSystem::solve, SparseMatrices.hh:2515-2606).

@@ -76,6 +76,20 @@ mfh_status mfh_debug_block_gram(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, c
 /* Y = A C through k_block_update: A n x p and Y n x q column-major, C p x q row-major */
 mfh_status mfh_debug_block_update(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, const double* A, const double* C, double* Y);
 
+/* test hooks: the step kernels of mfh_newmark (mfh_dynamics.hip) on host arrays of n doubles. mask: n bytes or NULL (non-zero = fixed variable).
+ * predict: ut = u + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a (both 0 where masked), w = gamma / (beta dt) ut - vt,
+ *   xm = density (ut / (beta dt^2) + rayleighMass w), xk = rayleighStiff w (xk may be NULL) */
+mfh_status mfh_debug_newmark_predict(mfh_ctx* ctx, int64_t n, double dt, double beta, double gamma, double density, double rayleighMass, double rayleighStiff,
+                                     const uint8_t* mask, const double* u, const double* v, const double* a, double* ut, double* vt, double* xm, double* xk);
+/* rhs: b = g f + y (f may be NULL), 0 where masked; *bb = b . b through the two-stage sum */
+mfh_status mfh_debug_newmark_rhs(mfh_ctx* ctx, int64_t n, double g, const double* f, const double* y, const uint8_t* mask, double* b, double* bb);
+/* correct: a = (x - ut) / (beta dt^2), v = vt + gamma dt a, u = x; probeOut[j] = x[probeVars[j]]; snapshot (n doubles or NULL) = x */
+mfh_status mfh_debug_newmark_correct(mfh_ctx* ctx, int64_t n, double dt, double beta, double gamma, const double* x, const double* ut, const double* vt,
+                                     double* u, double* v, double* a, const int64_t* probeVars, int32_t nProbe, double* probeOut, double* snapshot);
+/* y = cK K x + cM M x (M with density 1) through the context's operator and k_spmv_kron_acc, rows of fixed variables zeroed if masked != 0;
+ * *dot (may be NULL) = x . y from the kernel's partials. cK == 0 skips the K product */
+mfh_status mfh_debug_pencil_apply(mfh_ctx* ctx, double cK, double cM, int32_t masked, const double* x, double* y, double* dot);
+
 
 /* ---------------------------------------------------------------- device-pointer building blocks
  * (multi-GPU driver: local kernels here, RCCL halo exchange / all-reduce in between)           */

@@ -17,6 +17,7 @@ SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED = 1, 2, 4
 MEASURE_VON_MISES, MEASURE_EIGENVALUES, MEASURE_EIGENVECTORS = 1, 2, 4
 FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE = 0, 1, 2
 MODES_FREE = 1
+DYN_HAVE_ACCEL, DYN_ENERGIES = 1, 2
 
 
 class SamplerGridInfo(C.Structure):
@@ -41,6 +42,23 @@ class ModesInfo(C.Structure):
     _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("nLocked", C.c_int32), ("precondUsed", C.c_int32),
                 ("blockSize", C.c_int32), ("restarts", C.c_int32), ("maxResidual", C.c_double), ("solve_ms", C.c_double),
                 ("setup_ms", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
+class NewmarkParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("density", C.c_double), ("rayleighMass", C.c_double),
+                ("rayleighStiff", C.c_double), ("rtol", C.c_double), ("nSteps", C.c_int32), ("maxit", C.c_int32), ("snapshotStride", C.c_int32),
+                ("flags", C.c_int32)]
+
+
+class NewmarkInfo(C.Structure):
+    _fields_ = [("stepsDone", C.c_int32), ("iterationsTotal", C.c_int32), ("iterationsMax", C.c_int32), ("iterationsInit", C.c_int32),
+                ("precondUsed", C.c_int32), ("cK", C.c_double), ("cM", C.c_double), ("solve_ms", C.c_double), ("setup_ms", C.c_double),
+                ("note", C.c_char_p)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -161,6 +179,7 @@ PROTOTYPES = {
     "mfh_mass_lumped": (_i32, [_P, _P, _i32]),
     "mfh_divergence": (_i32, [_P, _P, _P]),
     "mfh_modes": (_i32, [_P, _i32, _f64, _i32, _f64, _i32, _P, _P, _P, C.POINTER(ModesInfo)]),
+    "mfh_newmark": (_i32, [_P, C.POINTER(NewmarkParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(NewmarkInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -218,6 +237,10 @@ PROTOTYPES = {
     "mfh_debug_sym_gen_eig": (_i32, [_i64, _P, _P, _P, _P]),
     "mfh_debug_block_gram": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
     "mfh_debug_block_update": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
+    "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
+    "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),
+    "mfh_debug_pencil_apply": (_i32, [_P, _f64, _f64, _i32, _P, _P, _P]),
 }
 
 # callback types of mfh_comm_create_callbacks

@@ -425,6 +425,89 @@ class Context:
         self._ck(st)
         return lam, X, d
 
+    def newmark(self, dt, n_steps, u0=None, v0=None, a0=None, f=None, amplitude=None, density=1.0, damping=(0.0, 0.0), beta=0.25, gamma=0.5,
+                rtol=1e-8, maxit=10000, probes=None, snapshot_stride=0, energies=False):
+        """Implicit Newmark time stepping of M u'' + C u' + K u = g(t) f on the device (mfh_newmark): M = density x the consistent vector-valued
+        mass matrix, C = damping[0] M + damping[1] K, the context's fixed variables held at zero. u0 / v0: the state at step 0 (None: rest);
+        a0: its acceleration (None: from M a0 = g0 f - C v0 - K u0; pass the "a" of an earlier call to continue that run); amplitude: g at the
+        steps 0 .. n_steps (None: 1). Returns a dict: "u", "v", "a" (the state after the last step), "probes" [(n_steps + 1), len(probes)],
+        "snapshots" [n_steps // snapshot_stride + 1, dim * n_dof] (snapshot_stride > 0), "energies" [(n_steps + 1), 3] = kinetic, strain,
+        g f.u (energies=True) and "info". Raises on MFH_ERR_NOT_CONVERGED like solve(); what was reached (info["stepsDone"] steps) is then in
+        self.last_newmark."""
+        n = self.bs * self.n_dof
+        n_steps = int(n_steps)
+        rows = max(n_steps, 0) + 1
+
+        def state(x):
+            x = np.zeros(n) if x is None else np.array(x, dtype=np.float64).reshape(-1)
+            if x.size != n:
+                raise ValueError("newmark: a state vector needs dim * n_dof = %d entries, got %d" % (n, x.size))
+            return np.ascontiguousarray(x)
+        u, v, a = state(u0), state(v0), state(a0)
+        f = None if f is None else as_f64(np.asarray(f, dtype=np.float64).reshape(-1))
+        if f is not None and f.size != n:
+            raise ValueError("newmark: f needs dim * n_dof = %d entries, got %d" % (n, f.size))
+        amp = None if amplitude is None else as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
+        if amp is not None and amp.size != rows:
+            raise ValueError("newmark: amplitude needs n_steps + 1 = %d entries, got %d" % (rows, amp.size))
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros((rows, n_probe)) if n_probe else None
+        stride = int(snapshot_stride)
+        snaps = np.zeros((max(n_steps, 0) // stride + 1, n)) if stride > 0 else None
+        en = np.zeros((rows, 3)) if energies else None
+        prm = L.NewmarkParams(float(dt), float(beta), float(gamma), float(density), float(damping[0]), float(damping[1]), float(rtol), n_steps,
+                              int(maxit), stride, (L.DYN_HAVE_ACCEL if a0 is not None else 0) | (L.DYN_ENERGIES if energies else 0))
+        info = L.NewmarkInfo()
+        st = self.lib.mfh_newmark(self.h, C.byref(prm), ptr(u), ptr(v), ptr(a), ptr(f), ptr(amp), ptr(pv), n_probe, ptr(pout), ptr(snaps), ptr(en),
+                                  C.byref(info))
+        out = {"u": u, "v": v, "a": a, "probes": pout, "snapshots": snaps, "energies": en, "info": info.as_dict()}
+        self.last_newmark = out
+        self._ck(st)
+        return out
+
+    def debug_newmark_predict(self, dt, beta, gamma, density, damping, u, v, a, mask=None, want_xk=True):
+        """(ut, vt, xm, xk) of k_newmark_predict on host arrays (test hook mfh_debug_newmark_predict)."""
+        u, v, a = as_f64(u), as_f64(v), as_f64(a)
+        n = u.size
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        ut, vt, xm = np.empty(n), np.empty(n), np.empty(n)
+        xk = np.empty(n) if want_xk else None
+        self._ck(self.lib.mfh_debug_newmark_predict(self.h, n, float(dt), float(beta), float(gamma), float(density), float(damping[0]), float(damping[1]),
+                                                    ptr(m), ptr(u), ptr(v), ptr(a), ptr(ut), ptr(vt), ptr(xm), ptr(xk)))
+        return ut, vt, xm, xk
+
+    def debug_newmark_rhs(self, g, f, y, mask=None):
+        """(b, b . b) of k_newmark_rhs and its second stage (test hook mfh_debug_newmark_rhs)."""
+        y = as_f64(y)
+        f = None if f is None else as_f64(f)
+        n = y.size
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        b, bb = np.empty(n), np.zeros(1)
+        self._ck(self.lib.mfh_debug_newmark_rhs(self.h, n, float(g), ptr(f), ptr(y), ptr(m), ptr(b), ptr(bb)))
+        return b, float(bb[0])
+
+    def debug_newmark_correct(self, dt, beta, gamma, x, ut, vt, probes=None, snapshot=True):
+        """(u, v, a, probe values, snapshot row) of k_newmark_correct (test hook mfh_debug_newmark_correct)."""
+        x, ut, vt = as_f64(x), as_f64(ut), as_f64(vt)
+        n = x.size
+        pv = None if probes is None else as_i64(probes)
+        n_probe = 0 if pv is None else pv.size
+        u, v, a = np.empty(n), np.empty(n), np.empty(n)
+        pout = np.empty(n_probe) if n_probe else None
+        snap = np.empty(n) if snapshot else None
+        self._ck(self.lib.mfh_debug_newmark_correct(self.h, n, float(dt), float(beta), float(gamma), ptr(x), ptr(ut), ptr(vt), ptr(u), ptr(v), ptr(a),
+                                                    ptr(pv), n_probe, ptr(pout), ptr(snap)))
+        return u, v, a, pout, snap
+
+    def debug_pencil_apply(self, cK, cM, x, masked=True):
+        """(cK K x + cM M x, x . y) through the context's operator and k_spmv_kron_acc (test hook mfh_debug_pencil_apply; M with density 1)."""
+        x = as_f64(x)
+        y, dot = np.empty(self.bs * self.n_dof), np.zeros(1)
+        assert x.size == y.size
+        self._ck(self.lib.mfh_debug_pencil_apply(self.h, float(cK), float(cM), 1 if masked else 0, ptr(x), ptr(y), ptr(dot)))
+        return y, float(dot[0])
+
     def debug_sym_gen_eig(self, A, B):
         """(w, V) of the dense pencil A v = w B v by the Rayleigh-Ritz routine of mfh_modes (test hook mfh_debug_sym_gen_eig)."""
         A, B = as_f64(A), as_f64(B)

@@ -170,6 +170,9 @@ struct mfh_ctx {
     bool modesWide = false;           // mfh_modes in progress on a context whose storage rule says "upper triangle": the symbolic phase builds both
                                       // (resolve_upper_storage) until the call returns; option matrix_storage itself is not changed
     std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
+    std::string dynNote;              // mfh_newmark_info::note of the last mfh_newmark (mfh_dynamics.hip)
+    int dynGridCap = 2048;            // option "dyn_grid_cap" (1 .. 2048): workgroups of the vector kernels of mfh_newmark's PCG loop = partials per sum
+                                      // (the tests set 1, so that the lanes loop on a small mesh)
 
     // ---- constraints (SPSDSystem state)
     std::vector<int64_t> fixedVars;

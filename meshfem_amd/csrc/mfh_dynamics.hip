@@ -1,0 +1,911 @@
+// Transient dynamics (mfh_newmark, include/meshfem_hip.h; docs/design/04_13_dynamics.md): implicit Newmark time stepping of
+//   M u'' + C u' + K u = g(t) f,   M = density x the consistent vector mass matrix,  C = aR M + bR K,  fixed variables held at zero.
+// The reference has no time integrator; the scheme is checked against an independent recurrence (tests/dynamics_util.py). Every step solves
+//   A u+ = b,   A = cK K + cM M  (the "pencil operator"),   cK = 1 + gamma bR / (beta dt),  cM = density (1 / (beta dt^2) + gamma aR / (beta dt))
+// by a PCG loop of this file on the context's operator (apply_operator) and preconditioners (launch of k_pencil_dinv's blocks / tl_precond /
+// mg_precond), the way mfh_modes.hip builds on them without touching the pinned loops of mfh_solver.cpp.
+//   k_spmv_kron_acc    y = cK y + cM (M (x) I) x: k_spmv_kron's chunks and LDS partials, ADDING into the K product that apply_operator left in y
+//                      (cK == 0: y is not read), the fixed rows zeroed, x . y summed per workgroup in the same pass
+//   k_pencil_dinv      inverse diagonal blocks of A: cK K_ii + cM m_ii I (fixed rows / columns replaced by the identity), symmetric-packed
+//   k_newmark_predict  u~, v~, the vector M multiplies and the vector K multiplies, one pass over (u, v, a)
+//   k_newmark_rhs      b = g f + (products), masked, with b . b
+//   k_newmark_correct  a+, v+, u+, the probe values of the step and the snapshot row
+//   k_dyn_*            the PCG's vector kernels
+// Sums: every producing kernel leaves ONE partial per workgroup and sum (plain stores); k_dyn_reduce adds them in a fixed order (runs of consecutive
+// workgroups per lane, then an ordered two-level tree) and stores the total where the loop reads it. No floating-point atomics; the grids depend on n (and option dyn_grid_cap) only, so two
+// calls add in the same order.
+// Gate: the kernels of iteration `it` are no-ops once scal[4 it + 2] = r.r has met stop[0] (the idiom of the loops in mfh_solver.cpp; the layout of
+// the history -- {r.z, p.Ap, r.r, -} per iteration -- and of the control block is theirs, so that mg_precond's kernels take the same gate).
+#include "mfh_ctx.hh"
+#include "mfh_device.hh"
+
+namespace mfh { namespace k {
+
+namespace {
+
+constexpr int DYN_GRID_CAP = 2048;      // workgroups of k_spmv_kron_acc (k_spmv_kron's cap) and of the PCG's vector kernels at most = rows of the partials buffer
+constexpr int DYN_STEP_CAP = 256;       // workgroups of the three step kernels (once per step: one workgroup per CU is plenty)
+constexpr int DYN_NV = 4;               // sums a kernel may emit (stride of the partials)
+
+struct DynGate { const double *scal; int it; const double *stop; };
+DEV bool dyn_closed(const DynGate &g) {
+    if (!g.scal) return false;
+    const int it = g.it + (int)g.stop[3];
+    return it >= 0 && g.scal[(int64_t)it * 4 + 2] <= g.stop[0];
+}
+
+// the workgroup's sums (valid in thread 0 after block_sum) -> its row of the partials
+template <int NV> DEV void store_partials(double (&v)[NV], double *lds, double *__restrict__ partials) {
+    block_sum<NV>(v, lds);
+    if (threadIdx.x == 0 && partials) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) partials[(int64_t)blockIdx.x * DYN_NV + k] = v[k];
+    }
+}
+
+// second stage, in a fixed order that depends on nPart alone: lane l adds the G = ceil(nPart / 256) consecutive partials [l G, (l + 1) G) in workgroup
+// order, 16 lanes add 16 consecutive lane sums each, one lane adds those 16: dst[t] = scale[t] x the total of column col[t]. (One lane adding 2 048
+// partials one dependent load after the other took 0.3 ms, a tenth of a PCG iteration.)
+struct ReduceArgs {
+    int nPart, nv;
+    int col[DYN_NV];
+    double scale[DYN_NV];
+    double *dst[DYN_NV];
+};
+__global__ void __launch_bounds__(256) k_dyn_reduce(ReduceArgs a, const double *__restrict__ partials, DynGate g) {
+    __shared__ double lane_sum[256], group_sum[16];
+    if (dyn_closed(g)) return;          // (uniform over the workgroup)
+    const int l = threadIdx.x;
+    const int G = (a.nPart + 255) / 256;
+    for (int t = 0; t < a.nv; ++t) {
+        if (!a.dst[t]) continue;        // (uniform)
+        double v = 0.0;
+        const int b1 = min((l + 1) * G, a.nPart);
+        for (int b = l * G; b < b1; ++b) v += partials[(int64_t)b * DYN_NV + a.col[t]];
+        lane_sum[l] = v;
+        __syncthreads();
+        if (l < 16) {
+            double w = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) w += lane_sum[l * 16 + j];
+            group_sum[l] = w;
+        }
+        __syncthreads();
+        if (l == 0) {
+            double w = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) w += group_sum[j];
+            *a.dst[t] = a.scale[t] * w;
+        }
+        __syncthreads();
+    }
+}
+
+// y[N i + c] = cK y[N i + c] + cM sum_j m_ij x[N j + c] (ACC; else cM sum_j ... alone), zero on the fixed rows; partials[blockIdx.x][0] = x . y
+// over the workgroup's rows. The chunk walk and the LDS partials are k_spmv_kron's (mfh_kernels.hip): the lanes take consecutive stored blocks,
+// then one lane per scalar row adds the row's partials in slot order.
+template <int N, bool ACC>
+__global__ void __launch_bounds__(256) k_spmv_kron_acc(SpmvArgs a, double cK, double cM, const double *__restrict__ x, double *y,
+                                                      double *__restrict__ partials, DynGate g) {
+    extern __shared__ __attribute__((aligned(16))) double part[];  // [N][chunkSlots] + 16
+    const int CS = a.chunkSlots;
+    double *red = part + N * CS;
+    if (dyn_closed(g)) return;
+    double dot[1] = {0.0};
+    for (int64_t chunk = blockIdx.x; chunk < a.nChunk; chunk += gridDim.x) {
+        const int r0 = a.chunkRow[chunk], r1 = a.chunkRow[chunk + 1];
+        const int s0 = a.rowPtr[r0];
+        const int ns = a.rowPtr[r1] - s0;
+        for (int t = threadIdx.x; t < ns; t += 256) {
+            const int64_t s = (int64_t)s0 + t;
+            const int64_t col = a.colIdx[s];
+            const double m = a.vals[tiled_index(s, 0, 1)];
+#pragma unroll
+            for (int c = 0; c < N; ++c) part[c * CS + t] = m * x[col * N + c];
+        }
+        __syncthreads();
+        const int nscalar = (r1 - r0) * N;
+        for (int idx = threadIdx.x; idx < nscalar; idx += 256) {
+            const int rl = idx / N, c = idx - rl * N;
+            const int64_t r = r0 + rl;
+            const int b = a.rowPtr[r] - s0, e = a.rowPtr[r + 1] - s0;
+            double v = 0;
+            for (int t = b; t < e; ++t) v += part[c * CS + t];
+            const int64_t gi = r * N + c;
+            v *= cM;
+            if (ACC) v = fma(cK, y[gi], v);
+            if (a.fixedMask && a.fixedMask[gi]) v = 0.0;
+            y[gi] = v;
+            dot[0] = fma(v, x[gi], dot[0]);
+        }
+        __syncthreads();
+    }
+    store_partials<1>(dot, red, partials);
+}
+
+template <int DIM> DEV void sym_block_inverse(const double *A, double *Inv) {
+    if (DIM == 2) {
+        const double det = A[0] * A[3] - A[1] * A[2];
+        Inv[0] = A[3] / det; Inv[1] = -A[1] / det; Inv[2] = -A[2] / det; Inv[3] = A[0] / det;
+    } else {
+        const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
+        const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
+        Inv[0] = c00 / det; Inv[1] = (A[2] * A[7] - A[1] * A[8]) / det; Inv[2] = (A[1] * A[5] - A[2] * A[4]) / det;
+        Inv[3] = c01 / det; Inv[4] = (A[0] * A[8] - A[2] * A[6]) / det; Inv[5] = (A[2] * A[3] - A[0] * A[5]) / det;
+        Inv[6] = c02 / det; Inv[7] = (A[1] * A[6] - A[0] * A[7]) / det; Inv[8] = (A[0] * A[4] - A[1] * A[3]) / det;
+    }
+}
+
+// Inverse diagonal blocks of the pencil operator, in the layout of k_diag_inv (symmetric-packed, flat_idx): cK K_rr + cM m_rr I with the rows and
+// columns of fixed variables replaced by the identity. kVals: K's tiled dense blocks (null with cK == 0), mVals: one value per block; both on
+// the pattern (rowPtr, colIdx), whose columns are sorted within a row.
+template <int DIM>
+__global__ void __launch_bounds__(256) k_pencil_dinv(int64_t nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colIdx,
+                                                    const double *__restrict__ kVals, const double *__restrict__ mVals, double cK, double cM,
+                                                    const uint8_t *__restrict__ fixedMask, double *__restrict__ dinv) {
+    constexpr int NB = DIM * DIM, NS = DIM * (DIM + 1) / 2;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < nRows; r += (int64_t)gridDim.x * 256) {
+        double A[NB], Inv[NB];
+#pragma unroll
+        for (int c = 0; c < NB; ++c) A[c] = (c % (DIM + 1) == 0) ? 1.0 : 0.0;
+        int lo = rowPtr[r], hi = rowPtr[r + 1];
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            const int cv = colIdx[mid];
+            if (cv == r) {
+                const double mrr = cM * mVals[tiled_index(mid, 0, 1)];
+#pragma unroll
+                for (int c = 0; c < NB; ++c) A[c] = (kVals ? cK * kVals[tiled_index(mid, c, NB)] : 0.0) + ((c % (DIM + 1) == 0) ? mrr : 0.0);
+                break;
+            }
+            if (cv < r) lo = mid + 1; else hi = mid;
+        }
+        if (fixedMask) {
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+                if (fixedMask[r * DIM + c]) {
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) { A[c * DIM + d] = 0.0; A[d * DIM + c] = 0.0; }
+                    A[c * DIM + c] = 1.0;
+                }
+        }
+        sym_block_inverse<DIM>(A, Inv);
+#pragma unroll
+        for (int c = 0; c < DIM; ++c)
+#pragma unroll
+            for (int d = c; d < DIM; ++d) dinv[r * NS + flat_idx<DIM>(c, d)] = 0.5 * (Inv[c * DIM + d] + Inv[d * DIM + c]);
+    }
+}
+
+template <int DIM> DEV void apply_packed(const double *__restrict__ Dm, const double *r, double *z) {
+    constexpr int NS = DIM * (DIM + 1) / 2;
+    double m[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) m[q] = Dm[q];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double v = 0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) v += m[flat_idx<DIM>(c, d)] * r[d];
+        z[c] = v;
+    }
+}
+
+// ---- the step kernels
+struct PredictArgs {
+    int64_t n;
+    double dt, cua, cva;       // u~ = u + dt v + cua a,  v~ = v + cva a
+    double cw;                 // w = cw u~ - v~  (the vector C multiplies; cw = gamma / (beta dt))
+    double cmu, cmw, ckw;      // xm = cmu u~ + cmw w (density inside),  xk = ckw w
+};
+__global__ void __launch_bounds__(256) k_newmark_predict(PredictArgs p, const double *__restrict__ u, const double *__restrict__ v, const double *__restrict__ a,
+                                                        const uint8_t *__restrict__ mask, double *__restrict__ ut, double *__restrict__ vt,
+                                                        double *__restrict__ xm, double *__restrict__ xk) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * 256) {
+        const double ai = a[i], vi = v[i];
+        double up = fma(p.cua, ai, fma(p.dt, vi, u[i])), vp = fma(p.cva, ai, vi);
+        if (mask && mask[i]) { up = 0.0; vp = 0.0; }
+        const double w = fma(p.cw, up, -vp);
+        ut[i] = up;
+        vt[i] = vp;
+        xm[i] = fma(p.cmu, up, p.cmw * w);
+        if (xk) xk[i] = p.ckw * w;
+    }
+}
+
+// b = g f + y (f null: y alone), zero on the fixed variables; partials[.][0] = b . b
+__global__ void __launch_bounds__(256) k_newmark_rhs(int64_t n, double g, const double *__restrict__ f, const double *__restrict__ y,
+                                                    const uint8_t *__restrict__ mask, double *__restrict__ b, double *__restrict__ partials) {
+    __shared__ double red[8];
+    double acc[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double v = f ? fma(g, f[i], y[i]) : y[i];
+        if (mask && mask[i]) v = 0.0;
+        b[i] = v;
+        acc[0] = fma(v, v, acc[0]);
+    }
+    store_partials<1>(acc, red, partials);
+}
+
+struct CorrectArgs {
+    int64_t n;
+    double ca, cv;             // a+ = ca (x - u~),  v+ = v~ + cv a+   (ca = 1 / (beta dt^2), cv = gamma dt)
+    int recordOnly;            // 1: u, v, a stay; the probe values and the snapshot row are taken from u (step 0)
+    int nProbe;
+    const int64_t *probeVars;
+    double *probeRow;          // nProbe values of this step (null: no probes)
+    double *snapRow;           // n values (null: not a snapshot step)
+};
+__global__ void __launch_bounds__(256) k_newmark_correct(CorrectArgs p, const double *__restrict__ x, const double *__restrict__ ut, const double *__restrict__ vt,
+                                                        double *__restrict__ u, double *__restrict__ v, double *__restrict__ a) {
+    const double *src = p.recordOnly ? u : x;
+    // the probes read the solution itself, which no lane of this kernel writes (x) or which stays as it is (u, recordOnly)
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.nProbe; j += (int64_t)gridDim.x * 256) p.probeRow[j] = src[p.probeVars[j]];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * 256) {
+        const double xi = src[i];
+        if (p.snapRow) p.snapRow[i] = xi;
+        if (!p.recordOnly) {
+            const double an = p.ca * (xi - ut[i]);
+            a[i] = an;
+            v[i] = fma(p.cv, an, vt[i]);
+            u[i] = xi;
+        }
+    }
+}
+
+// partials[.][0] = a . b, [.][1] = c . a (c null: 0)
+__global__ void __launch_bounds__(256) k_dyn_dot2(int64_t n, const double *__restrict__ a, const double *__restrict__ b, const double *__restrict__ c,
+                                                 double *__restrict__ partials) {
+    __shared__ double red[8];
+    double acc[2] = {0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double ai = a[i];
+        acc[0] = fma(ai, b[i], acc[0]);
+        if (c) acc[1] = fma(c[i], ai, acc[1]);
+    }
+    store_partials<2>(acc, red, partials);
+}
+
+// ---- the PCG's vector kernels (one lane per block row: DIM consecutive variables)
+// r = b - Ax; BJ: z = Dinv r, p = z, partials {r.z, r.r}; else partials {-, r.r}. bb == 0 (a zero right-hand side): x = 0 is the solution (the rule of
+// mfh_solve), r = z = p = 0.
+template <int DIM, bool BJ>
+__global__ void __launch_bounds__(256) k_dyn_init(int64_t nRows, const double *__restrict__ dinv, const double *__restrict__ b, const double *__restrict__ Ax,
+                                                 const double *__restrict__ bb, double *__restrict__ x, double *__restrict__ r, double *__restrict__ z,
+                                                 double *__restrict__ p, double *__restrict__ partials) {
+    __shared__ double red[8];
+    constexpr int NS = DIM * (DIM + 1) / 2;
+    const bool zeroRhs = bb[0] == 0.0;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < nRows; n += (int64_t)gridDim.x * 256) {
+        double rv[DIM], zv[DIM];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) rv[c] = zeroRhs ? 0.0 : b[n * DIM + c] - Ax[n * DIM + c];
+        if (BJ) apply_packed<DIM>(dinv + n * NS, rv, zv);
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            r[n * DIM + c] = rv[c];
+            if (zeroRhs) x[n * DIM + c] = 0.0;
+            if (BJ) { z[n * DIM + c] = zv[c]; p[n * DIM + c] = zv[c]; acc[0] = fma(rv[c], zv[c], acc[0]); }
+            acc[1] = fma(rv[c], rv[c], acc[1]);
+        }
+    }
+    store_partials<2>(acc, red, partials);
+}
+
+// alpha = r.z / p.Ap of iteration it;  x += alpha p;  r -= alpha Ap;  BJ: z = Dinv r, partials {r.z, r.r}; else {-, r.r}
+template <int DIM, bool BJ>
+__global__ void __launch_bounds__(256) k_dyn_update(int64_t nRows, const double *__restrict__ dinv, const double *__restrict__ Ap, const double *__restrict__ p,
+                                                   double *__restrict__ x, double *__restrict__ r, double *__restrict__ z, DynGate g,
+                                                   double *__restrict__ partials) {
+    __shared__ double red[8];
+    constexpr int NS = DIM * (DIM + 1) / 2;
+    if (dyn_closed(g)) return;
+    const double *sc = g.scal + (int64_t)(g.it + (int)g.stop[3]) * 4;
+    const double alpha = sc[0] / sc[1];
+    double acc[2] = {0.0, 0.0};
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < nRows; n += (int64_t)gridDim.x * 256) {
+        double rv[DIM], zv[DIM];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            const int64_t i = n * DIM + c;
+            x[i] = fma(alpha, p[i], x[i]);
+            rv[c] = fma(-alpha, Ap[i], r[i]);
+            r[i] = rv[c];
+            acc[1] = fma(rv[c], rv[c], acc[1]);
+        }
+        if (BJ) {
+            apply_packed<DIM>(dinv + n * NS, rv, zv);
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) { z[n * DIM + c] = zv[c]; acc[0] = fma(rv[c], zv[c], acc[0]); }
+        }
+    }
+    store_partials<2>(acc, red, partials);
+}
+
+// after the two-level / multigrid preconditioner: z = r on the fixed variables (r is 0 there), partials {r.z}
+__global__ void __launch_bounds__(256) k_dyn_rz(int64_t n, const double *__restrict__ r, double *__restrict__ z, const uint8_t *__restrict__ mask, DynGate g,
+                                               double *__restrict__ partials) {
+    __shared__ double red[8];
+    if (dyn_closed(g)) return;
+    double acc[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double zv = z[i];
+        const double rv = r[i];
+        if (mask && mask[i]) { zv = rv; z[i] = zv; }
+        acc[0] = fma(rv, zv, acc[0]);
+    }
+    store_partials<1>(acc, red, partials);
+}
+
+// p = z + beta p, beta = r.z of iteration it + 1 over r.z of iteration it (first: p = z)
+__global__ void __launch_bounds__(256) k_dyn_direction(int64_t n, const double *__restrict__ z, double *__restrict__ p, DynGate g, int first) {
+    if (dyn_closed(g)) return;
+    double beta = 0.0;
+    if (!first) {
+        const double *sc = g.scal + (int64_t)(g.it + (int)g.stop[3]) * 4;
+        beta = sc[4] / sc[0];
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = first ? z[i] : fma(beta, p[i], z[i]);
+}
+
+int dyn_grid(int64_t n, int cap = DYN_STEP_CAP) { return grid_for(n, cap); }
+
+void launch_reduce(int nPart, int nv, const int *col, const double *scale, double *const *dst, const double *partials, const DynGate &g, hipStream_t s) {
+    ReduceArgs a{};
+    a.nPart = nPart; a.nv = nv;
+    for (int t = 0; t < nv; ++t) { a.col[t] = col[t]; a.scale[t] = scale[t]; a.dst[t] = dst[t]; }
+    hipLaunchKernelGGL(k_dyn_reduce, dim3(1), dim3(256), 0, s, a, partials, g);
+    CHECK_LAUNCH();
+}
+
+// y = cK y + cM M x (acc) or cM M x; the workgroups' x . y in partials[.][0] (null: not wanted). Returns the number of partials.
+int launch_spmv_kron_acc(const SpmvArgs &a, bool acc, double cK, double cM, const double *x, double *y, double *partials, const DynGate &g, hipStream_t s,
+                         int cap = DYN_GRID_CAP) {
+    if (a.nChunk <= 0) return 0;
+    if (a.dim != 2 && a.dim != 3) throw mfh::Error(MFH_ERR_UNSUPPORTED, "k_spmv_kron_acc: 2D / 3D only");
+    const size_t lds = ((size_t)a.dim * a.chunkSlots + 16) * sizeof(double);
+    const int grid = (int)std::min<int64_t>(a.nChunk, std::max(1, std::min(cap, DYN_GRID_CAP)));
+    if (a.dim == 3) {
+        if (acc) hipLaunchKernelGGL((k_spmv_kron_acc<3, true>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
+        else hipLaunchKernelGGL((k_spmv_kron_acc<3, false>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
+    } else {
+        if (acc) hipLaunchKernelGGL((k_spmv_kron_acc<2, true>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
+        else hipLaunchKernelGGL((k_spmv_kron_acc<2, false>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
+    }
+    CHECK_LAUNCH();
+    return grid;
+}
+
+void launch_pencil_dinv(int dim, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *kVals, const double *mVals, double cK, double cM,
+                        const uint8_t *mask, double *dinv, hipStream_t s) {
+    if (dim == 3) hipLaunchKernelGGL(k_pencil_dinv<3>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, rowPtr, colIdx, kVals, mVals, cK, cM, mask, dinv);
+    else hipLaunchKernelGGL(k_pencil_dinv<2>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, rowPtr, colIdx, kVals, mVals, cK, cM, mask, dinv);
+    CHECK_LAUNCH();
+}
+
+void launch_newmark_predict(const PredictArgs &p, const double *u, const double *v, const double *a, const uint8_t *mask, double *ut, double *vt, double *xm,
+                            double *xk, hipStream_t s) {
+    hipLaunchKernelGGL(k_newmark_predict, dim3(dyn_grid(p.n)), dim3(256), 0, s, p, u, v, a, mask, ut, vt, xm, xk);
+    CHECK_LAUNCH();
+}
+
+int launch_newmark_rhs(int64_t n, double g, const double *f, const double *y, const uint8_t *mask, double *b, double *partials, hipStream_t s) {
+    const int grid = dyn_grid(n);
+    hipLaunchKernelGGL(k_newmark_rhs, dim3(grid), dim3(256), 0, s, n, g, f, y, mask, b, partials);
+    CHECK_LAUNCH();
+    return grid;
+}
+
+void launch_newmark_correct(const CorrectArgs &p, const double *x, const double *ut, const double *vt, double *u, double *v, double *a, hipStream_t s) {
+    hipLaunchKernelGGL(k_newmark_correct, dim3(dyn_grid(p.n)), dim3(256), 0, s, p, x, ut, vt, u, v, a);
+    CHECK_LAUNCH();
+}
+
+}   // namespace
+}}   // namespace mfh::k
+
+using namespace mfh;
+using namespace mfhi;
+using k::DynGate;
+using k::DYN_NV;
+
+namespace {
+
+struct NewmarkWork {
+    mfh_ctx *c;
+    hipStream_t s;
+    int d;
+    int64_t n, nRows;
+    bool masked, useMG = false, useTL = false;
+    const uint8_t *mask = nullptr;
+    DBuf<double> vec, partials, scal, ctl, dinv;
+    double *u, *v, *a, *ut, *vt, *xm, *xk, *f, *b, *x, *r, *z, *p, *Ap;
+    double *stop, *bb;                 // ctl: [0..3] the control block {threshold, -, -, iteration base}, [4] b . b
+    int maxit = 0, batch = 8;
+    double rtol = 0;
+    double dinvCK = -1, dinvCM = -1;   // the pencil the inverse diagonal blocks were built for
+    // per-phase device time (scripts/probe_dynamics.py: env MFH_DYN_TIMING=1 puts a synchronisation at every phase boundary)
+    bool timing = false;
+    double tPhase[7] = {0, 0, 0, 0, 0, 0, 0};   // K products, M products + p.Ap, residual update (+ block-Jacobi), coarse preconditioner + r.z, direction, read-back, step kernels
+    double tMark = 0;
+    void lap(int phase) {
+        if (!timing) return;
+        MFH_HIP(hipStreamSynchronize(s));
+        const double t = now_ms();
+        if (phase >= 0) tPhase[phase] += t - tMark;
+        tMark = t;
+    }
+
+    DynGate gate(int it) const { return DynGate{scal.p, it, stop}; }
+    DynGate open() const { return DynGate{nullptr, 0, nullptr}; }
+    void reduce(int nPart, int nv, const int *col, const double *scale, double *const *dst, const DynGate &g) {
+        k::launch_reduce(nPart, nv, col, scale, dst, partials.p, g, s);
+    }
+    // y = cK K x + cM M x on the free variables; dst (may be null) = x . y
+    void pencil(double cK, double cM, const double *xin, double *y, double *dotDst, const DynGate &g) {
+        lap(-1);
+        if (cK != 0.0) apply_operator(c, masked, xin, y, nullptr);
+        lap(0);
+        const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, masked), cK != 0.0, cK, cM, xin, y, dotDst ? partials.p : nullptr, g, s, c->dynGridCap);
+        if (dotDst) {
+            const int col[1] = {0};
+            const double sc[1] = {1.0};
+            double *const dst[1] = {dotDst};
+            reduce(np, 1, col, sc, dst, g);
+        }
+        lap(1);
+    }
+    void ensure_dinv(double cK, double cM) {
+        if (dinvCK == cK && dinvCM == cM) return;
+        dinv.alloc((size_t)nRows * (size_t)(d * (d + 1) / 2));
+        k::launch_pencil_dinv(d, nRows, c->dRowPtr.p, c->dColIdx.p, cK != 0.0 ? c->dVals.p : nullptr, c->dMassVals.p, cK, cM, mask, dinv.p, s);
+        dinvCK = cK; dinvCM = cM;
+    }
+    int vec_grid(int64_t count) const { return k::dyn_grid(count, std::max(1, std::min(c->dynGridCap, k::DYN_GRID_CAP))); }
+    template <bool BJ> void launch_init() {
+        const int grid = vec_grid(nRows);
+        if (d == 3) hipLaunchKernelGGL((k::k_dyn_init<3, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)b, (const double *)Ap, (const double *)bb, x, r, z, p, partials.p);
+        else hipLaunchKernelGGL((k::k_dyn_init<2, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)b, (const double *)Ap, (const double *)bb, x, r, z, p, partials.p);
+        CHECK_LAUNCH();
+        const int col[2] = {0, 1};
+        const double sc[2] = {1.0, 1.0};
+        double *const dst[2] = {BJ ? scal.p : nullptr, scal.p + 2};
+        reduce(grid, 2, col, sc, dst, open());
+    }
+    template <bool BJ> void launch_update(int it) {
+        const int grid = vec_grid(nRows);
+        const DynGate g = gate(it);
+        if (d == 3) hipLaunchKernelGGL((k::k_dyn_update<3, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)Ap, (const double *)p, x, r, z, g, partials.p);
+        else hipLaunchKernelGGL((k::k_dyn_update<2, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)Ap, (const double *)p, x, r, z, g, partials.p);
+        CHECK_LAUNCH();
+        const int col[2] = {0, 1};
+        const double sc[2] = {1.0, 1.0};
+        double *const dst[2] = {BJ ? scal.p + (size_t)(it + 1) * 4 : nullptr, scal.p + (size_t)(it + 1) * 4 + 2};
+        reduce(grid, 2, col, sc, dst, g);
+    }
+    // z = B r with the hierarchy of K (B ~ K^-1: its scaling by 1 / cK changes no PCG iterate and is left out), then r . z of iteration it + 1
+    void coarse_precond(int it) {
+        const DynGate g = it >= 0 ? gate(it) : open();
+        if (useMG) mg_precond(c, r, z, it >= 0 ? scal.p : nullptr, it, it >= 0 ? stop : nullptr);
+        else tl_precond(c, r, z, nullptr, -1);
+        const int grid = vec_grid(n);
+        hipLaunchKernelGGL(k::k_dyn_rz, dim3(grid), dim3(256), 0, s, n, (const double *)r, z, mask, g, partials.p);
+        CHECK_LAUNCH();
+        const int col[1] = {0};
+        const double sc[1] = {1.0};
+        double *const dst[1] = {scal.p + (size_t)(it + 1) * 4};
+        reduce(grid, 1, col, sc, dst, g);
+    }
+    void direction(int it, bool first) {
+        hipLaunchKernelGGL(k::k_dyn_direction, dim3(vec_grid(n)), dim3(256), 0, s, n, (const double *)z, p, first ? open() : gate(it), first ? 1 : 0);
+        CHECK_LAUNCH();
+    }
+
+    // PCG on A = cK K + cM M: b in this->b with b . b in bb[0] and the threshold in stop[0] (set_threshold), the start vector in x. Returns the
+    // iterations taken, -1: maxit reached (x then holds the last iterate), -2: breakdown (a residual norm is not finite).
+    int solve(double cK, double cM, bool jacobi) {
+        MFH_HIP(hipMemsetAsync(scal.p, 0, scal.n * sizeof(double), s));
+        if (jacobi) ensure_dinv(cK, cM);
+        pencil(cK, cM, x, Ap, nullptr, open());
+        if (jacobi) launch_init<true>();
+        else {
+            launch_init<false>();
+            coarse_precond(-1);
+            direction(-1, true);
+        }
+        std::vector<double> hs;
+        double hctl[5];
+        int it = 0, lastChecked = 0;
+        for (;;) {
+            const int itEnd = std::min(maxit, it + batch);
+            for (; it < itEnd; ++it) {
+                pencil(cK, cM, p, Ap, scal.p + (size_t)it * 4 + 1, gate(it));
+                if (jacobi) { launch_update<true>(it); lap(2); }
+                else { launch_update<false>(it); lap(2); coarse_precond(it); lap(3); }
+                direction(it, false);
+                lap(4);
+            }
+            hs.resize((size_t)(it - lastChecked + 1) * 4);
+            MFH_HIP(hipMemcpyAsync(hs.data(), scal.p + (size_t)lastChecked * 4, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            MFH_HIP(hipMemcpyAsync(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost, s));
+            MFH_HIP(hipStreamSynchronize(s));
+            lap(5);
+            for (int q = lastChecked; q <= it; ++q) {
+                const double rr = hs[(size_t)(q - lastChecked) * 4 + 2];
+                if (!std::isfinite(rr)) return -2;
+                if (rr <= hctl[0]) {
+                    batch = std::max(2, std::min(q + 1, c->checkEvery));      // the next solve of the run needs about as many: one read-back
+                    return q;
+                }
+            }
+            if (it >= maxit) return -1;
+            lastChecked = it;
+            batch = std::max(2, std::min(2 * batch, c->checkEvery));
+        }
+    }
+    // b . b of the right-hand side just formed (the partials of k_newmark_rhs) -> bb[0] and the threshold rtol^2 b . b -> stop[0]
+    void set_threshold(int nPart) {
+        const int col[2] = {0, 0};
+        const double sc[2] = {rtol * rtol, 1.0};
+        double *const dst[2] = {stop, bb};
+        reduce(nPart, 2, col, sc, dst, open());
+    }
+};
+
+void check_params(const mfh_newmark_params *p) {
+    require(p != nullptr, MFH_ERR_INVALID, "mfh_newmark: params is null");
+    require(p->dt > 0.0 && std::isfinite(p->dt), MFH_ERR_INVALID, "mfh_newmark: dt > 0");
+    require(p->beta > 0.0 && std::isfinite(p->beta), MFH_ERR_INVALID, "mfh_newmark: beta > 0");
+    require(p->gamma >= 0.5 && std::isfinite(p->gamma), MFH_ERR_INVALID, "mfh_newmark: gamma >= 1/2");
+    require(p->density > 0.0 && std::isfinite(p->density), MFH_ERR_INVALID, "mfh_newmark: density > 0");
+    require(p->rayleighMass >= 0.0 && p->rayleighStiff >= 0.0 && std::isfinite(p->rayleighMass) && std::isfinite(p->rayleighStiff), MFH_ERR_INVALID,
+            "mfh_newmark: the Rayleigh coefficients are not negative");
+    require(p->rtol > 0.0 && p->rtol < 1.0, MFH_ERR_INVALID, "mfh_newmark: 0 < rtol < 1");
+    require(p->nSteps >= 0 && p->maxit > 0 && p->snapshotStride >= 0, MFH_ERR_INVALID, "mfh_newmark: nSteps >= 0, maxit > 0, snapshotStride >= 0");
+    require((p->flags & ~(MFH_DYN_HAVE_ACCEL | MFH_DYN_ENERGIES)) == 0, MFH_ERR_INVALID, "mfh_newmark: unknown flag");
+}
+
+// the context conditions of mfh_newmark (those of mfh_modes, but the set of fixed variables may be empty) and the device state both products need
+void prepare_pencil(mfh_ctx *c, const char *who) {
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "no mesh set");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    if (!(c->op == MFH_OP_ELASTICITY && c->opDegree != 1))
+        throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": the operators are (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
+    if (!(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF)) throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": unpartitioned contexts only");
+    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "2D / 3D meshes");
+}
+
+// the storage of the pattern for the duration of a call (see mfh_ctx::modesWide): both triangles, and back
+struct WideGuard {
+    mfh_ctx *c;
+    bool widened = false;
+    explicit WideGuard(mfh_ctx *c_) : c(c_) {
+        if (resolve_upper_storage(c)) { c->modesWide = true; widened = true; }
+    }
+    ~WideGuard() {
+        if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
+    }
+};
+
+void upload(double *dst, const double *src, int64_t n, hipStream_t s) { MFH_HIP(hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s)); }
+
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_newmark(mfh_ctx *c, const mfh_newmark_params *prm, double *u, double *v, double *a, const double *f, const double *amplitude,
+                       const int64_t *probeVars, int32_t nProbe, double *probeOut, double *snapshots, double *energies, mfh_newmark_info *info) {
+    if (info) { *info = mfh_newmark_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_newmark: null context");
+    check_params(prm);
+    const mfh_newmark_params P = *prm;
+    require(u && v && a, MFH_ERR_INVALID, "mfh_newmark: u, v and a are not null");
+    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeOut)), MFH_ERR_INVALID, "mfh_newmark: probes need their variables and their output");
+    const bool wantE = (P.flags & MFH_DYN_ENERGIES) != 0;
+    require(!energies || wantE, MFH_ERR_INVALID, "mfh_newmark: energies given without MFH_DYN_ENERGIES");
+    require(!wantE || energies, MFH_ERR_INVALID, "mfh_newmark: MFH_DYN_ENERGIES needs the energies array");
+    require(!snapshots || P.snapshotStride > 0, MFH_ERR_INVALID, "mfh_newmark: snapshots need snapshotStride > 0");
+    {
+        const int64_t nv = (int64_t)c->bs() * c->nDoF;
+        for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_newmark: probe variable out of range");
+    }
+    prepare_pencil(c, "mfh_newmark");
+    hipStream_t s = c->stream;
+    c->dynNote.clear();
+    auto note = [&](const std::string &t) { if (!c->dynNote.empty()) c->dynNote += "; "; c->dynNote += t; };
+    WideGuard guard(c);
+    if (guard.widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    if (2.0 * P.beta < P.gamma) note("2 beta < gamma: the scheme is only conditionally stable");
+    EventTimer tsetup(s);
+    const bool masked = !c->fixedVars.empty();
+    const double bdt = P.beta * P.dt;
+    const double cK = 1.0 + P.gamma * P.rayleighStiff / bdt;
+    const double cM = P.density * (1.0 / (bdt * P.dt) + P.gamma * P.rayleighMass / bdt);
+    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of A itself otherwise
+    ensure_precond(c);
+    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
+    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_newmark: unpartitioned contexts only");
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_newmark");
+
+    NewmarkWork w;
+    w.c = c; w.s = s; w.d = c->bs();
+    w.nRows = c->sym.nRows;
+    w.n = (int64_t)w.d * c->nDoF;
+    w.masked = masked;
+    w.mask = masked ? c->dFixedMask.p : nullptr;
+    w.maxit = P.maxit; w.rtol = P.rtol;
+    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
+    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
+    const bool stepJacobi = !(w.useMG || w.useTL);
+    if (wantCoarse && !masked) note("no fixed variables (K singular, A not): block-Jacobi of A in place of the two-level / multigrid preconditioner");
+    else if (wantCoarse && stepJacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of A") : c->precondNote + " (block-Jacobi of A)");
+    else if (!wantCoarse) note("block-Jacobi of A = cK K + cM M");
+    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K") : c->precondNote);
+    const int64_t ld = (w.n + 31) / 32 * 32;
+    w.vec.alloc((size_t)ld * 14);
+    w.vec.zero(s);
+    {
+        double *q = w.vec.p;
+        double **slots[14] = {&w.u, &w.v, &w.a, &w.ut, &w.vt, &w.xm, &w.xk, &w.f, &w.b, &w.x, &w.r, &w.z, &w.p, &w.Ap};
+        for (auto sl : slots) { *sl = q; q += ld; }
+    }
+    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
+    w.scal.alloc(((size_t)P.maxit + 2) * 4);
+    w.ctl.alloc(8);
+    w.ctl.zero(s);
+    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
+    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
+    c->stop.zero(s);
+    w.batch = std::max(2, std::min(8, c->checkEvery));
+    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
+
+    const int nSteps = P.nSteps;
+    const int stride = snapshots ? P.snapshotStride : 0;
+    const int64_t nSnapRows = stride ? nSteps / stride + 1 : 0;
+    // snapshot rows wait on the device and leave in groups (256 MB at most, one row at least)
+    const int64_t snapCap = stride ? std::max<int64_t>(1, std::min<int64_t>(nSnapRows, ((int64_t)1 << 25) / std::max<int64_t>(w.n, 1))) : 0;
+    DBuf<double> dSnap, dProbe, dEnergy;
+    DBuf<int64_t> dProbeVars;
+    if (stride) dSnap.alloc((size_t)snapCap * (size_t)w.n);
+    if (nProbe) {
+        dProbe.alloc((size_t)(nSteps + 1) * (size_t)nProbe);
+        dProbeVars.alloc((size_t)nProbe);
+        MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    }
+    if (wantE) { dEnergy.alloc((size_t)(nSteps + 1) * 3); dEnergy.zero(s); }
+    upload(w.u, u, w.n, s);
+    upload(w.v, v, w.n, s);
+    if (P.flags & MFH_DYN_HAVE_ACCEL) upload(w.a, a, w.n, s);
+    if (f) upload(w.f, f, w.n, s);
+    if (masked) { k::launch_mask(w.n, w.mask, w.u, s); k::launch_mask(w.n, w.mask, w.v, s); k::launch_mask(w.n, w.mask, w.a, s); }
+    MFH_HIP(hipStreamSynchronize(s));
+    const double setupMs = tsetup.stop();
+
+    EventTimer tsolve(s);
+    int stepsDone = 0, itTotal = 0, itMax = 0, itInit = 0;
+    int64_t snapHeld = 0, snapWritten = 0;
+    auto flush_snapshots = [&]() {
+        if (snapHeld) MFH_HIP(hipMemcpyAsync(snapshots + (size_t)snapWritten * (size_t)w.n, dSnap.p, (size_t)snapHeld * (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+        MFH_HIP(hipStreamSynchronize(s));
+        snapWritten += snapHeld;
+        snapHeld = 0;
+    };
+    // probe values, snapshot row and energies of the state (u, v) at step `step`; x: the solution the correction reads (null: record only)
+    auto finish_step = [&](int step, const double *x) {
+        k::CorrectArgs ca{};
+        ca.n = w.n; ca.ca = 1.0 / (bdt * P.dt); ca.cv = P.gamma * P.dt; ca.recordOnly = x ? 0 : 1;
+        ca.nProbe = nProbe; ca.probeVars = dProbeVars.p; ca.probeRow = nProbe ? dProbe.p + (size_t)step * (size_t)nProbe : nullptr;
+        if (stride && step % stride == 0) {
+            if (snapHeld == snapCap) flush_snapshots();
+            ca.snapRow = dSnap.p + (size_t)snapHeld * (size_t)w.n;
+            ++snapHeld;
+        }
+        k::launch_newmark_correct(ca, x ? x : w.u, w.ut, w.vt, w.u, w.v, w.a, s);
+        if (wantE) {
+            const double g = amplitude ? amplitude[step] : 1.0;
+            double *row = dEnergy.p + (size_t)step * 3;
+            // kinetic: 1/2 v . (density M) v through the accumulate kernel's dot; strain and work: K u, then {u . K u, f . u}
+            const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, masked), false, 0.0, P.density, w.v, w.r, w.partials.p, w.open(), s, c->dynGridCap);
+            { const int col[1] = {0}; const double sc[1] = {0.5}; double *const dst[1] = {row}; w.reduce(np, 1, col, sc, dst, w.open()); }
+            apply_operator(c, masked, w.u, w.r, nullptr);
+            const int grid = w.vec_grid(w.n);
+            hipLaunchKernelGGL(k::k_dyn_dot2, dim3(grid), dim3(256), 0, s, w.n, (const double *)w.u, (const double *)w.r, f ? (const double *)w.f : (const double *)nullptr, w.partials.p);
+            CHECK_LAUNCH();
+            { const int col[2] = {0, 1}; const double sc[2] = {0.5, g}; double *const dst[2] = {row + 1, row + 2}; w.reduce(grid, 2, col, sc, dst, w.open()); }
+        }
+    };
+    mfh_status failure = MFH_OK;
+    std::string failText;
+    bool step0Done = (P.flags & MFH_DYN_HAVE_ACCEL) != 0;
+    // ---- a0 from M a0 = g0 f - C v0 - K u0: the pencil solve with cK = 0, block-Jacobi of density M
+    if (!(P.flags & MFH_DYN_HAVE_ACCEL)) {
+        const double g0 = amplitude ? amplitude[0] : 1.0;
+        // xm = -density aR v0 (M multiplies it), xk = -(u0 + bR v0) (K multiplies it)
+        MFH_HIP(hipMemcpyAsync(w.xm, w.v, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        k::launch_axpby(w.n, 0.0, w.xm, -P.density * P.rayleighMass, w.xm, s);
+        MFH_HIP(hipMemcpyAsync(w.xk, w.u, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        k::launch_axpby(w.n, -P.rayleighStiff, w.v, -1.0, w.xk, s);
+        apply_operator(c, masked, w.xk, w.Ap, nullptr);
+        k::launch_spmv_kron_acc(mass_spmv_args(c, masked), true, 1.0, 1.0, w.xm, w.Ap, nullptr, w.open(), s, c->dynGridCap);
+        const int np = k::launch_newmark_rhs(w.n, g0, f ? w.f : nullptr, w.Ap, w.mask, w.b, w.partials.p, s);
+        w.set_threshold(np);
+        MFH_HIP(hipMemsetAsync(w.x, 0, (size_t)w.n * sizeof(double), s));
+        const int its = w.solve(0.0, P.density, true);
+        if (its < 0) {
+            failure = MFH_ERR_NOT_CONVERGED;
+            failText = its == -1 ? "mfh_newmark: the PCG for the initial acceleration reached maxit" : "mfh_newmark: PCG breakdown in the solve for the initial acceleration";
+        } else {
+            itInit = its;
+            step0Done = true;
+            MFH_HIP(hipMemcpyAsync(w.a, w.x, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (failure == MFH_OK) {
+        finish_step(0, nullptr);
+        k::PredictArgs pa{};
+        pa.n = w.n; pa.dt = P.dt; pa.cua = P.dt * P.dt * (0.5 - P.beta); pa.cva = P.dt * (1.0 - P.gamma);
+        pa.cw = P.gamma / bdt; pa.cmu = P.density / (bdt * P.dt); pa.cmw = P.density * P.rayleighMass; pa.ckw = P.rayleighStiff;
+        const bool haveCK = P.rayleighStiff != 0.0;
+        for (int step = 1; step <= nSteps; ++step) {
+            const double g = amplitude ? amplitude[step] : 1.0;
+            w.lap(-1);
+            k::launch_newmark_predict(pa, w.u, w.v, w.a, w.mask, w.ut, w.vt, w.xm, haveCK ? w.xk : nullptr, s);
+            if (haveCK) apply_operator(c, masked, w.xk, w.Ap, nullptr);
+            k::launch_spmv_kron_acc(mass_spmv_args(c, masked), haveCK, 1.0, 1.0, w.xm, w.Ap, nullptr, w.open(), s, c->dynGridCap);
+            const int np = k::launch_newmark_rhs(w.n, g, f ? w.f : nullptr, w.Ap, w.mask, w.b, w.partials.p, s);
+            w.set_threshold(np);
+            MFH_HIP(hipMemcpyAsync(w.x, w.ut, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice, s));      // warm start
+            w.lap(6);
+            const int its = w.solve(cK, cM, stepJacobi);
+            if (its < 0) {
+                failure = MFH_ERR_NOT_CONVERGED;
+                failText = its == -1 ? "mfh_newmark: the PCG of step " + std::to_string(step) + " reached maxit" : "mfh_newmark: PCG breakdown in step " + std::to_string(step);
+                break;
+            }
+            itTotal += its;
+            itMax = std::max(itMax, its);
+            w.lap(-1);
+            finish_step(step, w.x);
+            w.lap(6);
+            stepsDone = step;
+        }
+    }
+    if (stride) flush_snapshots();
+    if (step0Done) {        // (a failed solve for a0 leaves the caller's arrays as they were)
+        MFH_HIP(hipMemcpyAsync(u, w.u, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+        MFH_HIP(hipMemcpyAsync(v, w.v, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+        MFH_HIP(hipMemcpyAsync(a, w.a, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+        const size_t rows = (size_t)stepsDone + 1;
+        if (nProbe) MFH_HIP(hipMemcpyAsync(probeOut, dProbe.p, rows * (size_t)nProbe * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (wantE) MFH_HIP(hipMemcpyAsync(energies, dEnergy.p, rows * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    MFH_HIP(hipStreamSynchronize(s));
+    const double solveMs = tsolve.stop();
+    if (w.timing)
+        fprintf(stderr, "[mfh_newmark] n %lld steps %d iterations %d | ms: K %.3f M %.3f update %.3f precond %.3f direction %.3f readback %.3f step-kernels %.3f\n",
+                (long long)w.n, stepsDone, itTotal, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6]);
+    if (info) {
+        info->stepsDone = stepsDone;
+        info->iterationsTotal = itTotal;
+        info->iterationsMax = itMax;
+        info->iterationsInit = itInit;
+        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : MFH_PRECOND_BLOCK_JACOBI);
+        info->cK = cK; info->cM = cM;
+        info->solve_ms = solveMs; info->setup_ms = setupMs;
+        info->note = c->dynNote.c_str();
+    }
+    if (failure != MFH_OK) throw Error(failure, failText);
+    MFH_CATCH(c)
+}
+
+// ---- test hooks (include/meshfem_hip_extras.h): the step kernels on host arrays, the pencil product on the context's operators
+mfh_status mfh_debug_newmark_predict(mfh_ctx *c, int64_t n, double dt, double beta, double gamma, double density, double rayleighMass, double rayleighStiff,
+                                     const uint8_t *mask, const double *u, const double *v, const double *a, double *ut, double *vt, double *xm, double *xk) {
+    MFH_TRY(c)
+    require(c && n >= 1 && u && v && a && ut && vt && xm && dt > 0 && beta > 0, MFH_ERR_INVALID, "mfh_debug_newmark_predict: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DBuf<double> in, out;
+    DBuf<uint8_t> dm;
+    in.alloc((size_t)n * 3); out.alloc((size_t)n * 4);
+    upload(in.p, u, n, s); upload(in.p + n, v, n, s); upload(in.p + 2 * n, a, n, s);
+    if (mask) dm.upload(mask, (size_t)n, s);
+    k::PredictArgs pa{};
+    const double bdt = beta * dt;
+    pa.n = n; pa.dt = dt; pa.cua = dt * dt * (0.5 - beta); pa.cva = dt * (1.0 - gamma);
+    pa.cw = gamma / bdt; pa.cmu = density / (bdt * dt); pa.cmw = density * rayleighMass; pa.ckw = rayleighStiff;
+    k::launch_newmark_predict(pa, in.p, in.p + n, in.p + 2 * n, mask ? dm.p : nullptr, out.p, out.p + n, out.p + 2 * n, xk ? out.p + 3 * n : nullptr, s);
+    MFH_HIP(hipMemcpyAsync(ut, out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(vt, out.p + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(xm, out.p + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (xk) MFH_HIP(hipMemcpyAsync(xk, out.p + 3 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_newmark_rhs(mfh_ctx *c, int64_t n, double g, const double *f, const double *y, const uint8_t *mask, double *b, double *bb) {
+    MFH_TRY(c)
+    require(c && n >= 1 && y && b && bb, MFH_ERR_INVALID, "mfh_debug_newmark_rhs: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DBuf<double> in, out, part;
+    DBuf<uint8_t> dm;
+    in.alloc((size_t)n * 2); out.alloc((size_t)n + 1); part.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
+    upload(in.p, y, n, s);
+    if (f) upload(in.p + n, f, n, s);
+    if (mask) dm.upload(mask, (size_t)n, s);
+    const int np = k::launch_newmark_rhs(n, g, f ? in.p + n : nullptr, in.p, mask ? dm.p : nullptr, out.p, part.p, s);
+    const int col[1] = {0};
+    const double sc[1] = {1.0};
+    double *const dst[1] = {out.p + n};
+    k::launch_reduce(np, 1, col, sc, dst, part.p, DynGate{nullptr, 0, nullptr}, s);
+    MFH_HIP(hipMemcpyAsync(b, out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(bb, out.p + n, sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_newmark_correct(mfh_ctx *c, int64_t n, double dt, double beta, double gamma, const double *x, const double *ut, const double *vt,
+                                     double *u, double *v, double *a, const int64_t *probeVars, int32_t nProbe, double *probeOut, double *snapshot) {
+    MFH_TRY(c)
+    require(c && n >= 1 && x && ut && vt && u && v && a && dt > 0 && beta > 0 && nProbe >= 0 && (nProbe == 0 || (probeVars && probeOut)), MFH_ERR_INVALID,
+            "mfh_debug_newmark_correct: arguments");
+    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < n, MFH_ERR_INVALID, "mfh_debug_newmark_correct: probe variable out of range");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DBuf<double> in, out;
+    DBuf<int64_t> dv;
+    in.alloc((size_t)n * 3); out.alloc((size_t)n * 4 + (size_t)std::max(nProbe, 1));
+    upload(in.p, x, n, s); upload(in.p + n, ut, n, s); upload(in.p + 2 * n, vt, n, s);
+    if (nProbe) { dv.alloc((size_t)nProbe); MFH_HIP(hipMemcpyAsync(dv.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s)); }
+    k::CorrectArgs ca{};
+    ca.n = n; ca.ca = 1.0 / (beta * dt * dt); ca.cv = gamma * dt; ca.recordOnly = 0;
+    ca.nProbe = nProbe; ca.probeVars = dv.p; ca.probeRow = nProbe ? out.p + 4 * n : nullptr;
+    ca.snapRow = snapshot ? out.p + 3 * n : nullptr;
+    k::launch_newmark_correct(ca, in.p, in.p + n, in.p + 2 * n, out.p, out.p + n, out.p + 2 * n, s);
+    MFH_HIP(hipMemcpyAsync(u, out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(v, out.p + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(a, out.p + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (snapshot) MFH_HIP(hipMemcpyAsync(snapshot, out.p + 3 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (nProbe) MFH_HIP(hipMemcpyAsync(probeOut, out.p + 4 * n, (size_t)nProbe * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_pencil_apply(mfh_ctx *c, double cK, double cM, int32_t masked, const double *x, double *y, double *dot) {
+    MFH_TRY(c)
+    require(c && x && y && std::isfinite(cK) && std::isfinite(cM), MFH_ERR_INVALID, "mfh_debug_pencil_apply: arguments");
+    prepare_pencil(c, "mfh_debug_pencil_apply");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    ensure_precond(c);                 // (K assembled, the fixed-variable mask on the device)
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_debug_pencil_apply");
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    const bool m = masked != 0 && !c->fixedVars.empty();
+    DBuf<double> dx, dy, part;
+    dx.alloc((size_t)n); dy.alloc((size_t)n + 1); part.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
+    upload(dx.p, x, n, s);
+    if (cK != 0.0) apply_operator(c, m, dx.p, dy.p, nullptr);
+    const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, m), cK != 0.0, cK, cM, dx.p, dy.p, part.p, DynGate{nullptr, 0, nullptr}, s, c->dynGridCap);
+    const int col[1] = {0};
+    const double sc[1] = {1.0};
+    double *const dst[1] = {dy.p + n};
+    k::launch_reduce(np, 1, col, sc, dst, part.p, DynGate{nullptr, 0, nullptr}, s);
+    MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (dot) MFH_HIP(hipMemcpyAsync(dot, dy.p + n, sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+}   // extern "C"

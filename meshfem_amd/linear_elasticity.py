@@ -155,6 +155,54 @@ class Simulator:
             X = X[:, dof, :]
         return np.sqrt(lam) / (2.0 * np.pi), X
 
+    def transient(self, dt, n_steps, amplitude=None, u0=None, v0=None, density=1.0, damping=(0, 0), beta=0.25, gamma=0.5, probes=None,
+                  snapshot_stride=0, a0=None, energies=False, rtol=None, maxit=None):
+        """The response to the load history amplitude[n] x neumannLoad() by implicit Newmark time stepping on the device (mfh_newmark):
+        M u'' + C u' + K u = g(t) f with M = density x the consistent mass matrix, C = damping[0] M + damping[1] K. The Dirichlet variables of the
+        applied boundary conditions are the clamp, held at zero (their values play no part, as in vibrational_modes); u0 / v0 / a0: nodal fields
+        [nNode, N] (None: rest; a0 None: from the equation of motion at step 0 -- pass the "a" of an earlier call to continue it). probes: (node,
+        component) pairs whose displacement is recorded at every step. Returns a dict of nodal fields: "u", "v", "a" [nNode, N] after the last
+        step, "probes" [n_steps + 1, len(probes)], "snapshots" [n_steps // snapshot_stride + 1, nNode, N] (snapshot_stride > 0), "energies"
+        [n_steps + 1, 3] = kinetic, strain, g f.u (energies=True). self.transient_info holds the solver's record."""
+        ctx = self.ctx
+        v, _ = ctx.bc_dirichlet_vars()
+        ctx.clear_fixed()
+        if len(v):
+            ctx.fix_variables(v)
+        mapped = ctx.n_dof != ctx.n_node                   # a DoF map (periodic conditions): a DoF takes the value of its first node
+        dof = ctx.get_dof_map()[0] if mapped else None
+        if mapped:
+            first = np.full(ctx.n_dof, -1, dtype=np.int64)
+            first[dof[::-1]] = np.arange(ctx.n_node)[::-1]
+
+        def to_dofs(x):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=np.float64).reshape(ctx.n_node, self.N)
+            return x[first] if mapped else x
+
+        def to_nodes(x):
+            x = x.reshape(x.shape[:-1] + (ctx.n_dof, self.N))
+            return x[..., dof, :] if mapped else x
+        f = self.neumannLoad()
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        try:
+            r = ctx.newmark(dt, n_steps, u0=to_dofs(u0), v0=to_dofs(v0), a0=to_dofs(a0), f=None if not np.any(f) else f, amplitude=amplitude,
+                            density=density, damping=damping, beta=beta, gamma=gamma, rtol=self.rtol if rtol is None else rtol,
+                            maxit=self.maxit if maxit is None else maxit, probes=pv, snapshot_stride=snapshot_stride, energies=energies)
+        finally:
+            self.transient_info = getattr(ctx, "last_newmark", {}).get("info")
+        out = dict(r)
+        for k in ("u", "v", "a"):
+            out[k] = to_nodes(r[k])
+        if r["snapshots"] is not None:
+            out["snapshots"] = to_nodes(r["snapshots"])
+        del out["info"]
+        return out
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 
