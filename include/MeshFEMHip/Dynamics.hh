@@ -1,7 +1,7 @@
 // Transient dynamics on the MI355X path: implicit Newmark time stepping over the C ABI (include/meshfem_hip.h, "transient dynamics"). The reference has
 // no time integrator, so there is no counterpart to cite; the layout follows Eigensolver.hh.
 //   transient(sim, dt, nSteps, opt)   M u'' + C u' + K u = g(t) f with K = the Simulator's stiffness matrix, M = opt.density x the consistent vector-valued
-//                                     mass matrix, C = opt.rayleighMass M + opt.rayleighStiff K, f = the Simulator's neumannLoad(), g = opt.amplitude (steps
+//                                     mass matrix, C = opt.rayleighMass M + opt.rayleighStiff K, f = the Simulator's neumannLoad() or opt.load, g = opt.amplitude (steps
 //                                     0 .. nSteps; empty: 1). The Dirichlet variables of the boundary conditions applied to the Simulator are the clamp,
 //                                     held at zero. opt.u0 / v0 / a0: the state at step 0, one N-vector per DoF (empty: rest; a0 empty: from the equation
 //                                     of motion at step 0 -- pass the a of an earlier result to continue that run).
@@ -24,6 +24,7 @@ struct TransientOptions {
     int maxit = 10000;
     std::vector<Real> amplitude;                          // nSteps + 1 values, or empty (= 1)
     VField u0, v0, a0;                                    // one N-vector per DoF, or empty
+    VField load;                                          // f, one N-vector per DoF (a volume load of VolumeLoads.hh, a sum of loads); empty: neumannLoad()
     std::vector<std::pair<size_t, int>> probes;           // (DoF, component) pairs recorded at every step
     int snapshotStride = 0;                               // > 0: the displacement at the steps 0, stride, 2 stride, ...
     bool energies = false;
@@ -66,7 +67,8 @@ TransientResult<typename Sim::VField> transient(const Sim &sim, Real dt, int nSt
     TransientResult<VField> r;
     r.u = state(opt.u0, "u0"); r.v = state(opt.v0, "v0"); r.a = state(opt.a0, "a0");
     if (!opt.amplitude.empty() && opt.amplitude.size() != rows) throw std::runtime_error("transient: amplitude needs nSteps + 1 values");
-    const VField f = sim.neumannLoad();
+    if (!opt.load.empty() && opt.load.size() != nDoF) throw std::runtime_error("transient: load needs one entry per DoF");
+    const VField f = opt.load.empty() ? sim.neumannLoad() : opt.load;
     bool loaded = false;
     for (const auto &e : f)
         for (size_t a = 0; a < N; ++a) loaded = loaded || e[a] != 0.0;

@@ -379,6 +379,15 @@ public:
         check(ctx(), mfh_constant_strain_load(ctx(), cstrainFlat.data(), &f[0][0]));
         return f;
     }
+    // load of a per-element stress field (flattened, TENSOR shear): f_i = sum_e sigma_e . int_e grad phi_i   (:564-577 over :135-151);
+    // strain = true: the field holds strains and sigma_e = C_e : eps_e (one strain everywhere: constantStrainLoad). Gathered per DoF on the
+    // device without atomics. More volume loads (body forces, thermal strain): VolumeLoads.hh
+    VField perElementStressFieldLoad(const SMField &field, bool strain = false) const {
+        if (field.size() != (size_t)m_numElements) throw std::runtime_error("perElementStressFieldLoad: one tensor per element expected");
+        VField f(m_numDoFs);
+        check(ctx(), mfh_stress_field_load(ctx(), strain ? MFH_FIELD_LOAD_STRAIN : MFH_FIELD_LOAD_STRESS, &field[0][0], nullptr, 0, &f[0][0]));
+        return f;
+    }
 
     // per-DoF field -> per-node field through the DoF map (identity unless periodic conditions are installed)   (:664-677)
     VField dofToNodeField(const VField &dofField) const {

@@ -298,6 +298,33 @@ mfh_status mfh_pin_node(const mfh_ctx* ctx, int64_t* node);
 mfh_status mfh_neumann_load(mfh_ctx* ctx, double* out);
 /* == Simulator::constantStrainLoad (:551-562, :135-162); cstrain flattened (flatLen, TENSOR shear) */
 mfh_status mfh_constant_strain_load(mfh_ctx* ctx, const double* cstrainFlat, double* out);
+/* Volume loads (docs/design/04_14_volume_loads.md). Both gather over the (element, local node) pairs of every DoF in a fixed order -- ascending by
+ * element, the images of a periodic DoF in one list -- and write every entry of out once: no floating-point atomics, the same call on the same
+ * context returns the same bits, and out needs no zeroing by the caller (a DoF without elements gets 0).
+ * flags: MFH_LOAD_ADD        out += the load (out holds dim*nDoF values on entry) instead of out = the load
+ *        MFH_LOAD_ON_DEVICE  every array is a device pointer; the call returns after the context's stream is synchronised (as for mfh_mass_lumped)
+ * MFH_ERR_STATE: no mesh (also: a matrix from mfh_matrix_set_upper_triplets); MFH_ERR_UNSUPPORTED: a row-partitioned context (nOwned < nNode: the
+ * elements of other ranks are missing at the interface, as for mfh_vertex_average); MFH_ERR_INVALID, before anything is written: an unknown kind,
+ * a null array that the kind needs, stressOut with MFH_FIELD_LOAD_STRESS, a density entry that is negative or not finite (a host array is scanned on
+ * the host; a device array, MFH_LOAD_ON_DEVICE, by a reduction kernel on the device before the load kernel is launched).
+ *   mfh_body_force_load   f_i = sum_e density_e int_e phi_i b (no counterpart in the reference: gravity, centrifugal and inertial forces). kind
+ *                         MFH_BODY_CONSTANT: b is one vector [dim] (always a host pointer); MFH_BODY_ELEMENT: [nElem][dim], constant per element;
+ *                         MFH_BODY_NODE: [nNode][dim], interpolated with the mesh's shape functions (the element mass coefficients int phi_i phi_j).
+ *                         density: [nElem] or NULL (= 1). The nodal weights int phi_i / vol of a quadratic element are 0 (triangle) and -1/20
+ *                         (tet) at the vertices: the load of a vertex DoF may point against b (see mfh_mass_lumped).
+ *   mfh_stress_field_load == Simulator::perElementStressFieldLoad (LinearElasticity.hh:564-577 over perElementConstantStressLoad :135-151):
+ *                         f_i = sum_e sigma_e . int_e grad phi_i. field: [nElem][flatLen], TENSOR shear, the layout of mfh_average_stress.
+ *                         MFH_FIELD_LOAD_STRESS: field is sigma_e; MFH_FIELD_LOAD_STRAIN: field is a strain and sigma_e = C_e : eps_e (for one strain
+ *                         everywhere: mfh_constant_strain_load), stressOut (optional) receives C_e : eps_e -- what a caller subtracts from the
+ *                         stress of the solution to get the thermal stress C : (eps(u) - eps_th). Elasticity operator only (MFH_ERR_UNSUPPORTED). */
+enum { MFH_BODY_CONSTANT = 0, MFH_BODY_ELEMENT = 1, MFH_BODY_NODE = 2 };
+enum { MFH_FIELD_LOAD_STRESS = 0, MFH_FIELD_LOAD_STRAIN = 1 };
+enum { MFH_LOAD_ADD = 1, MFH_LOAD_ON_DEVICE = 2 };
+mfh_status mfh_body_force_load(mfh_ctx* ctx, int32_t kind, const double* b, const double* density /* nElem or NULL */,
+                               int32_t flags, double* out /* dim*nDoF */);
+mfh_status mfh_stress_field_load(mfh_ctx* ctx, int32_t kind, const double* field /* nElem x flatLen */,
+                                 double* stressOut /* nElem x flatLen or NULL; STRAIN kind only */,
+                                 int32_t flags, double* out /* dim*nDoF */);
 /* == Simulator::solve(f) (:479-487 -> m_buildConstrainedSystem :1377-1404): assembles if needed,
  * fixes the Dirichlet variables (+ the pin node if usePin), PCG-solves, returns dofToNodeField
  * (:664-677) as nNode x dim. f==NULL uses neumannLoad() (:657).                                */

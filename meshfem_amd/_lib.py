@@ -15,6 +15,9 @@ PRECOND_BLOCK_JACOBI, PRECOND_JACOBI, PRECOND_NONE, PRECOND_TWO_LEVEL, PRECOND_M
 OP_ELASTICITY, OP_LAPLACIAN, OP_MASS, OP_MASS_VECTOR = 0, 1, 2, 3
 SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED = 1, 2, 4
 MEASURE_VON_MISES, MEASURE_EIGENVALUES, MEASURE_EIGENVECTORS = 1, 2, 4
+BODY_CONSTANT, BODY_ELEMENT, BODY_NODE = 0, 1, 2
+FIELD_LOAD_STRESS, FIELD_LOAD_STRAIN = 0, 1
+LOAD_ADD, LOAD_ON_DEVICE = 1, 2
 FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE = 0, 1, 2
 MODES_FREE = 1
 DYN_HAVE_ACCEL, DYN_ENERGIES = 1, 2
@@ -149,6 +152,8 @@ PROTOTYPES = {
     "mfh_pin_node": (_i32, [_P, _pi64]),
     "mfh_neumann_load": (_i32, [_P, _P]),
     "mfh_constant_strain_load": (_i32, [_P, _P, _P]),
+    "mfh_body_force_load": (_i32, [_P, _i32, _P, _P, _i32, _P]),
+    "mfh_stress_field_load": (_i32, [_P, _i32, _P, _P, _i32, _P]),
     "mfh_sim_solve": (_i32, [_P, _P, _i32, _P, _f64, _i32, C.POINTER(SolveInfo)]),
     "mfh_average_strain": (_i32, [_P, _P, _P]),
     "mfh_average_stress": (_i32, [_P, _P, _P]),

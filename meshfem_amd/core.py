@@ -597,6 +597,53 @@ class Context:
         self._ck(self.lib.mfh_constant_strain_load(self.h, ptr(e), ptr(out)))
         return out
 
+    def _load_out(self, out, add):
+        if out is None:
+            if add:
+                raise ValueError("add=True needs the vector to add to (out=...)")
+            return np.empty((self.n_dof, self.dim))
+        if out.dtype != np.float64 or not out.flags.c_contiguous or out.size != self.n_dof * self.dim:
+            raise ValueError("out: a C-contiguous float64 array of n_dof * dim values")
+        return out
+
+    def body_force_load(self, b, density=None, out=None, add=False):
+        """Per-DoF load [nDoF, dim] of the body force density * b (mfh_body_force_load): b is one vector (dim,), one vector per element
+        (nElem, dim) -- constant on each element -- or a nodal field (nNode, dim) interpolated with the mesh's shape functions; density:
+        per element (nElem,) or None (= 1). out: the array to write (add=True: to add to). Gathered per DoF in a fixed order without atomics:
+        the same call returns the same bits."""
+        b = as_f64(b)
+        d = self.dim
+        kinds = [k for k, shp in ((L.BODY_CONSTANT, (d,)), (L.BODY_ELEMENT, (self.n_elem, d)), (L.BODY_NODE, (self.n_node, d))) if b.shape == shp]
+        if len(kinds) != 1:
+            raise ValueError("b of shape %s is %s: expected (dim,), (nElem, dim) or (nNode, dim)%s"
+                             % (b.shape, "ambiguous" if kinds else "not a body force",
+                                "; nElem == nNode on this mesh, call mfh_body_force_load with the kind" if kinds else ""))
+        rho = None
+        if density is not None:
+            rho = as_f64(density)
+            if rho.shape != (self.n_elem,):
+                raise ValueError("density: one value per element")
+        out = self._load_out(out, add)
+        self._ck(self.lib.mfh_body_force_load(self.h, kinds[0], ptr(b), ptr(rho), L.LOAD_ADD if add else 0, ptr(out)))
+        return out
+
+    def stress_field_load(self, field, kind="stress", return_stress=False, out=None, add=False):
+        """Per-DoF load [nDoF, dim] f_i = sum_e sigma_e . int_e grad phi_i of a per-element symmetric tensor field [nElem, flatLen] (tensor
+        shear entries, the layout of average_stress): perElementStressFieldLoad (mfh_stress_field_load). kind "stress": field is sigma_e;
+        kind "strain": sigma_e = C_e : field_e, and return_stress=True also returns that array: (load, C : field)."""
+        if kind not in ("stress", "strain"):
+            raise ValueError('kind: "stress" or "strain"')
+        if return_stress and kind != "strain":
+            raise ValueError('return_stress goes with kind="strain"')
+        f = as_f64(field)
+        if f.shape != (self.n_elem, flat_len(self.dim)):
+            raise ValueError("field: [nElem, flatLen]")
+        out = self._load_out(out, add)
+        sig = np.empty_like(f) if return_stress else None
+        self._ck(self.lib.mfh_stress_field_load(self.h, L.FIELD_LOAD_STRAIN if kind == "strain" else L.FIELD_LOAD_STRESS, ptr(f), ptr(sig),
+                                                L.LOAD_ADD if add else 0, ptr(out)))
+        return (out, sig) if return_stress else out
+
     def sim_solve(self, f=None, use_pin=False, rtol=1e-8, maxit=100000):
         fp = None if f is None else as_f64(f)
         u = np.empty((self.n_node, self.bs))

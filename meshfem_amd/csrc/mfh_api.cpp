@@ -110,6 +110,7 @@ void upload_mesh(mfh_ctx *c, bool deviceTables) {
     drop_p1_view(c);                 // a forced-degree-1 view belongs to the previous mesh
     c->opDegree = 0;
     c->nodePairsValid = false;
+    c->dofPairsValid = false;
     sampler_drop(c);
     if (!c->hostOnly && !deviceTables) {      // (deviceTables: the device topology has written both from the vertices)
         require_device(c);
@@ -353,6 +354,26 @@ void ensure_node_pairs(mfh_ctx *c) {
     c->dNodePair.upload(pairs, c->stream);
     c->nodePairsValid = true;
 }
+
+// the same codes grouped by DoF (dofForNode[node]) and ascending by element inside a group: the gather list of the volume loads. All images of a
+// periodic DoF land in one group, in a fixed order. Valid until the mesh or the DoF map changes; under the identity map the node list is the DoF list.
+void ensure_dof_pairs(mfh_ctx *c) {
+    if (c->dofForNode.empty()) { ensure_node_pairs(c); return; }
+    if (c->dofPairsValid) return;
+    const HostMesh &m = c->mesh;
+    const int npe = m.npe;
+    std::vector<int32_t> ptr((size_t)c->nDoF + 1, 0), pairs((size_t)m.nElem * npe);
+    require((int64_t)pairs.size() <= 2147483647LL, MFH_ERR_UNSUPPORTED, "more than 2^31 (element, node) pairs");
+    for (size_t k2 = 0; k2 < pairs.size(); ++k2) ++ptr[(size_t)c->dofForNode[(size_t)m.elemNodes[k2]] + 1];
+    for (int64_t n = 0; n < c->nDoF; ++n) ptr[(size_t)n + 1] += ptr[(size_t)n];
+    std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
+    for (size_t k2 = 0; k2 < pairs.size(); ++k2) pairs[(size_t)cur[(size_t)c->dofForNode[(size_t)m.elemNodes[k2]]]++] = (int32_t)k2;
+    c->dDofPtr.upload(ptr, c->stream);
+    c->dDofPair.upload(pairs, c->stream);
+    c->dofPairsValid = true;
+}
+const int32_t *dof_pair_ptr(const mfh_ctx *c) { return c->dofForNode.empty() ? c->dNodePtr.p : c->dDofPtr.p; }
+const int32_t *dof_pair_list(const mfh_ctx *c) { return c->dofForNode.empty() ? c->dNodePair.p : c->dDofPair.p; }
 
 k::AsmArgs asm_args(mfh_ctx *c) {
     const HostMesh &m = c->mesh;
@@ -1476,6 +1497,7 @@ mfh_status mfh_dof_map(mfh_ctx *c, const int32_t *dofForNode, int64_t nDoF) {
     require(!(c && c->opDegree == 1 && c->p1), MFH_ERR_STATE, "a forced-degree-1 view is in force (mfh_set_operator_degree): it is defined for the identity DoF map");
     require(c && c->haveMesh, MFH_ERR_STATE, "no mesh set");
     c->nOwnedDoFSet = -1;
+    c->dofPairsValid = false;
     if (!dofForNode) {
         c->dofForNode.clear();
         c->nDoF = c->mesh.nNode;
@@ -1506,6 +1528,7 @@ mfh_status mfh_dof_map_partitioned(mfh_ctx *c, const int32_t *dofForNode, int64_
     c->dofForNode.assign(dofForNode, dofForNode + c->mesh.nNode);
     c->nDoF = nDoF;
     c->nOwnedDoFSet = nOwnedDoF;
+    c->dofPairsValid = false;
     invalidate_symbolic(c);
     clear_fixed(c);
     dist_detach(c);                  // exchange lists are in DoF numbers: mfh_dist_setup must run (again)
@@ -1524,6 +1547,7 @@ mfh_status mfh_apply_periodic_conditions(mfh_ctx *c, double eps, int64_t *nDoF) 
     if (nd == c->nDoF && dof == c->dofForNode) return MFH_OK;
     c->dofForNode.swap(dof);
     c->nDoF = nd;
+    c->dofPairsValid = false;
     invalidate_symbolic(c);
     clear_fixed(c);
     MFH_CATCH(c)
@@ -1679,6 +1703,7 @@ mfh_status mfh_matrix_set_upper_triplets(mfh_ctx *c, int64_t n, int64_t nnz, con
     c->external = true;
     c->op = MFH_OP_ELASTICITY;
     c->dofForNode.clear();
+    c->dofPairsValid = false;
     c->nDoF = n;
     c->dRowPtr.upload(S.rowPtr, c->stream);
     c->dColIdx.upload(S.colIdx, c->stream);

@@ -57,6 +57,8 @@ struct mfh_ctx {
     int64_t geoGen = 0, p1GeoGen = -1;   // element records (re)written / the generation the view's matrices were assembled from
     DBuf<int32_t> dNodePtr, dNodePair;   // ensure_node_pairs: (element, local node) pairs grouped by node
     bool nodePairsValid = false;
+    DBuf<int32_t> dDofPtr, dDofPair;     // ensure_dof_pairs: the same codes grouped by DoF (empty under the identity map: the node list serves)
+    bool dofPairsValid = false;
     // Field sampler (mfh_sampler.hip, docs/design/04_11_field_sampler.md): uniform cell grids over the elements and over the boundary elements,
     // built on first use and dropped with the mesh or its vertex positions (sampler_drop). A grid lists every item in each cell its inflated
     // bounding box overlaps; the list of a cell is ascending in item index.
@@ -472,6 +474,9 @@ void add_fixed(mfh_ctx *c, int64_t n, const int64_t *vars, const double *vals);
 void ensure_geometry(mfh_ctx *c, bool deferCheck = false);
 void finish_geometry(mfh_ctx *c);
 void ensure_node_pairs(mfh_ctx *c);    // dNodePtr / dNodePair of the current mesh
+void ensure_dof_pairs(mfh_ctx *c);     // the pair list grouped by DoF of the current mesh and DoF map: dof_pair_ptr / dof_pair_list
+const int32_t *dof_pair_ptr(const mfh_ctx *c);
+const int32_t *dof_pair_list(const mfh_ctx *c);
 void sampler_drop(mfh_ctx *c);         // the field sampler's grids describe the previous mesh / vertex positions (mfh_sampler.hip)
 void ensure_mf_cluster(mfh_ctx *c);
 void upload_mesh(mfh_ctx *c, bool deviceTables);

@@ -133,6 +133,40 @@ template <int DIM, int DEG> DEV int sup_t(int i) {
 }
 
 
+// C_e : (shear-doubled flat strain) from the element record's material entries (g[13 ..]); the result has TENSOR shear entries
+template <int DIM, int MAT>
+DEV void elem_D_apply(const double *__restrict__ g, const double *sd /* shear-doubled flat strain */, double *out) {
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    if (MAT == MAT_ISO) {
+        const double lam = g[13], mu = g[14];
+        double tr = 0;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) tr += sd[a];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) out[a] = lam * tr + 2 * mu * sd[a];
+#pragma unroll
+        for (int k = DIM; k < FL; ++k) out[k] = mu * sd[k];
+    } else if (MAT == MAT_ORTHO) {
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            double v = 0;
+#pragma unroll
+            for (int b = 0; b < DIM; ++b) v += g[13 + npack<DIM>(a, b)] * sd[b];
+            out[a] = v;
+        }
+#pragma unroll
+        for (int k = DIM; k < FL; ++k) out[k] = g[ortho_shear_offset<DIM>() + k - DIM] * sd[k];
+    } else {
+#pragma unroll
+        for (int r = 0; r < FL; ++r) {
+            double v = 0;
+#pragma unroll
+            for (int c = 0; c < FL; ++c) v += g[13 + dpack<DIM>(r, c)] * sd[c];
+            out[r] = v;
+        }
+    }
+}
+
 // ---- launch helpers
 static inline int grid_for(int64_t n, int cap = 2048) {
     int64_t g = (n + 255) / 256;

@@ -472,6 +472,15 @@ void launch_mutual_energy_differential(const AsmArgs &a, const int32_t *elemNode
                                        int64_t nNode, int64_t nVert, double *out, hipStream_t s);
 void launch_average_gradient(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, double *out,
                              hipStream_t s);
+// Volume loads (mfh_loads.hip): gather over the DoF-pair list (dofPtr: nDoF + 1, dofPair: code = e npe + i, ascending by element per DoF), no
+// atomics; add: out += the load instead of out = the load. strainKind: field holds strains, the kernel applies C_e.
+void launch_stress_field_load(const AsmArgs &a, int64_t nDoF, const int32_t *dofPtr, const int32_t *dofPair, const ShapeTables &T, int strainKind,
+                              const double *field, int add, double *out, hipStream_t s);
+void launch_field_stress(const AsmArgs &a, const double *strain, double *out, hipStream_t s);      // out[e] = C_e : strain[e]
+// kind: MFH_BODY_CONSTANT (bConst: dim host values) | MFH_BODY_ELEMENT (b: [nElem][dim]) | MFH_BODY_NODE (b: [nNode][dim]); density: [nElem] or null
+void launch_body_force_load(const AsmArgs &a, int64_t nDoF, const int32_t *dofPtr, const int32_t *dofPair, const ShapeTables &T, int kind,
+                            const int32_t *elemNodes, const double *b, const double *bConst, const double *density, int add, double *out, hipStream_t s);
+void launch_density_check(int64_t n, const double *density, int *flag, hipStream_t s);              // flag[0] = 1 on a negative or non-finite entry
 
 struct SpmvArgs {
     int dim;

@@ -543,39 +543,6 @@ __global__ void __launch_bounds__(256) k_element_stiffness(AsmArgs a, int64_t fi
 // integrals of the nodal coefficients (Interpolant::integrate, Functions.hh:246-253).
 // K10: per-element averaged strain / stress (LinearElasticity.hh:99-123, :528-549).
 // ------------------------------------------------------------------------------------------------
-template <int DIM, int MAT>
-DEV void elem_D_apply(const double *__restrict__ g, const double *sd /* shear-doubled flat strain */, double *out) {
-    constexpr int FL = DIM * (DIM + 1) / 2;
-    if (MAT == MAT_ISO) {
-        const double lam = g[13], mu = g[14];
-        double tr = 0;
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) tr += sd[a];
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) out[a] = lam * tr + 2 * mu * sd[a];
-#pragma unroll
-        for (int k = DIM; k < FL; ++k) out[k] = mu * sd[k];
-    } else if (MAT == MAT_ORTHO) {
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) {
-            double v = 0;
-#pragma unroll
-            for (int b = 0; b < DIM; ++b) v += g[13 + npack<DIM>(a, b)] * sd[b];
-            out[a] = v;
-        }
-#pragma unroll
-        for (int k = DIM; k < FL; ++k) out[k] = g[ortho_shear_offset<DIM>() + k - DIM] * sd[k];
-    } else {
-#pragma unroll
-        for (int r = 0; r < FL; ++r) {
-            double v = 0;
-#pragma unroll
-            for (int c = 0; c < FL; ++c) v += g[13 + dpack<DIM>(r, c)] * sd[c];
-            out[r] = v;
-        }
-    }
-}
-
 template <int DIM>
 DEV void load_corner_perturbation(const double *__restrict__ g, const int32_t *__restrict__ en, const double *__restrict__ deltaP,
                                   double (&gl)[DIM + 1][DIM], double (&dgl)[DIM + 1][DIM], double &relDeltaVol);

@@ -982,6 +982,94 @@ mfh_status mfh_vertex_averaged_strain(mfh_ctx *c, const double *uNodes, int32_t 
     MFH_CATCH(c)
 }
 
+// ---- volume loads: body forces and per-element stress / strain fields (docs/design/04_14_volume_loads.md)
+namespace {
+void require_volume_load_context(mfh_ctx *c) {
+    require(c->mesh.nOwned == c->mesh.nNode, MFH_ERR_UNSUPPORTED,
+            "volume loads need all rows owned: the elements of other ranks are missing at the interface nodes of a row-partitioned context");
+}
+// the load vector as the kernels write it: the caller's device pointer, or a device buffer (holding the caller's values under MFH_LOAD_ADD)
+struct LoadOutput {
+    DevOutput o;
+    LoadOutput(double *dst, size_t n, int32_t flags, hipStream_t s) : o(dst, n, true, (flags & MFH_LOAD_ON_DEVICE) != 0) {
+        if (o.host && (flags & MFH_LOAD_ADD) && n) MFH_HIP(hipMemcpyAsync(o.p, dst, n * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+};
+void require_density(mfh_ctx *c, const double *density, bool onDevice) {
+    if (!density) return;
+    const int64_t n = c->mesh.nElem;
+    bool bad = false;
+    if (!onDevice) {
+        for (int64_t e = 0; e < n && !bad; ++e) bad = !(density[e] >= 0.0) || !std::isfinite(density[e]);
+    } else {
+        require_device(c);
+        MFH_HIP(hipSetDevice(c->device));
+        DBuf<int> flag;
+        flag.alloc(1);
+        flag.zero(c->stream);
+        k::launch_density_check(n, density, flag.p, c->stream);
+        int h = 0;
+        flag.download(&h, 1, c->stream);
+        bad = h != 0;
+    }
+    require(!bad, MFH_ERR_INVALID, "density: an entry is negative or not finite");
+}
+} // namespace
+
+mfh_status mfh_body_force_load(mfh_ctx *c, int32_t kind, const double *b, const double *density, int32_t flags, double *out) {
+    MFH_TRY(c)
+    require(c && c->haveMesh && !c->external, MFH_ERR_STATE, "no mesh set");
+    require_volume_load_context(c);
+    require(kind == MFH_BODY_CONSTANT || kind == MFH_BODY_ELEMENT || kind == MFH_BODY_NODE, MFH_ERR_INVALID, "kind: MFH_BODY_CONSTANT | MFH_BODY_ELEMENT | MFH_BODY_NODE");
+    require(b && out, MFH_ERR_INVALID, "null argument");
+    require((flags & ~(MFH_LOAD_ADD | MFH_LOAD_ON_DEVICE)) == 0, MFH_ERR_INVALID, "flags: MFH_LOAD_ADD | MFH_LOAD_ON_DEVICE");
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    require_density(c, density, onDevice);
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_geometry(c);
+    ensure_dof_pairs(c);
+    const HostMesh &m = c->mesh;
+    const size_t d = (size_t)m.dim, n = d * (size_t)c->nDoF;
+    const size_t nb = kind == MFH_BODY_ELEMENT ? (size_t)m.nElem * d : (kind == MFH_BODY_NODE ? (size_t)m.nNode * d : 0);
+    DevInput bIn(kind == MFH_BODY_CONSTANT ? nullptr : b, nb, onDevice, c->stream), rho(density, density ? (size_t)m.nElem : 0, onDevice, c->stream);
+    LoadOutput res(out, n, flags, c->stream);
+    k::launch_body_force_load(asm_args(c), c->nDoF, dof_pair_ptr(c), dof_pair_list(c), c->tables, kind, c->dElemNodes.p, bIn.p, b, density ? rho.p : nullptr,
+                              (flags & MFH_LOAD_ADD) != 0, res.o.p, c->stream);
+    res.o.finish(c->stream);
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_stress_field_load(mfh_ctx *c, int32_t kind, const double *field, double *stressOut, int32_t flags, double *out) {
+    MFH_TRY(c)
+    require(c && c->haveMesh && !c->external, MFH_ERR_STATE, "no mesh set");
+    require_volume_load_context(c);
+    require(c->op == MFH_OP_ELASTICITY, MFH_ERR_UNSUPPORTED, "the stress-field load is defined for the elasticity operator");
+    require(kind == MFH_FIELD_LOAD_STRESS || kind == MFH_FIELD_LOAD_STRAIN, MFH_ERR_INVALID, "kind: MFH_FIELD_LOAD_STRESS | MFH_FIELD_LOAD_STRAIN");
+    require(field && out, MFH_ERR_INVALID, "null argument");
+    require(!(stressOut && kind == MFH_FIELD_LOAD_STRESS), MFH_ERR_INVALID, "stressOut goes with MFH_FIELD_LOAD_STRAIN: a stress field is its own stress");
+    require((flags & ~(MFH_LOAD_ADD | MFH_LOAD_ON_DEVICE)) == 0, MFH_ERR_INVALID, "flags: MFH_LOAD_ADD | MFH_LOAD_ON_DEVICE");
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_geometry(c);
+    ensure_dof_pairs(c);
+    const HostMesh &m = c->mesh;
+    const size_t nf = (size_t)m.nElem * flat_len(m.dim), n = (size_t)m.dim * (size_t)c->nDoF;
+    DevInput in(field, nf, onDevice, c->stream);
+    LoadOutput res(out, n, flags, c->stream);
+    DevOutput sig(stressOut, nf, stressOut != nullptr, onDevice);
+    const k::AsmArgs a = asm_args(c);
+    k::launch_stress_field_load(a, c->nDoF, dof_pair_ptr(c), dof_pair_list(c), c->tables, kind == MFH_FIELD_LOAD_STRAIN, in.p, (flags & MFH_LOAD_ADD) != 0,
+                                res.o.p, c->stream);
+    if (stressOut) k::launch_field_stress(a, in.p, sig.p, c->stream);
+    res.o.finish(c->stream);
+    sig.finish(c->stream);
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    MFH_CATCH(c)
+}
+
 mfh_status mfh_peak_von_mises(mfh_ctx *c, const double *uNodes, int32_t wantStress, double *value, int64_t *cornerIndex) {
     MFH_TRY(c)
     require(c && c->haveMesh && uNodes, MFH_ERR_STATE, "no mesh set");

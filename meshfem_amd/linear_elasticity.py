@@ -102,6 +102,54 @@ class Simulator:
     def constantStrainLoad(self, cstrain_flat):                         # :551-562
         return self.ctx.constant_strain_load(cstrain_flat)
 
+    def perElementStressFieldLoad(self, stress):                        # :564-577
+        """Per-DoF load of a per-element stress field [nElem, flatLen] (tensor shear): f_i = sum_e sigma_e . int_e grad phi_i."""
+        return self.ctx.stress_field_load(stress, "stress")
+
+    def perElementStrainFieldLoad(self, strain):
+        """perElementStressFieldLoad(C_e : strain_e); with one strain everywhere this is constantStrainLoad."""
+        return self.ctx.stress_field_load(strain, "strain")
+
+    def _element_density(self, density):
+        rho = np.asarray(density, dtype=np.float64)
+        return np.full(self.numElements(), float(rho)) if rho.ndim == 0 else rho
+
+    def bodyForceLoad(self, b, density=None):
+        """Per-DoF load of the body force density * b: b one vector (N,), per element (nElem, N) or a nodal field (nNode, N); density per
+        element or None (= 1). No counterpart in the reference."""
+        return self.ctx.body_force_load(b, density)
+
+    def gravityLoad(self, g, density=1.0):
+        """Self-weight: the load of density * g for the acceleration vector g; density a scalar or per element."""
+        return self.ctx.body_force_load(np.asarray(g, dtype=np.float64).reshape(self.N), self._element_density(density))
+
+    def centrifugalLoad(self, omega, axis_point, axis_dir, density=1.0):
+        """The load of a body spinning at angular velocity omega about the axis through axis_point along axis_dir (2D: about the point, the
+        axis is normal to the plane and axis_dir is ignored): density * omega^2 * r_perp(x). The field is linear in x, so its nodal
+        interpolation is exact."""
+        x = self.nodes() - np.asarray(axis_point, dtype=np.float64).reshape(1, self.N)
+        if self.N == 3:
+            a = np.asarray(axis_dir, dtype=np.float64).reshape(3)
+            a = a / np.linalg.norm(a)
+            x = x - np.outer(x @ a, a)
+        return self.ctx.body_force_load(np.ascontiguousarray(float(omega) ** 2 * x), self._element_density(density))
+
+    def _thermal_strain(self, alpha, dT):
+        a, t = np.asarray(alpha, dtype=np.float64), np.asarray(dT, dtype=np.float64)
+        eps = np.zeros((self.numElements(), flat_len(self.N)))
+        eps[:, :self.N] = (a * t * np.ones(self.numElements()))[:, None]
+        return eps
+
+    def thermalLoad(self, alpha, dT):
+        """The load of the thermal strain eps_th = alpha dT I (alpha: scalar or per element, dT: per element or scalar):
+        perElementStrainFieldLoad(eps_th); solve() of it gives the displacement of the heated body."""
+        return self.ctx.stress_field_load(self._thermal_strain(alpha, dT), "strain")
+
+    def thermalStress(self, u_nodes, alpha, dT):
+        """stressField(u) - C : eps_th, the stress in the heated body, with stressField's corner layout [nElem, NQ, flatLen]."""
+        _, sig_th = self.ctx.stress_field_load(self._thermal_strain(alpha, dT), "strain", return_stress=True)
+        return self.stressField(u_nodes) - sig_th[:, None, :]
+
     def solve(self, f=None):                                            # :479-487, :657
         f = None if f is None else np.asarray(f, dtype=np.float64).ravel()
         flags = (L.SOLVE_PIN if self._use_pin else 0) | (L.SOLVE_NO_RIGID_MOTION if self._no_rigid_motion else 0)
@@ -156,8 +204,8 @@ class Simulator:
         return np.sqrt(lam) / (2.0 * np.pi), X
 
     def transient(self, dt, n_steps, amplitude=None, u0=None, v0=None, density=1.0, damping=(0, 0), beta=0.25, gamma=0.5, probes=None,
-                  snapshot_stride=0, a0=None, energies=False, rtol=None, maxit=None):
-        """The response to the load history amplitude[n] x neumannLoad() by implicit Newmark time stepping on the device (mfh_newmark):
+                  snapshot_stride=0, a0=None, energies=False, rtol=None, maxit=None, load=None):
+        """The response to the load history amplitude[n] x f, f = neumannLoad() or the per-DoF vector `load` (a volume load, a sum of loads), by implicit Newmark time stepping on the device (mfh_newmark):
         M u'' + C u' + K u = g(t) f with M = density x the consistent mass matrix, C = damping[0] M + damping[1] K. The Dirichlet variables of the
         applied boundary conditions are the clamp, held at zero (their values play no part, as in vibrational_modes); u0 / v0 / a0: nodal fields
         [nNode, N] (None: rest; a0 None: from the equation of motion at step 0 -- pass the "a" of an earlier call to continue it). probes: (node,
@@ -184,7 +232,7 @@ class Simulator:
         def to_nodes(x):
             x = x.reshape(x.shape[:-1] + (ctx.n_dof, self.N))
             return x[..., dof, :] if mapped else x
-        f = self.neumannLoad()
+        f = self.neumannLoad() if load is None else np.asarray(load, dtype=np.float64).reshape(ctx.n_dof, self.N)
         pv = None
         if probes is not None:
             pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
