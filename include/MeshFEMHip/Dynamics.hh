@@ -19,6 +19,7 @@ namespace MeshFEMHip {
 template <class VField>
 struct TransientOptions {
     Real density = 1.0, rayleighMass = 0.0, rayleighStiff = 0.0;
+    std::vector<Real> elementDensity;                     // one value per element: becomes the context's density field (mfh_set_density; density multiplies it); empty: the field in force
     Real beta = 0.25, gamma = 0.5;
     Real rtol = 1e-8;       // ||r||_2 <= rtol ||b||_2 in every step's solve
     int maxit = 10000;
@@ -54,6 +55,7 @@ TransientResult<typename Sim::VField> transient(const Sim &sim, Real dt, int nSt
         check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
         check(c, mfh_fix_variables(c, nv, vars.data(), nullptr));
     }
+    if (!opt.elementDensity.empty()) check(c, mfh_set_density(c, opt.elementDensity.data(), (int64_t)opt.elementDensity.size(), 0));
     const size_t nDoF = sim.numDoFs(), n = nDoF * N, rows = (size_t)(nSteps > 0 ? nSteps : 0) + 1;
     auto state = [&](const VField &x, const char *name) {
         VField y(nDoF);

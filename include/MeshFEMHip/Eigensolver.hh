@@ -6,6 +6,7 @@
 //   the same pencil with Dirichlet variables removed                 vibrationalModes(sim, nev, density, free = false): the Dirichlet variables of the
 //                                                                      boundary conditions applied to the Simulator are the clamp
 //   largest eigenvalues, negativeCurvatureDirection                  not offered
+//   (no counterpart: the reference's M is at unit density)           vibrationalModes(sim, nev, elementDensity, free): one density per element
 // Returns {lambda (ascending, nev), modes (nev fields of one N-vector per DoF, M-orthonormal, largest entry positive)}; the natural frequencies are
 // sqrt(lambda) / 2 pi. LOBPCG on the device with the Simulator's preconditioner (mfh_set_preconditioner); throws std::runtime_error where the C
 // call fails, a tolerance that maxit iterations do not reach included.
@@ -46,6 +47,16 @@ std::pair<std::vector<Real>, std::vector<typename Sim::VField>> vibrationalModes
         for (size_t i = 0; i < nDoF; ++i)
             for (size_t a = 0; a < N; ++a) modes[m][i][a] = flat[(m * nDoF + i) * N + a];
     return {lambda, modes};
+}
+
+// the same with one density per element: the field becomes the context's (mfh_set_density, MassProperties.hh) and stays in force after the call
+template <class Sim>
+std::pair<std::vector<Real>, std::vector<typename Sim::VField>> vibrationalModes(const Sim &sim, int nev, const std::vector<Real> &elementDensity,
+                                                                                 bool free = false, const ModesOptions &opt = ModesOptions(),
+                                                                                 mfh_modes_info *info = nullptr) {
+    mfh_ctx *c = sim.ctx();
+    check(c, mfh_set_density(c, elementDensity.data(), (int64_t)elementDensity.size(), 0));
+    return vibrationalModes(sim, nev, Real(1.0), free, opt, info);
 }
 
 } // namespace MeshFEMHip

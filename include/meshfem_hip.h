@@ -494,7 +494,8 @@ mfh_status mfh_divergence(mfh_ctx* ctx, const double* elemVectors /* nElem x dim
 
 /* ---------------------------------------------------------------- vibrational modes
  * The nev smallest eigenpairs of K x = lambda M x (1 <= nev <= 20): K the elasticity operator of the context, M = density (> 0) times the consistent
- * vector-valued mass matrix of the mesh's own degree (MassMatrix::construct_vector_valued) -- the reference's
+ * vector-valued mass matrix of the mesh's own degree (MassMatrix::construct_vector_valued; weighted by the per-element field of mfh_set_density when
+ * one is set) -- the reference's
  * smallestNonzeroGenEigenpairsPSDKnownKernel (Eigensolver.hh; shift-invert Lanczos over CHOLMOD there). Here: LOBPCG on the device with the
  * context's preconditioner (docs/design/04_12_modes.md). lambda ascending; the rows of X are M-orthonormal, each with its entry of largest
  * modulus positive.
@@ -558,6 +559,35 @@ mfh_status mfh_newmark(mfh_ctx* ctx, const mfh_newmark_params* params,
                        double* snapshots,                        /* (nSteps/stride + 1) x dim*nDoF or NULL */
                        double* energies,                         /* (nSteps+1) x 3: kinetic, strain, g_n f.u_n; needs MFH_DYN_ENERGIES */
                        mfh_newmark_info* info);
+
+/* ---------------------------------------------------------------- per-element density, the product with M, mass properties
+ * (docs/design/04_15_density.md.) The mass matrix of mfh_modes and mfh_newmark is assembled from a density field of the context:
+ *     M = sum_e rho_e int_e phi_i phi_j   on displacement vectors (kron with the identity of size dim),   rho = 1 until a field is set.
+ * The scalar `density` of mfh_modes and of mfh_newmark_params keeps its meaning: it multiplies whatever field is in force.
+ *   mfh_set_density      rho: one value per element (n == nElem), copied to a device buffer the context owns; NULL restores unit density. flags: 0, or
+ *                        MFH_LOAD_ON_DEVICE (rho is a device pointer). The field survives mfh_mesh_update_vertices, DoF maps and boundary
+ *                        conditions; a new mesh (mfh_mesh_build / mfh_mesh_set) clears it. The resident mass values are reassembled by the next
+ *                        call that needs them. MFH_ERR_INVALID before any device work -- the field in force stays -- on n != nElem or an entry
+ *                        that is not finite or not strictly positive (M must stay positive definite: unlike mfh_body_force_load, 0 is refused; a
+ *                        host array is scanned on the host, a device array by a kernel whose lanes store a flag). MFH_ERR_STATE: no mesh, a
+ *                        host-only context, a matrix from mfh_matrix_set_upper_triplets. MFH_ERR_UNSUPPORTED: a row-partitioned context.
+ *   mfh_mass_apply       y = M x on displacement vectors (dim*nDoF, under the context's DoF map), no fixed variables masked; x and y must not
+ *                        overlap. flags as above (both arrays on the device). For participation factors and orthonormality checks of mfh_modes'
+ *                        rows. The contexts mfh_modes accepts (elasticity, the mesh's own degree, unpartitioned); like it the call holds both
+ *                        triangles of the pattern for its own duration.
+ *   mfh_mass_properties  mass = scale int rho, com = the centre of mass, S = scale int rho (x - com)(x - com)^T (dim x dim, row-major, symmetric)
+ *                        over the straight-sided elements, with the context's field (or rho = 1) and the scalar scale > 0 (the `density` of
+ *                        mfh_modes). The 3D inertia tensor about the centre is tr(S) I - S, the 2D polar moment tr(S). Any output may be NULL;
+ *                        flags is reserved (0). Two passes on the device -- mass and first moments, then second moments about the centre of
+ *                        pass 1, so that nothing cancels for a body far from the origin -- each an ordered two-stage sum without
+ *                        floating-point atomics: the same call returns the same bits. Errors as for mfh_set_density.
+ * The operators MFH_OP_MASS / MFH_OP_MASS_VECTOR of mfh_set_operator (assembled into K's value buffer, with matrix-free forms) and mfh_mass_lumped
+ * are separate from this and stay at unit density. */
+mfh_status mfh_set_density(mfh_ctx* ctx, const double* rho /* nElem, or NULL = clear */, int64_t n, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+mfh_status mfh_mass_apply(mfh_ctx* ctx, const double* x /* dim*nDoF */, double* y /* dim*nDoF */, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+mfh_status mfh_mass_properties(mfh_ctx* ctx, double scale,
+                               double* mass, double* com /* dim */, double* S /* dim*dim, row-major */,
+                               int32_t flags /* 0 */);
 
 /* ---------------------------------------------------------------- multi-GPU solve (one process per GPU)
  * The reference is single-process (TBB, Parallelism.hh:31-43): these entry points have no counterpart to cite beyond the

@@ -12,6 +12,10 @@ extern "C" {
 /* average device time (ms, HIP events on the context stream) of `reps` back-to-back launches of
  * the numeric assembly kernel alone (geometry kernel excluded) -- used by bench.py's roofline   */
 mfh_status mfh_time_assembly_kernel(mfh_ctx* ctx, int32_t mode, int32_t reps, double* avg_ms);
+/* device time (ms, one entry per repetition) of the mass assembly pass into the resident buffer of mfh_modes / mfh_newmark: the unit-density pass and,
+ * field_ms != NULL, the density-weighted pass of the field set with mfh_set_density, launched in turns (scripts/density_probe.py). Needs both
+ * triangles of the pattern (option "matrix_storage" 0 on quadratic meshes). */
+mfh_status mfh_time_mass_assembly(mfh_ctx* ctx, int32_t reps, double* unit_ms /* reps */, double* field_ms /* reps or NULL */);
 /* the same for one application of the operator the PCG uses (see "matrix_free") on internal scratch vectors */
 mfh_status mfh_time_spmv_kernel(mfh_ctx* ctx, int32_t reps, double* avg_ms);
 /* average device time (ms) of `reps` back-to-back k_block_gram calls (both stages) on hashed n x p and n x q blocks, and of `reps` device-to-device

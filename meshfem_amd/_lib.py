@@ -184,6 +184,9 @@ PROTOTYPES = {
     "mfh_mass_lumped": (_i32, [_P, _P, _i32]),
     "mfh_divergence": (_i32, [_P, _P, _P]),
     "mfh_modes": (_i32, [_P, _i32, _f64, _i32, _f64, _i32, _P, _P, _P, C.POINTER(ModesInfo)]),
+    "mfh_set_density": (_i32, [_P, _P, _i64, _i32]),
+    "mfh_mass_apply": (_i32, [_P, _P, _P, _i32]),
+    "mfh_mass_properties": (_i32, [_P, _f64, C.POINTER(_f64), _P, _P, _i32]),
     "mfh_newmark": (_i32, [_P, C.POINTER(NewmarkParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(NewmarkInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
@@ -227,6 +230,7 @@ PROTOTYPES = {
     "mfh_get_timing": (_i32, [_P, C.POINTER(Timing)]),
     "mfh_time_assembly_kernel": (_i32, [_P, _i32, _i32, C.POINTER(_f64)]),
     "mfh_time_spmv_kernel": (_i32, [_P, _i32, C.POINTER(_f64)]),
+    "mfh_time_mass_assembly": (_i32, [_P, _i32, _P, _P]),
     "mfh_time_block_gram": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_set_option": (_i32, [_P, C.c_char_p, _f64]),
     "mfh_debug_spd_inverse": (_i32, [_i64, _P]),

@@ -466,6 +466,40 @@ class Context:
         self._ck(st)
         return out
 
+    # ---------------------------------------------------------------- per-element density (docs/design/04_15_density.md)
+    def set_density(self, rho):
+        """The density field of the mass matrix of modes() and newmark() (mfh_set_density): one strictly positive value per element, or
+        None for unit density. Their scalar density= multiplies the field. It survives mesh_update_vertices; a new mesh clears it."""
+        if rho is None:
+            self._ck(self.lib.mfh_set_density(self.h, None, 0, 0))
+            return
+        rho = as_f64(np.asarray(rho, dtype=np.float64).reshape(-1))
+        self._ck(self.lib.mfh_set_density(self.h, ptr(rho), rho.size, 0))
+
+    def mass_apply(self, x, out=None):
+        """y = M x on a displacement vector of dim * n_dof entries (mfh_mass_apply): M the consistent vector-valued mass matrix with the
+        context's density field, no fixed variables masked. Returns an array of x's shape (out: a C-contiguous float64 array to write)."""
+        x = as_f64(x)
+        n = self.dim * self.n_dof
+        if x.size != n:
+            raise ValueError("mass_apply: x needs dim * n_dof = %d entries, got %d" % (n, x.size))
+        if out is None:
+            out = np.empty(x.shape)
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size != n or np.shares_memory(out, x):
+            raise ValueError("out: a C-contiguous float64 array of dim * n_dof values that does not overlap x")
+        self._ck(self.lib.mfh_mass_apply(self.h, ptr(x), ptr(out), 0))
+        return out
+
+    def mass_properties(self, scale=1.0):
+        """{"mass", "com", "second_moment", "inertia"} of the body with the context's density field times scale (mfh_mass_properties):
+        second_moment = int rho (x - com)(x - com)^T [dim, dim]; inertia = tr(S) I - S in 3D (the tensor about the centre of mass), the
+        polar moment tr(S) in 2D. Ordered sums on the device: the same call returns the same bits."""
+        d = self.dim
+        mass, com, S = C.c_double(), np.zeros(d), np.zeros((d, d))
+        self._ck(self.lib.mfh_mass_properties(self.h, float(scale), C.byref(mass), ptr(com), ptr(S), 0))
+        inertia = np.trace(S) * np.eye(3) - S if d == 3 else float(np.trace(S))
+        return {"mass": mass.value, "com": com, "second_moment": S, "inertia": inertia}
+
     def debug_newmark_predict(self, dt, beta, gamma, density, damping, u, v, a, mask=None, want_xk=True):
         """(ut, vt, xm, xk) of k_newmark_predict on host arrays (test hook mfh_debug_newmark_predict)."""
         u, v, a = as_f64(u), as_f64(v), as_f64(a)

@@ -50,6 +50,12 @@ void drop_mass(mfh_ctx *c) {
     c->dMassVals.release();
     c->massValid = false;
     c->massGeoGen = -1;
+    c->massDensityGen = -1;
+}
+void clear_density(mfh_ctx *c) {
+    c->dDensity.release();
+    c->haveDensity = false;
+    ++c->densityGen;
 }
 void invalidate_symbolic(mfh_ctx *c) {
     drop_mass(c);
@@ -112,6 +118,7 @@ void upload_mesh(mfh_ctx *c, bool deviceTables) {
     c->nodePairsValid = false;
     c->dofPairsValid = false;
     sampler_drop(c);
+    clear_density(c);                // one value per element of the previous mesh
     if (!c->hostOnly && !deviceTables) {      // (deviceTables: the device topology has written both from the vertices)
         require_device(c);
         MFH_HIP(hipSetDevice(c->device));
@@ -495,15 +502,17 @@ void ensure_mass(mfh_ctx *c) {
     ensure_geometry(c);
     ensure_symbolic(c, false);
     require_full_storage(c, "the resident mass matrix (k_spmv_kron)");
-    if (c->massValid && c->massGeoGen == c->geoGen && c->dMassVals.p) return;
+    if (c->massValid && c->massGeoGen == c->geoGen && c->massDensityGen == c->densityGen && c->dMassVals.p) return;
     c->dMassVals.alloc(tiled_count(c->sym.nnzb, 1));
     c->dMassVals.zero(c->stream);      // (the padding of the last tile)
     k::AsmArgs a = asm_args(c);
     a.mat = MAT_MASS;
+    if (c->haveDensity) { a.mat = MAT_MASS_RHO; a.density = c->dDensity.p; }     // (no field: the launch of the unit-density pass, unchanged)
     a.vals = c->dMassVals.p;
     k::launch_assemble_gather(a, c->stream);
     c->massValid = true;
     c->massGeoGen = c->geoGen;
+    c->massDensityGen = c->densityGen;
 }
 
 k::SpmvArgs mass_spmv_args(mfh_ctx *c, bool masked) {

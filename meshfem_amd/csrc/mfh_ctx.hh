@@ -163,12 +163,18 @@ struct mfh_ctx {
     DBuf<float> dVals32;              // FP32 copy of dVals for the smoother of a multigrid linear level (built by ensure_multigrid, dropped whenever dVals is rewritten)
     bool assembled = false;
     // The consistent mass matrix resident BESIDE K (mfh_modes, mfh_modes.hip): one double per stored block of the pattern, both triangles, density 1
-    // (the caller of the product scales). Written by k_assemble_gather<DIM, DEG, MAT_MASS> into this buffer, multiplied by k_spmv_kron from it;
-    // neither touches dVals, and mfh_set_operator does not touch this. Derived from the pattern and the element records: dropped with either
-    // (drop_mass; massGeoGen = the geoGen it was assembled from).
+    // or the context's density field (the caller of the product scales by its scalar). Written by k_assemble_gather<DIM, DEG, MAT_MASS> -- MAT_MASS_RHO
+    // with a field -- into this buffer, multiplied by k_spmv_kron from it; neither touches dVals, and mfh_set_operator does not touch this. Derived
+    // from the pattern, the element records and the density field: dropped with the pattern (drop_mass), reassembled when massGeoGen / massDensityGen
+    // (the geoGen / densityGen it was assembled from) are stale.
     DBuf<double> dMassVals;
     bool massValid = false;
-    int64_t massGeoGen = -1;
+    int64_t massGeoGen = -1, massDensityGen = -1;
+    // The density field of mfh_set_density (docs/design/04_15_density.md): nElem values on the device, owned by the context. It survives vertex
+    // updates and DoF maps; a new mesh (upload_mesh) clears it. densityGen counts every change, the clearing included.
+    DBuf<double> dDensity;
+    bool haveDensity = false;
+    int64_t densityGen = 0;
     bool modesWide = false;           // mfh_modes in progress on a context whose storage rule says "upper triangle": the symbolic phase builds both
                                       // (resolve_upper_storage) until the call returns; option matrix_storage itself is not changed
     std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
@@ -450,7 +456,8 @@ inline void require_full_storage(const mfh_ctx *c, const char *what) {
 inline int32_t dof_of(const mfh_ctx *c, int64_t node) { return c->dofForNode.empty() ? (int32_t)node : c->dofForNode[node]; }
 void invalidate_matrix(mfh_ctx *c);
 void drop_mass(mfh_ctx *c);            // the resident mass buffer describes the previous pattern / vertex positions
-void ensure_mass(mfh_ctx *c);          // dMassVals of the current pattern and element records (both triangles required)
+void clear_density(mfh_ctx *c);        // back to unit density (mfh_set_density(NULL), a new mesh)
+void ensure_mass(mfh_ctx *c);          // dMassVals of the current pattern, element records and density field (both triangles required)
 k::SpmvArgs mass_spmv_args(mfh_ctx *c, bool masked);   // k_spmv_kron on dMassVals
 void ensure_symbolic(mfh_ctx *c, bool wantScatter);
 void ensure_dirichlet_tables(mfh_ctx *c);

@@ -881,6 +881,32 @@ mfh_status mfh_debug_newmark_correct(mfh_ctx *c, int64_t n, double dt, double be
     MFH_CATCH(c)
 }
 
+// y = M x on displacement vectors, unmasked: the resident mass buffer (the context's density field in it) through k_spmv_kron_acc
+mfh_status mfh_mass_apply(mfh_ctx *c, const double *x, double *y, int32_t flags) {
+    MFH_TRY(c)
+    require(c && x && y, MFH_ERR_INVALID, "mfh_mass_apply: null argument");
+    require((flags & ~MFH_LOAD_ON_DEVICE) == 0, MFH_ERR_INVALID, "flags: 0 | MFH_LOAD_ON_DEVICE");
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the resident mass matrix needs a mesh on a device");
+    prepare_pencil(c, "mfh_mass_apply");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    ensure_mass(c);
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    const int64_t n = (int64_t)c->mesh.dim * c->nDoF;
+    DBuf<double> dx, dy;
+    const double *xin = x;
+    double *yout = y;
+    if (!onDevice) {
+        dx.alloc((size_t)n); dy.alloc((size_t)n);
+        upload(dx.p, x, n, s);
+        xin = dx.p; yout = dy.p;
+    }
+    k::launch_spmv_kron_acc(mass_spmv_args(c, false), false, 0.0, 1.0, xin, yout, nullptr, DynGate{nullptr, 0, nullptr}, s, c->dynGridCap);
+    if (!onDevice) MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
 mfh_status mfh_debug_pencil_apply(mfh_ctx *c, double cK, double cM, int32_t masked, const double *x, double *y, double *dot) {
     MFH_TRY(c)
     require(c && x && y && std::isfinite(cK) && std::isfinite(cM), MFH_ERR_INVALID, "mfh_debug_pencil_apply: arguments");

@@ -177,8 +177,9 @@ constexpr int GEO_ORTHO_STRIDE = 24;    // 12 + 1 + 6 normal + 3 shear (+2 pad) 
                                         // matrix-free operator, which runs every PCG iteration, 0.310 vs 0.291 ms -- 192 B it is.
 
 // MAT_LAPLACE / MAT_MASS: scalar operators on the same machinery (1x1 blocks; Laplacian.hh:27-57, MassMatrix.hh:50-86)
-enum MaterialKind { MAT_ISO = 0, MAT_GENERAL = 1, MAT_LAPLACE = 2, MAT_MASS = 3, MAT_ORTHO = 4 };
-inline bool mat_is_scalar(int mat) { return mat == MAT_LAPLACE || mat == MAT_MASS; }
+// MAT_MASS_RHO: MAT_MASS weighted by the context's per-element density (AsmArgs::density; the gather assembly of ensure_mass only)
+enum MaterialKind { MAT_ISO = 0, MAT_GENERAL = 1, MAT_LAPLACE = 2, MAT_MASS = 3, MAT_ORTHO = 4, MAT_MASS_RHO = 5 };
+inline bool mat_is_scalar(int mat) { return mat == MAT_LAPLACE || mat == MAT_MASS || mat == MAT_MASS_RHO; }
 
 // ------------------------------------------------------------------------------------------------
 // Host-side mesh (FEMMesh restatement)
@@ -424,6 +425,7 @@ struct AsmArgs {
     const int32_t *chunkOrder;          // workgroup b takes chunk chunkOrder[b] (nullptr: b): chunks visited in element order
     int upperOnly;                      // the lists cover the blocks (r, c >= r) only (names the kernel instantiation)
     int det;                            // option "deterministic": the waves of a workgroup add their contributions in wave order
+    const double *density;              // MAT_MASS_RHO: nElem densities (mfh_set_density); not read by any other flavour
 };
 
 void launch_geometry(int dim, int deg, int mat, int64_t nElem, const int32_t *elemNodes, int npe,
@@ -481,6 +483,13 @@ void launch_field_stress(const AsmArgs &a, const double *strain, double *out, hi
 void launch_body_force_load(const AsmArgs &a, int64_t nDoF, const int32_t *dofPtr, const int32_t *dofPair, const ShapeTables &T, int kind,
                             const int32_t *elemNodes, const double *b, const double *bConst, const double *density, int add, double *out, hipStream_t s);
 void launch_density_check(int64_t n, const double *density, int *flag, hipStream_t s);              // flag[0] = 1 on a negative or non-finite entry
+// mfh_mass.hip: the density field of a context and the mass properties of the body
+constexpr int MASS_GRID_CAP = 512;       // workgroups of k_mass_moments (= partials the second stage adds per entry); the lanes stride beyond it
+constexpr int MASS_PARTIALS = MASS_GRID_CAP * 6;
+void launch_density_positive(int64_t n, const double *density, int *flag, hipStream_t s);           // flag[0] = 1 on an entry that is not finite or not > 0
+int mass_moments_grid(int64_t nElem);
+void launch_mass_properties(int dim, int64_t nElem, const int32_t *elemNodes, int npe, const double *vertPos, const double *density, double scale,
+                            double *partials, double *props, double *second, hipStream_t s);
 
 struct SpmvArgs {
     int dim;

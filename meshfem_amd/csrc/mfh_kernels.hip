@@ -21,7 +21,7 @@ namespace mfh { namespace k {
 // (same quadrature rule and points as the reference: GaussQuadrature.hh:115-127,283-295).
 // ------------------------------------------------------------------------------------------------
 // components per matrix entry: dim x dim blocks for elasticity, 1 for the scalar operators
-template <int DIM, int MAT> DEV constexpr int mat_nb() { return (MAT == MAT_LAPLACE || MAT == MAT_MASS) ? 1 : DIM * DIM; }
+template <int DIM, int MAT> DEV constexpr int mat_nb() { return (MAT == MAT_LAPLACE || MAT == MAT_MASS || MAT == MAT_MASS_RHO) ? 1 : DIM * DIM; }
 
 // material part of a block: K from H = sum_q w_q grad phi_i (x) grad phi_j and the element's tensor
 template <int DIM, int MAT>
@@ -61,7 +61,7 @@ template <int DIM, int DEG, int MAT>
 DEV void elem_block(const double *__restrict__ g, const double *__restrict__ pairTab, const PairConst &pc, int i, int j, double *K) {
     constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
     const double vol = g[12];
-    if (MAT == MAT_MASS) {
+    if (MAT == MAT_MASS || MAT == MAT_MASS_RHO) {
         // int phi_i phi_j = vol * (reference value): exact for straight-sided simplices, equal to the
         // reference's Quadrature<K, 2 Deg> (exact for this integrand) up to rounding (MassMatrix.hh:66-77)
         K[0] = vol * pairTab[i * NPE + j];
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(256) k_geometry(int64_t nElem, const int32_t *
 // (i, j): built by the workgroup from 3.2 KB of L2-resident data) instead of re-deriving them per contribution from the node
 // indices (support-vertex lookups, vertex / edge selects, the closed form of the coefficients: ~50 of the 141 VALU instructions
 // per contribution of the round-2 kernel).
-template <int DIM, int DEG, int MAT> DEV constexpr bool asm_uses_table() { return DEG == 2 && MAT != MAT_MASS; }
+template <int DIM, int DEG, int MAT> DEV constexpr bool asm_uses_table() { return DEG == 2 && MAT != MAT_MASS && MAT != MAT_MASS_RHO; }
 constexpr int ASM_CODE_SHIFT = 7;
 
 template <int DIM, int DEG, int MAT, bool UPPER = false, bool DET = false>
@@ -393,7 +393,8 @@ __global__ void __launch_bounds__(256, (MAT == MAT_GENERAL || MAT == MAT_ORTHO) 
                 block_from_H<DIM, MAT>(g, H, K);
             } else {
                 const int i = ij / NPE, j = ij - i * NPE;
-                elem_block<DIM, DEG, MAT>(g, MAT == MAT_MASS ? a.massTable : a.pairTable, pc, i, j, K);
+                elem_block<DIM, DEG, MAT>(g, (MAT == MAT_MASS || MAT == MAT_MASS_RHO) ? a.massTable : a.pairTable, pc, i, j, K);
+                if (MAT == MAT_MASS_RHO) K[0] *= a.density[e];     // the context's density field (mfh_set_density): rho_e vol_e m_ij
             }
             }
             if (det) {
@@ -2590,10 +2591,19 @@ void launch_geometry(int dim, int /*deg*/, int /*mat*/, int64_t nElem, const int
         }                                                                                \
     } while (0)
 
+// the density-weighted mass flavour exists for the gather assembly only (ensure_mass with a density field set): the atomic variant and the
+// dense element matrices never see it
+#define MFH_DISPATCH_MASS_RHO(a, CALL)                                                   \
+    do {                                                                                 \
+        if (a.dim == 3) { if (a.deg == 2) { CALL(3, 2, MAT_MASS_RHO); } else { CALL(3, 1, MAT_MASS_RHO); } } \
+        else { if (a.deg == 2) { CALL(2, 2, MAT_MASS_RHO); } else { CALL(2, 1, MAT_MASS_RHO); } }           \
+    } while (0)
+
 void launch_assemble_gather(const AsmArgs &a, hipStream_t s) {
     if (a.nChunk == 0) return;
+    if (a.mat == MAT_MASS_RHO && !a.density) throw Error(MFH_ERR_STATE, "density-weighted mass assembly without a density field");
     size_t lds = (size_t)(mat_is_scalar(a.mat) ? 1 : a.dim * a.dim) * (a.chunkSlots + 2) * sizeof(double);
-    if (a.deg == 2 && a.mat != MAT_MASS) lds += (size_t)a.npe * a.npe * (4 * sizeof(double) + sizeof(uint32_t));   // pair table
+    if (a.deg == 2 && a.mat != MAT_MASS && a.mat != MAT_MASS_RHO) lds += (size_t)a.npe * a.npe * (4 * sizeof(double) + sizeof(uint32_t));   // pair table
     // (the token of the deterministic flavour sits behind the pair-table region whether or not the flavour has a table)
     if (a.det) lds = (size_t)(mat_is_scalar(a.mat) ? 1 : a.dim * a.dim) * (a.chunkSlots + 2) * sizeof(double) + (size_t)a.npe * a.npe * (4 * sizeof(double) + sizeof(uint32_t)) + 16;
 #define CALLV(D, G, M, UP, DT)                                                                                 \
@@ -2606,7 +2616,8 @@ void launch_assemble_gather(const AsmArgs &a, hipStream_t s) {
 #define CALL(D, G, M)                                                     \
     if (a.det) { if (a.upperOnly) CALLV(D, G, M, true, true); else CALLV(D, G, M, false, true); } \
     else { if (a.upperOnly) CALLV(D, G, M, true, false); else CALLV(D, G, M, false, false); }
-    MFH_DISPATCH_ASM(a, CALL);
+    if (a.mat == MAT_MASS_RHO) MFH_DISPATCH_MASS_RHO(a, CALL);
+    else MFH_DISPATCH_ASM(a, CALL);
 #undef CALL
 #undef CALLV
     CHECK_LAUNCH();

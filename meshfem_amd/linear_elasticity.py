@@ -184,8 +184,52 @@ class Simulator:
         self.info = dict(infos[-1])
         return [w[k] for k in range(len(w))]
 
+    def setDensity(self, density):
+        """The per-element density [nElem] of the mass matrix of vibrational_modes and transient (None: unit density). Their scalar density=
+        multiplies it. It survives vertex updates; a new mesh clears it."""
+        self.ctx.set_density(density)
+
+    def _density_scalar(self, density):
+        """density= of vibrational_modes / transient: an array of one value per element becomes the context's field and the scalar 1."""
+        rho = np.asarray(density, dtype=np.float64)
+        if rho.ndim == 0:
+            return float(rho)
+        if rho.shape != (self.numElements(),):
+            raise ValueError("density: a scalar or one value per element")
+        self.setDensity(rho)
+        return 1.0
+
+    def massProperties(self, density=1.0):
+        """{"mass", "com", "second_moment", "inertia"} of the body under the density field of setDensity times the scalar density: the second
+        moments int rho (x - com)(x - com)^T and the inertia tensor tr(S) I - S about the centre of mass (2D: the polar moment tr(S))."""
+        return self.ctx.mass_properties(density)
+
+    def applyMassMatrix(self, x_dofs):
+        """M x on a per-DoF displacement vector [nDoF, N]: the consistent mass matrix with the density field of setDensity."""
+        return self.ctx.mass_apply(np.asarray(x_dofs, dtype=np.float64).reshape(self.ctx.n_dof, self.N))
+
+    def modalEffectiveMass(self, X):
+        """[nev, N]: (x_j^T M r_d)^2 for the mode shapes x_j -- the nodal fields [nev, nNode, N] of vibrational_modes or per-DoF rows
+        [nev, nDoF * N], M-orthonormal -- and the unit translations r_d. Summed over all modes of a body a column gives the mass that moves
+        in direction d."""
+        ctx = self.ctx
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 3 and X.shape[1] == ctx.n_node and ctx.n_dof != ctx.n_node:     # nodal fields under a DoF map: a DoF takes its first node's value
+            dof = ctx.get_dof_map()[0]
+            first = np.full(ctx.n_dof, -1, dtype=np.int64)
+            first[dof[::-1]] = np.arange(ctx.n_node)[::-1]
+            X = X[:, first, :]
+        X = X.reshape(len(X), ctx.n_dof * self.N)
+        out = np.empty((len(X), self.N))
+        for d in range(self.N):
+            r = np.zeros((ctx.n_dof, self.N))
+            r[:, d] = 1.0
+            out[:, d] = (X @ ctx.mass_apply(r).reshape(-1)) ** 2
+        return out
+
     def vibrational_modes(self, nev, density=1.0, free=None, rtol=1e-6, maxit=500):
-        """(frequencies, modes): the nev lowest natural frequencies sqrt(lam) / 2 pi of K x = lam M x (M = density x the consistent mass matrix)
+        """(frequencies, modes): the nev lowest natural frequencies sqrt(lam) / 2 pi of K x = lam M x (M = density x the consistent mass matrix;
+        density: a scalar that multiplies the field of setDensity, or one value per element, which becomes that field)
         and the mode shapes as nodal fields [nev, nNode, N] -- the reference's smallestNonzeroGenEigenpairsPSDKnownKernel (Eigensolver.hh)
         on the device (mfh_modes). The Dirichlet variables of the applied boundary conditions are the clamp (their values play no part);
         free=None means "free body exactly when no Dirichlet condition is present". self.modes_info holds the solver's record."""
@@ -195,7 +239,7 @@ class Simulator:
         self.ctx.clear_fixed()
         if not free and len(v):
             self.ctx.fix_variables(v)
-        lam, X, info = self.ctx.modes(nev, density=density, free=free, rtol=rtol, maxit=maxit)
+        lam, X, info = self.ctx.modes(nev, density=self._density_scalar(density), free=free, rtol=rtol, maxit=maxit)
         self.modes_info = info
         X = X.reshape(len(lam), self.ctx.n_dof, self.N)
         if self.ctx.n_dof != self.ctx.n_node:               # a DoF map (periodic conditions): every node takes its DoF's value
@@ -206,13 +250,14 @@ class Simulator:
     def transient(self, dt, n_steps, amplitude=None, u0=None, v0=None, density=1.0, damping=(0, 0), beta=0.25, gamma=0.5, probes=None,
                   snapshot_stride=0, a0=None, energies=False, rtol=None, maxit=None, load=None):
         """The response to the load history amplitude[n] x f, f = neumannLoad() or the per-DoF vector `load` (a volume load, a sum of loads), by implicit Newmark time stepping on the device (mfh_newmark):
-        M u'' + C u' + K u = g(t) f with M = density x the consistent mass matrix, C = damping[0] M + damping[1] K. The Dirichlet variables of the
+        M u'' + C u' + K u = g(t) f with M = density x the consistent mass matrix (density: a scalar or one value per element, as in vibrational_modes), C = damping[0] M + damping[1] K. The Dirichlet variables of the
         applied boundary conditions are the clamp, held at zero (their values play no part, as in vibrational_modes); u0 / v0 / a0: nodal fields
         [nNode, N] (None: rest; a0 None: from the equation of motion at step 0 -- pass the "a" of an earlier call to continue it). probes: (node,
         component) pairs whose displacement is recorded at every step. Returns a dict of nodal fields: "u", "v", "a" [nNode, N] after the last
         step, "probes" [n_steps + 1, len(probes)], "snapshots" [n_steps // snapshot_stride + 1, nNode, N] (snapshot_stride > 0), "energies"
         [n_steps + 1, 3] = kinetic, strain, g f.u (energies=True). self.transient_info holds the solver's record."""
         ctx = self.ctx
+        density = self._density_scalar(density)
         v, _ = ctx.bc_dirichlet_vars()
         ctx.clear_fixed()
         if len(v):
