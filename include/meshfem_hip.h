@@ -589,6 +589,53 @@ mfh_status mfh_mass_properties(mfh_ctx* ctx, double scale,
                                double* mass, double* com /* dim */, double* S /* dim*dim, row-major */,
                                int32_t flags /* 0 */);
 
+/* ---------------------------------------------------------------- linear buckling: prestress, geometric stiffness, critical load factors
+ * (docs/design/04_16_buckling.md.) The context owns a prestress field: one symmetric tensor sigma_e per element, [nElem][flatLen] in the layout
+ * and shear convention of mfh_average_stress (TENSOR shear entries). Its geometric stiffness on displacement vectors is
+ *     Kg[(i,a),(j,b)] = delta_ab sum_e int_e grad phi_i . sigma_e grad phi_j      (one scalar per node block, kron with the identity of size dim),
+ * with the ELEMENT-AVERAGE stress: exact for linear elements, O(h) for quadratic ones, whose stress varies inside an element. sigma = I gives the
+ * Laplacian. The reference has no counterpart (its Eigensolver.hh has no buckling entry).
+ *   mfh_set_prestress    sigma: n == nElem tensors, any finite values (the field is indefinite by nature), copied to a device buffer the context
+ *                        owns; NULL clears it. flags: 0, or MFH_LOAD_ON_DEVICE (sigma is a device pointer; it is scanned for non-finite entries by
+ *                        a kernel whose lanes store a flag). The field survives mfh_mesh_update_vertices, DoF maps and boundary conditions; a new
+ *                        mesh clears it. MFH_ERR_INVALID before any device work that changes state -- the field in force stays -- on n != nElem,
+ *                        a non-finite entry or an unknown flag. MFH_ERR_STATE: no mesh, a host-only context, a matrix from
+ *                        mfh_matrix_set_upper_triplets. MFH_ERR_UNSUPPORTED: a row-partitioned context.
+ *   mfh_prestress_from_displacement   sigma_e = C_e : (element-average strain of u), u per NODE (nNode x dim, what mfh_sim_solve returns), written
+ *                        on the device into the context's buffer by the kernel of mfh_average_stress: no host trip. Elasticity on the mesh's own
+ *                        degree (MFH_ERR_UNSUPPORTED otherwise).
+ *   mfh_geometric_apply  y = Kg x on displacement vectors (dim*nDoF, under the context's DoF map), no fixed variables masked; x and y must not
+ *                        overlap. The contract and the contexts of mfh_mass_apply; MFH_ERR_STATE without a prestress field. Like mfh_mass_apply the
+ *                        call holds both triangles of the pattern for its own duration: on a context that stores the upper triangle -- every
+ *                        elasticity context with default options -- EVERY call re-runs the symbolic phase and reassembles Kg, and the next call
+ *                        of another entry point rebuilds the upper-triangle pattern (cost: profiles/r12_buckling.md). Callers who apply Kg many
+ *                        times set option "matrix_storage" 0 once; the buffer is then assembled once per prestress. Kg is always assembled by the
+ *                        turn-taking (deterministic) flavour of the gather assembly, so two calls return the same bits in either case.
+ *   mfh_buckling         the nev (1 .. 20) smallest eigenvalues mu of Kg x = mu K x on the clamped context, i.e. (K + factor Kg) x = 0 with
+ *                        factor = -1/mu: the multiples of the prestress at which the body buckles, smallest first. The LOBPCG loop of mfh_modes
+ *                        on the pencil (Kg, K): Kg indefinite, K the context's elasticity operator carrying the inner product, the context's
+ *                        preconditioner of K. The fixed variables (values taken as 0) are removed from the pencil and must leave no rigid motion
+ *                        free (MFH_ERR_UNSUPPORTED otherwise). A column counts as converged at ||Kg x - mu K x||_2 / (|mu| ||K x||_2) <= rtol
+ *                        (written to residuals, may be null). mu ascending; the rows of X are K-orthonormal, each with its entry of largest
+ *                        modulus positive, and zero at the fixed variables. A mu_j that is not negative beyond rounding (mu_j >= -1e-12 max|mu|:
+ *                        no buckling in the direction of the prestress, e.g. pure tension) gives factors[j] = +INFINITY; info->nBuckling counts
+ *                        the negative ones. flags is reserved (0). maxit reached: MFH_ERR_NOT_CONVERGED with the outputs filled. MFH_ERR_INVALID:
+ *                        nev outside 1 .. 20 or more than the pencil has, an unknown flag. MFH_ERR_STATE: no prestress field, no mesh, a
+ *                        host-only context, an external matrix. MFH_ERR_UNSUPPORTED: a row-partitioned context, an operator other than
+ *                        elasticity, the forced-degree-1 view. Like mfh_modes the call holds both triangles of the pattern for its own duration
+ *                        (info->note says so). */
+typedef struct mfh_buckling_info {
+    int32_t converged, iterations, nLocked, precondUsed, blockSize, restarts, nBuckling;   /* nBuckling: returned factors that are finite */
+    double  maxResidual, solve_ms, setup_ms;
+    const char* note;                                                                       /* owned by the context, valid until its next call */
+} mfh_buckling_info;
+mfh_status mfh_set_prestress(mfh_ctx* ctx, const double* sigma /* nElem x flatLen, or NULL = clear */, int64_t n, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+mfh_status mfh_prestress_from_displacement(mfh_ctx* ctx, const double* uNodes /* nNode x dim */, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+mfh_status mfh_geometric_apply(mfh_ctx* ctx, const double* x /* dim*nDoF */, double* y /* dim*nDoF */, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+mfh_status mfh_buckling(mfh_ctx* ctx, int32_t nev, int32_t flags /* 0 */, double rtol, int32_t maxit,
+                        double* factors /* nev */, double* X /* nev x dim*nDoF, row per mode */, double* residuals /* nev or NULL */,
+                        mfh_buckling_info* info);
+
 /* ---------------------------------------------------------------- multi-GPU solve (one process per GPU)
  * The reference is single-process (TBB, Parallelism.hh:31-43): these entry points have no counterpart to cite beyond the
  * serial path they parallelise (Simulator::solve, LinearElasticity.hh:479-487; SPSDSystem::solve, SparseMatrices.hh:2515-2606).

@@ -16,6 +16,12 @@ mfh_status mfh_time_assembly_kernel(mfh_ctx* ctx, int32_t mode, int32_t reps, do
  * field_ms != NULL, the density-weighted pass of the field set with mfh_set_density, launched in turns (scripts/density_probe.py). Needs both
  * triangles of the pattern (option "matrix_storage" 0 on quadratic meshes). */
 mfh_status mfh_time_mass_assembly(mfh_ctx* ctx, int32_t reps, double* unit_ms /* reps */, double* field_ms /* reps or NULL */);
+/* device time (ms, one entry per repetition) of the gather assembly pass into the resident geometric-stiffness buffer as the Laplacian, the
+ * unit-density mass and the geometric stiffness of the prestress in force in the context's flavour, then the geometric stiffness in the turn-taking
+ * (deterministic) flavour that the library itself launches for it, in turns (scripts/probe_buckling.py). Needs a prestress field and both triangles
+ * of the pattern (option "matrix_storage" 0 on quadratic meshes). */
+mfh_status mfh_time_geometric_assembly(mfh_ctx* ctx, int32_t reps, double* laplace_ms /* reps */, double* mass_ms /* reps */, double* geom_ms /* reps */,
+                                       double* geom_det_ms /* reps */);
 /* the same for one application of the operator the PCG uses (see "matrix_free") on internal scratch vectors */
 mfh_status mfh_time_spmv_kernel(mfh_ctx* ctx, int32_t reps, double* avg_ms);
 /* average device time (ms) of `reps` back-to-back k_block_gram calls (both stages) on hashed n x p and n x q blocks, and of `reps` device-to-device

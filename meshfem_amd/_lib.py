@@ -52,6 +52,17 @@ class ModesInfo(C.Structure):
         return d
 
 
+class BucklingInfo(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("nLocked", C.c_int32), ("precondUsed", C.c_int32),
+                ("blockSize", C.c_int32), ("restarts", C.c_int32), ("nBuckling", C.c_int32), ("maxResidual", C.c_double),
+                ("solve_ms", C.c_double), ("setup_ms", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
 class NewmarkParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("density", C.c_double), ("rayleighMass", C.c_double),
                 ("rayleighStiff", C.c_double), ("rtol", C.c_double), ("nSteps", C.c_int32), ("maxit", C.c_int32), ("snapshotStride", C.c_int32),
@@ -187,6 +198,10 @@ PROTOTYPES = {
     "mfh_set_density": (_i32, [_P, _P, _i64, _i32]),
     "mfh_mass_apply": (_i32, [_P, _P, _P, _i32]),
     "mfh_mass_properties": (_i32, [_P, _f64, C.POINTER(_f64), _P, _P, _i32]),
+    "mfh_set_prestress": (_i32, [_P, _P, _i64, _i32]),
+    "mfh_prestress_from_displacement": (_i32, [_P, _P, _i32]),
+    "mfh_geometric_apply": (_i32, [_P, _P, _P, _i32]),
+    "mfh_buckling": (_i32, [_P, _i32, _i32, _f64, _i32, _P, _P, _P, C.POINTER(BucklingInfo)]),
     "mfh_newmark": (_i32, [_P, C.POINTER(NewmarkParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(NewmarkInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
@@ -231,6 +246,7 @@ PROTOTYPES = {
     "mfh_time_assembly_kernel": (_i32, [_P, _i32, _i32, C.POINTER(_f64)]),
     "mfh_time_spmv_kernel": (_i32, [_P, _i32, C.POINTER(_f64)]),
     "mfh_time_mass_assembly": (_i32, [_P, _i32, _P, _P]),
+    "mfh_time_geometric_assembly": (_i32, [_P, _i32, _P, _P, _P, _P]),
     "mfh_time_block_gram": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_set_option": (_i32, [_P, C.c_char_p, _f64]),
     "mfh_debug_spd_inverse": (_i32, [_i64, _P]),

@@ -500,6 +500,58 @@ class Context:
         inertia = np.trace(S) * np.eye(3) - S if d == 3 else float(np.trace(S))
         return {"mass": mass.value, "com": com, "second_moment": S, "inertia": inertia}
 
+    # ---------------------------------------------------------------- linear buckling (docs/design/04_16_buckling.md)
+    def set_prestress(self, sigma):
+        """The prestress field of geometric_apply() and buckling() (mfh_set_prestress): one symmetric tensor per element [nElem, flatLen] in the
+        layout of average_stress (tensor shear entries), any finite values, or None to clear it. It survives mesh_update_vertices; a new mesh
+        clears it."""
+        if sigma is None:
+            self._ck(self.lib.mfh_set_prestress(self.h, None, 0, 0))
+            return
+        sigma = as_f64(np.asarray(sigma, dtype=np.float64))
+        fl = flat_len(self.dim)
+        if sigma.ndim != 2 or sigma.shape[1] != fl:
+            raise ValueError("sigma: [nElem, flatLen = %d]" % fl)
+        self._ck(self.lib.mfh_set_prestress(self.h, ptr(sigma), sigma.shape[0], 0))
+
+    def prestress_from_displacement(self, u_nodes):
+        """Sets the prestress field to C_e : (element-average strain of u) for a per-node displacement [nNode, dim], on the device
+        (mfh_prestress_from_displacement): what average_stress(u) returns, without the host trip."""
+        u = as_f64(u_nodes)
+        if u.size != self.n_node * self.dim:
+            raise ValueError("prestress_from_displacement: u needs n_node * dim = %d entries, got %d" % (self.n_node * self.dim, u.size))
+        self._ck(self.lib.mfh_prestress_from_displacement(self.h, ptr(u), 0))
+
+    def geometric_apply(self, x, out=None):
+        """y = Kg x on a displacement vector of dim * n_dof entries (mfh_geometric_apply): Kg the geometric stiffness of the context's prestress
+        field, no fixed variables masked. Returns an array of x's shape (out: a C-contiguous float64 array to write)."""
+        x = as_f64(x)
+        n = self.dim * self.n_dof
+        if x.size != n:
+            raise ValueError("geometric_apply: x needs dim * n_dof = %d entries, got %d" % (n, x.size))
+        if out is None:
+            out = np.empty(x.shape)
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size != n or np.shares_memory(out, x):
+            raise ValueError("out: a C-contiguous float64 array of dim * n_dof values that does not overlap x")
+        self._ck(self.lib.mfh_geometric_apply(self.h, ptr(x), ptr(out), 0))
+        return out
+
+    def buckling(self, nev, rtol=1e-6, maxit=500):
+        """(factors, X, info): the nev smallest load factors of (K + factor Kg) x = 0 on the clamped context (mfh_buckling), Kg the geometric
+        stiffness of the prestress field. factors ascending, +inf where the prestress does not buckle the body; X: [nev, dim * n_dof], rows
+        K-orthonormal; info["residuals"] holds ||Kg x - mu K x|| / (|mu| ||K x||) per mode, info["nBuckling"] the number of finite factors.
+        Raises on MFH_ERR_NOT_CONVERGED like solve(); what was reached is then in self.last_buckling = (factors, X, info)."""
+        nev = int(nev)
+        n = self.bs * self.n_dof
+        fac, X, res = np.zeros(max(nev, 0)), np.zeros((max(nev, 0), n)), np.zeros(max(nev, 0))
+        info = L.BucklingInfo()
+        st = self.lib.mfh_buckling(self.h, nev, 0, float(rtol), int(maxit), ptr(fac), ptr(X), ptr(res), C.byref(info))
+        d = info.as_dict()
+        d["residuals"] = res
+        self.last_buckling = (fac, X, d)
+        self._ck(st)
+        return fac, X, d
+
     def debug_newmark_predict(self, dt, beta, gamma, density, damping, u, v, a, mask=None, want_xk=True):
         """(ut, vt, xm, xk) of k_newmark_predict on host arrays (test hook mfh_debug_newmark_predict)."""
         u, v, a = as_f64(u), as_f64(v), as_f64(a)

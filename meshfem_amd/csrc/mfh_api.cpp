@@ -51,6 +51,15 @@ void drop_mass(mfh_ctx *c) {
     c->massValid = false;
     c->massGeoGen = -1;
     c->massDensityGen = -1;
+    c->dGeomVals.release();           // (the geometric stiffness has the same storage and the same dependences)
+    c->geomValid = false;
+    c->geomGeoGen = -1;
+    c->geomPrestressGen = -1;
+}
+void clear_prestress(mfh_ctx *c) {
+    c->dPrestress.release();
+    c->havePrestress = false;
+    ++c->prestressGen;
 }
 void clear_density(mfh_ctx *c) {
     c->dDensity.release();
@@ -119,6 +128,7 @@ void upload_mesh(mfh_ctx *c, bool deviceTables) {
     c->dofPairsValid = false;
     sampler_drop(c);
     clear_density(c);                // one value per element of the previous mesh
+    clear_prestress(c);
     if (!c->hostOnly && !deviceTables) {      // (deviceTables: the device topology has written both from the vertices)
         require_device(c);
         MFH_HIP(hipSetDevice(c->device));
@@ -513,6 +523,37 @@ void ensure_mass(mfh_ctx *c) {
     c->massValid = true;
     c->massGeoGen = c->geoGen;
     c->massDensityGen = c->densityGen;
+}
+
+// The geometric stiffness beside K and M: the gather assembly with MAT_GEOM (H : sigma_e of the context's prestress) into a value buffer of its
+// own, on the pattern and gather lists K is assembled with; both triangles, like the mass buffer.
+void ensure_geometric(mfh_ctx *c) {
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the geometric stiffness needs a mesh on a device");
+    require(c->havePrestress && c->dPrestress.p, MFH_ERR_STATE, "no prestress field set (mfh_set_prestress / mfh_prestress_from_displacement)");
+    ensure_geometry(c);
+    ensure_symbolic(c, false);
+    require_full_storage(c, "the resident geometric stiffness (k_spmv_kron)");
+    if (c->geomValid && c->geomGeoGen == c->geoGen && c->geomPrestressGen == c->prestressGen && c->dGeomVals.p) return;
+    c->dGeomVals.alloc(tiled_count(c->sym.nnzb, 1));
+    c->dGeomVals.zero(c->stream);      // (the padding of the last tile)
+    k::AsmArgs a = asm_args(c);
+    a.mat = MAT_GEOM;
+    a.sigma = c->dPrestress.p;
+    a.vals = c->dGeomVals.p;
+    // always the turn-taking flavour: a context on the upper-triangle storage drops this buffer after every call that widened the pattern (WideGuard)
+    // and reassembles it in the next, and the plain flavour adds in arrival order -- two calls would differ in their last bits. The pass runs once
+    // per prestress and pattern, not per iteration.
+    a.det = 1;
+    k::launch_assemble_gather(a, c->stream);
+    c->geomValid = true;
+    c->geomGeoGen = c->geoGen;
+    c->geomPrestressGen = c->prestressGen;
+}
+
+k::SpmvArgs geom_spmv_args(mfh_ctx *c, bool masked) {
+    k::SpmvArgs a = mass_spmv_args(c, masked);
+    a.vals = c->dGeomVals.p;
+    return a;
 }
 
 k::SpmvArgs mass_spmv_args(mfh_ctx *c, bool masked) {

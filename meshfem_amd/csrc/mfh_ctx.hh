@@ -175,6 +175,18 @@ struct mfh_ctx {
     DBuf<double> dDensity;
     bool haveDensity = false;
     int64_t densityGen = 0;
+    // The prestress field of mfh_set_prestress (docs/design/04_16_buckling.md): nElem x flatLen values on the device (the layout of
+    // mfh_average_stress: flat_idx order, tensor shear entries), owned by the context; any finite values. It survives vertex updates, DoF maps and
+    // boundary conditions; a new mesh (upload_mesh) clears it. prestressGen counts every change, the clearing included.
+    DBuf<double> dPrestress;
+    bool havePrestress = false;
+    int64_t prestressGen = 0;
+    // The geometric stiffness Kg resident beside K and M (mfh_buckling, mfh_geometric_apply): one double per stored block, both triangles, the
+    // storage shape of dMassVals. Written by k_assemble_gather<DIM, DEG, MAT_GEOM>, multiplied by k_spmv_kron. Dropped wherever dMassVals is
+    // (drop_mass), reassembled when geomGeoGen / geomPrestressGen (the geoGen / prestressGen it was assembled from) are stale.
+    DBuf<double> dGeomVals;
+    bool geomValid = false;
+    int64_t geomGeoGen = -1, geomPrestressGen = -1;
     bool modesWide = false;           // mfh_modes in progress on a context whose storage rule says "upper triangle": the symbolic phase builds both
                                       // (resolve_upper_storage) until the call returns; option matrix_storage itself is not changed
     std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
@@ -459,6 +471,21 @@ void drop_mass(mfh_ctx *c);            // the resident mass buffer describes the
 void clear_density(mfh_ctx *c);        // back to unit density (mfh_set_density(NULL), a new mesh)
 void ensure_mass(mfh_ctx *c);          // dMassVals of the current pattern, element records and density field (both triangles required)
 k::SpmvArgs mass_spmv_args(mfh_ctx *c, bool masked);   // k_spmv_kron on dMassVals
+void clear_prestress(mfh_ctx *c);      // no prestress field (mfh_set_prestress(NULL), a new mesh)
+void ensure_geometric(mfh_ctx *c);     // dGeomVals of the current pattern, element records and prestress field (both triangles required)
+k::SpmvArgs geom_spmv_args(mfh_ctx *c, bool masked);   // k_spmv_kron on dGeomVals
+void refresh_storage_rule(mfh_ctx *c);
+// the storage of the pattern for the duration of a call (see mfh_ctx::modesWide): both triangles, and back
+struct WideGuard {
+    mfh_ctx *c;
+    bool widened = false;
+    explicit WideGuard(mfh_ctx *c_) : c(c_) {
+        if (resolve_upper_storage(c)) { c->modesWide = true; widened = true; }
+    }
+    ~WideGuard() {
+        if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
+    }
+};
 void ensure_symbolic(mfh_ctx *c, bool wantScatter);
 void ensure_dirichlet_tables(mfh_ctx *c);
 void dist_detach(mfh_ctx *c);

@@ -577,19 +577,25 @@ void prepare_pencil(mfh_ctx *c, const char *who) {
     require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "2D / 3D meshes");
 }
 
-// the storage of the pattern for the duration of a call (see mfh_ctx::modesWide): both triangles, and back
-struct WideGuard {
-    mfh_ctx *c;
-    bool widened = false;
-    explicit WideGuard(mfh_ctx *c_) : c(c_) {
-        if (resolve_upper_storage(c)) { c->modesWide = true; widened = true; }
-    }
-    ~WideGuard() {
-        if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
-    }
-};
-
 void upload(double *dst, const double *src, int64_t n, hipStream_t s) { MFH_HIP(hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s)); }
+
+// y = (one double per block, kron I) x for host or device vectors of dim * nDoF entries (mfh_mass_apply, mfh_geometric_apply)
+void kron_apply(mfh_ctx *c, const k::SpmvArgs &args, const double *x, double *y, int32_t flags) {
+    hipStream_t s = c->stream;
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    const int64_t n = (int64_t)c->mesh.dim * c->nDoF;
+    DBuf<double> dx, dy;
+    const double *xin = x;
+    double *yout = y;
+    if (!onDevice) {
+        dx.alloc((size_t)n); dy.alloc((size_t)n);
+        upload(dx.p, x, n, s);
+        xin = dx.p; yout = dy.p;
+    }
+    k::launch_spmv_kron_acc(args, false, 0.0, 1.0, xin, yout, nullptr, DynGate{nullptr, 0, nullptr}, s, c->dynGridCap);
+    if (!onDevice) MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+}
 
 }   // namespace
 
@@ -888,22 +894,23 @@ mfh_status mfh_mass_apply(mfh_ctx *c, const double *x, double *y, int32_t flags)
     require((flags & ~MFH_LOAD_ON_DEVICE) == 0, MFH_ERR_INVALID, "flags: 0 | MFH_LOAD_ON_DEVICE");
     require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the resident mass matrix needs a mesh on a device");
     prepare_pencil(c, "mfh_mass_apply");
-    hipStream_t s = c->stream;
     WideGuard guard(c);
     ensure_mass(c);
-    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
-    const int64_t n = (int64_t)c->mesh.dim * c->nDoF;
-    DBuf<double> dx, dy;
-    const double *xin = x;
-    double *yout = y;
-    if (!onDevice) {
-        dx.alloc((size_t)n); dy.alloc((size_t)n);
-        upload(dx.p, x, n, s);
-        xin = dx.p; yout = dy.p;
-    }
-    k::launch_spmv_kron_acc(mass_spmv_args(c, false), false, 0.0, 1.0, xin, yout, nullptr, DynGate{nullptr, 0, nullptr}, s, c->dynGridCap);
-    if (!onDevice) MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFH_HIP(hipStreamSynchronize(s));
+    kron_apply(c, mass_spmv_args(c, false), x, y, flags);
+    MFH_CATCH(c)
+}
+
+// y = Kg x on displacement vectors, unmasked: the resident geometric stiffness of the context's prestress, the same way
+mfh_status mfh_geometric_apply(mfh_ctx *c, const double *x, double *y, int32_t flags) {
+    MFH_TRY(c)
+    require(c && x && y, MFH_ERR_INVALID, "mfh_geometric_apply: null argument");
+    require((flags & ~MFH_LOAD_ON_DEVICE) == 0, MFH_ERR_INVALID, "flags: 0 | MFH_LOAD_ON_DEVICE");
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the resident geometric stiffness needs a mesh on a device");
+    prepare_pencil(c, "mfh_geometric_apply");
+    require(c->havePrestress, MFH_ERR_STATE, "mfh_geometric_apply: no prestress field set (mfh_set_prestress / mfh_prestress_from_displacement)");
+    WideGuard guard(c);
+    ensure_geometric(c);
+    kron_apply(c, geom_spmv_args(c, false), x, y, flags);
     MFH_CATCH(c)
 }
 

@@ -177,9 +177,10 @@ constexpr int GEO_ORTHO_STRIDE = 24;    // 12 + 1 + 6 normal + 3 shear (+2 pad) 
                                         // matrix-free operator, which runs every PCG iteration, 0.310 vs 0.291 ms -- 192 B it is.
 
 // MAT_LAPLACE / MAT_MASS: scalar operators on the same machinery (1x1 blocks; Laplacian.hh:27-57, MassMatrix.hh:50-86)
+// MAT_GEOM: the geometric stiffness H : sigma_e of the context's prestress (AsmArgs::sigma; the gather assembly of ensure_geometric only)
 // MAT_MASS_RHO: MAT_MASS weighted by the context's per-element density (AsmArgs::density; the gather assembly of ensure_mass only)
-enum MaterialKind { MAT_ISO = 0, MAT_GENERAL = 1, MAT_LAPLACE = 2, MAT_MASS = 3, MAT_ORTHO = 4, MAT_MASS_RHO = 5 };
-inline bool mat_is_scalar(int mat) { return mat == MAT_LAPLACE || mat == MAT_MASS || mat == MAT_MASS_RHO; }
+enum MaterialKind { MAT_ISO = 0, MAT_GENERAL = 1, MAT_LAPLACE = 2, MAT_MASS = 3, MAT_ORTHO = 4, MAT_MASS_RHO = 5, MAT_GEOM = 6 };
+inline bool mat_is_scalar(int mat) { return mat == MAT_LAPLACE || mat == MAT_MASS || mat == MAT_MASS_RHO || mat == MAT_GEOM; }
 
 // ------------------------------------------------------------------------------------------------
 // Host-side mesh (FEMMesh restatement)
@@ -426,6 +427,7 @@ struct AsmArgs {
     int upperOnly;                      // the lists cover the blocks (r, c >= r) only (names the kernel instantiation)
     int det;                            // option "deterministic": the waves of a workgroup add their contributions in wave order
     const double *density;              // MAT_MASS_RHO: nElem densities (mfh_set_density); not read by any other flavour
+    const double *sigma;                // MAT_GEOM: nElem x flatLen prestresses, tensor shear entries (mfh_set_prestress); not read by any other flavour
 };
 
 void launch_geometry(int dim, int deg, int mat, int64_t nElem, const int32_t *elemNodes, int npe,
@@ -483,6 +485,8 @@ void launch_field_stress(const AsmArgs &a, const double *strain, double *out, hi
 void launch_body_force_load(const AsmArgs &a, int64_t nDoF, const int32_t *dofPtr, const int32_t *dofPair, const ShapeTables &T, int kind,
                             const int32_t *elemNodes, const double *b, const double *bConst, const double *density, int add, double *out, hipStream_t s);
 void launch_density_check(int64_t n, const double *density, int *flag, hipStream_t s);              // flag[0] = 1 on a negative or non-finite entry
+// mfh_modes.hip (linear buckling): the prestress field of a context
+void launch_prestress_finite(int64_t n, const double *sigma, int *flag, hipStream_t s);             // flag[0] = 1 on an entry that is not finite
 // mfh_mass.hip: the density field of a context and the mass properties of the body
 constexpr int MASS_GRID_CAP = 512;       // workgroups of k_mass_moments (= partials the second stage adds per entry); the lanes stride beyond it
 constexpr int MASS_PARTIALS = MASS_GRID_CAP * 6;

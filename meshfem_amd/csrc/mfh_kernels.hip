@@ -21,11 +21,12 @@ namespace mfh { namespace k {
 // (same quadrature rule and points as the reference: GaussQuadrature.hh:115-127,283-295).
 // ------------------------------------------------------------------------------------------------
 // components per matrix entry: dim x dim blocks for elasticity, 1 for the scalar operators
-template <int DIM, int MAT> DEV constexpr int mat_nb() { return (MAT == MAT_LAPLACE || MAT == MAT_MASS || MAT == MAT_MASS_RHO) ? 1 : DIM * DIM; }
+template <int DIM, int MAT> DEV constexpr int mat_nb() { return (MAT == MAT_LAPLACE || MAT == MAT_MASS || MAT == MAT_MASS_RHO || MAT == MAT_GEOM) ? 1 : DIM * DIM; }
 
 // material part of a block: K from H = sum_q w_q grad phi_i (x) grad phi_j and the element's tensor
+// (sig: the element's prestress, MAT_GEOM only -- flattened, tensor shear entries; no other flavour reads it)
 template <int DIM, int MAT>
-DEV void block_from_H(const double *__restrict__ g, const double (&H)[DIM][DIM], double *K);
+DEV void block_from_H(const double *__restrict__ g, const double (&H)[DIM][DIM], double *K, const double *__restrict__ sig = nullptr);
 
 // H from the (s,t) support offsets of the two nodes and the pair's four quadrature coefficients (one row of
 // ShapeTables::pairTable): the table-driven form of the assembly kernel (quadratic elements)
@@ -58,7 +59,8 @@ DEV void pair_H(const double *__restrict__ g, uint32_t offs /* bytes: 3 DIM-offs
 }
 
 template <int DIM, int DEG, int MAT>
-DEV void elem_block(const double *__restrict__ g, const double *__restrict__ pairTab, const PairConst &pc, int i, int j, double *K) {
+DEV void elem_block(const double *__restrict__ g, const double *__restrict__ pairTab, const PairConst &pc, int i, int j, double *K,
+                    const double *__restrict__ sig = nullptr) {
     constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
     const double vol = g[12];
     if (MAT == MAT_MASS || MAT == MAT_MASS_RHO) {
@@ -111,12 +113,24 @@ DEV void elem_block(const double *__restrict__ g, const double *__restrict__ pai
 #pragma unroll
             for (int b = 0; b < DIM; ++b) H[a][b] = ua[a] * p[b] + ub[a] * q[b];
     }
-    block_from_H<DIM, MAT>(g, H, K);
+    block_from_H<DIM, MAT>(g, H, K, sig);
 }
 
 template <int DIM, int MAT>
-DEV void block_from_H(const double *__restrict__ g, const double (&H)[DIM][DIM], double *K) {
-    if (MAT == MAT_LAPLACE) {
+DEV void block_from_H(const double *__restrict__ g, const double (&H)[DIM][DIM], double *K, const double *__restrict__ sig) {
+    if (MAT == MAT_GEOM) {
+        // geometric stiffness: int grad phi_i . sigma_e grad phi_j = H : sigma_e (sigma constant on the element; sigma = I is MAT_LAPLACE)
+        constexpr int FL = DIM * (DIM + 1) / 2;
+        double sg[FL];
+#pragma unroll
+        for (int q = 0; q < FL; ++q) sg[q] = sig[q];
+        double v = 0;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a)
+#pragma unroll
+            for (int b = 0; b < DIM; ++b) v += H[a][b] * sg[flat_idx<DIM>(a, b)];
+        K[0] = v;
+    } else if (MAT == MAT_LAPLACE) {
         // int grad phi_i . grad phi_j = tr(H)   (Laplacian.hh:38-48; Poisson.hh:33-38)
         double tr = 0;
 #pragma unroll
@@ -390,10 +404,12 @@ __global__ void __launch_bounds__(256, (MAT == MAT_GENERAL || MAT == MAT_ORTHO) 
                 const uint32_t offs = tabO[ij];
                 double H[DIM][DIM];
                 pair_H<DIM>(g, offs, s01.x, s01.y, s23.x, s23.y, H);
-                block_from_H<DIM, MAT>(g, H, K);
+                if (MAT == MAT_GEOM) block_from_H<DIM, MAT>(g, H, K, a.sigma + (int64_t)e * (DIM * (DIM + 1) / 2));   // the context's prestress (mfh_set_prestress)
+                else block_from_H<DIM, MAT>(g, H, K);
             } else {
                 const int i = ij / NPE, j = ij - i * NPE;
-                elem_block<DIM, DEG, MAT>(g, (MAT == MAT_MASS || MAT == MAT_MASS_RHO) ? a.massTable : a.pairTable, pc, i, j, K);
+                if (MAT == MAT_GEOM) elem_block<DIM, DEG, MAT>(g, a.pairTable, pc, i, j, K, a.sigma + (int64_t)e * (DIM * (DIM + 1) / 2));
+                else elem_block<DIM, DEG, MAT>(g, (MAT == MAT_MASS || MAT == MAT_MASS_RHO) ? a.massTable : a.pairTable, pc, i, j, K);
                 if (MAT == MAT_MASS_RHO) K[0] *= a.density[e];     // the context's density field (mfh_set_density): rho_e vol_e m_ij
             }
             }
@@ -2599,8 +2615,16 @@ void launch_geometry(int dim, int /*deg*/, int /*mat*/, int64_t nElem, const int
         else { if (a.deg == 2) { CALL(2, 2, MAT_MASS_RHO); } else { CALL(2, 1, MAT_MASS_RHO); } }           \
     } while (0)
 
+// the geometric-stiffness flavour (H : sigma_e, ensure_geometric): like the density-weighted mass, the gather assembly only
+#define MFH_DISPATCH_GEOM(a, CALL)                                                       \
+    do {                                                                                 \
+        if (a.dim == 3) { if (a.deg == 2) { CALL(3, 2, MAT_GEOM); } else { CALL(3, 1, MAT_GEOM); } } \
+        else { if (a.deg == 2) { CALL(2, 2, MAT_GEOM); } else { CALL(2, 1, MAT_GEOM); } }           \
+    } while (0)
+
 void launch_assemble_gather(const AsmArgs &a, hipStream_t s) {
     if (a.nChunk == 0) return;
+    if (a.mat == MAT_GEOM && !a.sigma) throw Error(MFH_ERR_STATE, "geometric-stiffness assembly without a prestress field");
     if (a.mat == MAT_MASS_RHO && !a.density) throw Error(MFH_ERR_STATE, "density-weighted mass assembly without a density field");
     size_t lds = (size_t)(mat_is_scalar(a.mat) ? 1 : a.dim * a.dim) * (a.chunkSlots + 2) * sizeof(double);
     if (a.deg == 2 && a.mat != MAT_MASS && a.mat != MAT_MASS_RHO) lds += (size_t)a.npe * a.npe * (4 * sizeof(double) + sizeof(uint32_t));   // pair table
@@ -2617,6 +2641,7 @@ void launch_assemble_gather(const AsmArgs &a, hipStream_t s) {
     if (a.det) { if (a.upperOnly) CALLV(D, G, M, true, true); else CALLV(D, G, M, false, true); } \
     else { if (a.upperOnly) CALLV(D, G, M, true, false); else CALLV(D, G, M, false, false); }
     if (a.mat == MAT_MASS_RHO) MFH_DISPATCH_MASS_RHO(a, CALL);
+    else if (a.mat == MAT_GEOM) MFH_DISPATCH_GEOM(a, CALL);
     else MFH_DISPATCH_ASM(a, CALL);
 #undef CALL
 #undef CALLV

@@ -172,6 +172,14 @@ __global__ void __launch_bounds__(256) k_block_residual(ResArgs a, double *__res
         partials[(int64_t)blockIdx.x * 2 * BLK_MAXC + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
+// flags a prestress entry that is not finite (the lanes store the flag: no atomic)
+__global__ void __launch_bounds__(256) k_prestress_finite(int64_t n, const double *__restrict__ sigma, int *__restrict__ flag) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const double v = sigma[e];
+        if (!(v - v == 0.0)) flag[0] = 1;
+    }
+}
+
 int gram_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, GRAM_GRID_CAP)); }
 
 // G (device, p x q row-major) = A^T B; partials: scratch of GRAM_GRID_CAP * 576 doubles
@@ -197,6 +205,12 @@ void launch_block_residual(const ResArgs &a, double *partials, double *norms, hi
 }
 
 }   // namespace
+
+void launch_prestress_finite(int64_t n, const double *sigma, int *flag, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_prestress_finite, dim3(grid_for(n)), dim3(256), 0, s, n, sigma, flag);
+    CHECK_LAUNCH();
+}
 }}   // namespace mfh::k
 
 using namespace mfh;
@@ -385,8 +399,10 @@ struct ModesWork {
     hipStream_t s;
     int d, m;                          // variables per DoF, block size
     int64_t n, ld;
-    double density;
+    double density = 1.0;
     bool masked;
+    bool buckling = false;             // the pencil: (K, density M) of mfh_modes, or (Kg, K) of mfh_buckling
+    const char *who = "mfh_modes";     // the entry point, for messages
     DBuf<double> vec, zvec, gramPart, resPart, small, coef;
     double *X, *W, *P, *KX, *KW, *KP, *MX, *MW, *MP, *R;
     double *Z = nullptr, *KZ = nullptr, *MZ = nullptr;
@@ -419,7 +435,7 @@ struct ModesWork {
         coefUsed = 0;
     }
     double *small_slot(size_t count) {
-        require(smallUsed + count <= small.n, MFH_ERR_STATE, "mfh_modes: Gram staging overflow");
+        need(smallUsed + count <= small.n, MFH_ERR_STATE, "Gram staging overflow");
         double *p = small.p + smallUsed;
         smallUsed += count;
         return p;
@@ -431,18 +447,26 @@ struct ModesWork {
         return G;
     }
     const double *upload_coef(std::vector<double> &&h) {
-        require(coefUsed + h.size() <= coef.n, MFH_ERR_STATE, "mfh_modes: coefficient staging overflow");
+        need(coefUsed + h.size() <= coef.n, MFH_ERR_STATE, "coefficient staging overflow");
         staged.push_back(std::move(h));
         double *p = coef.p + coefUsed;
         coefUsed += staged.back().size();
         MFH_HIP(hipMemcpyAsync(p, staged.back().data(), staged.back().size() * sizeof(double), hipMemcpyHostToDevice, s));
         return p;
     }
-    void apply_K(const double *x, double *y) { apply_operator(c, masked, x, y, nullptr); }
-    void apply_M(const double *x, double *y) {
+    // The pencil (A, B) the loop works on. Vibration: A = K, B = density M. Buckling: A = Kg (indefinite), B = K. In the loop the blocks named K*
+    // hold the A-images and the blocks named M* the B-images; B carries the inner product, and the preconditioner approximates K^-1 in both.
+    void apply_A(const double *x, double *y) {
+        if (buckling) k::launch_spmv(geom_spmv_args(c, masked), x, y, nullptr, s);
+        else apply_operator(c, masked, x, y, nullptr);
+    }
+    void apply_B(const double *x, double *y) {
+        if (buckling) { apply_operator(c, masked, x, y, nullptr); return; }
         k::launch_spmv(mass_spmv_args(c, masked), x, y, nullptr, s);
         if (density != 1.0) k::launch_axpby(n, 0.0, y, density, y, s);      // the buffer holds density 1
     }
+    void need(bool cond, mfh_status code, const char *what) const { if (!cond) throw fail(code, what); }
+    Error fail(mfh_status code, const char *what) const { return Error(code, std::string(who) + ": " + what); }
     void precond(const double *r, double *z) {
         if (useMG) mg_precond(c, r, z, nullptr, -1, nullptr);
         else if (useTL) tl_precond(c, r, z, nullptr, -1);
@@ -595,66 +619,25 @@ mfh_status mfh_debug_block_update(mfh_ctx *c, int64_t n, int32_t p, int32_t q, c
     MFH_CATCH(c)
 }
 
-mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, double rtol, int32_t maxit, double *lambda, double *Xout, double *residuals,
-                     mfh_modes_info *info) {
-    if (info) { *info = mfh_modes_info{}; info->note = ""; }
-    MFH_TRY(c)
-    require(c && nev >= 1 && nev <= 20 && density > 0.0 && std::isfinite(density) && lambda && Xout && rtol > 0.0 && maxit > 0 && (flags & ~MFH_MODES_FREE) == 0,
-            MFH_ERR_INVALID, "mfh_modes: 1 <= nev <= 20, density > 0, rtol > 0, maxit > 0, lambda and X not null");
-    require(c->haveMesh && !c->external, MFH_ERR_STATE, "mfh_modes: no mesh set");
-    require_device(c);
-    MFH_HIP(hipSetDevice(c->device));
-    const bool freeBody = (flags & MFH_MODES_FREE) != 0;
-    require(c->op == MFH_OP_ELASTICITY && c->opDegree != 1, MFH_ERR_UNSUPPORTED, "mfh_modes: the pencil is (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
-    require(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
-    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "mfh_modes: 2D / 3D meshes");
-    if (freeBody) require(c->fixedVars.empty() && c->dofForNode.empty(), MFH_ERR_UNSUPPORTED, "mfh_modes: the free-free case takes no fixed variables and the identity DoF map");
-    else {
-        const int q = free_rigid_motions(c);
-        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables, or ask for MFH_MODES_FREE)");
-    }
-    hipStream_t s = c->stream;
-    c->modesNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
-    // the storage of the pattern for the duration of the call (see mfh_ctx::modesWide); the guard also restores the solver's singular-system switch
-    struct Guard {
-        mfh_ctx *c;
-        ~Guard() {
-            c->tlSuppress = false;
-            if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
-        }
-    } guard{c};
-    if (resolve_upper_storage(c)) {
-        c->modesWide = true;
-        note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
-    }
-    EventTimer tsetup(s);
-    // ---- preconditioner: what the next solve of this kind would use
-    c->tlSuppress = freeBody;
-    ensure_precond(c);
-    if (freeBody) {
-        c->precondNote.clear();
-        if (c->precond == MFH_PRECOND_MULTIGRID && ensure_multigrid(c)) note("multigrid preconditioner on the singular K of the free body: dense level pinned");
-        else if (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) note("two-level / multigrid preconditioner unavailable on the singular K of the free body: using block-Jacobi");
-    } else
-        ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes");
+}   // extern "C"
 
-    ModesWork w;
-    w.c = c; w.s = s; w.d = c->bs();
-    w.n = (int64_t)w.d * c->nDoF; w.ld = (w.n + 31) / 32 * 32;
-    w.density = density;
-    w.masked = !c->fixedVars.empty();
-    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
-    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
-    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
-    if (!freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+namespace {
+
+struct LoopOut {
+    int iterations = 0, restarts = 0, locked = 0, blockSize = 0;
+    bool done = false;
+    double maxResidual = 0, setupMs = 0, solveMs = 0;
+};
+
+// The block LOBPCG loop on the pencil (A, B) of w (ModesWork::apply_A / apply_B): the nev smallest eigenpairs of A x = lambda B x, B-orthonormal
+// columns with the sign rule, the relative residuals ||A x - lambda B x|| / (|lambda| ||B x||). The caller has prepared the context (the operators'
+// buffers, the preconditioner) and the fields of w up to useTL; tsetup is its running set-up timer. Shared by mfh_modes and mfh_buckling.
+void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, EventTimer &tsetup, double *lambda, double *Xout, double *residuals, LoopOut &o) {
+    mfh_ctx *c = w.c;
+    hipStream_t s = w.s;
     w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
     const int64_t nEff = w.n - (int64_t)c->fixedVars.size() - w.nz;        // dimension of the space the iteration lives in
-    require(nev <= nEff, MFH_ERR_INVALID, "mfh_modes: more modes asked for than the pencil has");
+    w.need(nev <= nEff, MFH_ERR_INVALID, "more modes asked for than the pencil has");
     const int m = (int)std::min<int64_t>(std::min(nev + std::max(2, (nev + 3) / 4), BLK_MAXC), nEff);
     w.m = m;
     const size_t L = (size_t)w.ld;
@@ -699,8 +682,8 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
         }
         MFH_HIP(hipMemcpyAsync(w.Z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, s));
         MFH_HIP(hipStreamSynchronize(s));
-        for (int j = 0; j < nz; ++j) w.apply_M(w.col(w.Z, j), w.col(w.MZ, j));
-        if (!chol_qr_block(w, w.Z, nullptr, w.MZ, zall)) throw Error(MFH_ERR_STATE, "mfh_modes: the rigid-body modes of the mesh are linearly dependent");
+        for (int j = 0; j < nz; ++j) w.apply_B(w.col(w.Z, j), w.col(w.MZ, j));
+        if (!chol_qr_block(w, w.Z, nullptr, w.MZ, zall)) throw w.fail(MFH_ERR_STATE, "the rigid-body modes of the mesh are linearly dependent");
         // (KZ stays zero: K Z = 0 up to rounding, and the updates below want a K-image of every input block)
     }
     // W -= Z (MZ^T W) on the listed columns of a block (and of its M-image if given)
@@ -734,9 +717,9 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
         w.precond(w.col(w.W, j), w.col(w.X, j));
     }
     project_out_Z(w.X, nullptr, all);
-    for (int j = 0; j < m; ++j) w.apply_M(w.col(w.X, j), w.col(w.MX, j));
-    if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw Error(MFH_ERR_STATE, "mfh_modes: the start block is rank deficient");
-    for (int j = 0; j < m; ++j) { w.apply_K(w.col(w.X, j), w.col(w.KX, j)); w.apply_M(w.col(w.X, j), w.col(w.MX, j)); }
+    for (int j = 0; j < m; ++j) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
+    if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw w.fail(MFH_ERR_STATE, "the start block is rank deficient");
+    for (int j = 0; j < m; ++j) { w.apply_A(w.col(w.X, j), w.col(w.KX, j)); w.apply_B(w.col(w.X, j), w.col(w.MX, j)); }
     std::vector<double> lam((size_t)m, 0.0);
     {
         double *GK = w.gram(w.ref(w.X, all), w.ref(w.KX, all));
@@ -745,7 +728,7 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
         MFH_HIP(hipMemcpyAsync(hK.data(), GK, hK.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         MFH_HIP(hipMemcpyAsync(hM.data(), GM, hM.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         w.sync();
-        if (!sym_gen_eig(m, hK.data(), hM.data(), ev.data(), V.data())) throw Error(MFH_ERR_STATE, "mfh_modes: the start block lost its M-orthonormality");
+        if (!sym_gen_eig(m, hK.data(), hM.data(), ev.data(), V.data())) throw w.fail(MFH_ERR_STATE, "the start block lost its M-orthonormality");
         UpdCall u;
         u.inputs(0, all); u.outputs(0, all);
         u.finish();
@@ -783,7 +766,7 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
             for (int j = 0; j < m; ++j) {
                 const double den = std::fabs(lam[(size_t)j]) * std::sqrt(hn[2 * j + 1]);
                 res[(size_t)j] = den > 0 ? std::sqrt(hn[2 * j]) / den : (hn[2 * j] == 0.0 ? 0.0 : 1e300);
-                if (!std::isfinite(res[(size_t)j])) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (a residual is not finite)");
+                if (!std::isfinite(res[(size_t)j])) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (a residual is not finite)");
                 conv[(size_t)j] = res[(size_t)j] <= rtol;
             }
         }
@@ -797,16 +780,16 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
         for (int j : act) w.precond(w.col(w.R, j), w.col(w.W, j));
         w.lap(2);
         project_out_Z(w.W, nullptr, act);
-        for (int j : act) w.apply_K(w.col(w.W, j), w.col(w.KW, j));
+        for (int j : act) w.apply_A(w.col(w.W, j), w.col(w.KW, j));
         w.lap(0);
-        for (int j : act) w.apply_M(w.col(w.W, j), w.col(w.MW, j));
+        for (int j : act) w.apply_B(w.col(w.W, j), w.col(w.MW, j));
         w.lap(1);
         std::vector<int> pact = haveP ? act : std::vector<int>();
         // Cholesky-QR of the basis S = [X W P], twice: Gram-Schmidt in that order, so W leaves M-orthogonal to X
         std::vector<int> wact = act;
         for (int pass = 0; pass < 2; ++pass) {
             for (int attempt = 0;; ++attempt) {
-                require(attempt < 2 * BLK_MAXC + 2, MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (the basis cannot be orthonormalised)");
+                w.need(attempt < 2 * BLK_MAXC + 2, MFH_ERR_NOT_CONVERGED, "breakdown (the basis cannot be orthonormalised)");
                 const int nx = m, nw = (int)wact.size(), np = (int)pact.size(), kb = nx + nw + np;
                 const double *blk[3] = {w.X, w.W, w.P}, *mblk[3] = {w.MX, w.MW, w.MP};
                 const std::vector<int> *cl[3] = {&all, &wact, &pact};
@@ -843,7 +826,7 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
                 if (bad >= 0) {
                     if (bad >= off[2]) { pact.clear(); haveP = false; ++restarts; continue; }       // restart: P leaves the basis for this iteration
                     if (bad >= off[1]) { wact.erase(wact.begin() + (bad - off[1])); if (!pact.empty()) { pact.clear(); haveP = false; ++restarts; } continue; }
-                    throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (the Ritz block lost its rank)");
+                    throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the Ritz block lost its rank)");
                 }
                 // S <- S U, images alike: first W and P (they read the old X), then X
                 const double *kblk[3] = {w.KX, w.KW, w.KP};
@@ -945,7 +928,11 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
     // ---- the returned columns: one final M-orthonormalisation, sign rule, download
     std::vector<int> ret;
     for (int j = 0; j < nev; ++j) ret.push_back(j);
-    if (!chol_qr_block(w, w.X, nullptr, w.MX, ret)) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modes: breakdown (the returned modes lost their rank)");
+    // B = K is ill-conditioned where the mass matrix is not: the B-images carried through hundreds of block updates have drifted from K X by far
+    // more than M X ever does (X K X^T - I of 3e-12 after 200 block-Jacobi iterations at cond 7e4), so the buckling pencil takes them afresh
+    if (w.buckling)
+        for (int j : ret) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
+    if (!chol_qr_block(w, w.X, nullptr, w.MX, ret)) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the returned modes lost their rank)");
     MFH_HIP(hipMemcpy2DAsync(Xout, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nev, hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
     const double solveMs = tsolve.stop();
@@ -962,25 +949,277 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
         if (residuals) residuals[j] = res[(size_t)j];
     }
     if (w.timing)
-        fprintf(stderr, "[mfh_modes] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f\n",
-                (long long)w.n, m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6]);
+        fprintf(stderr, "[%s] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f\n",
+                w.who, (long long)w.n, m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6]);
+    int locked = 0;
+    double mr = 0;
+    for (int j = 0; j < m; ++j) locked += conv[(size_t)j] ? 1 : 0;
+    for (int j = 0; j < nev; ++j) mr = std::max(mr, res[(size_t)j]);
+    o.iterations = it; o.restarts = restarts; o.locked = locked; o.blockSize = m; o.done = done; o.maxResidual = mr; o.setupMs = setupMs; o.solveMs = solveMs;
+}
+
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, double rtol, int32_t maxit, double *lambda, double *Xout, double *residuals,
+                     mfh_modes_info *info) {
+    if (info) { *info = mfh_modes_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c && nev >= 1 && nev <= 20 && density > 0.0 && std::isfinite(density) && lambda && Xout && rtol > 0.0 && maxit > 0 && (flags & ~MFH_MODES_FREE) == 0,
+            MFH_ERR_INVALID, "mfh_modes: 1 <= nev <= 20, density > 0, rtol > 0, maxit > 0, lambda and X not null");
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "mfh_modes: no mesh set");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    const bool freeBody = (flags & MFH_MODES_FREE) != 0;
+    require(c->op == MFH_OP_ELASTICITY && c->opDegree != 1, MFH_ERR_UNSUPPORTED, "mfh_modes: the pencil is (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
+    require(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
+    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "mfh_modes: 2D / 3D meshes");
+    if (freeBody) require(c->fixedVars.empty() && c->dofForNode.empty(), MFH_ERR_UNSUPPORTED, "mfh_modes: the free-free case takes no fixed variables and the identity DoF map");
+    else {
+        const int q = free_rigid_motions(c);
+        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables, or ask for MFH_MODES_FREE)");
+    }
+    hipStream_t s = c->stream;
+    c->modesNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
+    // the storage of the pattern for the duration of the call (see mfh_ctx::modesWide); the guard also restores the solver's singular-system switch
+    struct Guard {
+        mfh_ctx *c;
+        ~Guard() {
+            c->tlSuppress = false;
+            if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
+        }
+    } guard{c};
+    if (resolve_upper_storage(c)) {
+        c->modesWide = true;
+        note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    }
+    EventTimer tsetup(s);
+    // ---- preconditioner: what the next solve of this kind would use
+    c->tlSuppress = freeBody;
+    ensure_precond(c);
+    if (freeBody) {
+        c->precondNote.clear();
+        if (c->precond == MFH_PRECOND_MULTIGRID && ensure_multigrid(c)) note("multigrid preconditioner on the singular K of the free body: dense level pinned");
+        else if (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) note("two-level / multigrid preconditioner unavailable on the singular K of the free body: using block-Jacobi");
+    } else
+        ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes");
+
+    ModesWork w;
+    w.c = c; w.s = s; w.d = c->bs();
+    w.n = (int64_t)w.d * c->nDoF; w.ld = (w.n + 31) / 32 * 32;
+    w.density = density;
+    w.masked = !c->fixedVars.empty();
+    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
+    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
+    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
+    if (!freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    LoopOut lo;
+    lobpcg_run(w, nev, freeBody, rtol, maxit, tsetup, lambda, Xout, residuals, lo);
     if (info) {
-        info->converged = done ? 1 : 0;
-        info->iterations = it;
-        int locked = 0;
-        double mr = 0;
-        for (int j = 0; j < m; ++j) locked += conv[(size_t)j] ? 1 : 0;
-        for (int j = 0; j < nev; ++j) mr = std::max(mr, res[(size_t)j]);
-        info->nLocked = locked;
+        info->converged = lo.done ? 1 : 0;
+        info->iterations = lo.iterations;
+        info->nLocked = lo.locked;
         info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
-        info->blockSize = m;
-        info->restarts = restarts;
-        info->maxResidual = mr;
-        info->solve_ms = solveMs;
-        info->setup_ms = setupMs;
+        info->blockSize = lo.blockSize;
+        info->restarts = lo.restarts;
+        info->maxResidual = lo.maxResidual;
+        info->solve_ms = lo.solveMs;
+        info->setup_ms = lo.setupMs;
         info->note = c->modesNote.c_str();
     }
-    if (!done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    MFH_CATCH(c)
+}
+
+}   // extern "C"
+
+// ---------------------------------------------------------------- linear buckling (docs/design/04_16_buckling.md)
+namespace {
+// the contexts a prestress field is defined on: those of mfh_set_density
+void require_prestress_context(mfh_ctx *c, const char *who) {
+    if (!c) throw Error(MFH_ERR_INVALID, std::string(who) + ": null context");
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the prestress field needs a mesh on a device");
+    if (!(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF)) throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": unpartitioned contexts only");
+    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "2D / 3D meshes");
+}
+// ... and those Kg is defined on: the elasticity operator on the mesh's own degree (the conditions of mfh_modes)
+void require_geometric_context(mfh_ctx *c, const char *who) {
+    require_prestress_context(c, who);
+    if (!(c->op == MFH_OP_ELASTICITY && c->opDegree != 1))
+        throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": the pencil is (geometric stiffness, elasticity) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
+    if (!c->havePrestress) throw Error(MFH_ERR_STATE, std::string(who) + ": no prestress field set (mfh_set_prestress / mfh_prestress_from_displacement)");
+}
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_set_prestress(mfh_ctx *c, const double *sigma, int64_t n, int32_t flags) {
+    MFH_TRY(c)
+    require_prestress_context(c, "mfh_set_prestress");
+    require((flags & ~MFH_LOAD_ON_DEVICE) == 0, MFH_ERR_INVALID, "flags: 0 | MFH_LOAD_ON_DEVICE");
+    if (!sigma) {
+        if (c->havePrestress) clear_prestress(c);
+        return MFH_OK;
+    }
+    const int64_t nElem = c->mesh.nElem, fl = flat_len(c->mesh.dim), count = nElem * fl;
+    require(n == nElem, MFH_ERR_INVALID, "mfh_set_prestress: one symmetric tensor (flatLen values) per element");
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    MFH_HIP(hipSetDevice(c->device));
+    bool bad = false;
+    if (!onDevice) {
+        for (int64_t q = 0; q < count && !bad; ++q) bad = !std::isfinite(sigma[q]);
+    } else {
+        DBuf<int> flag;
+        flag.alloc(1);
+        flag.zero(c->stream);
+        k::launch_prestress_finite(count, sigma, flag.p, c->stream);
+        int h = 0;
+        flag.download(&h, 1, c->stream);
+        bad = h != 0;
+    }
+    require(!bad, MFH_ERR_INVALID, "mfh_set_prestress: an entry is not finite");
+    // a buffer of its own every time: the field in force stays untouched until the new one is complete
+    DBuf<double> fresh;
+    fresh.alloc((size_t)count);
+    MFH_HIP(hipMemcpyAsync(fresh.p, sigma, (size_t)count * sizeof(double), onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    MFH_HIP(hipStreamSynchronize(c->stream));
+    c->dPrestress.swap(fresh);
+    c->havePrestress = true;
+    ++c->prestressGen;
+    MFH_CATCH(c)
+}
+
+// sigma_e = C_e : (element-average strain of u), written by k_average_strain into a fresh buffer of the context
+mfh_status mfh_prestress_from_displacement(mfh_ctx *c, const double *uNodes, int32_t flags) {
+    MFH_TRY(c)
+    require_prestress_context(c, "mfh_prestress_from_displacement");
+    require(uNodes != nullptr, MFH_ERR_INVALID, "mfh_prestress_from_displacement: null displacement");
+    require((flags & ~MFH_LOAD_ON_DEVICE) == 0, MFH_ERR_INVALID, "flags: 0 | MFH_LOAD_ON_DEVICE");
+    require(c->op == MFH_OP_ELASTICITY && c->opDegree != 1, MFH_ERR_UNSUPPORTED, "mfh_prestress_from_displacement: the stress field is defined for the elasticity operator on the mesh's own degree");
+    MFH_HIP(hipSetDevice(c->device));
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    const HostMesh &m = c->mesh;
+    const int d = m.dim, fl = flat_len(d);
+    const size_t nu = (size_t)m.nNode * d;
+    if (!onDevice)
+        for (size_t q = 0; q < nu; ++q) require(std::isfinite(uNodes[q]), MFH_ERR_INVALID, "mfh_prestress_from_displacement: an entry is not finite");
+    ensure_geometry(c);
+    DBuf<double> du, fresh;
+    DBuf<int> flag;
+    const double *u = uNodes;
+    if (!onDevice) {
+        du.alloc(nu);
+        MFH_HIP(hipMemcpyAsync(du.p, uNodes, nu * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        u = du.p;
+    }
+    fresh.alloc((size_t)m.nElem * fl);
+    k::launch_average_strain(asm_args(c), c->dElemNodes.p, c->tables.intGrad.data(), u, fresh.p, 1, nullptr, nullptr, c->stream);
+    flag.alloc(1);
+    flag.zero(c->stream);
+    k::launch_prestress_finite((int64_t)m.nElem * fl, fresh.p, flag.p, c->stream);
+    int h = 0;
+    flag.download(&h, 1, c->stream);
+    require(h == 0, MFH_ERR_INVALID, "mfh_prestress_from_displacement: the stress of this displacement is not finite");
+    c->dPrestress.swap(fresh);
+    c->havePrestress = true;
+    ++c->prestressGen;
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_buckling(mfh_ctx *c, int32_t nev, int32_t flags, double rtol, int32_t maxit, double *factors, double *Xout, double *residuals,
+                        mfh_buckling_info *info) {
+    if (info) { *info = mfh_buckling_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c && nev >= 1 && nev <= 20 && factors && Xout && rtol > 0.0 && maxit > 0 && flags == 0, MFH_ERR_INVALID,
+            "mfh_buckling: 1 <= nev <= 20, flags 0, rtol > 0, maxit > 0, factors and X not null");
+    require_geometric_context(c, "mfh_buckling");
+    MFH_HIP(hipSetDevice(c->device));
+    {
+        const int q = free_rigid_motions(c);
+        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: K is singular there and the pencil (Kg, K) undefined (fix more variables)");
+    }
+    const int64_t nAll = (int64_t)c->bs() * c->nDoF;
+    require(nev <= nAll - (int64_t)c->fixedVars.size(), MFH_ERR_INVALID, "mfh_buckling: more modes asked for than the pencil has");
+    hipStream_t s = c->stream;
+    c->modesNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
+    WideGuard guard(c);
+    if (guard.widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    EventTimer tsetup(s);
+    // ---- the preconditioner of K (what the next solve would use): here it approximates B^-1
+    ensure_precond(c);
+    ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_buckling: unpartitioned contexts only");
+    ensure_geometric(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_buckling");
+
+    ModesWork w;
+    w.c = c; w.s = s; w.d = c->bs();
+    w.n = nAll; w.ld = (w.n + 31) / 32 * 32;
+    w.buckling = true;
+    w.who = "mfh_buckling";
+    w.masked = !c->fixedVars.empty();
+    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
+    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
+    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid;
+    if (!w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    std::vector<double> mu((size_t)nev, 0.0);
+    LoopOut lo;
+    lobpcg_run(w, nev, false, rtol, maxit, tsetup, mu.data(), Xout, residuals, lo);
+    // mu ascending; a load factor exists where mu is negative beyond rounding
+    double muMax = 0.0;
+    for (int j = 0; j < nev; ++j) muMax = std::max(muMax, std::fabs(mu[(size_t)j]));
+    int nNeg = 0;
+    for (int j = 0; j < nev; ++j) {
+        if (mu[(size_t)j] >= -1e-12 * muMax) factors[j] = INFINITY;
+        else { factors[j] = -1.0 / mu[(size_t)j]; ++nNeg; }
+    }
+    if (info) {
+        info->converged = lo.done ? 1 : 0;
+        info->iterations = lo.iterations;
+        info->nLocked = lo.locked;
+        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
+        info->blockSize = lo.blockSize;
+        info->restarts = lo.restarts;
+        info->nBuckling = nNeg;
+        info->maxResidual = lo.maxResidual;
+        info->solve_ms = lo.solveMs;
+        info->setup_ms = lo.setupMs;
+        info->note = c->modesNote.c_str();
+    }
+    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    MFH_CATCH(c)
+}
+
+// measurement (meshfem_hip_extras.h): the gather assembly pass into the resident one-double-per-block buffer as the Laplacian (MAT_LAPLACE), the
+// unit-density mass (MAT_MASS) and the geometric stiffness of the prestress in force (MAT_GEOM) in the context's own flavour, and MAT_GEOM in the
+// turn-taking flavour that ensure_geometric launches, in turns
+mfh_status mfh_time_geometric_assembly(mfh_ctx *c, int32_t reps, double *laplace_ms, double *mass_ms, double *geom_ms, double *geom_det_ms) {
+    MFH_TRY(c)
+    require(c && laplace_ms && mass_ms && geom_ms && geom_det_ms && reps > 0, MFH_ERR_INVALID, "bad arguments");
+    require_geometric_context(c, "mfh_time_geometric_assembly");
+    MFH_HIP(hipSetDevice(c->device));
+    ensure_geometric(c);                         // geometry, pattern (both triangles: option matrix_storage 0), the buffer
+    k::AsmArgs a = asm_args(c);
+    a.vals = c->dGeomVals.p;
+    const int det = a.det;
+    for (int r = 0; r < reps; ++r) {
+        a.mat = MAT_LAPLACE; a.sigma = nullptr; a.det = det;
+        { EventTimer t(c->stream); k::launch_assemble_gather(a, c->stream); laplace_ms[r] = t.stop(); }
+        a.mat = MAT_MASS;
+        { EventTimer t(c->stream); k::launch_assemble_gather(a, c->stream); mass_ms[r] = t.stop(); }
+        a.mat = MAT_GEOM; a.sigma = c->dPrestress.p;
+        { EventTimer t(c->stream); k::launch_assemble_gather(a, c->stream); geom_ms[r] = t.stop(); }
+        a.det = 1;                               // (last: the buffer is left as ensure_geometric would leave it)
+        { EventTimer t(c->stream); k::launch_assemble_gather(a, c->stream); geom_det_ms[r] = t.stop(); }
+    }
     MFH_CATCH(c)
 }
 

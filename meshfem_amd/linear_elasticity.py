@@ -247,6 +247,40 @@ class Simulator:
             X = X[:, dof, :]
         return np.sqrt(lam) / (2.0 * np.pi), X
 
+    # ---- linear buckling (docs/design/04_16_buckling.md)
+    def setPrestress(self, stress):
+        """The per-element prestress [nElem, flatLen] (tensor shear entries, the layout of averageStressField) of applyGeometricStiffness and
+        buckling (None: no field). It survives vertex updates; a new mesh clears it."""
+        self.ctx.set_prestress(stress)
+
+    def applyGeometricStiffness(self, x_dofs):
+        """Kg x on a per-DoF displacement vector [nDoF, N]: the geometric stiffness of the prestress field."""
+        return self.ctx.geometric_apply(np.asarray(x_dofs, dtype=np.float64).reshape(self.ctx.n_dof, self.N))
+
+    def buckling(self, nev, load=None, rtol=1e-6, maxit=500):
+        """(factors, modes, u): solves the static problem under the current boundary conditions (load: a per-DoF vector such as bodyForceLoad's,
+        None = neumannLoad()), makes the element-average stress of its displacement u the prestress on the device, and returns the nev smallest
+        multiples of the load at which the clamped body buckles (mfh_buckling; +inf where it does not), the buckling shapes as nodal fields
+        [nev, nNode, N] and u [nNode, N]. The Dirichlet variables of the applied conditions are the clamp, as in vibrational_modes.
+        self.buckling_info holds the solver's record."""
+        ctx = self.ctx
+        u = self.solve(None if load is None else np.asarray(load, dtype=np.float64).reshape(ctx.n_dof, self.N))
+        ctx.prestress_from_displacement(u)
+        v, _ = ctx.bc_dirichlet_vars()
+        ctx.clear_fixed()
+        if len(v):
+            ctx.fix_variables(v)
+        try:
+            fac, X, info = ctx.buckling(nev, rtol=rtol, maxit=maxit)
+        finally:
+            last = getattr(ctx, "last_buckling", None)
+            self.buckling_info = last[2] if last else None
+        X = X.reshape(len(fac), ctx.n_dof, self.N)
+        if ctx.n_dof != ctx.n_node:                         # a DoF map (periodic conditions): every node takes its DoF's value
+            dof, _ = ctx.get_dof_map()
+            X = X[:, dof, :]
+        return fac, X, u
+
     def transient(self, dt, n_steps, amplitude=None, u0=None, v0=None, density=1.0, damping=(0, 0), beta=0.25, gamma=0.5, probes=None,
                   snapshot_stride=0, a0=None, energies=False, rtol=None, maxit=None, load=None):
         """The response to the load history amplitude[n] x f, f = neumannLoad() or the per-DoF vector `load` (a volume load, a sum of loads), by implicit Newmark time stepping on the device (mfh_newmark):
