@@ -18,6 +18,7 @@
 // the history -- {r.z, p.Ap, r.r, -} per iteration -- and of the control block is theirs, so that mg_precond's kernels take the same gate).
 #include "mfh_ctx.hh"
 #include "mfh_device.hh"
+#include "mfh_dispatch.hh"
 
 namespace mfh { namespace k {
 
@@ -366,21 +367,16 @@ int launch_spmv_kron_acc(const SpmvArgs &a, bool acc, double cK, double cM, cons
     if (a.dim != 2 && a.dim != 3) throw mfh::Error(MFH_ERR_UNSUPPORTED, "k_spmv_kron_acc: 2D / 3D only");
     const size_t lds = ((size_t)a.dim * a.chunkSlots + 16) * sizeof(double);
     const int grid = (int)std::min<int64_t>(a.nChunk, std::max(1, std::min(cap, DYN_GRID_CAP)));
-    if (a.dim == 3) {
-        if (acc) hipLaunchKernelGGL((k_spmv_kron_acc<3, true>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
-        else hipLaunchKernelGGL((k_spmv_kron_acc<3, false>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
-    } else {
-        if (acc) hipLaunchKernelGGL((k_spmv_kron_acc<2, true>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
-        else hipLaunchKernelGGL((k_spmv_kron_acc<2, false>), dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
-    }
+    with_dim(a.dim, [&](auto D) { with_bool(acc, [&](auto ACC) {
+        launch_k(k_spmv_kron_acc<D(), ACC()>, dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
+    }); });
     CHECK_LAUNCH();
     return grid;
 }
 
 void launch_pencil_dinv(int dim, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *kVals, const double *mVals, double cK, double cM,
                         const uint8_t *mask, double *dinv, hipStream_t s) {
-    if (dim == 3) hipLaunchKernelGGL(k_pencil_dinv<3>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, rowPtr, colIdx, kVals, mVals, cK, cM, mask, dinv);
-    else hipLaunchKernelGGL(k_pencil_dinv<2>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, rowPtr, colIdx, kVals, mVals, cK, cM, mask, dinv);
+    with_dim(dim, [&](auto D) { launch_k(k_pencil_dinv<D()>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, rowPtr, colIdx, kVals, mVals, cK, cM, mask, dinv); });
     CHECK_LAUNCH();
 }
 
@@ -465,8 +461,9 @@ struct NewmarkWork {
     int vec_grid(int64_t count) const { return k::dyn_grid(count, std::max(1, std::min(c->dynGridCap, k::DYN_GRID_CAP))); }
     template <bool BJ> void launch_init() {
         const int grid = vec_grid(nRows);
-        if (d == 3) hipLaunchKernelGGL((k::k_dyn_init<3, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)b, (const double *)Ap, (const double *)bb, x, r, z, p, partials.p);
-        else hipLaunchKernelGGL((k::k_dyn_init<2, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)b, (const double *)Ap, (const double *)bb, x, r, z, p, partials.p);
+        k::with_dim(d, [&](auto D) {
+            k::launch_k(k::k_dyn_init<D(), BJ>, dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)b, (const double *)Ap, (const double *)bb, x, r, z, p, partials.p);
+        });
         CHECK_LAUNCH();
         const int col[2] = {0, 1};
         const double sc[2] = {1.0, 1.0};
@@ -476,8 +473,9 @@ struct NewmarkWork {
     template <bool BJ> void launch_update(int it) {
         const int grid = vec_grid(nRows);
         const DynGate g = gate(it);
-        if (d == 3) hipLaunchKernelGGL((k::k_dyn_update<3, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)Ap, (const double *)p, x, r, z, g, partials.p);
-        else hipLaunchKernelGGL((k::k_dyn_update<2, BJ>), dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)Ap, (const double *)p, x, r, z, g, partials.p);
+        k::with_dim(d, [&](auto D) {
+            k::launch_k(k::k_dyn_update<D(), BJ>, dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)Ap, (const double *)p, x, r, z, g, partials.p);
+        });
         CHECK_LAUNCH();
         const int col[2] = {0, 1};
         const double sc[2] = {1.0, 1.0};

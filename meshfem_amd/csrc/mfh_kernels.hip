@@ -9,6 +9,7 @@
 // own consecutive slots therefore read/write 512 contiguous bytes per component: every wave-wide
 // load/store of K is a fully coalesced 8 B/lane access on both the assembly and the SpMV side.
 #include "mfh_device.hh"
+#include "mfh_dispatch.hh"
 
 namespace mfh { namespace k {
 
@@ -2554,73 +2555,16 @@ __global__ void __launch_bounds__(256) k_flag_halo_chunks(int64_t nChunk, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers
+// launchers (the instantiation tables: mfh_dispatch.hh)
 // ------------------------------------------------------------------------------------------------
 
 void launch_geometry(int dim, int /*deg*/, int /*mat*/, int64_t nElem, const int32_t *elemNodes, int npe, const double *vertPos,
                      const double *matParams, int matMode, double *geo, int geoStride, int *negCount, hipStream_t s) {
     const int grid = (int)((nElem + 255) / 256);
     const size_t lds = (size_t)256 * (geoStride + 1) * sizeof(double);
-    if (lds > 64 * 1024) {
-        MFH_HIP(hipFuncSetAttribute((const void *)k_geometry<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MFH_HIP(hipFuncSetAttribute((const void *)k_geometry<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    if (dim == 3) hipLaunchKernelGGL(k_geometry<3>, dim3(grid), dim3(256), lds, s, nElem, elemNodes, npe, vertPos, matParams, matMode, geo, geoStride, negCount);
-    else hipLaunchKernelGGL(k_geometry<2>, dim3(grid), dim3(256), lds, s, nElem, elemNodes, npe, vertPos, matParams, matMode, geo, geoStride, negCount);
+    with_dim(dim, [&](auto D) { launch_k(k_geometry<D()>, dim3(grid), dim3(256), lds, s, nElem, elemNodes, npe, vertPos, matParams, matMode, geo, geoStride, negCount); });
     CHECK_LAUNCH();
 }
-
-// dispatch on (dim, deg, mat)
-#define MFH_DISPATCH(a, CALL)                                                            \
-    do {                                                                                 \
-        const int key_ = (a.dim == 3 ? 0 : 6) + (a.deg == 2 ? 3 : 0) + (a.mat == MAT_GENERAL ? 1 : (a.mat == MAT_ORTHO ? 2 : 0)); \
-        switch (key_) {                                                                  \
-        case 0: { CALL(3, 1, MAT_ISO); } break;                                           \
-        case 1: { CALL(3, 1, MAT_GENERAL); } break;                                       \
-        case 2: { CALL(3, 1, MAT_ORTHO); } break;                                         \
-        case 3: { CALL(3, 2, MAT_ISO); } break;                                           \
-        case 4: { CALL(3, 2, MAT_GENERAL); } break;                                       \
-        case 5: { CALL(3, 2, MAT_ORTHO); } break;                                         \
-        case 6: { CALL(2, 1, MAT_ISO); } break;                                           \
-        case 7: { CALL(2, 1, MAT_GENERAL); } break;                                       \
-        case 8: { CALL(2, 1, MAT_ORTHO); } break;                                         \
-        case 9: { CALL(2, 2, MAT_ISO); } break;                                           \
-        case 10: { CALL(2, 2, MAT_GENERAL); } break;                                      \
-        default: { CALL(2, 2, MAT_ORTHO); } break;                                        \
-        }                                                                                \
-    } while (0)
-
-// assembly kernels also come in the scalar-operator flavours
-#define MFH_DISPATCH_ASM(a, CALL)                                                        \
-    do {                                                                                 \
-        if (!mat_is_scalar(a.mat)) { MFH_DISPATCH(a, CALL); break; }                     \
-        const int key_ = (a.dim == 3 ? 0 : 4) + (a.deg == 2 ? 2 : 0) + (a.mat == MAT_MASS ? 1 : 0); \
-        switch (key_) {                                                                  \
-        case 0: { CALL(3, 1, MAT_LAPLACE); } break;                                       \
-        case 1: { CALL(3, 1, MAT_MASS); } break;                                          \
-        case 2: { CALL(3, 2, MAT_LAPLACE); } break;                                       \
-        case 3: { CALL(3, 2, MAT_MASS); } break;                                          \
-        case 4: { CALL(2, 1, MAT_LAPLACE); } break;                                       \
-        case 5: { CALL(2, 1, MAT_MASS); } break;                                          \
-        case 6: { CALL(2, 2, MAT_LAPLACE); } break;                                       \
-        default: { CALL(2, 2, MAT_MASS); } break;                                         \
-        }                                                                                \
-    } while (0)
-
-// the density-weighted mass flavour exists for the gather assembly only (ensure_mass with a density field set): the atomic variant and the
-// dense element matrices never see it
-#define MFH_DISPATCH_MASS_RHO(a, CALL)                                                   \
-    do {                                                                                 \
-        if (a.dim == 3) { if (a.deg == 2) { CALL(3, 2, MAT_MASS_RHO); } else { CALL(3, 1, MAT_MASS_RHO); } } \
-        else { if (a.deg == 2) { CALL(2, 2, MAT_MASS_RHO); } else { CALL(2, 1, MAT_MASS_RHO); } }           \
-    } while (0)
-
-// the geometric-stiffness flavour (H : sigma_e, ensure_geometric): like the density-weighted mass, the gather assembly only
-#define MFH_DISPATCH_GEOM(a, CALL)                                                       \
-    do {                                                                                 \
-        if (a.dim == 3) { if (a.deg == 2) { CALL(3, 2, MAT_GEOM); } else { CALL(3, 1, MAT_GEOM); } } \
-        else { if (a.deg == 2) { CALL(2, 2, MAT_GEOM); } else { CALL(2, 1, MAT_GEOM); } }           \
-    } while (0)
 
 void launch_assemble_gather(const AsmArgs &a, hipStream_t s) {
     if (a.nChunk == 0) return;
@@ -2630,21 +2574,14 @@ void launch_assemble_gather(const AsmArgs &a, hipStream_t s) {
     if (a.deg == 2 && a.mat != MAT_MASS && a.mat != MAT_MASS_RHO) lds += (size_t)a.npe * a.npe * (4 * sizeof(double) + sizeof(uint32_t));   // pair table
     // (the token of the deterministic flavour sits behind the pair-table region whether or not the flavour has a table)
     if (a.det) lds = (size_t)(mat_is_scalar(a.mat) ? 1 : a.dim * a.dim) * (a.chunkSlots + 2) * sizeof(double) + (size_t)a.npe * a.npe * (4 * sizeof(double) + sizeof(uint32_t)) + 16;
-#define CALLV(D, G, M, UP, DT)                                                                                 \
-    do {                                                                                                         \
-        if (lds > 64 * 1024)                                                                                     \
-            MFH_HIP(hipFuncSetAttribute((const void *)k_assemble_gather<D, G, M, UP, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_assemble_gather<D, G, M, UP, DT>), dim3((unsigned)a.nChunk), dim3(256), lds, s, a); \
-    } while (0)
-    // the deterministic flavour is an instantiation of its own (barriers inside the contribution loop): the default kernels keep the plain loop
-#define CALL(D, G, M)                                                     \
-    if (a.det) { if (a.upperOnly) CALLV(D, G, M, true, true); else CALLV(D, G, M, false, true); } \
-    else { if (a.upperOnly) CALLV(D, G, M, true, false); else CALLV(D, G, M, false, false); }
-    if (a.mat == MAT_MASS_RHO) MFH_DISPATCH_MASS_RHO(a, CALL);
-    else if (a.mat == MAT_GEOM) MFH_DISPATCH_GEOM(a, CALL);
-    else MFH_DISPATCH_ASM(a, CALL);
-#undef CALL
-#undef CALLV
+    // the density-weighted mass (ensure_mass with a density field set) and the geometric stiffness (H : sigma_e, ensure_geometric) exist for the
+    // gather assembly only: the atomic variant and the dense element matrices never see them.
+    // The deterministic flavour is an instantiation of its own (barriers inside the contribution loop): the default kernels keep the plain loop
+    with_elem_asm<MAT_MASS_RHO, MAT_GEOM>(a, [&](auto D, auto G, auto M) {
+        with_bool(a.upperOnly, [&](auto UP) { with_bool(a.det, [&](auto DT) {
+            launch_k(k_assemble_gather<D(), G(), M(), UP(), DT()>, dim3((unsigned)a.nChunk), dim3(256), lds, s, a);
+        }); });
+    });
     CHECK_LAUNCH();
 }
 
@@ -2672,17 +2609,13 @@ bool launch_pack_codes(int64_t nChunk, const int64_t *contribPtr, uint32_t *cont
 void launch_assemble_atomic(const AsmArgs &a, hipStream_t s) {
     const int64_t total = a.nElem * a.npe * a.npe;
     const int grid = grid_for(total, 256 * 32);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_assemble_atomic<D, G, M>), dim3(grid), dim3(256), 0, s, a)
-    MFH_DISPATCH_ASM(a, CALL);
-#undef CALL
+    with_elem_asm(a, [&](auto D, auto G, auto M) { launch_k(k_assemble_atomic<D(), G(), M()>, dim3(grid), dim3(256), 0, s, a); });
     CHECK_LAUNCH();
 }
 
 void launch_element_stiffness(const AsmArgs &a, int64_t first, int64_t count, double *KeOut, hipStream_t s) {
     const int grid = grid_for(count * a.npe * a.npe);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_element_stiffness<D, G, M>), dim3(grid), dim3(256), 0, s, a, first, count, KeOut)
-    MFH_DISPATCH_ASM(a, CALL);
-#undef CALL
+    with_elem_asm(a, [&](auto D, auto G, auto M) { launch_k(k_element_stiffness<D(), G(), M()>, dim3(grid), dim3(256), 0, s, a, first, count, KeOut); });
     CHECK_LAUNCH();
 }
 
@@ -2699,9 +2632,7 @@ void launch_constant_strain_load(const AsmArgs &a, const int32_t *elemNodes, con
                                  const double *cstrain, const double *deltaP, double *out, hipStream_t s) {
     const LoadArgs l = make_load_args(a, elemNodes, dofForNode, intGrad, cstrain);
     const int grid = grid_for(a.nElem * a.npe, 8192);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_constant_strain_load<D, G, M>), dim3(grid), dim3(256), 0, s, l, deltaP, out)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_constant_strain_load<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, deltaP, out); });
     CHECK_LAUNCH();
 }
 
@@ -2723,9 +2654,9 @@ void launch_average_strain(const AsmArgs &a, const int32_t *elemNodes, const dou
     const int grid = grid_for(a.nElem, integral ? 1024 : 8192);
     StrainShift add{};
     if (addStrain) { add.on = 1; for (int q = 0; q < a.dim * (a.dim + 1) / 2; ++q) add.v[q] = addStrain[q]; }
-#define CALL(D, G, M) hipLaunchKernelGGL((k_average_strain<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, out, wantStress, uFixed, deltaP, add, integral)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) {
+        launch_k(k_average_strain<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, uNodes, out, wantStress, uFixed, deltaP, add, integral);
+    });
     CHECK_LAUNCH();
 }
 
@@ -2733,9 +2664,7 @@ void launch_apply_delta_K(const AsmArgs &a, const int32_t *elemNodes, const int3
                           const double *uNodes, const double *deltaP, double *out, hipStream_t s) {
     const LoadArgs l = make_load_args(a, elemNodes, dofForNode, intGrad, nullptr);
     const int grid = grid_for(a.nElem, 8192);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_apply_delta_K<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, deltaP, out)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_apply_delta_K<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, uNodes, deltaP, out); });
     CHECK_LAUNCH();
 }
 
@@ -2744,9 +2673,7 @@ void launch_mutual_energies(const AsmArgs &a, const int32_t *elemNodes, const do
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int fl = a.dim * (a.dim + 1) / 2;
     const dim3 grid(grid_for(a.nElem, 4096), fl * (fl + 1) / 2);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_mutual_energies<D, G, M>), grid, dim3(256), 0, s, l, w, nNode, deltaP, out)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_mutual_energies<D(), G(), M()>, grid, dim3(256), 0, s, l, w, nNode, deltaP, out); });
     CHECK_LAUNCH();
 }
 
@@ -2754,17 +2681,14 @@ void launch_strain_field(const AsmArgs &a, const int32_t *elemNodes, const doubl
                          double *out, hipStream_t s) {
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int grid = grid_for(a.nElem, 8192);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_strain_field<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, out)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_strain_field<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, out); });
     CHECK_LAUNCH();
 }
 
 void launch_sym_measures(int dim, int64_t n, const double *field, int what, double *vm, double *eval, double *evec, hipStream_t s) {
     if (n <= 0) return;
     const int grid = grid_for(n, 8192);
-    if (dim == 3) hipLaunchKernelGGL((k_sym_measures<3>), dim3(grid), dim3(256), 0, s, n, field, what, vm, eval, evec);
-    else hipLaunchKernelGGL((k_sym_measures<2>), dim3(grid), dim3(256), 0, s, n, field, what, vm, eval, evec);
+    with_dim(dim, [&](auto D) { launch_k(k_sym_measures<D()>, dim3(grid), dim3(256), 0, s, n, field, what, vm, eval, evec); });
     CHECK_LAUNCH();
 }
 
@@ -2772,9 +2696,9 @@ void launch_stress_measures(const AsmArgs &a, const int32_t *elemNodes, const do
                             double *vm, double *eval, double *evec, hipStream_t s) {
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int grid = grid_for(a.nElem, 8192);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_stress_measures<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, what, vm, eval, evec)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) {
+        launch_k(k_stress_measures<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, what, vm, eval, evec);
+    });
     CHECK_LAUNCH();
 }
 
@@ -2783,9 +2707,7 @@ void launch_peak_von_mises(const AsmArgs &a, const int32_t *elemNodes, const dou
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int grid = grid_for(a.nElem, PEAK_GRID_CAP);
     long long *pI = reinterpret_cast<long long *>(partI), *oI = reinterpret_cast<long long *>(outI);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_peak_von_mises<D, G, M>), dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, partV, pI)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_peak_von_mises<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, partV, pI); });
     hipLaunchKernelGGL(k_peak_finish, dim3(1), dim3(256), 0, s, grid, (const double *)partV, (const long long *)pI, outV, oI);
     CHECK_LAUNCH();
 }
@@ -2796,19 +2718,9 @@ void launch_vertex_average(int dim, int npe, int64_t nVert, const int32_t *nodeP
     const int grid = grid_for(nVert);
     for (int c0 = 0; c0 < nComp; c0 += 9) {          // components in register blocks of at most 9 (a full dim x dim tensor in 3D)
         const int cb = std::min(9, nComp - c0);
-#define VA(CB) hipLaunchKernelGGL((k_vertex_average<CB>), dim3(grid), dim3(256), 0, s, nVert, nodePtr, nodePair, npe, dim + 1, geo, geoStride, field, nq, nComp, c0, out)
-        switch (cb) {
-        case 1: VA(1); break;
-        case 2: VA(2); break;
-        case 3: VA(3); break;
-        case 4: VA(4); break;
-        case 5: VA(5); break;
-        case 6: VA(6); break;
-        case 7: VA(7); break;
-        case 8: VA(8); break;
-        default: VA(9); break;
-        }
-#undef VA
+        with_int<1, 2, 3, 4, 5, 6, 7, 8, 9>(cb, [&](auto CB) {
+            launch_k(k_vertex_average<CB()>, dim3(grid), dim3(256), 0, s, nVert, nodePtr, nodePair, npe, dim + 1, geo, geoStride, field, nq, nComp, c0, out);
+        });
     }
     CHECK_LAUNCH();
 }
@@ -2819,10 +2731,9 @@ void launch_boundary_strain_field(const AsmArgs &a, const int32_t *elemNodes, co
     if (nBE == 0) return;
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int grid = grid_for(nBE, 8192);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_boundary_strain_field<D, G, M>), dim3(grid), dim3(256), 0, s, l, nBE, bdryParent, \
-                                         bdryElemNodes, npbe, uNodes, wantStress, out)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) {
+        launch_k(k_boundary_strain_field<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, nBE, bdryParent, bdryElemNodes, npbe, uNodes, wantStress, out);
+    });
     CHECK_LAUNCH();
 }
 
@@ -2831,9 +2742,7 @@ void launch_mutual_energy_differential(const AsmArgs &a, const int32_t *elemNode
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int fl = a.dim * (a.dim + 1) / 2;
     const dim3 grid(grid_for(a.nElem, 4096), fl * (fl + 1) / 2);
-#define CALL(D, G, M) hipLaunchKernelGGL((k_mutual_energy_differential<D, G, M>), grid, dim3(256), 0, s, l, w, nNode, nVert, out)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_mutual_energy_differential<D(), G(), M()>, grid, dim3(256), 0, s, l, w, nNode, nVert, out); });
     CHECK_LAUNCH();
 }
 
@@ -2841,13 +2750,7 @@ void launch_average_gradient(const AsmArgs &a, const int32_t *elemNodes, const d
                              hipStream_t s) {
     const LoadArgs l = make_load_args(a, elemNodes, nullptr, intGrad, nullptr);
     const int grid = grid_for(a.nElem, 8192);
-    if (a.dim == 3) {
-        if (a.deg == 2) hipLaunchKernelGGL((k_average_gradient<3, 2>), dim3(grid), dim3(256), 0, s, l, uNodes, out);
-        else hipLaunchKernelGGL((k_average_gradient<3, 1>), dim3(grid), dim3(256), 0, s, l, uNodes, out);
-    } else {
-        if (a.deg == 2) hipLaunchKernelGGL((k_average_gradient<2, 2>), dim3(grid), dim3(256), 0, s, l, uNodes, out);
-        else hipLaunchKernelGGL((k_average_gradient<2, 1>), dim3(grid), dim3(256), 0, s, l, uNodes, out);
-    }
+    with_dim_deg(a.dim, a.deg, [&](auto D, auto G) { launch_k(k_average_gradient<D(), G()>, dim3(grid), dim3(256), 0, s, l, uNodes, out); });
     CHECK_LAUNCH();
 }
 
@@ -2868,23 +2771,14 @@ static void launch_spmv_mode(const SpmvArgs &a_, int mode, const double *x, doub
     const int grid = det_grid(persistent_grid(n, 256 * 8));
     if (a.kron) {           // one value per block (MFH_OP_MASS_VECTOR): plain product or the classic PCG's bookkeeping
         if (mode == 2 || a.vals32 || (a.dim != 2 && a.dim != 3)) throw mfh::Error(MFH_ERR_UNSUPPORTED, "k_spmv_kron serves the plain product and the classic PCG loop in 2D / 3D only");
-        if (a.dim == 3) {
-            if (mode == 1) hipLaunchKernelGGL((k_spmv_kron<3, 1>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);
-            else hipLaunchKernelGGL((k_spmv_kron<3, 0>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);
-        } else {
-            if (mode == 1) hipLaunchKernelGGL((k_spmv_kron<2, 1>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);
-            else hipLaunchKernelGGL((k_spmv_kron<2, 0>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);
-        }
-        if (dotOut || scal) launch_det_finish(s);
-        CHECK_LAUNCH();
-        return;
+        with_dim(a.dim, [&](auto D) { with_int<1, 0>(mode, [&](auto MODE) {
+            launch_k(k_spmv_kron<D(), MODE()>, dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);
+        }); });
+    } else {
+        with_dim132(a.dim, [&](auto D) { with_int<0, 1, 2>(mode, [&](auto MODE) {
+            launch_k(k_spmv<D(), MODE()>, dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);
+        }); });
     }
-#define SPMV(D)                                                                                                                               \
-    if (mode == 0) hipLaunchKernelGGL((k_spmv<D, 0>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList);     \
-    else if (mode == 1) hipLaunchKernelGGL((k_spmv<D, 1>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList); \
-    else hipLaunchKernelGGL((k_spmv<D, 2>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, stopPtr, chunkList, nList)
-    if (a.dim == 1) { SPMV(1); } else if (a.dim == 3) { SPMV(3); } else { SPMV(2); }
-#undef SPMV
     if (dotOut || scal) launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2896,8 +2790,7 @@ void launch_spmv(const SpmvArgs &a, const double *x, double *y, double *dotOut, 
 void launch_row_sums(int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *vals, int rep, bool upperOnly, double *out, hipStream_t s) {
     if (nRows <= 0) return;
     const int grid = grid_for(nRows, 8192);
-    if (upperOnly) hipLaunchKernelGGL((k_row_sums<true>), dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, rep, out);
-    else hipLaunchKernelGGL((k_row_sums<false>), dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, rep, out);
+    with_bool(upperOnly, [&](auto UP) { launch_k(k_row_sums<UP()>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, rep, out); });
     CHECK_LAUNCH();
 }
 
@@ -2905,8 +2798,7 @@ void launch_divergence(int dim, int64_t nNode, const int32_t *nodePtr, const int
                        double *out, hipStream_t s) {
     if (nNode <= 0) return;
     const int grid = grid_for(nNode, 8192);
-    if (dim == 3) hipLaunchKernelGGL((k_divergence<3>), dim3(grid), dim3(256), 0, s, nNode, nodePtr, nodePair, geo, geoStride, elemVec, out);
-    else hipLaunchKernelGGL((k_divergence<2>), dim3(grid), dim3(256), 0, s, nNode, nodePtr, nodePair, geo, geoStride, elemVec, out);
+    with_dim(dim, [&](auto D) { launch_k(k_divergence<D()>, dim3(grid), dim3(256), 0, s, nNode, nodePtr, nodePair, geo, geoStride, elemVec, out); });
     CHECK_LAUNCH();
 }
 
@@ -2917,9 +2809,7 @@ void launch_spmv_sym(const SpmvArgs &a, int64_t nRows, const double *x, double *
     MFH_HIP(hipMemsetAsync(y, 0, (size_t)nRows * a.dim * sizeof(double), s));
     const size_t lds = ((size_t)a.dim * a.chunkSlots + 16) * sizeof(double) + (size_t)a.chunkSlots * sizeof(unsigned short);
     const int grid = spmv_grid(a);
-    if (a.dim == 1) hipLaunchKernelGGL((k_spmv_sym<1>), dim3(grid), dim3(256), lds, s, a, nRows, x, y);
-    else if (a.dim == 3) hipLaunchKernelGGL((k_spmv_sym<3>), dim3(grid), dim3(256), lds, s, a, nRows, x, y);
-    else hipLaunchKernelGGL((k_spmv_sym<2>), dim3(grid), dim3(256), lds, s, a, nRows, x, y);
+    with_dim132(a.dim, [&](auto D) { launch_k(k_spmv_sym<D()>, dim3(grid), dim3(256), lds, s, a, nRows, x, y); });
     CHECK_LAUNCH();
     if (dotOut) launch_dot(nRows * a.dim, x, y, dotOut, s);
 }
@@ -2934,11 +2824,10 @@ void launch_spmv_mf(const SpmvMfArgs &a, const double *x, double *y, double *dot
     const int bs = mat_is_scalar(a.mat) ? 1 : a.dim;
     const size_t lds = ((size_t)a.maxRows * bs + 16) * sizeof(double);
     const int grid = persistent_grid(a.nChunk, 256 * 8);
-#define CALL(D, G, M)                                                                                                          \
-    if (pcg) hipLaunchKernelGGL((k_spmv_mf<D, G, M, true>), dim3(grid), dim3(256), lds, s, a, x, y, (double *)nullptr, scal, it, stopPtr); \
-    else hipLaunchKernelGGL((k_spmv_mf<D, G, M, false>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, (double *)nullptr, 0, (const double *)nullptr)
-    MFH_DISPATCH_ASM(a, CALL);
-#undef CALL
+    with_elem_asm(a, [&](auto D, auto G, auto M) {
+        if (pcg) launch_k(k_spmv_mf<D(), G(), M(), true>, dim3(grid), dim3(256), lds, s, a, x, y, (double *)nullptr, scal, it, stopPtr);
+        else launch_k(k_spmv_mf<D(), G(), M(), false>, dim3(grid), dim3(256), lds, s, a, x, y, dotOut, (double *)nullptr, 0, (const double *)nullptr);
+    });
     CHECK_LAUNCH();
 }
 
@@ -2950,13 +2839,9 @@ static void launch_mf_rows_mode(const SpmvMfArgs &a_, int mode, const double *x,
     const SpmvMfArgs &a = ad;
     const size_t lds = ((size_t)a.maxRows * a.dim + 16) * sizeof(double);
     const int grid = det_grid(persistent_grid(a.nChunk, 256 * 8));
-#define ROWS(D, DT)                                                                                                                               \
-    if (mode == 0) hipLaunchKernelGGL((k_mf_rows<D, 0, DT>), dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, stopPtr);     \
-    else if (mode == 1) hipLaunchKernelGGL((k_mf_rows<D, 1, DT>), dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, stopPtr); \
-    else hipLaunchKernelGGL((k_mf_rows<D, 2, DT>), dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, stopPtr)
-    if (a.det.partials) { if (a.dim == 3) { ROWS(3, true); } else { ROWS(2, true); } }
-    else { if (a.dim == 3) { ROWS(3, false); } else { ROWS(2, false); } }
-#undef ROWS
+    with_dim(a.dim, [&](auto D) { with_int<0, 1, 2>(mode, [&](auto MODE) { with_bool(a.det.partials != nullptr, [&](auto DT) {
+        launch_k(k_mf_rows<D(), MODE(), DT()>, dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, stopPtr);
+    }); }); });
     if (dotOut || scal) launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2966,9 +2851,9 @@ void launch_spmv_mf2(const SpmvMfArgs &a, const double *x, double *y, double *do
                      bool pcg, hipStream_t s) {
     if (a.nChunk == 0) return;
     const int gridE = persistent_grid((a.nElem + 255) / 256, 256 * 32);   // persistent over element groups
-#define CALL(D, G, M) hipLaunchKernelGGL((k_mf_forces<D, G, M>), dim3(gridE), dim3(256), 0, s, a, x, a.sig, pcg ? (const double *)scal : (const double *)nullptr, it, stopPtr)
-    MFH_DISPATCH(a, CALL);
-#undef CALL
+    with_elem(a, [&](auto D, auto G, auto M) {
+        launch_k(k_mf_forces<D(), G(), M()>, dim3(gridE), dim3(256), 0, s, a, x, a.sig, pcg ? (const double *)scal : (const double *)nullptr, it, stopPtr);
+    });
     CHECK_LAUNCH();
     launch_mf_rows_mode(a, pcg ? 1 : 0, x, y, pcg ? nullptr : dotOut, pcg ? scal : nullptr, pcg ? it : 0, pcg ? stopPtr : nullptr, s);
 }
@@ -2982,22 +2867,12 @@ static void launch_mf_cluster_mode(const SpmvMfArgs &a_, int mode, const double 
     const SpmvMfArgs &a = ad;
     const size_t ldsC = ((size_t)(a.det.partials ? 5 : 2) * a.clMaxLocal * a.dim + 16) * sizeof(double);
     const int gridC = det_grid((int)std::min<int64_t>(nList, 256 * 64));
-#define CALLG(D, G, M, GV, DT)                                                                                                                                     \
-    if (ldsC > 64 * 1024) {                                                                                                                                        \
-        MFH_HIP(hipFuncSetAttribute((const void *)k_mf_cluster<D, G, M, 0, GV, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsC));                          \
-        MFH_HIP(hipFuncSetAttribute((const void *)k_mf_cluster<D, G, M, 1, GV, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsC));                          \
-        MFH_HIP(hipFuncSetAttribute((const void *)k_mf_cluster<D, G, M, 2, GV, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsC));                          \
-    }                                                                                                                                                              \
-    if (mode == 0) hipLaunchKernelGGL((k_mf_cluster<D, G, M, 0, GV, DT>), dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, x, y, dotOut, scal, it, stopPtr, blockList, nList);     \
-    else if (mode == 1) hipLaunchKernelGGL((k_mf_cluster<D, G, M, 1, GV, DT>), dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, x, y, dotOut, scal, it, stopPtr, blockList, nList); \
-    else hipLaunchKernelGGL((k_mf_cluster<D, G, M, 2, GV, DT>), dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, x, y, dotOut, scal, it, stopPtr, blockList, nList)
     // the deterministic flavour (per-wave accumulators) is an instantiation of its own
-#define CALL(D, G, M)                                                                                  \
-    if (a.det.partials) { if (a.vertPos) { CALLG(D, G, M, true, true); } else { CALLG(D, G, M, false, true); } } \
-    else { if (a.vertPos) { CALLG(D, G, M, true, false); } else { CALLG(D, G, M, false, false); } }
-    MFH_DISPATCH(a, CALL);
-#undef CALL
-#undef CALLG
+    with_elem(a, [&](auto D, auto G, auto M) { with_int<0, 1, 2>(mode, [&](auto MODE) {
+        with_bool(a.vertPos != nullptr, [&](auto GV) { with_bool(a.det.partials != nullptr, [&](auto DT) {
+            launch_k(k_mf_cluster<D(), G(), M(), MODE(), GV(), DT()>, dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, x, y, dotOut, scal, it, stopPtr, blockList, nList);
+        }); });
+    }); });
     if (dotOut || scal) launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -3012,16 +2887,10 @@ void launch_mf_cluster_constant_strain(const SpmvMfArgs &a_, const double *cstra
     if (a.clBlocks > 0) {
         const size_t ldsC = ((size_t)2 * a.clMaxLocal * a.dim + 16) * sizeof(double);
         const int gridC = (int)std::min<int64_t>(a.clBlocks, 256 * 64);
-#define CALLS(D, G, M, GV)                                                                                                                                    \
-    do {                                                                                                                                                      \
-        if (ldsC > 64 * 1024) MFH_HIP(hipFuncSetAttribute((const void *)k_mf_cluster<D, G, M, 0, GV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsC)); \
-        hipLaunchKernelGGL((k_mf_cluster<D, G, M, 0, GV, false, true>), dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, (const double *)y, y, (double *)nullptr, (double *)nullptr, 0, \
-                           (const double *)nullptr, (const int32_t *)nullptr, a.clBlocks);                                                                    \
-    } while (0)
-#define CALL(D, G, M) if (a.vertPos) { CALLS(D, G, M, true); } else { CALLS(D, G, M, false); }
-        MFH_DISPATCH(a, CALL);
-#undef CALL
-#undef CALLS
+        with_elem(a, [&](auto D, auto G, auto M) { with_bool(a.vertPos != nullptr, [&](auto GV) {
+            launch_k(k_mf_cluster<D(), G(), M(), 0, GV(), false, true>, dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, (const double *)y, y, (double *)nullptr, (double *)nullptr, 0,
+                     (const double *)nullptr, (const int32_t *)nullptr, a.clBlocks);
+        }); });
         CHECK_LAUNCH();
     }
     launch_mf_rows_mode(a, 0, y, y, nullptr, nullptr, 0, nullptr, s);
@@ -3035,9 +2904,8 @@ void launch_spmv_mf_cluster(const SpmvMfArgs &a, const double *x, double *y, dou
     launch_mf_rows_mode(a, mode, x, y, pcg ? nullptr : dotOut, pcg ? scal : nullptr, pcg ? it : 0, pcg ? stopPtr : nullptr, s);
 }
 
-// ---- operators of the batched / distributed PCG
-static int cluster_nrs(int dim, int nr) { return nr == 1 ? 1 : (dim == 3 ? 2 : 3); }
-bool op_batch_supported(int dim, int nr) { return nr == 1 || (dim == 3 && (nr == 2 || nr == 6)) || (dim == 2 && nr == 3) || (dim == 1 && (nr == 2 || nr == 3 || nr == 6)); }
+// ---- operators of the batched / distributed PCG (the batch shapes: select_batch / select_batch_1d, mfh_dispatch.hh)
+bool op_batch_supported(int dim, int nr) { return nr == 1 || select_batch_1d(dim, nr, [](auto, auto, auto) {}); }
 
 void launch_mf_cluster_nr(const SpmvMfArgs &a, int NR, const double *x, double *y, double *dotOut, double *scal, int it, const double *ctl,
                           const int32_t *blockList, int64_t nList, hipStream_t s) {
@@ -3045,24 +2913,11 @@ void launch_mf_cluster_nr(const SpmvMfArgs &a, int NR, const double *x, double *
     if (NR == 1) { launch_mf_cluster_mode(a, a.pcgMode ? a.pcgMode : (ctl ? 2 : 0), x, y, dotOut, scal, it, ctl, blockList, nList, s); return; }
     // only the instantiated batch sizes: any other NR would run a kernel built for a different vector stride
     if (!op_batch_supported(a.dim, NR)) throw Error(MFH_ERR_UNSUPPORTED, "cluster operator: unsupported batch size " + std::to_string(NR));
-    const int nrs = cluster_nrs(a.dim, NR);
-    const size_t ldsC = ((size_t)2 * a.clMaxLocal * a.dim * nrs + 8) * sizeof(double);
     const int gridC = (int)std::min<int64_t>(nList, 256 * 64);
-#define CALLN(D, G, M, N, NS)                                                                                                         \
-    do {                                                                                                                              \
-        if (ldsC > 64 * 1024) MFH_HIP(hipFuncSetAttribute((const void *)k_mf_cluster_nr<D, G, M, N, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsC)); \
-        hipLaunchKernelGGL((k_mf_cluster_nr<D, G, M, N, NS>), dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, x, y, dotOut, scal, it, ctl, blockList, nList); \
-    } while (0)
-#define CALL(D, G, M)                                          \
-    if (D == 3) {                                              \
-        if (NR == 2) CALLN(3, G, M, 2, 2);                     \
-        else if (NR == 6) CALLN(3, G, M, 6, 2);                \
-    } else {                                                   \
-        CALLN(2, G, M, 3, 3);                                  \
-    }
-    MFH_DISPATCH(a, CALL);
-#undef CALL
-#undef CALLN
+    with_batch(a.dim, NR, "cluster operator: unsupported batch size", [&](auto D, auto N, auto NS) { with_int<2, 1>(a.deg, [&](auto G) { with_elasticity(a.mat, [&](auto M) {
+        const size_t ldsC = ((size_t)2 * a.clMaxLocal * a.dim * NS() + 8) * sizeof(double);
+        launch_k(k_mf_cluster_nr<D(), G(), M(), N(), NS()>, dim3(gridC), dim3(MF_BLOCK), ldsC, s, a, x, y, dotOut, scal, it, ctl, blockList, nList);
+    }); }); });
     CHECK_LAUNCH();
 }
 
@@ -3070,16 +2925,11 @@ void launch_mf_rows_nr(const SpmvMfArgs &a, int NR, const double *x, double *y, 
     if (a.nChunk == 0) return;
     if (NR == 1) { launch_mf_rows_mode(a, a.pcgMode ? a.pcgMode : (ctl ? 2 : 0), x, y, dotOut, scal, it, ctl, s); return; }
     if (!op_batch_supported(a.dim, NR)) throw Error(MFH_ERR_UNSUPPORTED, "cluster operator (interface rows): unsupported batch size " + std::to_string(NR));
-    const int nrs = cluster_nrs(a.dim, NR);
-    const size_t lds = ((size_t)a.maxRows * a.dim * nrs + 8) * sizeof(double);
     const int grid = persistent_grid(a.nChunk, 256 * 8);
-#define ROWS(D, N, NS) hipLaunchKernelGGL((k_mf_rows_nr<D, N, NS>), dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, ctl)
-    if (a.dim == 3) {
-        if (NR == 2) ROWS(3, 2, 2); else if (NR == 6) ROWS(3, 6, 2);
-    } else {
-        ROWS(2, 3, 3);
-    }
-#undef ROWS
+    with_batch(a.dim, NR, "cluster operator (interface rows): unsupported batch size", [&](auto D, auto N, auto NS) {
+        const size_t lds = ((size_t)a.maxRows * a.dim * NS() + 8) * sizeof(double);
+        launch_k(k_mf_rows_nr<D(), N(), NS()>, dim3(grid), dim3(256), lds, s, a, (const double *)a.sig, x, y, dotOut, scal, it, ctl);
+    });
     CHECK_LAUNCH();
 }
 
@@ -3089,24 +2939,15 @@ void launch_spmv_nr(const SpmvArgs &a, int NR, const double *x, double *y, doubl
     if (NR == 1) { launch_spmv_mode(a, a.pcgMode ? a.pcgMode : (ctl ? 2 : 0), x, y, dotOut, scal, it, ctl, chunkList, nList, s); return; }
     if (a.kron) throw Error(MFH_ERR_UNSUPPORTED, "assembled SpMV: the batched product reads dense blocks; the one-value-per-block storage (MFH_OP_MASS_VECTOR) has k_spmv_kron only");
     if (!op_batch_supported(a.dim, NR)) throw Error(MFH_ERR_UNSUPPORTED, "assembled SpMV: unsupported batch size " + std::to_string(NR));
+    const int grid = persistent_grid(nList, 256 * 8);
+    auto launch = [&](auto D, auto N, auto NS) {
+        const size_t lds = ((size_t)a.dim * NS() * a.chunkSlots + 8) * sizeof(double);
+        launch_k(k_spmv_nr<D(), N(), NS()>, dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, ctl, chunkList, nList);
+    };
     // the smoother of a multigrid level (FP32 copy of the matrix) takes all six vectors in ONE pass over the matrix: it is bound by the matrix bytes
     const bool onePass = a.dim == 3 && NR == 6 && a.vals32 && ((size_t)a.dim * 6 * a.chunkSlots + 8) * sizeof(double) <= 80 * 1024;
-    const int nrs = onePass ? 6 : (a.dim == 1 ? (NR == 6 ? 3 : NR) : cluster_nrs(a.dim, NR));
-    const size_t lds = ((size_t)a.dim * nrs * a.chunkSlots + 8) * sizeof(double);
-    const int grid = persistent_grid(nList, 256 * 8);
-#define SPMV(D, N, NS)                                                                                                                 \
-    do {                                                                                                                               \
-        if (lds > 64 * 1024) MFH_HIP(hipFuncSetAttribute((const void *)k_spmv_nr<D, N, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_spmv_nr<D, N, NS>), dim3(grid), dim3(256), lds, s, a, x, y, dotOut, scal, it, ctl, chunkList, nList);     \
-    } while (0)
-    if (a.dim == 3) {
-        if (NR == 2) SPMV(3, 2, 2); else if (onePass) SPMV(3, 6, 6); else if (NR == 6) SPMV(3, 6, 2);
-    } else if (a.dim == 2) {
-        SPMV(2, 3, 3);
-    } else {
-        if (NR == 2) SPMV(1, 2, 2); else if (NR == 3) SPMV(1, 3, 3); else if (NR == 6) SPMV(1, 6, 3);
-    }
-#undef SPMV
+    if (onePass) launch(ic<3>{}, ic<6>{}, ic<6>{});
+    else with_batch_1d(a.dim, NR, "assembled SpMV: unsupported batch size", launch);
     CHECK_LAUNCH();
 }
 

@@ -2,6 +2,7 @@
 // two-level preconditioner (restriction, Galerkin product, prolongation), the dense SPD inverse of its coarse operator and
 // the fused PCG vector kernels. All arithmetic is FP64. See DESIGN.md sections 4.4b and 4.5.
 #include "mfh_device.hh"
+#include "mfh_dispatch.hh"
 
 namespace mfh { namespace k {
 
@@ -1994,26 +1995,19 @@ void launch_untile_vals(int dim, int64_t nnzb, const double *tiled, double *aos,
 void launch_extract_diag_inv(int dim, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *vals,
                              const uint8_t *fixedMask, int kind, double *dinv, hipStream_t s, bool kron) {
     const int grid = (int)((nRows + 255) / 256);
-    if (kron && dim == 3) hipLaunchKernelGGL((k_diag_inv<3, true>), dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
-    else if (kron) hipLaunchKernelGGL((k_diag_inv<2, true>), dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
-    else if (dim == 1) hipLaunchKernelGGL(k_diag_inv<1>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
-    else if (dim == 3) hipLaunchKernelGGL(k_diag_inv<3>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
-    else hipLaunchKernelGGL(k_diag_inv<2>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv);
+    if (kron) with_dim(dim, [&](auto D) { launch_k(k_diag_inv<D(), true>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv); });
+    else with_dim132(dim, [&](auto D) { launch_k(k_diag_inv<D()>, dim3(grid), dim3(256), 0, s, nRows, rowPtr, colIdx, vals, fixedMask, kind, dinv); });
     CHECK_LAUNCH();
 }
 
 void launch_precond(int dim, int64_t nRows, const double *dinv, const double *r, double *z, hipStream_t s) {
-    if (dim == 1) hipLaunchKernelGGL(k_precond<1>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, r, z);
-    else if (dim == 3) hipLaunchKernelGGL(k_precond<3>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, r, z);
-    else hipLaunchKernelGGL(k_precond<2>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, r, z);
+    with_dim132(dim, [&](auto D) { launch_k(k_precond<D()>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, r, z); });
     CHECK_LAUNCH();
 }
 
 void launch_pcg_init(int dim, int64_t nRows, const double *dinv, const double *b, double *x, double *r, double *z, double *p,
                      double *scal, hipStream_t s) {
-    if (dim == 1) hipLaunchKernelGGL(k_pcg_init<1>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, b, x, r, z, p, scal, t_det);
-    else if (dim == 3) hipLaunchKernelGGL(k_pcg_init<3>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, b, x, r, z, p, scal, t_det);
-    else hipLaunchKernelGGL(k_pcg_init<2>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, b, x, r, z, p, scal, t_det);
+    with_dim132(dim, [&](auto D) { launch_k(k_pcg_init<D()>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, dinv, b, x, r, z, p, scal, t_det); });
     launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2021,9 +2015,8 @@ void launch_pcg_init(int dim, int64_t nRows, const double *dinv, const double *b
 void launch_pcg_update(int dim, int64_t nRows, const double *dinv, const double *Ap, double *r,
                        double *z, double *scal, int it, const double *stopPtr, hipStream_t s) {
     const int grid = grid_for(nRows / 2);   // 2048 workgroups at most: each ends with two atomics on the same two scalars
-    if (dim == 1) hipLaunchKernelGGL((k_pcg_update<1, false>), dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det);
-    else if (dim == 3) hipLaunchKernelGGL((k_pcg_update<3, false>), dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det);
-    else hipLaunchKernelGGL((k_pcg_update<2, false>), dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det);
+    // (a function pointer carries no default arguments: zs = 1 spelled out)
+    with_dim132(dim, [&](auto D) { launch_k(k_pcg_update<D(), false, false, double>, dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det, 1.0); });
     launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2031,8 +2024,9 @@ void launch_pcg_update(int dim, int64_t nRows, const double *dinv, const double 
 void launch_pcg_update_noz(int dim, int64_t nRows, const double *Ap, double *r, double *scal, int it,
                            const double *stopPtr, hipStream_t s) {
     const int grid = grid_for(nRows / 2);
-    if (dim == 3) hipLaunchKernelGGL((k_pcg_update<3, true>), dim3(grid), dim3(256), 0, s, nRows, (const double *)nullptr, Ap, r, (double *)nullptr, scal, it, stopPtr, t_det);
-    else hipLaunchKernelGGL((k_pcg_update<2, true>), dim3(grid), dim3(256), 0, s, nRows, (const double *)nullptr, Ap, r, (double *)nullptr, scal, it, stopPtr, t_det);
+    with_dim(dim, [&](auto D) {
+        launch_k(k_pcg_update<D(), true, false, double>, dim3(grid), dim3(256), 0, s, nRows, (const double *)nullptr, Ap, r, (double *)nullptr, scal, it, stopPtr, t_det, 1.0);
+    });
     launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2041,30 +2035,25 @@ void launch_pcg_update_noz(int dim, int64_t nRows, const double *Ap, double *r, 
 void launch_pcg_update_presmooth(int dim, int64_t nRows, const double *dinv, const float *dinv32, const double *Ap, double *r, double *z, double zs, double *scal, int it,
                                  const double *stopPtr, hipStream_t s) {
     const int grid = grid_for(nRows / 2);
-    if (dinv32) {           // the smoother's FP32 copy of the inverse diagonal blocks: 5 vector passes instead of 6
-        if (dim == 3) hipLaunchKernelGGL((k_pcg_update<3, false, true, float>), dim3(grid), dim3(256), 0, s, nRows, dinv32, Ap, r, z, scal, it, stopPtr, t_det, zs);
-        else if (dim == 2) hipLaunchKernelGGL((k_pcg_update<2, false, true, float>), dim3(grid), dim3(256), 0, s, nRows, dinv32, Ap, r, z, scal, it, stopPtr, t_det, zs);
-        else hipLaunchKernelGGL((k_pcg_update<1, false, true, float>), dim3(grid), dim3(256), 0, s, nRows, dinv32, Ap, r, z, scal, it, stopPtr, t_det, zs);
-    } else
-    if (dim == 3) hipLaunchKernelGGL((k_pcg_update<3, false, true>), dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det, zs);
-    else if (dim == 2) hipLaunchKernelGGL((k_pcg_update<2, false, true>), dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det, zs);
-    else hipLaunchKernelGGL((k_pcg_update<1, false, true>), dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det, zs);
+    with_dim123(dim, [&](auto D) {
+        if (dinv32)         // the smoother's FP32 copy of the inverse diagonal blocks: 5 vector passes instead of 6
+            launch_k(k_pcg_update<D(), false, true, float>, dim3(grid), dim3(256), 0, s, nRows, dinv32, Ap, r, z, scal, it, stopPtr, t_det, zs);
+        else launch_k(k_pcg_update<D(), false, true, double>, dim3(grid), dim3(256), 0, s, nRows, dinv, Ap, r, z, scal, it, stopPtr, t_det, zs);
+    });
     launch_det_finish(s);
     CHECK_LAUNCH();
 }
 
 void launch_tl_fill(const TLArgs &t, const int32_t *colorOfAgg, int color, int mode, double *v, hipStream_t s) {
-    if (t.dim == 3) hipLaunchKernelGGL(k_tl_fill<3>, dim3(grid_for(t.nDoF)), dim3(256), 0, s, t, colorOfAgg, color, mode, v);
-    else hipLaunchKernelGGL(k_tl_fill<2>, dim3(grid_for(t.nDoF)), dim3(256), 0, s, t, colorOfAgg, color, mode, v);
+    with_dim(t.dim, [&](auto D) { launch_k(k_tl_fill<D()>, dim3(grid_for(t.nDoF)), dim3(256), 0, s, t, colorOfAgg, color, mode, v); });
     CHECK_LAUNCH();
 }
 void launch_tl_restrict(const TLArgs &t, const int32_t *aggPtr, const int32_t *dofsByAgg, const double *w, double *rc, hipStream_t s) {
     if (t.nDoF < (int64_t)t.nAgg * 160) {           // small aggregates: a wave each
         const unsigned grid = (unsigned)((t.nAgg + 3) / 4);
-        if (t.dim == 3) hipLaunchKernelGGL(k_tl_restrict_wave<3>, dim3(grid), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
-        else hipLaunchKernelGGL(k_tl_restrict_wave<2>, dim3(grid), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
-    } else if (t.dim == 3) hipLaunchKernelGGL(k_tl_restrict<3>, dim3(t.nAgg), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
-    else hipLaunchKernelGGL(k_tl_restrict<2>, dim3(t.nAgg), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
+        with_dim(t.dim, [&](auto D) { launch_k(k_tl_restrict_wave<D()>, dim3(grid), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc); });
+    } else
+        with_dim(t.dim, [&](auto D) { launch_k(k_tl_restrict<D()>, dim3(t.nAgg), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc); });
     CHECK_LAUNCH();
 }
 void launch_tl_scatter(int nAgg, int nModes, int nColor, const int32_t *nbrOfColor, int color, int mode, const double *R, double *Ac,
@@ -2075,8 +2064,7 @@ void launch_tl_scatter(int nAgg, int nModes, int nColor, const int32_t *nbrOfCol
 void launch_tl_rap(const TLArgs &t, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *vals, double *Ac,
                    hipStream_t s) {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nRows + 3) / 4, 256 * 16));
-    if (t.dim == 3) hipLaunchKernelGGL(k_tl_rap<3>, dim3(grid), dim3(256), 0, s, t, nRows, rowPtr, colIdx, vals, Ac);
-    else hipLaunchKernelGGL(k_tl_rap<2>, dim3(grid), dim3(256), 0, s, t, nRows, rowPtr, colIdx, vals, Ac);
+    with_dim(t.dim, [&](auto D) { launch_k(k_tl_rap<D()>, dim3(grid), dim3(256), 0, s, t, nRows, rowPtr, colIdx, vals, Ac); });
     CHECK_LAUNCH();
 }
 // Ac[i][j] and Ac[j][i] for entries of two DIFFERENT aggregates: both become the sum of the two partial values (see k_tl_rap_agg)
@@ -2121,8 +2109,10 @@ void launch_tl_rap_agg(const TLArgs &t, const int32_t *aggPtr, const int32_t *do
     const int NMl = t.dim == 3 ? 6 : 3, NSl = t.dim == 3 ? 27 : 9;
     const int threads = det ? 256 : 512;                    // deterministic: four waves, four neighbour tables (35 KB of LDS)
     const size_t lds = ((size_t)(det ? threads / 64 : 1) * NSl * NMl * NMl + (size_t)16 * NMl * NMl) * sizeof(double);
-    if (t.dim == 3) hipLaunchKernelGGL(k_tl_rap_agg<3>, dim3(t.nAgg), dim3(threads), lds, s, t, aggPtr, dofsByAgg, binCoord, rowPtr, colIdx, vals, Ac, upperOnly ? 1 : 0, nOwnedRows, stencil, farCount, wx, wy, wz, det);
-    else hipLaunchKernelGGL(k_tl_rap_agg<2>, dim3(t.nAgg), dim3(threads), lds, s, t, aggPtr, dofsByAgg, binCoord, rowPtr, colIdx, vals, Ac, upperOnly ? 1 : 0, nOwnedRows, stencil, farCount, wx, wy, wz, det);
+    with_dim(t.dim, [&](auto D) {
+        launch_k(k_tl_rap_agg<D()>, dim3(t.nAgg), dim3(threads), lds, s, t, aggPtr, dofsByAgg, binCoord, rowPtr, colIdx, vals, Ac, upperOnly ? 1 : 0, nOwnedRows, stencil, farCount,
+                 wx, wy, wz, det);
+    });
     if (stencil) { CHECK_LAUNCH(); return; }
     if (upperOnly) {
         const int64_t m = (int64_t)t.nAgg * (t.dim == 3 ? 6 : 3);
@@ -2169,8 +2159,7 @@ void launch_tl_gemv(int64_t m, int64_t ld, const double *A, const double *x, dou
 }
 void launch_tl_apply(const TLArgs &t, const double *dinv, const double *r, const double *yc, double *z, double *scal, int it,
                      const double *stopPtr, hipStream_t s) {
-    if (t.dim == 3) hipLaunchKernelGGL(k_tl_apply<3>, dim3(grid_for(t.nDoF)), dim3(256), 0, s, t, dinv, r, yc, z, scal, it, stopPtr, t_det);
-    else hipLaunchKernelGGL(k_tl_apply<2>, dim3(grid_for(t.nDoF)), dim3(256), 0, s, t, dinv, r, yc, z, scal, it, stopPtr, t_det);
+    with_dim(t.dim, [&](auto D) { launch_k(k_tl_apply<D()>, dim3(grid_for(t.nDoF)), dim3(256), 0, s, t, dinv, r, yc, z, scal, it, stopPtr, t_det); });
     launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2236,42 +2225,34 @@ void launch_cg_update(int dim, int64_t nRows, int NR, const double *dinv, double
                       double *scal, int it, const double *ctl, bool skipU, hipStream_t s) {
     if (NR == 1) {
         const int g1 = grid_for(nRows / 2);
-#define CALL1(D)                                                                                                                      \
-    if (skipU) hipLaunchKernelGGL((k_cg_update1<D, true>), dim3(g1), dim3(256), 0, s, nRows, dinv, u, w, p, sv, x, r, scal, it, ctl);     \
-    else hipLaunchKernelGGL((k_cg_update1<D, false>), dim3(g1), dim3(256), 0, s, nRows, dinv, u, w, p, sv, x, r, scal, it, ctl)
-        if (dim == 3) { CALL1(3); } else if (dim == 2) { CALL1(2); } else { CALL1(1); }
-#undef CALL1
+        with_dim123(dim, [&](auto D) { with_bool(skipU, [&](auto SKIP) {
+            launch_k(k_cg_update1<D(), SKIP()>, dim3(g1), dim3(256), 0, s, nRows, dinv, u, w, p, sv, x, r, scal, it, ctl);
+        }); });
         CHECK_LAUNCH();
         return;
     }
     const int grid = pair_grid(nRows * NR);
-#define CALL(D)                                                                                                                          \
-    if (skipU) hipLaunchKernelGGL((k_cg_update<D, true>), dim3(grid), dim3(256), 0, s, nRows, NR, dinv, u, w, p, sv, x, r, scal, it, ctl); \
-    else hipLaunchKernelGGL((k_cg_update<D, false>), dim3(grid), dim3(256), 0, s, nRows, NR, dinv, u, w, p, sv, x, r, scal, it, ctl)
-    if (dim == 3) { CALL(3); } else if (dim == 2) { CALL(2); } else { CALL(1); }
-#undef CALL
+    with_dim123(dim, [&](auto D) { with_bool(skipU, [&](auto SKIP) {
+        launch_k(k_cg_update<D(), SKIP()>, dim3(grid), dim3(256), 0, s, nRows, NR, dinv, u, w, p, sv, x, r, scal, it, ctl);
+    }); });
     CHECK_LAUNCH();
 }
 void launch_cg_init(int dim, int64_t nRows, int NR, const double *dinv, const double *r, double *u, double *scal, bool skipU, hipStream_t s) {
     const int grid = pair_grid(nRows * NR);
-#define CALL(D)                                                                                                  \
-    if (skipU) hipLaunchKernelGGL((k_cg_init<D, true>), dim3(grid), dim3(256), 0, s, nRows, NR, dinv, r, u, scal); \
-    else hipLaunchKernelGGL((k_cg_init<D, false>), dim3(grid), dim3(256), 0, s, nRows, NR, dinv, r, u, scal)
-    if (dim == 3) { CALL(3); } else if (dim == 2) { CALL(2); } else { CALL(1); }
-#undef CALL
+    with_dim123(dim, [&](auto D) { with_bool(skipU, [&](auto SKIP) {
+        launch_k(k_cg_init<D(), SKIP()>, dim3(grid), dim3(256), 0, s, nRows, NR, dinv, r, u, scal);
+    }); });
     CHECK_LAUNCH();
 }
 void launch_tl_restrict_nr(const TLArgs &t, int NR, const int32_t *aggPtr, const int32_t *dofsByAgg, const double *w, double *rc, hipStream_t s) {
-    if (t.nDoF < (int64_t)t.nAgg * 160 && ((t.dim == 3 && (NR == 2 || NR == 6)) || (t.dim == 2 && NR == 3))) {      // small aggregates: a wave each
-        const unsigned grid = (unsigned)((t.nAgg + 3) / 4);
-        if (t.dim == 3 && NR == 6) hipLaunchKernelGGL((k_tl_restrict_wave_nr<3, 6>), dim3(grid), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
-        else if (t.dim == 3) hipLaunchKernelGGL((k_tl_restrict_wave_nr<3, 2>), dim3(grid), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
-        else hipLaunchKernelGGL((k_tl_restrict_wave_nr<2, 3>), dim3(grid), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
+    // small aggregates: a wave each (the batch shapes only; any other pair takes the general kernel)
+    if (t.nDoF < (int64_t)t.nAgg * 160 && select_batch(t.dim, NR, [&](auto D, auto N, auto) {
+            launch_k(k_tl_restrict_wave_nr<D(), N()>, dim3((unsigned)((t.nAgg + 3) / 4)), dim3(256), 0, s, t, aggPtr, dofsByAgg, w, rc);
+        })) {
         CHECK_LAUNCH();
         return;
     }
-    if (t.dim == 3) hipLaunchKernelGGL(k_tl_restrict_nr<3>, dim3(t.nAgg), dim3(256), 0, s, t, NR, aggPtr, dofsByAgg, w, rc);
-    else hipLaunchKernelGGL(k_tl_restrict_nr<2>, dim3(t.nAgg), dim3(256), 0, s, t, NR, aggPtr, dofsByAgg, w, rc);
+    with_dim(t.dim, [&](auto D) { launch_k(k_tl_restrict_nr<D()>, dim3(t.nAgg), dim3(256), 0, s, t, NR, aggPtr, dofsByAgg, w, rc); });
     CHECK_LAUNCH();
 }
 void launch_tl_gemv_nr(int64_t m, int64_t ld, int NR, const double *A, const double *x, double *y, hipStream_t s) {
@@ -2281,8 +2262,7 @@ void launch_tl_gemv_nr(int64_t m, int64_t ld, int NR, const double *A, const dou
 void launch_tl_apply_nr(const TLArgs &t, int NR, const double *dinv, const double *r, const double *yc, double *z, double *scal, int it,
                         const double *ctl, hipStream_t s) {
     const int grid = pair_grid(t.nDoF * NR);
-    if (t.dim == 3) hipLaunchKernelGGL(k_tl_apply_nr<3>, dim3(grid), dim3(256), 0, s, t, NR, dinv, r, yc, z, scal, it, ctl);
-    else hipLaunchKernelGGL(k_tl_apply_nr<2>, dim3(grid), dim3(256), 0, s, t, NR, dinv, r, yc, z, scal, it, ctl);
+    with_dim(t.dim, [&](auto D) { launch_k(k_tl_apply_nr<D()>, dim3(grid), dim3(256), 0, s, t, NR, dinv, r, yc, z, scal, it, ctl); });
     CHECK_LAUNCH();
 }
 void launch_pack_rows(int64_t n, int W, const int32_t *idx, const double *src, double *dst, hipStream_t s) {
@@ -2332,51 +2312,48 @@ void launch_scatter_values_nr(int64_t n, int NR, int dim, const int64_t *idx, co
 thread_local int t_gateNr = 0;
 thread_local int64_t t_gateStride = 0;
 static MgGate mk_gate(const double *scal, int it, const double *stop) { return MgGate{scal, it, stop, t_gateNr, t_gateStride}; }
-// kernels templated on (DIM, NR): NR = 1 and the batch sizes of op_batch_supported (3D: 2, 6; 2D: 3)
-#define MG_NR_DISPATCH(dim, NR, K, grid, ...)                                                                     \
-    do {                                                                                                          \
-        if ((NR) == 1) {                                                                                          \
-            if ((dim) == 3) hipLaunchKernelGGL((K<3, 1>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);              \
-            else hipLaunchKernelGGL((K<2, 1>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);                         \
-        } else if ((dim) == 3 && (NR) == 2) hipLaunchKernelGGL((K<3, 2>), dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
-        else if ((dim) == 3 && (NR) == 6) hipLaunchKernelGGL((K<3, 6>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);   \
-        else if ((dim) == 2 && (NR) == 3) hipLaunchKernelGGL((K<2, 3>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);   \
-        else throw Error(MFH_ERR_UNSUPPORTED, "multigrid kernels: unsupported batch size");                      \
-        CHECK_LAUNCH();                                                                                           \
-    } while (0)
+// kernels templated on (DIM, NR): NR = 1 and the batch shapes (select_batch, mfh_dispatch.hh)
+template <class F> static void with_dim_nr(int dim, int NR, F &&f) {
+    if (NR == 1) with_dim(dim, [&](auto D) { f(D, ic<1>{}); });
+    else with_batch(dim, NR, "multigrid kernels: unsupported batch size", [&](auto D, auto N, auto) { f(D, N); });
+}
 void launch_mg_cheb(int dim, int64_t nRows, const double *dinv, const double *rin, const double *t, double *rout, double *d, double *x,
                     double a, double b, bool first, bool assign, const double *scal, int it, const double *stop, hipStream_t s, int NR) {
     const MgGate g = mk_gate(scal, it, stop);
     const int grid = grid_for(nRows * NR, g_vecGridCap);
-    if (dim == 1 && NR == 1) { hipLaunchKernelGGL(k_mg_cheb<1>, dim3(grid), dim3(256), 0, s, nRows, dinv, rin, t, rout, d, x, a, b, first ? 1 : 0, assign ? 1 : 0, g); CHECK_LAUNCH(); return; }
-    MG_NR_DISPATCH(dim, NR, k_mg_cheb, grid, nRows, dinv, rin, t, rout, d, x, a, b, first ? 1 : 0, assign ? 1 : 0, g);
+    auto launch = [&](auto D, auto N) { launch_k(k_mg_cheb<D(), N()>, dim3(grid), dim3(256), 0, s, nRows, dinv, rin, t, rout, d, x, a, b, first ? 1 : 0, assign ? 1 : 0, g); };
+    if (dim == 1 && NR == 1) launch(ic<1>{}, ic<1>{});
+    else with_dim_nr(dim, NR, launch);
+    CHECK_LAUNCH();
 }
 void launch_mg_restrict(int dim, int64_t nCoarse, const int32_t *fineOf, const int32_t *resPtr, const int32_t *resIdx, const double *r, const double *t,
                         const uint8_t *coarseMask, double *rc, const double *scal, int it, const double *stop, hipStream_t s, int NR, int64_t fineStride) {
     const MgGate g = mk_gate(scal, it, stop);
     const int grid = grid_for(nCoarse * MG_RESTRICT_LANES, MG_RESTRICT_LANES * g_vecGridCap);
-    MG_NR_DISPATCH(dim, NR, k_mg_restrict, grid, nCoarse, fineOf, resPtr, resIdx, r, t, fineStride, coarseMask, rc, g);
+    with_dim_nr(dim, NR, [&](auto D, auto N) {
+        launch_k(k_mg_restrict<D(), N()>, dim3(grid), dim3(256), 0, s, nCoarse, fineOf, resPtr, resIdx, r, t, fineStride, coarseMask, rc, g);
+    });
+    CHECK_LAUNCH();
 }
 void launch_mg_prolong_add(int dim, int64_t nFine, const int32_t *parA, const int32_t *parB, const double *xc, const uint8_t *fineMask, double *x,
                            const double *scal, int it, const double *stop, hipStream_t s, int ldc) {
     const MgGate g = mk_gate(scal, it, stop);
     if (ldc <= 0) ldc = dim;
-    if (dim == 3) hipLaunchKernelGGL(k_mg_prolong_add<3>, dim3(grid_for(nFine, g_vecGridCap)), dim3(256), 0, s, nFine, parA, parB, xc, ldc, fineMask, x, g);
-    else hipLaunchKernelGGL(k_mg_prolong_add<2>, dim3(grid_for(nFine, g_vecGridCap)), dim3(256), 0, s, nFine, parA, parB, xc, ldc, fineMask, x, g);
+    with_dim(dim, [&](auto D) { launch_k(k_mg_prolong_add<D()>, dim3(grid_for(nFine, g_vecGridCap)), dim3(256), 0, s, nFine, parA, parB, xc, ldc, fineMask, x, g); });
     CHECK_LAUNCH();
 }
 void launch_mg_prolong_add_nr(int dim, int NR, int64_t nFine, const int32_t *parA, const int32_t *parB, const double *xc, const uint8_t *fineMask, double *x,
                               int64_t vecStride, const double *scal, int64_t scalStride, int it, const double *stop, hipStream_t s) {
     const int grid = grid_for(nFine * NR, g_vecGridCap);
-    if (dim == 3 && NR == 6) hipLaunchKernelGGL((k_mg_prolong_add_nr<3, 6>), dim3(grid), dim3(256), 0, s, nFine, parA, parB, xc, fineMask, x, vecStride, scal, scalStride, it, stop);
-    else if (dim == 3 && NR == 2) hipLaunchKernelGGL((k_mg_prolong_add_nr<3, 2>), dim3(grid), dim3(256), 0, s, nFine, parA, parB, xc, fineMask, x, vecStride, scal, scalStride, it, stop);
-    else if (dim == 2 && NR == 3) hipLaunchKernelGGL((k_mg_prolong_add_nr<2, 3>), dim3(grid), dim3(256), 0, s, nFine, parA, parB, xc, fineMask, x, vecStride, scal, scalStride, it, stop);
-    else throw Error(MFH_ERR_UNSUPPORTED, "multigrid kernels: unsupported batch size");
+    with_batch(dim, NR, "multigrid kernels: unsupported batch size", [&](auto D, auto N, auto) {
+        launch_k(k_mg_prolong_add_nr<D(), N()>, dim3(grid), dim3(256), 0, s, nFine, parA, parB, xc, fineMask, x, vecStride, scal, scalStride, it, stop);
+    });
     CHECK_LAUNCH();
 }
 void launch_mg_tl_prolong_add(const TLArgs &t, const double *yc, double *x, double alpha, const double *scal, int it, const double *stop, hipStream_t s, int NR) {
     const MgGate g = mk_gate(scal, it, stop);
-    MG_NR_DISPATCH(t.dim, NR, k_mg_tl_prolong_add, grid_for(t.nDoF * NR, g_vecGridCap), t, yc, x, alpha, g);
+    with_dim_nr(t.dim, NR, [&](auto D, auto N) { launch_k(k_mg_tl_prolong_add<D(), N()>, dim3(grid_for(t.nDoF * NR, g_vecGridCap)), dim3(256), 0, s, t, yc, x, alpha, g); });
+    CHECK_LAUNCH();
 }
 void launch_fill_hash(int64_t n, double *v, hipStream_t s) {
     hipLaunchKernelGGL(k_fill_hash, dim3(grid_for(n, g_vecGridCap)), dim3(256), 0, s, n, v);
@@ -2403,14 +2380,10 @@ void launch_mg_rz(int64_t n, const double *r, double *z, const uint8_t *mask, do
 void launch_mg_cheb_rz(int dim, int64_t nRows, const double *dinv, const float *dinv32, const double *rin, const double *t, double *x, double b, const uint8_t *mask,
                        double *scalOut, int it, const double *scal, const double *stop, hipStream_t s) {
     const int grid = grid_for(nRows / 2);
-    if (dinv32) {
-        if (dim == 3) hipLaunchKernelGGL((k_mg_cheb_rz<3, float>), dim3(grid), dim3(256), 0, s, nRows, dinv32, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
-        else if (dim == 2) hipLaunchKernelGGL((k_mg_cheb_rz<2, float>), dim3(grid), dim3(256), 0, s, nRows, dinv32, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
-        else hipLaunchKernelGGL((k_mg_cheb_rz<1, float>), dim3(grid), dim3(256), 0, s, nRows, dinv32, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
-    } else
-    if (dim == 3) hipLaunchKernelGGL(k_mg_cheb_rz<3>, dim3(grid), dim3(256), 0, s, nRows, dinv, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
-    else if (dim == 2) hipLaunchKernelGGL(k_mg_cheb_rz<2>, dim3(grid), dim3(256), 0, s, nRows, dinv, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
-    else hipLaunchKernelGGL(k_mg_cheb_rz<1>, dim3(grid), dim3(256), 0, s, nRows, dinv, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
+    with_dim123(dim, [&](auto D) {
+        if (dinv32) launch_k(k_mg_cheb_rz<D(), float>, dim3(grid), dim3(256), 0, s, nRows, dinv32, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
+        else launch_k(k_mg_cheb_rz<D()>, dim3(grid), dim3(256), 0, s, nRows, dinv, rin, t, x, b, mask, scalOut, mk_gate(scal, it, stop), t_det);
+    });
     launch_det_finish(s);
     CHECK_LAUNCH();
 }
@@ -2418,38 +2391,47 @@ void launch_mg_cheb_rz(int dim, int64_t nRows, const double *dinv, const float *
 
 
 // ---- aggregate (lattice-stencil) levels of the multigrid hierarchy
-#define ST_DISPATCH(dim, K, grid, ...)                                                      \
-    do {                                                                                    \
-        if ((dim) == 3) hipLaunchKernelGGL(K<3>, dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL(K<2>, dim3(grid), dim3(256), 0, s, __VA_ARGS__);            \
-        CHECK_LAUNCH();                                                                     \
-    } while (0)
 void launch_st_spmv(int dim, int64_t nAgg, const int32_t *nbr, const double *A, const float *A32, const double *x, double *y, const double *scal, int it, const double *stop, hipStream_t s, int NR) {
-    MG_NR_DISPATCH(dim, NR, k_st_spmv, grid_for(nAgg * 6 * NR), nAgg, nbr, A, A32, x, y, mk_gate(scal, it, stop));
+    with_dim_nr(dim, NR, [&](auto D, auto N) { launch_k(k_st_spmv<D(), N()>, dim3(grid_for(nAgg * 6 * NR)), dim3(256), 0, s, nAgg, nbr, A, A32, x, y, mk_gate(scal, it, stop)); });
+    CHECK_LAUNCH();
 }
-void launch_st_dinv(int dim, int64_t nAgg, const double *A, double *Dinv, hipStream_t s) { ST_DISPATCH(dim, k_st_dinv, grid_for(nAgg), nAgg, A, Dinv); }
+void launch_st_dinv(int dim, int64_t nAgg, const double *A, double *Dinv, hipStream_t s) {
+    with_dim(dim, [&](auto D) { launch_k(k_st_dinv<D()>, dim3(grid_for(nAgg)), dim3(256), 0, s, nAgg, A, Dinv); });
+    CHECK_LAUNCH();
+}
 void launch_st_cheb(int dim, int64_t nAgg, const double *Dinv, const double *rin, const double *t, double *rout, double *d, double *x, double a, double b,
                     bool first, bool assign, const double *scal, int it, const double *stop, hipStream_t s, int NR) {
-    MG_NR_DISPATCH(dim, NR, k_st_cheb, grid_for(nAgg * NR), nAgg, Dinv, rin, t, rout, d, x, a, b, first ? 1 : 0, assign ? 1 : 0, mk_gate(scal, it, stop));
+    with_dim_nr(dim, NR, [&](auto D, auto N) {
+        launch_k(k_st_cheb<D(), N()>, dim3(grid_for(nAgg * NR)), dim3(256), 0, s, nAgg, Dinv, rin, t, rout, d, x, a, b, first ? 1 : 0, assign ? 1 : 0, mk_gate(scal, it, stop));
+    });
+    CHECK_LAUNCH();
 }
 void launch_st_rap(int dim, int64_t nParents, const int32_t *childPtr, const int32_t *childIdx, const int32_t *nbr, const double *A, const int32_t *parent,
                    const double *rel, const int32_t *coordC, double *Ac, const int *wrapNbC, hipStream_t s) {
     const int wx = wrapNbC ? wrapNbC[0] : 0, wy = wrapNbC ? wrapNbC[1] : 0, wz = wrapNbC ? wrapNbC[2] : 0;
-    ST_DISPATCH(dim, k_st_rap, grid_for(nParents * 27), nParents, childPtr, childIdx, nbr, A, parent, rel, coordC, Ac, wx, wy, wz);
+    with_dim(dim, [&](auto D) {
+        launch_k(k_st_rap<D()>, dim3(grid_for(nParents * 27)), dim3(256), 0, s, nParents, childPtr, childIdx, nbr, A, parent, rel, coordC, Ac, wx, wy, wz);
+    });
+    CHECK_LAUNCH();
 }
 void launch_st_restrict(int dim, int64_t nParents, const int32_t *childPtr, const int32_t *childIdx, const double *rel, const double *r, const double *t, double *rc,
                         const double *scal, int it, const double *stop, hipStream_t s, int NR) {
-    MG_NR_DISPATCH(dim, NR, k_st_restrict, grid_for(nParents * NR), nParents, childPtr, childIdx, rel, r, t, rc, mk_gate(scal, it, stop));
+    with_dim_nr(dim, NR, [&](auto D, auto N) {
+        launch_k(k_st_restrict<D(), N()>, dim3(grid_for(nParents * NR)), dim3(256), 0, s, nParents, childPtr, childIdx, rel, r, t, rc, mk_gate(scal, it, stop));
+    });
+    CHECK_LAUNCH();
 }
 void launch_st_prolong_add(int dim, int64_t nAgg, const int32_t *parent, const double *rel, const double *xc, double *x, double alpha, const double *scal, int it,
                            const double *stop, hipStream_t s, int NR) {
-    MG_NR_DISPATCH(dim, NR, k_st_prolong_add, grid_for(nAgg * NR), nAgg, parent, rel, xc, x, alpha, mk_gate(scal, it, stop));
+    with_dim_nr(dim, NR, [&](auto D, auto N) {
+        launch_k(k_st_prolong_add<D(), N()>, dim3(grid_for(nAgg * NR)), dim3(256), 0, s, nAgg, parent, rel, xc, x, alpha, mk_gate(scal, it, stop));
+    });
+    CHECK_LAUNCH();
 }
 void launch_st_to_dense(int dim, int64_t nAgg, const int32_t *nbr, const double *A, double *Ad, hipStream_t s) {
-    ST_DISPATCH(dim, k_st_to_dense, grid_for(nAgg * 27 * 36), nAgg, nbr, A, Ad);
+    with_dim(dim, [&](auto D) { launch_k(k_st_to_dense<D()>, dim3(grid_for(nAgg * 27 * 36)), dim3(256), 0, s, nAgg, nbr, A, Ad); });
+    CHECK_LAUNCH();
 }
-#undef ST_DISPATCH
-#undef MG_NR_DISPATCH
 void launch_mg_zero(int64_t n, double *v, const double *scal, int it, const double *stop, hipStream_t s) {
     hipLaunchKernelGGL(k_mg_zero, dim3(grid_for(n, g_vecGridCap)), dim3(256), 0, s, n, v, mk_gate(scal, it, stop));
     CHECK_LAUNCH();

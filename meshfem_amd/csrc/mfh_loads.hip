@@ -11,6 +11,7 @@
 // two calls return the same bits, and under a periodic DoF map the images of a DoF are added in a fixed order. A DoF without pairs gets 0.
 #include "mfh_ctx.hh"
 #include "mfh_device.hh"
+#include "mfh_dispatch.hh"
 
 namespace mfh { namespace k {
 
@@ -175,40 +176,19 @@ void launch_stress_field_load(const AsmArgs &a, int64_t nDoF, const int32_t *dof
     if (nDoF <= 0) return;
     const VolumeLoadArgs v = make_args(a, nDoF, dofPtr, dofPair, T, add);
     const int grid = grid_for(nDoF);
-    if (strainKind) {
-        const int key = (a.dim == 3 ? 0 : 6) + (a.deg == 2 ? 3 : 0) + (a.mat == MAT_GENERAL ? 1 : (a.mat == MAT_ORTHO ? 2 : 0));
-#define CALL(D, G, M) hipLaunchKernelGGL((k_stress_field_load<D, G, M, true>), dim3(grid), dim3(256), 0, s, v, field, out)
-        switch (key) {
-        case 0: CALL(3, 1, MAT_ISO); break;
-        case 1: CALL(3, 1, MAT_GENERAL); break;
-        case 2: CALL(3, 1, MAT_ORTHO); break;
-        case 3: CALL(3, 2, MAT_ISO); break;
-        case 4: CALL(3, 2, MAT_GENERAL); break;
-        case 5: CALL(3, 2, MAT_ORTHO); break;
-        case 6: CALL(2, 1, MAT_ISO); break;
-        case 7: CALL(2, 1, MAT_GENERAL); break;
-        case 8: CALL(2, 1, MAT_ORTHO); break;
-        case 9: CALL(2, 2, MAT_ISO); break;
-        case 10: CALL(2, 2, MAT_GENERAL); break;
-        default: CALL(2, 2, MAT_ORTHO); break;
-        }
-#undef CALL
-    } else {
-#define CALL(D, G) hipLaunchKernelGGL((k_stress_field_load<D, G, MAT_ISO, false>), dim3(grid), dim3(256), 0, s, v, field, out)
-        if (a.dim == 3) { if (a.deg == 2) CALL(3, 2); else CALL(3, 1); }
-        else { if (a.deg == 2) CALL(2, 2); else CALL(2, 1); }
-#undef CALL
-    }
+    if (strainKind)
+        with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_stress_field_load<D(), G(), M(), true>, dim3(grid), dim3(256), 0, s, v, field, out); });
+    else
+        with_dim_deg(a.dim, a.deg, [&](auto D, auto G) { launch_k(k_stress_field_load<D(), G(), MAT_ISO, false>, dim3(grid), dim3(256), 0, s, v, field, out); });
     CHECK_LAUNCH();
 }
 
 void launch_field_stress(const AsmArgs &a, const double *strain, double *out, hipStream_t s) {
     if (a.nElem <= 0) return;
     const int grid = grid_for(a.nElem, 8192);
-#define CALL(D, M) hipLaunchKernelGGL((k_field_stress<D, M>), dim3(grid), dim3(256), 0, s, a.nElem, a.geo, a.geoStride, strain, out)
-    if (a.dim == 3) { if (a.mat == MAT_GENERAL) CALL(3, MAT_GENERAL); else if (a.mat == MAT_ORTHO) CALL(3, MAT_ORTHO); else CALL(3, MAT_ISO); }
-    else { if (a.mat == MAT_GENERAL) CALL(2, MAT_GENERAL); else if (a.mat == MAT_ORTHO) CALL(2, MAT_ORTHO); else CALL(2, MAT_ISO); }
-#undef CALL
+    with_dim(a.dim, [&](auto D) { with_elasticity(a.mat, [&](auto M) {
+        launch_k(k_field_stress<D(), M()>, dim3(grid), dim3(256), 0, s, a.nElem, a.geo, a.geoStride, strain, out);
+    }); });
     CHECK_LAUNCH();
 }
 
@@ -221,17 +201,9 @@ void launch_body_force_load(const AsmArgs &a, int64_t nDoF, const int32_t *dofPt
     if (kind == MFH_BODY_CONSTANT)
         for (int c = 0; c < a.dim; ++c) v.b[c] = bConst[c];
     const int grid = grid_for(nDoF);
-#define CALL(D, G, K) hipLaunchKernelGGL((k_body_force_load<D, G, K>), dim3(grid), dim3(256), 0, s, v, mt, elemNodes, b, density, out)
-#define CALL_KIND(D, G)                                           \
-    do {                                                          \
-        if (kind == MFH_BODY_CONSTANT) CALL(D, G, MFH_BODY_CONSTANT); \
-        else if (kind == MFH_BODY_ELEMENT) CALL(D, G, MFH_BODY_ELEMENT); \
-        else CALL(D, G, MFH_BODY_NODE);                           \
-    } while (0)
-    if (a.dim == 3) { if (a.deg == 2) CALL_KIND(3, 2); else CALL_KIND(3, 1); }
-    else { if (a.deg == 2) CALL_KIND(2, 2); else CALL_KIND(2, 1); }
-#undef CALL_KIND
-#undef CALL
+    with_dim_deg(a.dim, a.deg, [&](auto D, auto G) { with_int<MFH_BODY_CONSTANT, MFH_BODY_ELEMENT, MFH_BODY_NODE>(kind, [&](auto K) {
+        launch_k(k_body_force_load<D(), G(), K()>, dim3(grid), dim3(256), 0, s, v, mt, elemNodes, b, density, out);
+    }); });
     CHECK_LAUNCH();
 }
 

@@ -12,6 +12,7 @@
 // order, and the grid depends on nElem only -- the same call returns the same bits.
 #include "mfh_ctx.hh"
 #include "mfh_device.hh"
+#include "mfh_dispatch.hh"
 
 namespace mfh { namespace k {
 
@@ -126,15 +127,12 @@ int mass_moments_grid(int64_t nElem) { return grid_for(nElem, MASS_GRID_CAP); }
 void launch_mass_properties(int dim, int64_t nElem, const int32_t *elemNodes, int npe, const double *vertPos, const double *density, double scale,
                             double *partials, double *props, double *second, hipStream_t s) {
     const int grid = mass_moments_grid(nElem);
-#define PASSES(D)                                                                                                                                  \
-    do {                                                                                                                                           \
-        hipLaunchKernelGGL((k_mass_moments<D, 1>), dim3(grid), dim3(256), 0, s, nElem, elemNodes, npe, vertPos, density, (const double *)props, partials); \
-        hipLaunchKernelGGL((k_mass_finish<D, 1>), dim3(1), dim3(64), 0, s, grid, scale, (const double *)partials, elemNodes, vertPos, props);            \
-        hipLaunchKernelGGL((k_mass_moments<D, 2>), dim3(grid), dim3(256), 0, s, nElem, elemNodes, npe, vertPos, density, (const double *)props, partials); \
-        hipLaunchKernelGGL((k_mass_finish<D, 2>), dim3(1), dim3(64), 0, s, grid, scale, (const double *)partials, elemNodes, vertPos, second);           \
-    } while (0)
-    if (dim == 3) PASSES(3); else PASSES(2);
-#undef PASSES
+    with_dim(dim, [&](auto D) {
+        launch_k(k_mass_moments<D(), 1>, dim3(grid), dim3(256), 0, s, nElem, elemNodes, npe, vertPos, density, (const double *)props, partials);
+        launch_k(k_mass_finish<D(), 1>, dim3(1), dim3(64), 0, s, grid, scale, (const double *)partials, elemNodes, vertPos, props);
+        launch_k(k_mass_moments<D(), 2>, dim3(grid), dim3(256), 0, s, nElem, elemNodes, npe, vertPos, density, (const double *)props, partials);
+        launch_k(k_mass_finish<D(), 2>, dim3(1), dim3(64), 0, s, grid, scale, (const double *)partials, elemNodes, vertPos, second);
+    });
     CHECK_LAUNCH();
 }
 

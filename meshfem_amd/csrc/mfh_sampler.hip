@@ -11,6 +11,7 @@
 // same context returns the same bits.
 #include "mfh_ctx.hh"
 #include "mfh_device.hh"
+#include "mfh_dispatch.hh"
 #include <rocprim/rocprim.hpp>
 
 namespace mfh { namespace k {
@@ -389,9 +390,11 @@ EdgeTable edge_table(int dim) {
     return et;
 }
 
-#define DIM_DISPATCH(dim, CALL) do { if ((dim) == 2) { CALL(2); } else { CALL(3); } } while (0)
-#define DIM_DEG_DISPATCH(dim, deg, CALL) do { if ((dim) == 2) { if ((deg) == 1) { CALL(2, 1); } else { CALL(2, 2); } } \
-                                              else { if ((deg) == 1) { CALL(3, 1); } else { CALL(3, 2); } } } while (0)
+// the ladders of this file end the other way round: a dimension other than 2 is 3, a degree other than 1 is 2
+template <class F> static void with_dim23(int dim, F &&f) { with_int<2, 3>(dim, f); }
+template <class F> static void with_dim23_deg(int dim, int deg, F &&f) {
+    with_dim23(dim, [&](auto D) { with_int<1, 2>(deg, [&](auto G) { f(D, G); }); });
+}
 
 // One grid over `n` items (rows of dVerts / hVerts, `stride` ints apart, the first nv entries vertex ids): cell sizes = scale x the mean
 // bounding-box extent of the items per axis, doubled until the pair count is at most 32 n and below 2^31 and the grid has at most 8 n + 4096
@@ -440,9 +443,7 @@ void build_grid(mfh_ctx *c, mfh_ctx::SamplerGrid &G, int64_t n, const int32_t *d
             const GridDesc g = grid_desc(G);
             MFH_HIP(hipMemsetAsync(cnt.p + n, 0, sizeof(unsigned long long), s));
             const int grid = grid_for(n, SAMPLER_BUILD_GRID_CAP);
-#define CALL(D) hipLaunchKernelGGL((k_grid_count<D>), dim3(grid), dim3(256), 0, s, n, dVerts, stride, nv, c->dVertPos.p, g, pad, cnt.p)
-            DIM_DISPATCH(dim, CALL);
-#undef CALL
+            with_dim23(dim, [&](auto D) { launch_k(k_grid_count<D()>, dim3(grid), dim3(256), 0, s, n, dVerts, stride, nv, c->dVertPos.p, g, pad, cnt.p); });
             CHECK_LAUNCH();
             size_t bytes = 0;
             MFH_HIP(rocprim::exclusive_scan(nullptr, bytes, cnt.p, off.p, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), s));
@@ -466,9 +467,10 @@ void build_grid(mfh_ctx *c, mfh_ctx::SamplerGrid &G, int64_t n, const int32_t *d
         DBuf<unsigned long long> keyA, keyB;
         keyA.alloc((size_t)total); keyB.alloc((size_t)total);
         const int grid = grid_for(n, SAMPLER_BUILD_GRID_CAP);
-#define CALL(D) hipLaunchKernelGGL((k_grid_fill<D>), dim3(grid), dim3(256), 0, s, n, dVerts, stride, nv, c->dVertPos.p, g, pad, off.p, keyA.p)
-        DIM_DISPATCH(dim, CALL);
-#undef CALL
+        with_dim23(dim, [&](auto D) {
+            launch_k(k_grid_fill<D()>, dim3(grid), dim3(256), 0, s, n, dVerts, stride, nv, c->dVertPos.p, g, pad, off.p,
+                     keyA.p);
+        });
         CHECK_LAUNCH();
         const unsigned endBit = 32 + bits_for((uint64_t)nCells);
         size_t bytes = 0;
@@ -587,10 +589,10 @@ void locate_device(mfh_ctx *c, int64_t nP, const double *dP, int32_t *elem, doub
     any.zero(c->stream);
     const int grid = grid_for(nP, SAMPLER_POINT_GRID_CAP);
     const GridDesc g = grid_desc(c->sampler.elem);
-#define CALL(D) hipLaunchKernelGGL((k_locate<D>), dim3(grid), dim3(256), 0, c->stream, nP, dP, g, c->dElemNodes.p, m.npe, c->dVertPos.p, c->dGeo.p, c->geoStride, \
-                                   elem, bary, closest, sqDist, flag.p, any.p)
-    DIM_DISPATCH(m.dim, CALL);
-#undef CALL
+    with_dim23(m.dim, [&](auto D) {
+        launch_k(k_locate<D()>, dim3(grid), dim3(256), 0, c->stream, nP, dP, g, c->dElemNodes.p, m.npe, c->dVertPos.p, c->dGeo.p, c->geoStride, elem, bary,
+                 closest, sqDist, flag.p, any.p);
+    });
     CHECK_LAUNCH();
     int someOutside = 0;
     any.download(&someOutside, 1, c->stream);
@@ -598,10 +600,10 @@ void locate_device(mfh_ctx *c, int64_t nP, const double *dP, int32_t *elem, doub
     ensure_boundary_grid(c);
     if (c->sampler.bdry.nItems == 0) return;
     const GridDesc gb = grid_desc(c->sampler.bdry);
-#define CALL(D) hipLaunchKernelGGL((k_closest_boundary<D>), dim3(grid), dim3(256), 0, c->stream, nP, dP, flag.p, gb, c->sampler.bdryVerts.p, c->sampler.bdryParent.p, \
-                                   c->dElemNodes.p, m.npe, c->dVertPos.p, c->dGeo.p, c->geoStride, elem, bary, closest, sqDist)
-    DIM_DISPATCH(m.dim, CALL);
-#undef CALL
+    with_dim23(m.dim, [&](auto D) {
+        launch_k(k_closest_boundary<D()>, dim3(grid), dim3(256), 0, c->stream, nP, dP, flag.p, gb, c->sampler.bdryVerts.p, c->sampler.bdryParent.p,
+                 c->dElemNodes.p, m.npe, c->dVertPos.p, c->dGeo.p, c->geoStride, elem, bary, closest, sqDist);
+    });
     CHECK_LAUNCH();
 }
 
@@ -670,9 +672,10 @@ mfh_status mfh_sample_field(mfh_ctx *c, int64_t nP, const double *P, int32_t kin
     locate_device(c, nP, pts.p, e.p, b.p, nullptr, nullptr);
     const EdgeTable et = edge_table(m.dim);
     const int grid = grid_for(nP, SAMPLER_POINT_GRID_CAP);
-#define CALL(D, G) hipLaunchKernelGGL((k_sample_field<D, G>), dim3(grid), dim3(256), 0, c->stream, nP, e.p, b.p, c->dElemNodes.p, et, (int)kind, f.p, (int)nComp, res.p)
-    DIM_DEG_DISPATCH(m.dim, m.deg, CALL);
-#undef CALL
+    with_dim23_deg(m.dim, m.deg, [&](auto D, auto G) {
+        launch_k(k_sample_field<D(), G()>, dim3(grid), dim3(256), 0, c->stream, nP, e.p, b.p, c->dElemNodes.p, et, (int)kind, f.p, (int)nComp,
+                 res.p);
+    });
     CHECK_LAUNCH();
     res.finish(c->stream);
     MFH_HIP(hipStreamSynchronize(c->stream));
@@ -697,9 +700,10 @@ mfh_status mfh_closest_node(mfh_ctx *c, int64_t nP, const double *P, int32_t *no
     locate_device(c, nP, pts.p, e.p, b.p, nullptr, nullptr);
     const EdgeTable et = edge_table(m.dim);
     const int grid = grid_for(nP, SAMPLER_POINT_GRID_CAP);
-#define CALL(D, G) hipLaunchKernelGGL((k_closest_node<D, G>), dim3(grid), dim3(256), 0, c->stream, nP, pts.p, e.p, b.p, c->dElemNodes.p, et, c->dVertPos.p, nd.p, sq.p)
-    DIM_DEG_DISPATCH(m.dim, m.deg, CALL);
-#undef CALL
+    with_dim23_deg(m.dim, m.deg, [&](auto D, auto G) {
+        launch_k(k_closest_node<D(), G()>, dim3(grid), dim3(256), 0, c->stream, nP, pts.p, e.p, b.p, c->dElemNodes.p, et, c->dVertPos.p, nd.p,
+                 sq.p);
+    });
     CHECK_LAUNCH();
     nd.finish(c->stream); sq.finish(c->stream);
     MFH_HIP(hipStreamSynchronize(c->stream));
