@@ -560,6 +560,45 @@ mfh_status mfh_newmark(mfh_ctx* ctx, const mfh_newmark_params* params,
                        double* energies,                         /* (nSteps+1) x 3: kinetic, strain, g_n f.u_n; needs MFH_DYN_ENERGIES */
                        mfh_newmark_info* info);
 
+/* ---------------------------------------------------------------- frequency response
+ * The steady state of M u'' + C u' + K u = Re(f^ e^{i w t}) on the device (docs/design/04_17_harmonic.md): for every frequency w of a list
+ *     (K + i w C - w^2 M) u^(w) = f^,    C = rayleighMass M + rayleighStiff K,   plus the structural term i lossFactor K,
+ * with K, M and the fixed variables (held at zero; their set may be empty for w > 0) as in mfh_newmark. The operator is the pencil
+ *     Z(w) = zK K + zM M,    zK = 1 + i (lossFactor + w rayleighStiff),   zM = density (-w^2 + i w rayleighMass),
+ * complex symmetric, solved by COCG (the PCG recurrence with the unconjugated x^T y) to the Hermitian ||r||_2 <= rtol ||f^||_2 with a real symmetric
+ * positive-definite preconditioner applied to the real and the imaginary plane: the context's two-level / multigrid hierarchy of K, or the
+ * block-Jacobi of K + w^2 density M (rebuilt per frequency) -- always the latter when there are no fixed variables; info->note says which. The
+ * reference has no counterpart.
+ *   omega        nFreq frequencies in rad per unit time, solved in this order; with MFH_HARM_WARM_START each starts from the previous solution
+ *   fRe, fIm     the load, dim*nDoF each (fIm NULL: real); entries on fixed variables are ignored. f^ = 0 gives u^ = 0 without an iteration
+ *   probeVars    nProbe variables: probeOut[nFreq x nProbe x {re, im}], gathered on the device
+ *   fields       nFreq x {re plane, im plane} x dim*nDoF (NULL: none); zero on the fixed variables
+ *   iterations, trueResiduals   per frequency (either may be NULL): COCG iterations, and ||f^ - Z u^||_2 / ||f^||_2 from one more product after
+ *                convergence (the recurrence's residual drifts on undamped, indefinite systems)
+ * A frequency that reaches maxit, or whose residual norm is not finite: MFH_ERR_NOT_CONVERGED, info->freqsDone and the outputs of the frequencies
+ * completed; the rest is not written. MFH_ERR_INVALID before any device work: null params, a frequency that is negative or not finite, w = 0
+ * without fixed variables, density <= 0, a negative Rayleigh coefficient or loss factor, rtol outside (0, 1), maxit <= 0, nFreq < 0, an unknown
+ * flag, a probe variable out of range, probes without their output. Contexts as for mfh_newmark (MFH_ERR_UNSUPPORTED); like it the call holds both
+ * triangles of the pattern for its own duration. */
+enum { MFH_HARM_WARM_START = 1 };
+typedef struct mfh_harmonic_params {
+    double density, rayleighMass, rayleighStiff, lossFactor, rtol;
+    int32_t nFreq, maxit, flags;
+} mfh_harmonic_params;
+typedef struct mfh_harmonic_info {
+    int32_t freqsDone, iterationsTotal, iterationsMax, precondUsed;
+    double worstTrueResidual, setupMs, solveMs;
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_harmonic_info;
+mfh_status mfh_harmonic(mfh_ctx* ctx, const mfh_harmonic_params* params,
+                        const double* omega,                      /* nFreq, rad per unit time */
+                        const double* fRe, const double* fIm,     /* dim*nDoF each; fIm may be NULL */
+                        const int64_t* probeVars, int32_t nProbe, double* probeOut,  /* nFreq x nProbe x {re, im} */
+                        double* fields,                           /* nFreq x {re plane, im plane} x dim*nDoF, or NULL */
+                        int32_t* iterations,                      /* nFreq or NULL */
+                        double* trueResiduals,                    /* nFreq or NULL */
+                        mfh_harmonic_info* info);
+
 /* ---------------------------------------------------------------- per-element density, the product with M, mass properties
  * (docs/design/04_15_density.md.) The mass matrix of mfh_modes and mfh_newmark is assembled from a density field of the context:
  *     M = sum_e rho_e int_e phi_i phi_j   on displacement vectors (kron with the identity of size dim),   rho = 1 until a field is set.

@@ -99,6 +99,11 @@ mfh_status mfh_debug_newmark_correct(mfh_ctx* ctx, int64_t n, double dt, double 
 /* y = cK K x + cM M x (M with density 1) through the context's operator and k_spmv_kron_acc, rows of fixed variables zeroed if masked != 0;
  * *dot (may be NULL) = x . y from the kernel's partials. cK == 0 skips the K product */
 mfh_status mfh_debug_pencil_apply(mfh_ctx* ctx, double cK, double cM, int32_t masked, const double* x, double* y, double* dot);
+/* y^ = zK K x^ + zM M x^ for complex zK, zM and x^ = xRe + i xIm (M with density 1) through the context's operator and k_spmv_kron_cacc -- or two
+ * launches of k_spmv_kron_acc and k_harm_combine under option harmonic_two_pass -- rows of fixed variables zeroed if masked != 0; dot (may be NULL):
+ * {Re, Im} of the unconjugated x^T y from the kernel's partials. zK == 0 skips the K products */
+mfh_status mfh_debug_harmonic_apply(mfh_ctx* ctx, double zKre, double zKim, double zMre, double zMim, int32_t masked, const double* xRe, const double* xIm,
+                                    double* yRe, double* yIm, double* dot);
 
 
 /* ---------------------------------------------------------------- device-pointer building blocks

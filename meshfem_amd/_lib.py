@@ -21,6 +21,7 @@ LOAD_ADD, LOAD_ON_DEVICE = 1, 2
 FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE = 0, 1, 2
 MODES_FREE = 1
 DYN_HAVE_ACCEL, DYN_ENERGIES = 1, 2
+HARM_WARM_START = 1
 
 
 class SamplerGridInfo(C.Structure):
@@ -73,6 +74,21 @@ class NewmarkInfo(C.Structure):
     _fields_ = [("stepsDone", C.c_int32), ("iterationsTotal", C.c_int32), ("iterationsMax", C.c_int32), ("iterationsInit", C.c_int32),
                 ("precondUsed", C.c_int32), ("cK", C.c_double), ("cM", C.c_double), ("solve_ms", C.c_double), ("setup_ms", C.c_double),
                 ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
+class HarmonicParams(C.Structure):
+    _fields_ = [("density", C.c_double), ("rayleighMass", C.c_double), ("rayleighStiff", C.c_double), ("lossFactor", C.c_double), ("rtol", C.c_double),
+                ("nFreq", C.c_int32), ("maxit", C.c_int32), ("flags", C.c_int32)]
+
+
+class HarmonicInfo(C.Structure):
+    _fields_ = [("freqsDone", C.c_int32), ("iterationsTotal", C.c_int32), ("iterationsMax", C.c_int32), ("precondUsed", C.c_int32),
+                ("worstTrueResidual", C.c_double), ("setupMs", C.c_double), ("solveMs", C.c_double), ("note", C.c_char_p)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -203,6 +219,7 @@ PROTOTYPES = {
     "mfh_geometric_apply": (_i32, [_P, _P, _P, _i32]),
     "mfh_buckling": (_i32, [_P, _i32, _i32, _f64, _i32, _P, _P, _P, C.POINTER(BucklingInfo)]),
     "mfh_newmark": (_i32, [_P, C.POINTER(NewmarkParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(NewmarkInfo)]),
+    "mfh_harmonic": (_i32, [_P, C.POINTER(HarmonicParams), _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(HarmonicInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -266,6 +283,7 @@ PROTOTYPES = {
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),
     "mfh_debug_pencil_apply": (_i32, [_P, _f64, _f64, _i32, _P, _P, _P]),
+    "mfh_debug_harmonic_apply": (_i32, [_P, _f64, _f64, _f64, _f64, _i32, _P, _P, _P, _P, _P]),
 }
 
 # callback types of mfh_comm_create_callbacks

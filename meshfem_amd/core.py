@@ -466,6 +466,44 @@ class Context:
         self._ck(st)
         return out
 
+    def harmonic(self, omega, f, f_imag=None, density=1.0, damping=(0.0, 0.0), loss_factor=0.0, rtol=1e-8, maxit=10000, probes=None, fields=True,
+                 warm_start=True):
+        """The frequency response (K + i w C - w^2 M) u^ = f^ at every w of omega (rad per unit time), on the device (mfh_harmonic): M = density x
+        the consistent vector-valued mass matrix, C = damping[0] M + damping[1] K plus the structural term i loss_factor K, the context's fixed
+        variables held at zero. f: the load, real or complex (f_imag: its imaginary plane given apart). Solved in the order given, each frequency
+        warm-started from the previous solution unless warm_start=False. Returns a dict: "u" complex [nFreq, dim * n_dof] (fields=True, else
+        None), "probes" complex [nFreq, len(probes)], "iterations" [nFreq], "true_residuals" [nFreq] = ||f^ - Z u^|| / ||f^|| and "info". Raises
+        on MFH_ERR_NOT_CONVERGED like solve(); what was reached (info["freqsDone"] frequencies) is then in self.last_harmonic."""
+        n = self.bs * self.n_dof
+        om = as_f64(np.asarray(omega, dtype=np.float64).reshape(-1))
+        nf = om.size
+        f = np.asarray(f).reshape(-1)
+        if f.size != n:
+            raise ValueError("harmonic: f needs dim * n_dof = %d entries, got %d" % (n, f.size))
+        f_re = np.ascontiguousarray(f.real, dtype=np.float64)
+        f_im = np.ascontiguousarray(f.imag, dtype=np.float64) if np.iscomplexobj(f) else None
+        if f_imag is not None:
+            fi = np.asarray(f_imag, dtype=np.float64).reshape(-1)
+            if fi.size != n:
+                raise ValueError("harmonic: f_imag needs dim * n_dof = %d entries, got %d" % (n, fi.size))
+            f_im = np.ascontiguousarray(fi if f_im is None else f_im + fi)
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros((nf, n_probe, 2)) if n_probe else None
+        fld = np.zeros((nf, 2, n)) if fields else None
+        its, res = np.zeros(nf, dtype=np.int32), np.zeros(nf)
+        prm = L.HarmonicParams(float(density), float(damping[0]), float(damping[1]), float(loss_factor), float(rtol), nf, int(maxit),
+                               L.HARM_WARM_START if warm_start else 0)
+        info = L.HarmonicInfo()
+        st = self.lib.mfh_harmonic(self.h, C.byref(prm), ptr(om), ptr(f_re), ptr(f_im), ptr(pv), n_probe, ptr(pout), ptr(fld), ptr(its), ptr(res),
+                                   C.byref(info))
+        out = {"u": None if fld is None else fld[:, 0, :] + 1j * fld[:, 1, :],
+               "probes": np.zeros((nf, 0), dtype=np.complex128) if pout is None else pout[:, :, 0] + 1j * pout[:, :, 1],
+               "iterations": its, "true_residuals": res, "info": info.as_dict()}
+        self.last_harmonic = out
+        self._ck(st)
+        return out
+
     # ---------------------------------------------------------------- per-element density (docs/design/04_15_density.md)
     def set_density(self, rho):
         """The density field of the mass matrix of modes() and newmark() (mfh_set_density): one strictly positive value per element, or
@@ -585,6 +623,19 @@ class Context:
         self._ck(self.lib.mfh_debug_newmark_correct(self.h, n, float(dt), float(beta), float(gamma), ptr(x), ptr(ut), ptr(vt), ptr(u), ptr(v), ptr(a),
                                                     ptr(pv), n_probe, ptr(pout), ptr(snap)))
         return u, v, a, pout, snap
+
+    def debug_harmonic_apply(self, zK, zM, x, masked=True):
+        """(zK K x + zM M x, x^T y) for complex zK, zM, x through the context's operator and k_spmv_kron_cacc (test hook
+        mfh_debug_harmonic_apply; M with density 1; option harmonic_two_pass selects the two-launch form)."""
+        x = np.asarray(x, dtype=np.complex128).reshape(-1)
+        n = self.bs * self.n_dof
+        assert x.size == n
+        xr, xi = np.ascontiguousarray(x.real), np.ascontiguousarray(x.imag)
+        yr, yi, dot = np.empty(n), np.empty(n), np.zeros(2)
+        zK, zM = complex(zK), complex(zM)
+        self._ck(self.lib.mfh_debug_harmonic_apply(self.h, zK.real, zK.imag, zM.real, zM.imag, 1 if masked else 0, ptr(xr), ptr(xi), ptr(yr), ptr(yi),
+                                                   ptr(dot)))
+        return yr + 1j * yi, complex(dot[0], dot[1])
 
     def debug_pencil_apply(self, cK, cM, x, masked=True):
         """(cK K x + cM M x, x . y) through the context's operator and k_spmv_kron_acc (test hook mfh_debug_pencil_apply; M with density 1)."""

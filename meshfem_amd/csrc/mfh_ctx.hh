@@ -192,7 +192,10 @@ struct mfh_ctx {
     std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
     std::string dynNote;              // mfh_newmark_info::note of the last mfh_newmark (mfh_dynamics.hip)
     int dynGridCap = 2048;            // option "dyn_grid_cap" (1 .. 2048): workgroups of the vector kernels of mfh_newmark's PCG loop = partials per sum
-                                      // (the tests set 1, so that the lanes loop on a small mesh)
+                                      // (the tests set 1, so that the lanes loop on a small mesh); mfh_harmonic's COCG loop reads it too
+    std::string harmNote;             // mfh_harmonic_info::note of the last mfh_harmonic (mfh_harmonic.hip)
+    bool harmTwoPass = false;         // option "harmonic_two_pass": the complex mass product as two launches of k_spmv_kron_acc and a combine kernel
+                                      // in place of k_spmv_kron_cacc (what the launcher does by itself where 2 dim planes of partials exceed the LDS)
 
     // ---- constraints (SPSDSystem state)
     std::vector<int64_t> fixedVars;

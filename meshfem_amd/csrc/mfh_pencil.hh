@@ -1,0 +1,240 @@
+// The pieces of the pencil operator A = cK K + cM M that mfh_dynamics.hip (real coefficients, PCG) and mfh_harmonic.hip (complex coefficients,
+// COCG) both build on: the iteration gate, the two-stage ordered sums, the accumulating mass product, the inverse diagonal blocks of the pencil
+// and the context conditions. Everything here has internal linkage (anonymous namespaces): each of the two translation units carries its own
+// copy of the kernels, which is what keeps this header a move of code and not a new layer. Not part of the ABI.
+//   k_spmv_kron_acc    y = cK y + cM (M (x) I) x: k_spmv_kron's chunks and LDS partials, ADDING into the K product that apply_operator left in y
+//                      (cK == 0: y is not read), the fixed rows zeroed, x . y summed per workgroup in the same pass
+//   k_pencil_dinv      inverse diagonal blocks of A: cK K_ii + cM m_ii I (fixed rows / columns replaced by the identity), symmetric-packed
+// Sums: every producing kernel leaves ONE partial per workgroup and sum (plain stores); k_dyn_reduce adds them in a fixed order (runs of consecutive
+// workgroups per lane, then an ordered two-level tree) and stores the total where the loop reads it. No floating-point atomics; the grids depend on n (and option dyn_grid_cap) only, so two
+// calls add in the same order.
+// Gate: the kernels of iteration `it` are no-ops once scal[4 it + 2] = r.r has met stop[0] (the idiom of the loops in mfh_solver.cpp; the layout of
+// the history -- {r.z, p.Ap, r.r, -} per iteration -- and of the control block is theirs, so that mg_precond's kernels take the same gate).
+#pragma once
+#include "mfh_ctx.hh"
+#include "mfh_device.hh"
+#include "mfh_dispatch.hh"
+
+namespace mfh { namespace k {
+
+namespace {
+
+constexpr int DYN_GRID_CAP = 2048;      // workgroups of k_spmv_kron_acc (k_spmv_kron's cap) and of the PCG's vector kernels at most = rows of the partials buffer
+constexpr int DYN_STEP_CAP = 256;       // workgroups of the three step kernels (once per step: one workgroup per CU is plenty)
+constexpr int DYN_NV = 4;               // sums a kernel may emit (stride of the partials)
+
+struct DynGate { const double *scal; int it; const double *stop; };
+DEV bool dyn_closed(const DynGate &g) {
+    if (!g.scal) return false;
+    const int it = g.it + (int)g.stop[3];
+    return it >= 0 && g.scal[(int64_t)it * 4 + 2] <= g.stop[0];
+}
+
+// the workgroup's sums (valid in thread 0 after block_sum) -> its row of the partials
+template <int NV> DEV void store_partials(double (&v)[NV], double *lds, double *__restrict__ partials) {
+    block_sum<NV>(v, lds);
+    if (threadIdx.x == 0 && partials) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) partials[(int64_t)blockIdx.x * DYN_NV + k] = v[k];
+    }
+}
+
+// second stage, in a fixed order that depends on nPart alone: lane l adds the G = ceil(nPart / 256) consecutive partials [l G, (l + 1) G) in workgroup
+// order, 16 lanes add 16 consecutive lane sums each, one lane adds those 16: dst[t] = scale[t] x the total of column col[t]. (One lane adding 2 048
+// partials one dependent load after the other took 0.3 ms, a tenth of a PCG iteration.)
+struct ReduceArgs {
+    int nPart, nv;
+    int col[DYN_NV];
+    double scale[DYN_NV];
+    double *dst[DYN_NV];
+};
+__global__ void __launch_bounds__(256) k_dyn_reduce(ReduceArgs a, const double *__restrict__ partials, DynGate g) {
+    __shared__ double lane_sum[256], group_sum[16];
+    if (dyn_closed(g)) return;          // (uniform over the workgroup)
+    const int l = threadIdx.x;
+    const int G = (a.nPart + 255) / 256;
+    for (int t = 0; t < a.nv; ++t) {
+        if (!a.dst[t]) continue;        // (uniform)
+        double v = 0.0;
+        const int b1 = min((l + 1) * G, a.nPart);
+        for (int b = l * G; b < b1; ++b) v += partials[(int64_t)b * DYN_NV + a.col[t]];
+        lane_sum[l] = v;
+        __syncthreads();
+        if (l < 16) {
+            double w = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) w += lane_sum[l * 16 + j];
+            group_sum[l] = w;
+        }
+        __syncthreads();
+        if (l == 0) {
+            double w = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) w += group_sum[j];
+            *a.dst[t] = a.scale[t] * w;
+        }
+        __syncthreads();
+    }
+}
+
+// y[N i + c] = cK y[N i + c] + cM sum_j m_ij x[N j + c] (ACC; else cM sum_j ... alone), zero on the fixed rows; partials[blockIdx.x][0] = x . y
+// over the workgroup's rows. The chunk walk and the LDS partials are k_spmv_kron's (mfh_kernels.hip): the lanes take consecutive stored blocks,
+// then one lane per scalar row adds the row's partials in slot order.
+template <int N, bool ACC>
+__global__ void __launch_bounds__(256) k_spmv_kron_acc(SpmvArgs a, double cK, double cM, const double *__restrict__ x, double *y,
+                                                      double *__restrict__ partials, DynGate g) {
+    extern __shared__ __attribute__((aligned(16))) double part[];  // [N][chunkSlots] + 16
+    const int CS = a.chunkSlots;
+    double *red = part + N * CS;
+    if (dyn_closed(g)) return;
+    double dot[1] = {0.0};
+    for (int64_t chunk = blockIdx.x; chunk < a.nChunk; chunk += gridDim.x) {
+        const int r0 = a.chunkRow[chunk], r1 = a.chunkRow[chunk + 1];
+        const int s0 = a.rowPtr[r0];
+        const int ns = a.rowPtr[r1] - s0;
+        for (int t = threadIdx.x; t < ns; t += 256) {
+            const int64_t s = (int64_t)s0 + t;
+            const int64_t col = a.colIdx[s];
+            const double m = a.vals[tiled_index(s, 0, 1)];
+#pragma unroll
+            for (int c = 0; c < N; ++c) part[c * CS + t] = m * x[col * N + c];
+        }
+        __syncthreads();
+        const int nscalar = (r1 - r0) * N;
+        for (int idx = threadIdx.x; idx < nscalar; idx += 256) {
+            const int rl = idx / N, c = idx - rl * N;
+            const int64_t r = r0 + rl;
+            const int b = a.rowPtr[r] - s0, e = a.rowPtr[r + 1] - s0;
+            double v = 0;
+            for (int t = b; t < e; ++t) v += part[c * CS + t];
+            const int64_t gi = r * N + c;
+            v *= cM;
+            if (ACC) v = fma(cK, y[gi], v);
+            if (a.fixedMask && a.fixedMask[gi]) v = 0.0;
+            y[gi] = v;
+            dot[0] = fma(v, x[gi], dot[0]);
+        }
+        __syncthreads();
+    }
+    store_partials<1>(dot, red, partials);
+}
+
+template <int DIM> DEV void sym_block_inverse(const double *A, double *Inv) {
+    if (DIM == 2) {
+        const double det = A[0] * A[3] - A[1] * A[2];
+        Inv[0] = A[3] / det; Inv[1] = -A[1] / det; Inv[2] = -A[2] / det; Inv[3] = A[0] / det;
+    } else {
+        const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
+        const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
+        Inv[0] = c00 / det; Inv[1] = (A[2] * A[7] - A[1] * A[8]) / det; Inv[2] = (A[1] * A[5] - A[2] * A[4]) / det;
+        Inv[3] = c01 / det; Inv[4] = (A[0] * A[8] - A[2] * A[6]) / det; Inv[5] = (A[2] * A[3] - A[0] * A[5]) / det;
+        Inv[6] = c02 / det; Inv[7] = (A[1] * A[6] - A[0] * A[7]) / det; Inv[8] = (A[0] * A[4] - A[1] * A[3]) / det;
+    }
+}
+
+// Inverse diagonal blocks of the pencil operator, in the layout of k_diag_inv (symmetric-packed, flat_idx): cK K_rr + cM m_rr I with the rows and
+// columns of fixed variables replaced by the identity. kVals: K's tiled dense blocks (null with cK == 0), mVals: one value per block; both on
+// the pattern (rowPtr, colIdx), whose columns are sorted within a row.
+template <int DIM>
+__global__ void __launch_bounds__(256) k_pencil_dinv(int64_t nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colIdx,
+                                                    const double *__restrict__ kVals, const double *__restrict__ mVals, double cK, double cM,
+                                                    const uint8_t *__restrict__ fixedMask, double *__restrict__ dinv) {
+    constexpr int NB = DIM * DIM, NS = DIM * (DIM + 1) / 2;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < nRows; r += (int64_t)gridDim.x * 256) {
+        double A[NB], Inv[NB];
+#pragma unroll
+        for (int c = 0; c < NB; ++c) A[c] = (c % (DIM + 1) == 0) ? 1.0 : 0.0;
+        int lo = rowPtr[r], hi = rowPtr[r + 1];
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            const int cv = colIdx[mid];
+            if (cv == r) {
+                const double mrr = cM * mVals[tiled_index(mid, 0, 1)];
+#pragma unroll
+                for (int c = 0; c < NB; ++c) A[c] = (kVals ? cK * kVals[tiled_index(mid, c, NB)] : 0.0) + ((c % (DIM + 1) == 0) ? mrr : 0.0);
+                break;
+            }
+            if (cv < r) lo = mid + 1; else hi = mid;
+        }
+        if (fixedMask) {
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+                if (fixedMask[r * DIM + c]) {
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) { A[c * DIM + d] = 0.0; A[d * DIM + c] = 0.0; }
+                    A[c * DIM + c] = 1.0;
+                }
+        }
+        sym_block_inverse<DIM>(A, Inv);
+#pragma unroll
+        for (int c = 0; c < DIM; ++c)
+#pragma unroll
+            for (int d = c; d < DIM; ++d) dinv[r * NS + flat_idx<DIM>(c, d)] = 0.5 * (Inv[c * DIM + d] + Inv[d * DIM + c]);
+    }
+}
+
+template <int DIM> DEV void apply_packed(const double *__restrict__ Dm, const double *r, double *z) {
+    constexpr int NS = DIM * (DIM + 1) / 2;
+    double m[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) m[q] = Dm[q];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double v = 0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) v += m[flat_idx<DIM>(c, d)] * r[d];
+        z[c] = v;
+    }
+}
+
+int dyn_grid(int64_t n, int cap = DYN_STEP_CAP) { return grid_for(n, cap); }
+
+void launch_reduce(int nPart, int nv, const int *col, const double *scale, double *const *dst, const double *partials, const DynGate &g, hipStream_t s) {
+    ReduceArgs a{};
+    a.nPart = nPart; a.nv = nv;
+    for (int t = 0; t < nv; ++t) { a.col[t] = col[t]; a.scale[t] = scale[t]; a.dst[t] = dst[t]; }
+    hipLaunchKernelGGL(k_dyn_reduce, dim3(1), dim3(256), 0, s, a, partials, g);
+    CHECK_LAUNCH();
+}
+
+// y = cK y + cM M x (acc) or cM M x; the workgroups' x . y in partials[.][0] (null: not wanted). Returns the number of partials.
+int launch_spmv_kron_acc(const SpmvArgs &a, bool acc, double cK, double cM, const double *x, double *y, double *partials, const DynGate &g, hipStream_t s,
+                         int cap = DYN_GRID_CAP) {
+    if (a.nChunk <= 0) return 0;
+    if (a.dim != 2 && a.dim != 3) throw mfh::Error(MFH_ERR_UNSUPPORTED, "k_spmv_kron_acc: 2D / 3D only");
+    const size_t lds = ((size_t)a.dim * a.chunkSlots + 16) * sizeof(double);
+    const int grid = (int)std::min<int64_t>(a.nChunk, std::max(1, std::min(cap, DYN_GRID_CAP)));
+    with_dim(a.dim, [&](auto D) { with_bool(acc, [&](auto ACC) {
+        launch_k(k_spmv_kron_acc<D(), ACC()>, dim3(grid), dim3(256), lds, s, a, cK, cM, x, y, partials, g);
+    }); });
+    CHECK_LAUNCH();
+    return grid;
+}
+
+void launch_pencil_dinv(int dim, int64_t nRows, const int32_t *rowPtr, const int32_t *colIdx, const double *kVals, const double *mVals, double cK, double cM,
+                        const uint8_t *mask, double *dinv, hipStream_t s) {
+    with_dim(dim, [&](auto D) { launch_k(k_pencil_dinv<D()>, dim3(grid_for(nRows)), dim3(256), 0, s, nRows, rowPtr, colIdx, kVals, mVals, cK, cM, mask, dinv); });
+    CHECK_LAUNCH();
+}
+
+}   // namespace
+}}   // namespace mfh::k
+
+namespace mfhi { namespace {
+
+using namespace mfh;
+
+// the context conditions of mfh_newmark (those of mfh_modes, but the set of fixed variables may be empty) and the device state both products need
+void prepare_pencil(mfh_ctx *c, const char *who) {
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "no mesh set");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    if (!(c->op == MFH_OP_ELASTICITY && c->opDegree != 1))
+        throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": the operators are (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
+    if (!(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF)) throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": unpartitioned contexts only");
+    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "2D / 3D meshes");
+}
+
+void upload(double *dst, const double *src, int64_t n, hipStream_t s) { MFH_HIP(hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s)); }
+
+}}   // namespace mfhi

@@ -330,6 +330,39 @@ class Simulator:
         del out["info"]
         return out
 
+    def frequencyResponse(self, omegas, load=None, density=1.0, damping=(0, 0), loss_factor=0.0, probes=None, fields=True, warm_start=True,
+                          rtol=None, maxit=None):
+        """The steady state u^(w) of M u'' + C u' + K u = Re(f^ e^{i w t}) at every w of omegas (rad per unit time), on the device (mfh_harmonic):
+        (K + i w C - w^2 M) u^ = f^ with M = density x the consistent mass matrix (density: a scalar or one value per element, as in transient),
+        C = damping[0] M + damping[1] K plus the structural term i loss_factor K; f^ = neumannLoad() or the per-DoF vector `load` (real or
+        complex: a volume load, a sum of loads). The Dirichlet variables of the applied boundary conditions are the clamp, held at zero.
+        probes: (node, component) pairs. Returns a dict: "u" complex nodal fields [nFreq, nNode, N] (fields=True), "probes" complex
+        [nFreq, len(probes)], "iterations", "true_residuals". self.harmonic_info holds the solver's record."""
+        ctx = self.ctx
+        density = self._density_scalar(density)
+        v, _ = ctx.bc_dirichlet_vars()
+        ctx.clear_fixed()
+        if len(v):
+            ctx.fix_variables(v)
+        mapped = ctx.n_dof != ctx.n_node                   # a DoF map (periodic conditions): every node takes its DoF's value
+        dof = ctx.get_dof_map()[0] if mapped else None
+        f = self.neumannLoad() if load is None else np.asarray(load).reshape(ctx.n_dof, self.N)
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        try:
+            r = ctx.harmonic(omegas, f, density=density, damping=damping, loss_factor=loss_factor, rtol=self.rtol if rtol is None else rtol,
+                             maxit=self.maxit if maxit is None else maxit, probes=pv, fields=fields, warm_start=warm_start)
+        finally:
+            self.harmonic_info = getattr(ctx, "last_harmonic", {}).get("info")
+        out = dict(r)
+        if r["u"] is not None:
+            u = r["u"].reshape(len(r["u"]), ctx.n_dof, self.N)
+            out["u"] = u[:, dof, :] if mapped else u
+        del out["info"]
+        return out
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 
