@@ -861,6 +861,9 @@ mfh_status mfh_get_timing(const mfh_ctx* ctx, mfh_timing* out);
  *   see mfh_dist_get_stats),
  * "symbolic_device", "topology_device", "tl_probe", "tl_host_inverse" (validation variants of setup phases) */
 mfh_status mfh_set_option(mfh_ctx* ctx, const char* key, double value);
+/* the current value of an option of this context (0 / 1 for the on-off options; a forced-degree-1 view is not followed); an unknown key fails like
+ * mfh_set_option's */
+mfh_status mfh_get_option(const mfh_ctx* ctx, const char* key, double* value);
 #ifdef __cplusplus
 }
 #endif

@@ -266,6 +266,7 @@ PROTOTYPES = {
     "mfh_time_geometric_assembly": (_i32, [_P, _i32, _P, _P, _P, _P]),
     "mfh_time_block_gram": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_set_option": (_i32, [_P, C.c_char_p, _f64]),
+    "mfh_get_option": (_i32, [_P, C.c_char_p, C.POINTER(_f64)]),
     "mfh_debug_spd_inverse": (_i32, [_i64, _P]),
     "mfh_debug_spd_inverse_device": (_i32, [_P, _i64, _P]),
     "mfh_debug_device_node_tables": (_i32, [_P, _P, _P]),

@@ -1160,6 +1160,12 @@ class Context:
     def set_option(self, key, value):
         self._ck(self.lib.mfh_set_option(self.h, key.encode(), float(value)))
 
+    def get_option(self, key):
+        """The current value of option `key` of this context (0.0 / 1.0 for the on-off options)."""
+        v = C.c_double()
+        self._ck(self.lib.mfh_get_option(self.h, key.encode(), C.byref(v)))
+        return v.value
+
 
 def sym_measures(field, what, ctx=None):
     """Measures (mask of MEASURE_*) of a field of flattened symmetric matrices [..., flatLen] (tensor shear; flatLen 3: 2D, 6: 3D) on the

@@ -42,9 +42,7 @@ void pack_gather_codes(mfh_ctx *c);
 void invalidate_matrix(mfh_ctx *c) {
     c->dVals32.release();
     c->assembled = false;
-    c->dinvValid = false;
-    c->tl.valid = false;
-    c->mg.valid = false;
+    invalidate_preconditioners(c);
 }
 void drop_mass(mfh_ctx *c) {
     c->dMassVals.release();
@@ -71,8 +69,7 @@ void invalidate_symbolic(mfh_ctx *c) {
     ++c->listsGen;                  // overlap lists of a partitioned solve (Dist::opList) are stale from here on
     c->symValid = false;
     c->mfValid = false;
-    c->mfcValid = false;
-    c->mfClusterUnfit = false;
+    invalidate_cluster(c);
     c->dofUploaded = false;
     invalidate_matrix(c);
 }
@@ -114,9 +111,7 @@ void clear_fixed(mfh_ctx *c) {
     else RawVec<uint8_t>().swap(c->hFixedMask);                // (sized again by the first use: mfh_fix_variables / the first solve)
     c->fixedUploaded = false;
     c->anyFixedNonzero = false;
-    c->dinvValid = false;
-    c->tl.valid = false;
-    c->mg.valid = false;
+    invalidate_preconditioners(c);
 }
 
 void upload_mesh(mfh_ctx *c, bool deviceTables) {
@@ -138,8 +133,7 @@ void upload_mesh(mfh_ctx *c, bool deviceTables) {
     c->timing.upload_ms = now_ms() - t0;
     c->haveMesh = true;
     c->external = false;
-    c->geoValid = false;
-    c->hGeoValid = false;
+    invalidate_geometry(c);
     c->dofForNode.clear();
     c->nDoF = c->mesh.nNode;
     build_shape_tables(c->mesh.dim, c->mesh.deg, c->tables);
@@ -157,8 +151,7 @@ void set_isotropic(mfh_ctx *c, double E, double nu) {
     c->matMode = 0;
     c->matKind = MAT_ISO;
     c->matParams = {lam, E / (2.0 + 2.0 * nu), E, nu};
-    c->geoValid = false;
-    c->hGeoValid = false;
+    invalidate_geometry(c);
     invalidate_matrix(c);
 }
 
@@ -1138,9 +1131,7 @@ void add_fixed(mfh_ctx *c, int64_t n, const int64_t *vars, const double *vals) {
         if (v != 0.0) c->anyFixedNonzero = true;
     }
     c->fixedUploaded = false;
-    c->dinvValid = false;
-    c->tl.valid = false;
-    c->mg.valid = false;
+    invalidate_preconditioners(c);
 }
 
 // element material tensor D (flatLen x flatLen) from the geometry record
@@ -1398,8 +1389,7 @@ mfh_status mfh_mesh_update_vertices(mfh_ctx *c, const double *vertPos) {
     }
     // topology, DoF map, sparsity pattern, gather lists and the matrix-free lists only depend on connectivity: kept
     c->autoStretch = -1.0;
-    c->geoValid = false;
-    c->hGeoValid = false;
+    invalidate_geometry(c);
     sampler_drop(c);                 // the cell grids hold the old positions
     drop_mass(c);
     invalidate_matrix(c);
@@ -1493,7 +1483,7 @@ mfh_status mfh_material_const(mfh_ctx *c, const double *D) {
             for (int cc = r; cc < fl; ++cc) c->matParams.push_back(D[r * fl + cc]);   // upper triangle (_MajorSymmetry)
         c->matMode = 2; c->matKind = MAT_GENERAL;
     }
-    c->geoValid = false; c->hGeoValid = false;
+    invalidate_geometry(c);
     invalidate_matrix(c);
     MFH_CATCH(c)
 }
@@ -1506,7 +1496,7 @@ mfh_status mfh_material_iso_field(mfh_ctx *c, const double *E, const double *nu)
     std::copy(E, E + n, c->matParams.begin());
     std::copy(nu, nu + n, c->matParams.begin() + n);
     c->matMode = 1; c->matKind = MAT_ISO;
-    c->geoValid = false; c->hGeoValid = false;
+    invalidate_geometry(c);
     invalidate_matrix(c);
     MFH_CATCH(c)
 }
@@ -1517,7 +1507,7 @@ mfh_status mfh_material_ortho_field(mfh_ctx *c, const double *params) {
     const int np = c->dim() == 3 ? 9 : 4;
     c->matParams.assign(params, params + (size_t)np * c->mesh.nElem);
     c->matMode = 3; c->matKind = MAT_ORTHO;   // compact record: 6 + 3 (3D) / 3 + 1 (2D) stiffnesses instead of the 21 / 6 of a general D
-    c->geoValid = false; c->hGeoValid = false;
+    invalidate_geometry(c);
     invalidate_matrix(c);
     MFH_CATCH(c)
 }
@@ -1528,7 +1518,7 @@ mfh_status mfh_material_tensor_field(mfh_ctx *c, const double *D) {
     const int fl = flat_len(c->dim());
     c->matParams.assign(D, D + (size_t)fl * fl * c->mesh.nElem);
     c->matMode = 4; c->matKind = MAT_GENERAL;
-    c->geoValid = false; c->hGeoValid = false;
+    invalidate_geometry(c);
     invalidate_matrix(c);
     MFH_CATCH(c)
 }
@@ -1657,7 +1647,7 @@ mfh_status mfh_assemble(mfh_ctx *c, int32_t mode) {
     require(c && c->haveMesh, MFH_ERR_STATE, "no mesh set");
     require(mode == MFH_ASSEMBLE_GATHER || mode == MFH_ASSEMBLE_ATOMIC, MFH_ERR_INVALID, "bad assembly mode");
     require(!(c->deterministic && mode == MFH_ASSEMBLE_ATOMIC), MFH_ERR_UNSUPPORTED, "option deterministic: the global-atomic assembly variant is not reproducible");
-    if (c->alwaysReembed) { c->geoValid = false; c->hGeoValid = false; }
+    if (c->alwaysReembed) invalidate_geometry(c);
     ensure_symbolic(c, mode == MFH_ASSEMBLE_ATOMIC);
     RoctxRange range("Assemble System");
     // embedding kernel and assembly kernel back to back, one synchronisation for both (their times and the embedding's
@@ -2365,100 +2355,6 @@ mfh_status mfh_debug_spd_inverse(int64_t n, double *A) {
     } catch (...) { return MFH_ERR_INVALID; }
 }
 
-mfh_status mfh_set_option(mfh_ctx *c, const char *key, double value) {
-    MFH_TRY(c)
-    require(c && key, MFH_ERR_INVALID, "null argument");
-    const std::string k2(key);
-    // A new option that assembly, the assembled product or the classic PCG reads: a forced-degree-1 view made LATER starts from the copies in
-    // mfh_set_operator_degree -- add the member there too (a view that exists already gets the call forwarded at the end of this function).
-    if (k2 == "asm_chunk_order") { c->asmChunkOrder = (int)value; }
-    else if (k2 == "mg_steps_fine") c->mgSteps0 = std::max(1, (int)value);
-    else if (k2 == "mg_steps_coarse") c->mgSteps1 = std::max(1, (int)value);
-    else if (k2 == "mg_ratio_fine") { require(value > 0 && value < 1, MFH_ERR_INVALID, "mg_ratio_fine must lie in (0, 1)"); c->mgRatio0 = value; }
-    else if (k2 == "mg_ratio_coarse") { require(value > 0 && value < 1, MFH_ERR_INVALID, "mg_ratio_coarse must lie in (0, 1)"); c->mgRatio1 = value; }
-    else if (k2 == "mg_coarse_cycles") c->mgCoarseCycles = std::max(1, (int)value);
-    else if (k2 == "placement_trials") { c->placementTrials = std::max(0, std::min(8, (int)value)); c->placementGen = -1; }
-    else if (k2 == "mg_eig_margin") { require(value >= 1.0, MFH_ERR_INVALID, "mg_eig_margin must be >= 1"); c->mgEigMargin = value; c->mg.valid = false; }
-    else if (k2 == "mg_agg_target") { c->mgAggTarget = std::max(0, (int)value); c->mg.valid = false; }
-    else if (k2 == "mg_coarse_fp32") { c->mgCoarseFp32 = value != 0; c->mg.valid = false; }
-    else if (k2 == "mg_over_correction") { require(value > 0 && value < 4, MFH_ERR_INVALID, "mg_over_correction must lie in (0, 4)"); c->mgOverCorrection = value; }
-    else if (k2 == "mg_dense_max") { c->mgDenseMax = std::max(8, (int)value); c->mg.valid = false; }
-    else if (k2 == "mg_steps_agg") c->mgStepsAgg = std::max(1, (int)value);
-    else if (k2 == "mg_ratio_agg") { require(value > 0 && value < 1, MFH_ERR_INVALID, "mg_ratio_agg must lie in (0, 1)"); c->mgRatioAgg = value; }
-    else if (k2 == "mg_anisotropic_bins") { c->mgAnisotropicBins = value != 0; c->mg.valid = false; }
-    else if (k2 == "mg_agg_nodes") { c->mgAggNodes = std::max(0, (int)value); c->mg.valid = false; }
-    else if (k2 == "mg_replicate_max") { c->mgReplicateMax = std::max(0, (int)value); c->mg.valid = false; }
-    else if (k2 == "asm_packed_codes") { c->asmPackedCodes = value != 0; invalidate_symbolic(c); }
-    else if (k2 == "chunk_slots") { c->chunkSlots = (int)value; invalidate_symbolic(c); }
-    else if (k2 == "contrib_order") { c->contribOrder = (int)value; invalidate_symbolic(c); }
-    else if (k2 == "check_every") { c->checkEvery = std::max(1, (int)value); }
-    else if (k2 == "keep_host_symbolic") { c->keepHostSymbolic = value != 0; }
-    else if (k2 == "reembed") { c->alwaysReembed = value != 0; }
-    else if (k2 == "periodic_ignore_mismatch") { c->periodicIgnoreMismatch = value != 0; }
-    else if (k2 == "solve_homogeneous") { c->solveHomogeneous = value != 0; }
-    else if (k2 == "periodic_ignore_dims") { c->periodicIgnoreDims = (int)value & 7; }
-    else if (k2 == "agg_nodes") { c->aggNodes = (int)value; c->tl.valid = false; }
-    else if (k2 == "topology_device") { c->topologyDevice = value != 0; }
-    else if (k2 == "matrix_storage") {
-        require(value == 0 || value == 1 || value == -1, MFH_ERR_INVALID, "matrix_storage: 0 = both triangles, 1 = blocks (r, c >= r) only, -1 = automatic");
-        c->matrixStorage = (int)value;
-    }
-    else if (k2 == "symbolic_device") { c->symbolicDevice = value != 0; invalidate_symbolic(c); }
-    else if (k2 == "sampler_cell_scale") {
-        require(value > 0 && std::isfinite(value), MFH_ERR_INVALID, "sampler_cell_scale must be positive and finite");
-        c->samplerCellScale = value;
-        sampler_drop(c);
-    }
-    else if (k2 == "xcd_swizzle") c->xcdSwizzle = std::max(0, (int)value);   // 1: contiguous eighths; G > 1: runs of G items per XCD
-    else if (k2 == "pcg_graph") c->useGraph = value != 0;
-    else if (k2 == "refine") c->refine = value != 0;
-    else if (k2 == "mf_geometry_from_vertices") c->mfGeoFromVerts = value != 0;
-    else if (k2 == "mf_xcd_group") c->mfXcdGroup = std::max(0, (int)value);
-    else if (k2 == "vec_grid_cap") k::g_vecGridCap = std::max(256, (int)value);
-    else if (k2 == "dyn_grid_cap") c->dynGridCap = std::max(1, std::min(2048, (int)value));
-    else if (k2 == "harmonic_two_pass") c->harmTwoPass = value != 0;
-    else if (k2 == "mf_lane_stride") c->mfLaneStride = std::max(1, (int)value);
-    else if (k2 == "mf_reorder") { c->mfReorder = value != 0; c->mfcValid = false; c->mfClusterUnfit = false; }
-    else if (k2 == "dist_pcg_variant") c->distPcgVariant = value != 0 ? 1 : 0;
-    else if (k2 == "dist_profile") c->dist.profile = value != 0;
-    else if (k2 == "deterministic") {
-        const bool on = value != 0;
-        if (on && !c->detPartials.p) {
-            require_device(c);
-            MFH_HIP(hipSetDevice(c->device));
-            c->detPartials.alloc((size_t)8 + (size_t)4096 * 4);      // header + 4 096 workgroups x 4 partials (launches with global sums use at most that many
-                                                                     // workgroups in this mode: the one-workgroup second stage reads 16 partials per lane and sum)
-            c->detPartials.zero(c->stream);
-            c->detCounter.alloc(64);
-            c->detCounter.zero(c->stream);
-            MFH_HIP(hipStreamSynchronize(c->stream));
-        }
-        if (on != c->deterministic) { c->deterministic = on; invalidate_matrix(c); destroy_multigrid(c); c->tl.valid = false; c->mfcValid = false; c->mfClusterUnfit = false; }   // (the block size of the cluster operator depends on it)
-    }
-    else if (k2 == "pcg_variant") c->pcgVariant = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    else if (k2 == "mg_batch") c->mgBatch = value != 0;
-    else if (k2 == "mg_fuse") c->mgFuse = value != 0;
-    else if (k2 == "mg_dinv_fp32") c->mgDinvFp32 = value != 0;
-    else if (k2 == "auto_stretch_max") { c->autoStretchMax = value > 1.0 ? value : 1.0; c->autoStretch = -1.0; }
-    else if (k2 == "batch_rhs") { if (c->batchRhs != (value != 0)) { c->mfcValid = false; c->mfClusterUnfit = false; } c->batchRhs = value != 0; }
-    else if (k2 == "matrix_free_mode") { c->mfMode = (int)value; c->mfClusterUnfit = false; }
-    else if (k2 == "mf_block_elems") { c->mfBlockElems = (int)value; c->mfcValid = false; c->mfClusterUnfit = false; }
-    else if (k2 == "mf_chunk_rows") { c->mfChunkRows = std::max(16, std::min(4096, (int)value)); c->mfValid = false; }
-    else if (k2 == "mf_chunk_pairs") { c->mfChunkPairs = std::max(256, (int)value); c->mfValid = false; }
-    else if (k2 == "matrix_free") c->matrixFree = value < 0 ? -1 : (value != 0 ? 1 : 0);   // K x without reading the assembled K (k_spmv_mf)
-    else if (k2 == "tl_rap_agg") { c->tlRapAgg = value != 0; c->tl.valid = false; }
-    else if (k2 == "tl_device_aggregates") { c->tlDeviceAggregates = value != 0; c->tl.valid = false; }
-    else if (k2 == "tl_probe") { c->tlProbe = value != 0; c->tl.valid = false; }
-    else if (k2 == "tl_host_inverse") { c->tlHostInverse = value != 0; c->tl.valid = false; }
-    else throw Error(MFH_ERR_INVALID, "unknown option " + k2);
-    refresh_storage_rule(c);   // matrix_storage, matrix_free, tl_probe, tl_rap_agg decide the storage of K
-    if (c->p1 && k2 != "matrix_free") {          // the forced-degree-1 view follows its context's options (it always multiplies by its assembled matrix)
-        const mfh_status st = mfh_set_option(c->p1, key, value);
-        if (st != MFH_OK) throw Error(st, c->p1->err);
-    }
-    MFH_CATCH(c)
-}
-
 mfh_status mfh_set_operator_degree(mfh_ctx *c, int32_t degree) {
     MFH_TRY(c)
     require(c && (degree == 0 || degree == 1), MFH_ERR_INVALID, "operator degree must be 0 (the mesh's own) or 1");
@@ -2473,10 +2369,10 @@ mfh_status mfh_set_operator_degree(mfh_ctx *c, int32_t degree) {
         mfh_ctx *v = make_linear_context(c, c->mesh.nVert, nullptr, true);
         c->p1 = v;
         c->p1GeoGen = -1;
+        inherit_options(v, c);                           // every option an existing view would have had forwarded, at its current value
         v->matrixFree = 0;                               // the view multiplies by its assembled matrix
-        v->matrixStorage = c->matrixStorage; v->chunkSlots = c->chunkSlots; v->contribOrder = c->contribOrder; v->keepHostSymbolic = c->keepHostSymbolic || c->hostOnly;
-        v->asmPackedCodes = c->asmPackedCodes; v->checkEvery = c->checkEvery; v->useGraph = c->useGraph; v->refine = c->refine; v->pcgVariant = c->pcgVariant;
-        v->precond = c->precond; v->precondAuto = c->precondAuto; v->asmChunkOrder = c->asmChunkOrder;
+        v->keepHostSymbolic = c->keepHostSymbolic || c->hostOnly;
+        v->precond = c->precond; v->precondAuto = c->precondAuto;
         if (c->deterministic) {                          // scratch of its own for the reproducible sums of the calls made on it
             v->deterministic = false;
             const mfh_status st = mfh_set_option(v, "deterministic", 1.0);

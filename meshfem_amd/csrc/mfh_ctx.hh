@@ -14,24 +14,10 @@ struct mfh_ctx {
     int device = 0;
     bool hostOnly = false;            // device == -1: mesh/symbolic host logic only (CPU tests)
     bool hierarchyLevel = false;      // the linear level of another context's multigrid hierarchy (mfh_multigrid.cpp)
-    bool keepHostSymbolic = false;
-    int xcdSwizzle = 0;              // option "xcd_swizzle": XCD-contiguous work mapping in the chunked kernels (measured SLOWER
-                                     // than the round-robin default on MI355X: DESIGN.md section 4.8)
     RawVec<double> hLoad, hX, hXBatch, hLoadBatch;   // host scratch of Simulator::solve (kept between solves; sized with resize_prefaulted: a value-initialising
                                      // resize of 1.4 GB at 119^3 is 0.25 s of single-threaded page faults, twice per first solve)
-    bool alwaysReembed = false;      // option "reembed": every mfh_assemble re-runs the embedding kernel
-    // option "deterministic": run-to-run bit-reproducible assembly, operator and PCG. The reference's scatter into the triplet list is serial
-    // and therefore reproducible (LinearElasticity.hh:1454-1455; the one place that is not, it documents and switches off,
-    // SparseMatrices.hh:288,319-324). Here the default kernels accumulate with LDS / global atomics in whatever order the waves arrive; the
-    // option orders them: the waves of a workgroup add one after the other (k_assemble_gather, k_mf_rows) or into arrays of their own
-    // (k_mf_cluster, k_tl_rap_agg), the dot products go through a fixed two-stage tree (commit_sums), the PCG runs the classic loop; the
-    // transfers and Galerkin products between the aggregate levels of the multigrid hierarchy gather (no atomics) in every mode. All
-    // preconditioners; contexts that own all their rows and row-partitioned ones (whose all-reduce is in rank order with the peer transfers).
-    bool deterministic = false;
-    DBuf<double> detPartials;
+    DBuf<double> detPartials;         // scratch of option "deterministic" (the reproducible global sums)
     DBuf<unsigned> detCounter;
-    bool periodicIgnoreMismatch = false;   // option "periodic_ignore_mismatch": PeriodicCondition(..., ignoreMismatch)
-    int periodicIgnoreDims = 0;            // option "periodic_ignore_dims": bit a set = dimension a is not periodic
     hipStream_t stream = nullptr;
     bool ownStream = true;
     bool arenaCounted = false;          // counted by the device arena (mfh_create of a device context): mfh_destroy reports the close
@@ -77,7 +63,6 @@ struct mfh_ctx {
         double bbMin[3] = {0, 0, 0}, bbMax[3] = {0, 0, 0};   // the mesh's bounding box (set with the element grid)
         DBuf<int32_t> bdryVerts, bdryParent;   // [nBE][dim] vertex ids, [nBE] parent element
     } sampler;
-    double samplerCellScale = 1.0;    // option "sampler_cell_scale": factor on the cell sizes (mean element bounding-box extent per axis)
     std::vector<double> matParams;    // host copy in the layout k_geometry expects
     DBuf<double> dMatParams;
     const double *dMatBorrowed = nullptr;   // linear level of a multigrid hierarchy: the parent's per-element table on the device (the child lives no longer than it)
@@ -109,10 +94,7 @@ struct mfh_ctx {
     // (LinearElasticity.hh assembles i <= j; SURVEY.md 8(d) "upper-only variant, matches reference storage"): 55 of an element's 100
     // blocks, half the bytes. Every consumer that needs K through its diagonal blocks, its stored triangle or the Galerkin product works
     // on it; what multiplies by the stored K (the assembled SpMV) needs both triangles.
-    // Option "matrix_storage": 1 upper, 0 both, -1 (default) automatic = upper exactly when nothing will multiply by the stored K:
-    // elasticity on the matrix-free operator (resolve_upper_storage). upperOnly is the state of the CURRENT symbolic phase.
-    int matrixStorage = -1;
-    bool upperOnly = false;
+    bool upperOnly = false;          // the state of the CURRENT symbolic phase (option "matrix_storage", below, decides the next one)
     int nCU = 256;                    // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     DBuf<uint32_t> dContribCode;
     DBuf<uint16_t> dContribSlot;
@@ -121,8 +103,6 @@ struct mfh_ctx {
     // matrix-free operator (option "matrix_free"): (element, node) pair lists by row chunks
     MfLists mf;
     bool mfValid = false;
-    int matrixFree = -1;              // option "matrix_free": 1 on, 0 off, -1 auto = on for elasticity (quadratic: 6x faster than the assembled SpMV; linear, since
-                                      // the blocks of the cluster operator hold 512-1024 elements: 0.15 against 0.27 ms at 6.3 M tets, 0.033 against 0.040 at 1 M)
     bool use_mf() const {
         if (external || !haveMesh || hostOnly || kron()) return false;
         return matrixFree == 1 || (matrixFree < 0 && op == MFH_OP_ELASTICITY);
@@ -134,29 +114,13 @@ struct mfh_ctx {
     MfClusterLists mfc;               // cluster variant (matrix_free_mode 4)
     MfClusterDev mfcDev;
     bool mfcValid = false;
-    int mfXcdGroup = 32;              // option "mf_xcd_group": every XCD takes runs of this many consecutive element blocks, all eight inside one
-                                      // window (neighbouring blocks share x entries and interface rows in one L2): 0.510 vs 0.527 ms at config 3;
-                                      // the same mapping makes the assembly kernel SLOWER (5.42 vs 5.34 ms) and is not used there
-    bool mfReorder = true;            // option "mf_reorder": the cluster operator walks the elements in Morton order of their centroids
     DBuf<int32_t> dMfElemPerm, dMfElemNodes;   // perm[new] = old, connectivity in the new order
-    int mfLaneStride = 37;            // option "mf_lane_stride": lane t of a block takes element (37 t) % blockElems, so that the lanes of a wave rarely
-                                      // add to the same LDS accumulator at once (operator 0.481 vs 0.519 ms at config 3 in one process; 5, 37, 101 alike)
-    bool mfGeoFromVerts = true;       // option "mf_geometry_from_vertices": constant materials recompute the gradients in the operator
-    int mfBlockElems = 0;             // option "mf_block_elems": elements per block of the cluster variant (0 = 256)
     DBuf<double> dMfSig;              // two-pass operator: per-element nodal forces
-    int mfChunkRows = 256, mfChunkPairs = 2048;   // options "mf_chunk_rows" / "mf_chunk_pairs"
     bool mfClusterUnfit = false;      // element order without locality on this mesh: cluster variant not applicable
     int mfModeEff() const { return (mfMode == 4 && mfClusterUnfit) ? 3 : mfMode; }
-    int mfMode = 4;                   // option "matrix_free_mode": 4 = cluster variant (default: forces of 256 consecutive elements
-                                      // summed in LDS, interface partials only in HBM); 3 = two-pass, forces in list order;
-                                      // 2 = two-pass, forces element-major; 1 = per-pair block evaluation (k_spmv_mf)
 
     // ---- numeric
     DBuf<double> dVals;
-    // Option "placement_trials" (0 default): at the first assembly after a symbolic phase the values buffer is allocated up to N more times and
-    // the assembly kernel timed on each; the fastest stays. Where the driver puts these bytes moves the kernel between 2.9 and 3.3 ms at 5 M
-    // quadratic tets (docs/design/04_2_k_assemble_gather.md (xi)); a caller that assembles hundreds of times may want to pay ~10 ms per trial once.
-    int placementTrials = 0;
     int64_t valsGen = 0, placementGen = -1;       // values buffer (re)allocated by the symbolic phase / generation the trials ran for
     std::vector<double> placementMs;              // kernel time on every candidate of the last trials (first = the buffer of the symbolic phase)
     std::string placementNote;        // why the trials stopped early (empty: they did not)
@@ -191,11 +155,7 @@ struct mfh_ctx {
                                       // (resolve_upper_storage) until the call returns; option matrix_storage itself is not changed
     std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
     std::string dynNote;              // mfh_newmark_info::note of the last mfh_newmark (mfh_dynamics.hip)
-    int dynGridCap = 2048;            // option "dyn_grid_cap" (1 .. 2048): workgroups of the vector kernels of mfh_newmark's PCG loop = partials per sum
-                                      // (the tests set 1, so that the lanes loop on a small mesh); mfh_harmonic's COCG loop reads it too
     std::string harmNote;             // mfh_harmonic_info::note of the last mfh_harmonic (mfh_harmonic.hip)
-    bool harmTwoPass = false;         // option "harmonic_two_pass": the complex mass product as two launches of k_spmv_kron_acc and a combine kernel
-                                      // in place of k_spmv_kron_cacc (what the launcher does by itself where 2 dim planes of partials exceed the LDS)
 
     // ---- constraints (SPSDSystem state)
     std::vector<int64_t> fixedVars;
@@ -206,10 +166,7 @@ struct mfh_ctx {
     DBuf<double> dFixedVal;
     bool fixedUploaded = false;
     bool anyFixedNonzero = false;
-    bool useGraph = true;             // option "pcg_graph": capture blocks of check_every PCG iterations in a hipGraph
     bool tlSuppress = false;          // solve_one: block-Jacobi for this solve (K singular on the free variables)
-    bool refine = true;               // option "refine": iterative refinement when the true residual of a converged solve ends above 2 rtol (solve_one)
-    bool solveHomogeneous = false;    // solve_one: treat the fixed values as 0 (columns of the Schur complement)
 
     // ---- solver
     int precond = MFH_PRECOND_BLOCK_JACOBI;
@@ -217,7 +174,7 @@ struct mfh_ctx {
     // a whole is stretched by more than autoStretchMax (option "auto_stretch_max"), where the two-level preconditioner is the faster one (measured
     // crossover at 8 : 1 : 1, docs/design/04_4c_multigrid.md). autoStretch < 0: not looked at yet (new vertices).
     bool precondAuto = false;
-    double autoStretch = -1.0, autoStretchMax = 8.0;
+    double autoStretch = -1.0;
     DBuf<double> dDinv;
     bool dinvValid = false;
     DBuf<float> dDinv32;              // FP32 copy of dDinv for the multigrid smoother's fused kernels (smoother_dinv32)
@@ -282,36 +239,9 @@ struct mfh_ctx {
         DBuf<double> relPos2, denseInv;
         int64_t denseM = 0, denseLd = 0;
     } mg;
-    int mgSteps0 = 1, mgSteps1 = 1;                  // options "mg_steps_fine" / "mg_steps_coarse": Chebyshev steps before and after the coarse correction
-    double mgRatio0 = 0.3, mgRatio1 = 0.3;           // options "mg_ratio_fine" / "mg_ratio_coarse": the smoothers act on [ratio lambda_max, lambda_max]
-    int mgCoarseCycles = 1;                          // option "mg_coarse_cycles": cycles of the linear level per application
-    double mgEigMargin = 1.1;                        // option "mg_eig_margin": factor on the power-iteration estimates of lambda_max
-    int mgAggTarget = 32, mgDenseMax = 1200;         // options "mg_agg_target" (DoFs of the linear level per finest aggregate; 0: no aggregate hierarchy),
-                                                     // "mg_dense_max" (aggregates of the level that is inverted densely)
-    bool mgCoarseFp32 = true;                        // option "mg_coarse_fp32": inside the multigrid preconditioner the assembled operator of the linear level and the
-                                                     // stencil operators of the aggregate levels are READ from FP32 copies (products and sums in FP64): those kernels are
-                                                     // bound by the matrix bytes, and a smoother / coarse correction needs no more than single precision of its matrix
-    double mgOverCorrection = 1.5;                   // option "mg_over_correction": factor on the corrections prolonged from aggregate levels (piecewise-rigid
-                                                     // coarse functions under-estimate smooth corrections; the cycle stays symmetric)
-    int mgStepsAgg = 2; double mgRatioAgg = 0.2;     // options "mg_steps_agg" / "mg_ratio_agg": Chebyshev smoother of the aggregate levels
-    int mgReplicateMax = 4096;                       // option "mg_replicate_max": row-partitioned contexts partition the aggregate levels with MORE aggregates than this
-                                                     // (stencil rows dealt out with the DoFs, one halo exchange per application); smaller levels are replicated on
-                                                     // every rank and summed with one small all-reduce. 0: every level replicated (rounds 3-4)
-    bool mgAnisotropicBins = false;                  // option "mg_anisotropic_bins": lattice bins of the aggregate levels with the elements' proportions (measured: no gain, DESIGN 4.4c)
-    int mgAggNodes = 0;                              // option "mg_agg_nodes": target DoFs per aggregate of the linear level's coarse space (0 = auto)
     // Chronopoulos-Gear PCG (mfh_solver.cpp): NR interleaved vectors
     DBuf<double> cgU, cgW, cgP, cgS, cgX, cgR, cgF, cgCtl, tlRcN, tlYcN;
     DBuf<double> wNodeField;          // nodal fields on their way to the host (dofToNodeField on the device, solve_multigrid_batch)
-    int pcgVariant = -1;              // option "pcg_variant": 1 = Chronopoulos-Gear, 0 = classic PCG, -1 (default) = classic for one
-                                      // right-hand side on an unpartitioned context (measured 6-14 % faster per iteration there: one
-                                      // vector pass fewer), Chronopoulos-Gear for batches and row-partitioned contexts
-    int distPcgVariant = 1;           // option "dist_pcg_variant": 1 = Chronopoulos-Gear (one all-reduce per iteration, default), 0 = classic
-                                      // (two all-reduces, one vector pass less per iteration)
-    bool mgDinvFp32 = true;           // option "mg_dinv_fp32": the fused kernels of mg_fuse read an FP32 copy of the quadratic level's inverse diagonal blocks (smoother only)
-    bool mgFuse = true;               // option "mg_fuse": the PCG loop's residual update / r.z share kernels with the V-cycle's first / last smoothing step (MgFuse)
-    bool mgBatch = true;              // option "mg_batch": several right-hand sides under the multigrid preconditioner share the linear and aggregate levels of
-                                      // every V-cycle (solve_multigrid_batch); 0: one right-hand side at a time
-    bool batchRhs = false;            // option "batch_rhs": several right-hand sides per operator pass (measured slower than one at a time, DESIGN.md 4.5a)
     // row-partitioned solve (mfh_dist_setup)
     struct Dist {
         mfh_comm *comm = nullptr;     // not owned
@@ -342,15 +272,7 @@ struct mfh_ctx {
         int profiled = 0;
     } dist;
     int64_t listsGen = 0;             // bumped whenever the element blocks of the cluster operator or the SpMV row chunks are rebuilt
-    int aggNodes = 0;                 // option "agg_nodes": target DoFs per aggregate (0 = auto)
-    bool topologyDevice = true;       // option "topology_device": edge numbering + boundary extraction by device radix sorts
-    bool symbolicDevice = true;       // option "symbolic_device": build pattern + gather lists on the GPU (element-major order)
-    bool tlRapAgg = true;             // option "tl_rap_agg": aggregate-centric Galerkin kernel (0: one wave per row, validation)
-    bool tlDeviceAggregates = true;   // option "tl_device_aggregates": build the aggregates on the device (0: host, validation)
-    bool tlProbe = false;             // option "tl_probe": build the coarse operator by SpMV probing (validation)
-    bool tlHostInverse = false;       // option "tl_host_inverse": invert the coarse operator on the host (validation)
     std::string precondNote;
-    int checkEvery = 50;
 
     // ---- Simulator-level boundary conditions
     std::vector<double> neumannTraction;   // nBE x dim
@@ -358,16 +280,105 @@ struct mfh_ctx {
     RawVec<double> dirVal;                 // nBdryNodes x dim
     std::vector<std::pair<int64_t, std::array<double, 3>>> deltaForces;
 
-    // ---- options
-    int asmChunkOrder = 0;           // option "asm_chunk_order": 1 = the assembly visits the row chunks in the order of the elements they gather
-                                     // from (an element's contributions then meet in time, its record is fetched once); 0 = in row order
-    DBuf<int32_t> dChunkOrder;
-    int64_t chunkOrderGen = -1;      // listsGen the order was built from
-    bool asmPackedCodes = true;      // option "asm_packed_codes": the device copy of the gather codes is chunk-relative and packed (k_assemble_gather)
-    bool codesPacked = false;        // state of dContribCode
-    DBuf<int32_t> dChunkElemBase;
+    // ---- options (mfh_set_option / mfh_get_option): one row each in the table of mfh_options.cpp, declared here in the order of that table
+    // -- context, mesh
+    bool keepHostSymbolic = false;
+    int xcdSwizzle = 0;              // option "xcd_swizzle": XCD-contiguous work mapping in the chunked kernels (measured SLOWER
+                                     // than the round-robin default on MI355X: DESIGN.md section 4.8)
+    bool alwaysReembed = false;      // option "reembed": every mfh_assemble re-runs the embedding kernel
+    // option "deterministic": run-to-run bit-reproducible assembly, operator and PCG. The reference's scatter into the triplet list is serial
+    // and therefore reproducible (LinearElasticity.hh:1454-1455; the one place that is not, it documents and switches off,
+    // SparseMatrices.hh:288,319-324). Here the default kernels accumulate with LDS / global atomics in whatever order the waves arrive; the
+    // option orders them: the waves of a workgroup add one after the other (k_assemble_gather, k_mf_rows) or into arrays of their own
+    // (k_mf_cluster, k_tl_rap_agg), the dot products go through a fixed two-stage tree (commit_sums), the PCG runs the classic loop; the
+    // transfers and Galerkin products between the aggregate levels of the multigrid hierarchy gather (no atomics) in every mode. All
+    // preconditioners; contexts that own all their rows and row-partitioned ones (whose all-reduce is in rank order with the peer transfers).
+    bool deterministic = false;
+    bool periodicIgnoreMismatch = false;   // option "periodic_ignore_mismatch": PeriodicCondition(..., ignoreMismatch)
+    int periodicIgnoreDims = 0;            // option "periodic_ignore_dims": bit a set = dimension a is not periodic
+    bool topologyDevice = true;       // option "topology_device": edge numbering + boundary extraction by device radix sorts
+    double samplerCellScale = 1.0;    // option "sampler_cell_scale": factor on the cell sizes (mean element bounding-box extent per axis)
+    // -- symbolic phase, assembly
+    bool symbolicDevice = true;       // option "symbolic_device": build pattern + gather lists on the GPU (element-major order)
+    // Option "matrix_storage": 1 upper, 0 both, -1 (default) automatic = upper exactly when nothing will multiply by the stored K:
+    // elasticity on the matrix-free operator (resolve_upper_storage).
+    int matrixStorage = -1;
     int chunkSlots = 256;            // assembly chunks: 18 KB of LDS accumulators, 8 workgroups per CU
     int contribOrder = 1;            // element-major: 12% faster than rank-major on MI355X (profiles/r01_assembly_variants.md)
+    bool asmPackedCodes = true;      // option "asm_packed_codes": the device copy of the gather codes is chunk-relative and packed (k_assemble_gather)
+    int asmChunkOrder = 0;           // option "asm_chunk_order": 1 = the assembly visits the row chunks in the order of the elements they gather
+                                     // from (an element's contributions then meet in time, its record is fetched once); 0 = in row order
+    // Option "placement_trials" (0 default): at the first assembly after a symbolic phase the values buffer is allocated up to N more times and
+    // the assembly kernel timed on each; the fastest stays. Where the driver puts these bytes moves the kernel between 2.9 and 3.3 ms at 5 M
+    // quadratic tets (docs/design/04_2_k_assemble_gather.md (xi)); a caller that assembles hundreds of times may want to pay ~10 ms per trial once.
+    int placementTrials = 0;
+    // -- matrix-free operator
+    int matrixFree = -1;              // option "matrix_free": 1 on, 0 off, -1 auto = on for elasticity (quadratic: 6x faster than the assembled SpMV; linear, since
+                                      // the blocks of the cluster operator hold 512-1024 elements: 0.15 against 0.27 ms at 6.3 M tets, 0.033 against 0.040 at 1 M)
+    int mfMode = 4;                   // option "matrix_free_mode": 4 = cluster variant (default: forces of 256 consecutive elements
+                                      // summed in LDS, interface partials only in HBM); 3 = two-pass, forces in list order;
+                                      // 2 = two-pass, forces element-major; 1 = per-pair block evaluation (k_spmv_mf)
+    int mfBlockElems = 0;             // option "mf_block_elems": elements per block of the cluster variant (0 = chosen by ensure_mf_cluster: 512, 1 024 for
+                                      // large linear meshes, 256 under "deterministic" / "batch_rhs")
+    bool mfReorder = true;            // option "mf_reorder": the cluster operator walks the elements in Morton order of their centroids
+    int mfXcdGroup = 32;              // option "mf_xcd_group": every XCD takes runs of this many consecutive element blocks, all eight inside one
+                                      // window (neighbouring blocks share x entries and interface rows in one L2): 0.510 vs 0.527 ms at config 3;
+                                      // the same mapping makes the assembly kernel SLOWER (5.42 vs 5.34 ms) and is not used there
+    int mfLaneStride = 37;            // option "mf_lane_stride": lane t of a block takes element (37 t) % blockElems, so that the lanes of a wave rarely
+                                      // add to the same LDS accumulator at once (operator 0.481 vs 0.519 ms at config 3 in one process; 5, 37, 101 alike)
+    bool mfGeoFromVerts = true;       // option "mf_geometry_from_vertices": constant materials recompute the gradients in the operator
+    int mfChunkRows = 256, mfChunkPairs = 2048;   // options "mf_chunk_rows" / "mf_chunk_pairs"
+    // -- vector kernels (option "vec_grid_cap" is the process-wide k::g_vecGridCap)
+    int dynGridCap = 2048;            // option "dyn_grid_cap" (1 .. 2048): workgroups of the vector kernels of mfh_newmark's PCG loop = partials per sum
+                                      // (the tests set 1, so that the lanes loop on a small mesh); mfh_harmonic's COCG loop reads it too
+    bool harmTwoPass = false;         // option "harmonic_two_pass": the complex mass product as two launches of k_spmv_kron_acc and a combine kernel
+                                      // in place of k_spmv_kron_cacc (what the launcher does by itself where 2 dim planes of partials exceed the LDS)
+    // -- PCG (option "dist_profile" is Dist::profile)
+    int checkEvery = 50;
+    bool useGraph = true;             // option "pcg_graph": capture blocks of check_every PCG iterations in a hipGraph
+    bool refine = true;               // option "refine": iterative refinement when the true residual of a converged solve ends above 2 rtol (solve_one)
+    bool solveHomogeneous = false;    // solve_one: treat the fixed values as 0 (columns of the Schur complement)
+    int pcgVariant = -1;              // option "pcg_variant": 1 = Chronopoulos-Gear, 0 = classic PCG, -1 (default) = classic for one
+                                      // right-hand side on an unpartitioned context (measured 6-14 % faster per iteration there: one
+                                      // vector pass fewer), Chronopoulos-Gear for batches and row-partitioned contexts
+    int distPcgVariant = 1;           // option "dist_pcg_variant": 1 = Chronopoulos-Gear (one all-reduce per iteration, default), 0 = classic
+                                      // (two all-reduces, one vector pass less per iteration)
+    bool batchRhs = false;            // option "batch_rhs": several right-hand sides per operator pass (measured slower than one at a time, DESIGN.md 4.5a)
+    double autoStretchMax = 8.0;      // option "auto_stretch_max" (see precondAuto)
+    // -- two-level preconditioner
+    int aggNodes = 0;                 // option "agg_nodes": target DoFs per aggregate (0 = auto)
+    bool tlRapAgg = true;             // option "tl_rap_agg": aggregate-centric Galerkin kernel (0: one wave per row, validation)
+    bool tlDeviceAggregates = true;   // option "tl_device_aggregates": build the aggregates on the device (0: host, validation)
+    bool tlProbe = false;             // option "tl_probe": build the coarse operator by SpMV probing (validation)
+    bool tlHostInverse = false;       // option "tl_host_inverse": invert the coarse operator on the host (validation)
+    // -- multigrid preconditioner
+    int mgSteps0 = 1, mgSteps1 = 1;                  // options "mg_steps_fine" / "mg_steps_coarse": Chebyshev steps before and after the coarse correction
+    double mgRatio0 = 0.3, mgRatio1 = 0.3;           // options "mg_ratio_fine" / "mg_ratio_coarse": the smoothers act on [ratio lambda_max, lambda_max]
+    int mgCoarseCycles = 1;                          // option "mg_coarse_cycles": cycles of the linear level per application
+    double mgEigMargin = 1.1;                        // option "mg_eig_margin": factor on the power-iteration estimates of lambda_max
+    int mgAggTarget = 32, mgDenseMax = 1200;         // options "mg_agg_target" (DoFs of the linear level per finest aggregate; 0: no aggregate hierarchy),
+                                                     // "mg_dense_max" (aggregates of the level that is inverted densely)
+    bool mgCoarseFp32 = true;                        // option "mg_coarse_fp32": inside the multigrid preconditioner the assembled operator of the linear level and the
+                                                     // stencil operators of the aggregate levels are READ from FP32 copies (products and sums in FP64): those kernels are
+                                                     // bound by the matrix bytes, and a smoother / coarse correction needs no more than single precision of its matrix
+    double mgOverCorrection = 1.5;                   // option "mg_over_correction": factor on the corrections prolonged from aggregate levels (piecewise-rigid
+                                                     // coarse functions under-estimate smooth corrections; the cycle stays symmetric)
+    int mgStepsAgg = 2; double mgRatioAgg = 0.2;     // options "mg_steps_agg" / "mg_ratio_agg": Chebyshev smoother of the aggregate levels
+    int mgReplicateMax = 4096;                       // option "mg_replicate_max": row-partitioned contexts partition the aggregate levels with MORE aggregates than this
+                                                     // (stencil rows dealt out with the DoFs, one halo exchange per application); smaller levels are replicated on
+                                                     // every rank and summed with one small all-reduce. 0: every level replicated (rounds 3-4)
+    bool mgAnisotropicBins = false;                  // option "mg_anisotropic_bins": lattice bins of the aggregate levels with the elements' proportions (measured: no gain, DESIGN 4.4c)
+    int mgAggNodes = 0;                              // option "mg_agg_nodes": target DoFs per aggregate of the linear level's coarse space (0 = auto)
+    bool mgDinvFp32 = true;           // option "mg_dinv_fp32": the fused kernels of mg_fuse read an FP32 copy of the quadratic level's inverse diagonal blocks (smoother only)
+    bool mgFuse = true;               // option "mg_fuse": the PCG loop's residual update / r.z share kernels with the V-cycle's first / last smoothing step (MgFuse)
+    bool mgBatch = true;              // option "mg_batch": several right-hand sides under the multigrid preconditioner share the linear and aggregate levels of
+                                      // every V-cycle (solve_multigrid_batch); 0: one right-hand side at a time
+
+    // ---- assembly lists
+    DBuf<int32_t> dChunkOrder;
+    int64_t chunkOrderGen = -1;      // listsGen the order was built from
+    bool codesPacked = false;        // state of dContribCode
+    DBuf<int32_t> dChunkElemBase;
     mfh_timing timing{0, 0, 0, 0};
 
     int dim() const { return mesh.dim; }
@@ -470,6 +481,12 @@ inline void require_full_storage(const mfh_ctx *c, const char *what) {
 
 inline int32_t dof_of(const mfh_ctx *c, int64_t node) { return c->dofForNode.empty() ? (int32_t)node : c->dofForNode[node]; }
 void invalidate_matrix(mfh_ctx *c);
+void invalidate_symbolic(mfh_ctx *c);
+// the invalidation groups that recur: each names ALL the flags of one piece of derived state (a site that clears only part of a group spells that part out)
+inline void invalidate_preconditioners(mfh_ctx *c) { c->dinvValid = false; c->tl.valid = false; c->mg.valid = false; }   // inverse diagonal blocks, two-level, multigrid
+inline void invalidate_geometry(mfh_ctx *c) { c->geoValid = false; c->hGeoValid = false; }                               // element records and their host copy
+inline void invalidate_cluster(mfh_ctx *c) { c->mfcValid = false; c->mfClusterUnfit = false; }                           // element blocks of the cluster operator and the verdict on them
+void inherit_options(mfh_ctx *view, const mfh_ctx *parent);   // mfh_options.cpp: a new forced-degree-1 view starts from its context's options
 void drop_mass(mfh_ctx *c);            // the resident mass buffer describes the previous pattern / vertex positions
 void clear_density(mfh_ctx *c);        // back to unit density (mfh_set_density(NULL), a new mesh)
 void ensure_mass(mfh_ctx *c);          // dMassVals of the current pattern, element records and density field (both triangles required)
