@@ -675,6 +675,31 @@ mfh_status mfh_buckling(mfh_ctx* ctx, int32_t nev, int32_t flags /* 0 */, double
                         double* factors /* nev */, double* X /* nev x dim*nDoF, row per mode */, double* residuals /* nev or NULL */,
                         mfh_buckling_info* info);
 
+/* ---------------------------------------------------------------- prestressed vibration: the modes of (K + s Kg, density M)
+ * (docs/design/04_18_prestressed_modes.md.) The frequencies of the clamped body UNDER the load whose stress is the prestress field in force
+ * (mfh_set_prestress / mfh_prestress_from_displacement), at the multiple s = loadFactor of it: tension stiffens, compression softens, and the
+ * first eigenvalue falls to zero as s reaches the critical factor of mfh_buckling. The reference has no counterpart.
+ *   mfh_modes_prestressed   the nev (1 .. 20) smallest eigenpairs of (K + loadFactor Kg) x = lambda density M x: K, M, density and the density field
+ *                        as in mfh_modes, Kg as in mfh_geometric_apply. The LOBPCG loop of mfh_modes on this pencil with the context's
+ *                        preconditioner of K; convergence at ||A x - lambda M x||_2 / (|lambda| ||M x||_2) <= rtol; the outputs as mfh_modes
+ *                        returns them (lambda ascending, rows of X M-orthonormal with the entry of largest modulus positive, zero at the fixed
+ *                        variables, which must leave no rigid motion free). Only M is factored, so K + loadFactor Kg may be indefinite: beyond the
+ *                        critical load the eigenvalues come out negative, are returned as they are, and info->note says how many and that the
+ *                        prestressed state is unstable at this factor. X0 (may be NULL): nev rows that replace the first nev columns of the start
+ *                        block (masked, then M-orthonormalised and Rayleigh-Ritz'ed with the rest): the shapes of a neighbouring load factor make
+ *                        a sweep cheap. maxit reached: MFH_ERR_NOT_CONVERGED with the outputs filled. MFH_ERR_INVALID: what mfh_modes calls
+ *                        invalid, a load factor or an entry of X0 that is not finite. MFH_ERR_UNSUPPORTED: flags != 0 -- in particular
+ *                        MFH_MODES_FREE: rigid rotations are not in the kernel of Kg, so the known-kernel variant does not apply --, a clamp that
+ *                        leaves rigid motions free, and what mfh_buckling calls unsupported. MFH_ERR_STATE: as mfh_buckling. All refusals come
+ *                        before any device work that changes state. Like mfh_modes the call holds both triangles of the pattern for its own
+ *                        duration (info->note says so).
+ *   mfh_tangent_apply    y = (K + loadFactor Kg) x on displacement vectors (dim*nDoF, under the context's DoF map), no fixed variables masked; x and
+ *                        y must not overlap. The contract, the contexts and the cost note of mfh_geometric_apply. */
+mfh_status mfh_modes_prestressed(mfh_ctx* ctx, int32_t nev, double density, double loadFactor, int32_t flags /* 0 */, double rtol, int32_t maxit,
+                                 const double* X0 /* nev x dim*nDoF or NULL */, double* lambda /* nev */, double* X /* nev x dim*nDoF, row per mode */,
+                                 double* residuals /* nev or NULL */, mfh_modes_info* info);
+mfh_status mfh_tangent_apply(mfh_ctx* ctx, double loadFactor, const double* x /* dim*nDoF */, double* y /* dim*nDoF */, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+
 /* ---------------------------------------------------------------- multi-GPU solve (one process per GPU)
  * The reference is single-process (TBB, Parallelism.hh:31-43): these entry points have no counterpart to cite beyond the
  * serial path they parallelise (Simulator::solve, LinearElasticity.hh:479-487; SPSDSystem::solve, SparseMatrices.hh:2515-2606).

@@ -22,6 +22,10 @@ mfh_status mfh_time_mass_assembly(mfh_ctx* ctx, int32_t reps, double* unit_ms /*
  * of the pattern (option "matrix_storage" 0 on quadratic meshes). */
 mfh_status mfh_time_geometric_assembly(mfh_ctx* ctx, int32_t reps, double* laplace_ms /* reps */, double* mass_ms /* reps */, double* geom_ms /* reps */,
                                        double* geom_det_ms /* reps */);
+/* average device time (ms) of one pair product of the prestressed loop (yA += s Kg x, yB = rho M x on hashed vectors) over `reps` launches: the single
+ * pass k_spmv_kron_pair, and the two launches (plus the density scaling) it replaces, in alternating groups after a warm-up of both
+ * (scripts/probe_prestressed_modes.py). Needs a prestress field; holds both triangles of the pattern for its own duration. */
+mfh_status mfh_time_kron_pair(mfh_ctx* ctx, int32_t reps, double* pair_ms, double* separate_ms);
 /* the same for one application of the operator the PCG uses (see "matrix_free") on internal scratch vectors */
 mfh_status mfh_time_spmv_kernel(mfh_ctx* ctx, int32_t reps, double* avg_ms);
 /* average device time (ms) of `reps` back-to-back k_block_gram calls (both stages) on hashed n x p and n x q blocks, and of `reps` device-to-device
@@ -104,6 +108,10 @@ mfh_status mfh_debug_pencil_apply(mfh_ctx* ctx, double cK, double cM, int32_t ma
  * {Re, Im} of the unconjugated x^T y from the kernel's partials. zK == 0 skips the K products */
 mfh_status mfh_debug_harmonic_apply(mfh_ctx* ctx, double zKre, double zKim, double zMre, double zMim, int32_t masked, const double* xRe, const double* xIm,
                                     double* yRe, double* yIm, double* dot);
+/* the pair product of mfh_modes_prestressed through the launcher its loop uses: yA (in: any vector, out: yA + s Kg x) and yB = rho M x (M with the
+ * density field in force), rows of fixed variables zeroed in both if masked != 0. k_spmv_kron_pair, or, if twoPass != 0 (or where its LDS does not
+ * fit), k_spmv_kron_acc on the geometric buffer followed by k_spmv_kron on the mass buffer and the density scaling */
+mfh_status mfh_debug_kron_pair(mfh_ctx* ctx, double s, double rho, int32_t masked, int32_t twoPass, const double* x, double* yA, double* yB);
 
 
 /* ---------------------------------------------------------------- device-pointer building blocks

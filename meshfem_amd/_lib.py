@@ -218,6 +218,8 @@ PROTOTYPES = {
     "mfh_prestress_from_displacement": (_i32, [_P, _P, _i32]),
     "mfh_geometric_apply": (_i32, [_P, _P, _P, _i32]),
     "mfh_buckling": (_i32, [_P, _i32, _i32, _f64, _i32, _P, _P, _P, C.POINTER(BucklingInfo)]),
+    "mfh_modes_prestressed": (_i32, [_P, _i32, _f64, _f64, _i32, _f64, _i32, _P, _P, _P, _P, C.POINTER(ModesInfo)]),
+    "mfh_tangent_apply": (_i32, [_P, _f64, _P, _P, _i32]),
     "mfh_newmark": (_i32, [_P, C.POINTER(NewmarkParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(NewmarkInfo)]),
     "mfh_harmonic": (_i32, [_P, C.POINTER(HarmonicParams), _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(HarmonicInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
@@ -264,6 +266,7 @@ PROTOTYPES = {
     "mfh_time_spmv_kernel": (_i32, [_P, _i32, C.POINTER(_f64)]),
     "mfh_time_mass_assembly": (_i32, [_P, _i32, _P, _P]),
     "mfh_time_geometric_assembly": (_i32, [_P, _i32, _P, _P, _P, _P]),
+    "mfh_time_kron_pair": (_i32, [_P, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_time_block_gram": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_set_option": (_i32, [_P, C.c_char_p, _f64]),
     "mfh_get_option": (_i32, [_P, C.c_char_p, C.POINTER(_f64)]),
@@ -284,6 +287,7 @@ PROTOTYPES = {
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),
     "mfh_debug_pencil_apply": (_i32, [_P, _f64, _f64, _i32, _P, _P, _P]),
+    "mfh_debug_kron_pair": (_i32, [_P, _f64, _f64, _i32, _i32, _P, _P, _P]),
     "mfh_debug_harmonic_apply": (_i32, [_P, _f64, _f64, _f64, _f64, _i32, _P, _P, _P, _P, _P]),
 }
 

@@ -590,6 +590,54 @@ class Context:
         self._ck(st)
         return fac, X, d
 
+    # ---------------------------------------------------------------- prestressed vibration (docs/design/04_18_prestressed_modes.md)
+    def modes_prestressed(self, nev, load_factor, density=1.0, x0=None, rtol=1e-6, maxit=500):
+        """(lam, X, info): the nev smallest eigenpairs of (K + load_factor Kg) x = lam density M x on the clamped context (mfh_modes_prestressed),
+        Kg the geometric stiffness of the prestress field. lam ascending -- negative beyond the critical load, info["note"] then says how many;
+        X: [nev, dim * n_dof], rows M-orthonormal; x0: [nev, dim * n_dof] shapes to start from (those of a neighbouring load factor).
+        info["residuals"] holds ||A x - lam M x|| / (|lam| ||M x||) per mode. Raises on MFH_ERR_NOT_CONVERGED like solve(); what was reached is
+        then in self.last_modes_prestressed = (lam, X, info)."""
+        nev = int(nev)
+        n = self.bs * self.n_dof
+        lam, X, res = np.zeros(max(nev, 0)), np.zeros((max(nev, 0), n)), np.zeros(max(nev, 0))
+        if x0 is not None:
+            x0 = as_f64(x0)
+            if x0.size != max(nev, 0) * n:
+                raise ValueError("x0: [nev, dim * n_dof] = [%d, %d]" % (nev, n))
+        info = L.ModesInfo()
+        st = self.lib.mfh_modes_prestressed(self.h, nev, float(density), float(load_factor), 0, float(rtol), int(maxit),
+                                            None if x0 is None else ptr(x0), ptr(lam), ptr(X), ptr(res), C.byref(info))
+        d = info.as_dict()
+        d["residuals"] = res
+        self.last_modes_prestressed = (lam, X, d)
+        self._ck(st)
+        return lam, X, d
+
+    def tangent_apply(self, x, load_factor, out=None):
+        """y = (K + load_factor Kg) x on a displacement vector of dim * n_dof entries (mfh_tangent_apply), no fixed variables masked. Returns an
+        array of x's shape (out: a C-contiguous float64 array to write)."""
+        x = as_f64(x)
+        n = self.dim * self.n_dof
+        if x.size != n:
+            raise ValueError("tangent_apply: x needs dim * n_dof = %d entries, got %d" % (n, x.size))
+        if out is None:
+            out = np.empty(x.shape)
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size != n or np.shares_memory(out, x):
+            raise ValueError("out: a C-contiguous float64 array of dim * n_dof values that does not overlap x")
+        self._ck(self.lib.mfh_tangent_apply(self.h, float(load_factor), ptr(x), ptr(out), 0))
+        return out
+
+    def debug_kron_pair(self, s, rho, x, yA, masked=True, two_pass=False):
+        """(yA + s Kg x, rho M x) through the launcher of the prestressed loop (test hook mfh_debug_kron_pair): k_spmv_kron_pair, or with
+        two_pass the two launches it replaces."""
+        x = as_f64(x)
+        a = np.array(as_f64(yA), dtype=np.float64).reshape(-1)
+        b = np.empty(self.bs * self.n_dof)
+        if x.size != b.size or a.size != b.size:
+            raise ValueError("x, yA: dim * n_dof = %d entries" % b.size)
+        self._ck(self.lib.mfh_debug_kron_pair(self.h, float(s), float(rho), 1 if masked else 0, 1 if two_pass else 0, ptr(x), ptr(a), ptr(b)))
+        return a, b
+
     def debug_newmark_predict(self, dt, beta, gamma, density, damping, u, v, a, mask=None, want_xk=True):
         """(ut, vt, xm, xk) of k_newmark_predict on host arrays (test hook mfh_debug_newmark_predict)."""
         u, v, a = as_f64(u), as_f64(v), as_f64(a)
@@ -1156,6 +1204,12 @@ class Context:
         g, cp = C.c_double(), C.c_double()
         self._ck(self.lib.mfh_time_block_gram(self.h, int(n), int(p), int(q), int(reps), C.byref(g), C.byref(cp)))
         return g.value, cp.value
+
+    def time_kron_pair(self, reps=40):
+        """(pair_ms, separate_ms): one pair product of the prestressed loop as k_spmv_kron_pair and as the two launches it replaces (mfh_time_kron_pair)."""
+        a, b = C.c_double(), C.c_double()
+        self._ck(self.lib.mfh_time_kron_pair(self.h, int(reps), C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_option(self, key, value):
         self._ck(self.lib.mfh_set_option(self.h, key.encode(), float(value)))

@@ -20,8 +20,6 @@ namespace mfh { namespace k {
 
 namespace {
 
-constexpr size_t HARM_LDS_MAX = 160 * 1024;     // what a workgroup of gfx950 can be granted (launch_k asks for anything above 64 KB)
-
 struct Cx { double re, im; };
 DEV Cx cmul(const Cx &a, const Cx &b) { return Cx{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
 DEV Cx cdiv(const Cx &a, const Cx &b) {

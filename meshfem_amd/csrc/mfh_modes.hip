@@ -8,9 +8,11 @@
 //                   wave-uniform scalar loads. One launch serves the vectors and their K- and M-images (blockIdx.y).
 //   k_block_residual  R = KX - MX diag(lambda) with the column norms of R and MX through the same two stages
 //   host            Cholesky-QR coefficients, Rayleigh-Ritz (sym_gen_eig: Cholesky reduction + cyclic Jacobi, <= 72 x 72), locking, the loop
+//   k_spmv_kron_pair  prestressed vibration (mfh_modes_prestressed; docs/design/04_18_prestressed_modes.md): yA += s (Kg (x) I) x and
+//                   yB = rho (M (x) I) x from ONE walk over the pattern -- k_spmv_kron_acc's chunks, every column index and x entry loaded once, two
+//                   interleaved planes of LDS partials [dim][chunkSlots][2]. No atomics.
 // FP64 throughout; two calls on one context with option "deterministic" return the same bits.
-#include "mfh_ctx.hh"
-#include "mfh_device.hh"
+#include "mfh_pencil.hh"      // k_spmv_kron_acc (the accumulate pass of the tangent product and of the two-launch form of the pair product)
 #include <deque>
 
 namespace mfh { namespace k {
@@ -180,6 +182,86 @@ __global__ void __launch_bounds__(256) k_prestress_finite(int64_t n, const doubl
     }
 }
 
+// The two one-double-per-block products of the prestressed pencil from ONE walk over the pattern (rowPtr, colIdx) of a (a.vals is not read):
+//     yA[N i + c] = yA[N i + c] + sG sum_j g_ij x[N j + c]      (g = the geometric stiffness buffer; yA holds K x on entry)
+//     yB[N i + c] =               rho sum_j m_ij x[N j + c]      (m = the mass buffer)
+// both zero on the fixed rows where a mask is given. The chunk walk and the tiling are k_spmv_kron_acc's; every column index and every x entry is
+// loaded once and multiplied by both stored values into two planes of LDS partials, [N][chunkSlots] pairs {g x, m x} (the pattern of
+// k_spmv_kron_cacc; the planes interleaved, so that a slot's pair is one 16-byte store and one 16-byte load). Then one lane per scalar row adds
+// the row's partials of both planes in slot order: the sums, and the two roundings of yA + sG sum, are those of k_spmv_kron_acc and k_spmv_kron,
+// so this kernel and the two-launch form give the same bits. No atomics.
+template <int N>
+__global__ void __launch_bounds__(256) k_spmv_kron_pair(SpmvArgs a, const double *__restrict__ gVals, const double *__restrict__ mVals, double sG, double rho,
+                                                       const double *__restrict__ x, double *yA, double *__restrict__ yB) {
+    extern __shared__ __attribute__((aligned(16))) double part[];  // [N][chunkSlots][2] + 16
+    double2 *pair = reinterpret_cast<double2 *>(part);
+    const int CS = a.chunkSlots;
+    for (int64_t chunk = blockIdx.x; chunk < a.nChunk; chunk += gridDim.x) {
+        const int r0 = a.chunkRow[chunk], r1 = a.chunkRow[chunk + 1];
+        const int s0 = a.rowPtr[r0];
+        const int ns = a.rowPtr[r1] - s0;
+        for (int t = threadIdx.x; t < ns; t += 256) {
+            const int64_t s = (int64_t)s0 + t;
+            const int64_t col = a.colIdx[s];
+            const int64_t at = tiled_index(s, 0, 1);
+            const double g = gVals[at], m = mVals[at];
+#pragma unroll
+            for (int c = 0; c < N; ++c) {
+                const double xv = x[col * N + c];
+                pair[c * CS + t] = make_double2(g * xv, m * xv);
+            }
+        }
+        __syncthreads();
+        const int nscalar = (r1 - r0) * N;
+        for (int idx = threadIdx.x; idx < nscalar; idx += 256) {
+            const int rl = idx / N, c = idx - rl * N;
+            const int64_t r = r0 + rl;
+            const int b = a.rowPtr[r] - s0, e = a.rowPtr[r + 1] - s0;
+            const double2 *pp = pair + c * CS;
+            double vg = 0, vm = 0;
+            for (int t = b; t < e; ++t) {
+                const double2 p = pp[t];
+                vg += p.x;
+                vm += p.y;
+            }
+            const int64_t gi = r * N + c;
+            {
+#pragma clang fp contract(off)                                          // (the product rounded before the sum, as the two-launch form rounds it)
+                vg = sG * vg;
+                vg = yA[gi] + vg;
+                vm = rho * vm;
+            }
+            if (a.fixedMask && a.fixedMask[gi]) { vg = 0.0; vm = 0.0; }
+            yA[gi] = vg;
+            yB[gi] = vm;
+        }
+        __syncthreads();
+    }
+}
+
+// yA += sG Kg x and yB = rho M x (pat: the pattern, chunks and mask of mass_spmv_args). One pass (k_spmv_kron_pair) where its LDS fits and twoPass is
+// not set; else the existing kernels in two launches: k_spmv_kron_acc on the geometric buffer, k_spmv_kron on the mass buffer and the density
+// scaling. The grids depend on the pattern alone. true: the single pass ran.
+bool launch_spmv_kron_pair(const SpmvArgs &pat, const double *gVals, const double *mVals, double sG, double rho, const double *x, double *yA, double *yB,
+                           int64_t n, bool twoPass, hipStream_t s) {
+    if (pat.nChunk <= 0) return false;
+    if (pat.dim != 2 && pat.dim != 3) throw mfh::Error(MFH_ERR_UNSUPPORTED, "k_spmv_kron_pair: 2D / 3D only");
+    const size_t lds = ((size_t)2 * pat.dim * pat.chunkSlots + 16) * sizeof(double);
+    if (!twoPass && lds <= HARM_LDS_MAX) {
+        const int grid = (int)std::min<int64_t>(pat.nChunk, DYN_GRID_CAP);
+        with_dim(pat.dim, [&](auto D) { launch_k(k_spmv_kron_pair<D()>, dim3(grid), dim3(256), lds, s, pat, gVals, mVals, sG, rho, x, yA, yB); });
+        CHECK_LAUNCH();
+        return true;
+    }
+    SpmvArgs a = pat;
+    a.vals = gVals;
+    launch_spmv_kron_acc(a, true, 1.0, sG, x, yA, nullptr, DynGate{nullptr, 0, nullptr}, s);
+    a.vals = mVals;
+    launch_spmv(a, x, yB, nullptr, s);
+    if (rho != 1.0) launch_axpby(n, 0.0, yB, rho, yB, s);
+    return false;
+}
+
 int gram_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, GRAM_GRID_CAP)); }
 
 // G (device, p x q row-major) = A^T B; partials: scratch of GRAM_GRID_CAP * 576 doubles
@@ -221,6 +303,9 @@ using k::BLK_MAXC;
 namespace {
 
 constexpr int RR_MAX = 72;              // largest Rayleigh-Ritz problem: three blocks of 24
+// the product form of the prestressed loop: k_spmv_kron_pair (true) or the two launches it replaces; settled by measurement (mfh_time_kron_pair,
+// profiles/r14_prestressed_modes.md: at 60^3 quadratic tets the single pass takes 1.01 to 1.03 x the two launches at density 1). Both forms give the same bits.
+constexpr bool PAIR_FUSED_DEFAULT = false;
 
 // All eigenpairs of A v = w B v, A symmetric, B symmetric positive definite (null: the identity), n x n row-major, upper triangles read. Cholesky
 // B = L L^T, C = L^-1 A L^-T, cyclic Jacobi on C (rotations of Rutishauser's form), V = L^-T Q. w ascending. false: B not positive definite.
@@ -401,7 +486,10 @@ struct ModesWork {
     int64_t n, ld;
     double density = 1.0;
     bool masked;
-    bool buckling = false;             // the pencil: (K, density M) of mfh_modes, or (Kg, K) of mfh_buckling
+    bool buckling = false;             // the pencil: (K, density M) of mfh_modes, or (Kg, K) of mfh_buckling, or ...
+    bool prestressed = false;          // ... (K + loadFactor Kg, density M) of mfh_modes_prestressed
+    double loadFactor = 0.0;
+    bool pairTwoPass = !PAIR_FUSED_DEFAULT;   // the product form of apply_AB (launch_spmv_kron_pair)
     const char *who = "mfh_modes";     // the entry point, for messages
     DBuf<double> vec, zvec, gramPart, resPart, small, coef;
     double *X, *W, *P, *KX, *KW, *KP, *MX, *MW, *MP, *R;
@@ -454,11 +542,21 @@ struct ModesWork {
         MFH_HIP(hipMemcpyAsync(p, staged.back().data(), staged.back().size() * sizeof(double), hipMemcpyHostToDevice, s));
         return p;
     }
-    // The pencil (A, B) the loop works on. Vibration: A = K, B = density M. Buckling: A = Kg (indefinite), B = K. In the loop the blocks named K*
-    // hold the A-images and the blocks named M* the B-images; B carries the inner product, and the preconditioner approximates K^-1 in both.
+    // The pencil (A, B) the loop works on. Vibration: A = K, B = density M. Buckling: A = Kg (indefinite), B = K. Prestressed vibration:
+    // A = K + loadFactor Kg (indefinite beyond the critical load), B = density M. In the loop the blocks named K* hold the A-images and the blocks
+    // named M* the B-images; B carries the inner product, and the preconditioner approximates K^-1 in all three.
     void apply_A(const double *x, double *y) {
         if (buckling) k::launch_spmv(geom_spmv_args(c, masked), x, y, nullptr, s);
         else apply_operator(c, masked, x, y, nullptr);
+        if (prestressed) k::launch_spmv_kron_acc(geom_spmv_args(c, masked), true, 1.0, loadFactor, x, y, nullptr, k::DynGate{nullptr, 0, nullptr}, s);
+    }
+    // both images of one column (the prestressed pencil only): K x into yA, then Kg's and M's parts from one walk over the pattern
+    // (book: under MFH_MODES_TIMING K's product goes to phase 0 and the pair product to phase 1)
+    void apply_AB(const double *x, double *yA, double *yB, bool book = false) {
+        apply_operator(c, masked, x, yA, nullptr);
+        if (book) lap(0);
+        k::launch_spmv_kron_pair(mass_spmv_args(c, masked), c->dGeomVals.p, c->dMassVals.p, loadFactor, density, x, yA, yB, n, pairTwoPass, s);
+        if (book) lap(1);
     }
     void apply_B(const double *x, double *y) {
         if (buckling) { apply_operator(c, masked, x, y, nullptr); return; }
@@ -632,7 +730,8 @@ struct LoopOut {
 // The block LOBPCG loop on the pencil (A, B) of w (ModesWork::apply_A / apply_B): the nev smallest eigenpairs of A x = lambda B x, B-orthonormal
 // columns with the sign rule, the relative residuals ||A x - lambda B x|| / (|lambda| ||B x||). The caller has prepared the context (the operators'
 // buffers, the preconditioner) and the fields of w up to useTL; tsetup is its running set-up timer. Shared by mfh_modes and mfh_buckling.
-void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, EventTimer &tsetup, double *lambda, double *Xout, double *residuals, LoopOut &o) {
+void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, EventTimer &tsetup, double *lambda, double *Xout, double *residuals, LoopOut &o,
+                const double *X0 = nullptr) {
     mfh_ctx *c = w.c;
     hipStream_t s = w.s;
     w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
@@ -716,10 +815,19 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
         if (w.masked) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.W, j), s);
         w.precond(w.col(w.W, j), w.col(w.X, j));
     }
+    if (X0) {                          // a warm start (host, nev x n): its rows take the place of the first nev columns as they are, masked
+        MFH_HIP(hipMemcpy2DAsync(w.X, (size_t)w.ld * sizeof(double), X0, (size_t)w.n * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nev, hipMemcpyHostToDevice, s));
+        if (w.masked)
+            for (int j = 0; j < nev; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.X, j), s);
+        MFH_HIP(hipStreamSynchronize(s));
+    }
     project_out_Z(w.X, nullptr, all);
     for (int j = 0; j < m; ++j) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
     if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw w.fail(MFH_ERR_STATE, "the start block is rank deficient");
-    for (int j = 0; j < m; ++j) { w.apply_A(w.col(w.X, j), w.col(w.KX, j)); w.apply_B(w.col(w.X, j), w.col(w.MX, j)); }
+    for (int j = 0; j < m; ++j) {
+        if (w.prestressed) w.apply_AB(w.col(w.X, j), w.col(w.KX, j), w.col(w.MX, j));
+        else { w.apply_A(w.col(w.X, j), w.col(w.KX, j)); w.apply_B(w.col(w.X, j), w.col(w.MX, j)); }
+    }
     std::vector<double> lam((size_t)m, 0.0);
     {
         double *GK = w.gram(w.ref(w.X, all), w.ref(w.KX, all));
@@ -780,10 +888,14 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
         for (int j : act) w.precond(w.col(w.R, j), w.col(w.W, j));
         w.lap(2);
         project_out_Z(w.W, nullptr, act);
-        for (int j : act) w.apply_A(w.col(w.W, j), w.col(w.KW, j));
-        w.lap(0);
-        for (int j : act) w.apply_B(w.col(w.W, j), w.col(w.MW, j));
-        w.lap(1);
+        if (w.prestressed) {
+            for (int j : act) w.apply_AB(w.col(w.W, j), w.col(w.KW, j), w.col(w.MW, j), true);
+        } else {
+            for (int j : act) w.apply_A(w.col(w.W, j), w.col(w.KW, j));
+            w.lap(0);
+            for (int j : act) w.apply_B(w.col(w.W, j), w.col(w.MW, j));
+            w.lap(1);
+        }
         std::vector<int> pact = haveP ? act : std::vector<int>();
         // Cholesky-QR of the basis S = [X W P], twice: Gram-Schmidt in that order, so W leaves M-orthogonal to X
         std::vector<int> wact = act;
@@ -1195,6 +1307,165 @@ mfh_status mfh_buckling(mfh_ctx *c, int32_t nev, int32_t flags, double rtol, int
         info->note = c->modesNote.c_str();
     }
     if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    MFH_CATCH(c)
+}
+
+// ---------------------------------------------------------------- prestressed vibration (docs/design/04_18_prestressed_modes.md)
+// the smallest eigenpairs of (K + loadFactor Kg) x = lambda density M x: the loop of mfh_modes on its third pencil, K's preconditioner
+mfh_status mfh_modes_prestressed(mfh_ctx *c, int32_t nev, double density, double loadFactor, int32_t flags, double rtol, int32_t maxit, const double *X0,
+                                 double *lambda, double *Xout, double *residuals, mfh_modes_info *info) {
+    if (info) { *info = mfh_modes_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c && nev >= 1 && nev <= 20 && density > 0.0 && std::isfinite(density) && std::isfinite(loadFactor) && lambda && Xout && rtol > 0.0 && maxit > 0,
+            MFH_ERR_INVALID, "mfh_modes_prestressed: 1 <= nev <= 20, density > 0, a finite load factor, rtol > 0, maxit > 0, lambda and X not null");
+    require(flags == 0, MFH_ERR_UNSUPPORTED,
+            "mfh_modes_prestressed: rigid rotations are not in the kernel of Kg, so the known-kernel variant (MFH_MODES_FREE) does not apply");
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "mfh_modes_prestressed: no mesh set");
+    require_geometric_context(c, "mfh_modes_prestressed");
+    MFH_HIP(hipSetDevice(c->device));
+    {
+        const int q = free_rigid_motions(c);
+        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables)");
+    }
+    const int64_t nAll = (int64_t)c->bs() * c->nDoF;
+    require(nev <= nAll - (int64_t)c->fixedVars.size(), MFH_ERR_INVALID, "mfh_modes_prestressed: more modes asked for than the pencil has");
+    if (X0)
+        for (int64_t q = 0; q < (int64_t)nev * nAll; ++q) require(std::isfinite(X0[q]), MFH_ERR_INVALID, "mfh_modes_prestressed: an entry of X0 is not finite");
+    hipStream_t s = c->stream;
+    c->modesNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
+    WideGuard guard(c);
+    if (guard.widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    EventTimer tsetup(s);
+    // ---- the preconditioner of K (what the next solve would use), as in mfh_modes: the shifted operator has none of its own
+    ensure_precond(c);
+    ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modes_prestressed: unpartitioned contexts only");
+    ensure_mass(c);
+    ensure_geometric(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes_prestressed");
+
+    ModesWork w;
+    w.c = c; w.s = s; w.d = c->bs();
+    w.n = nAll; w.ld = (w.n + 31) / 32 * 32;
+    w.density = density;
+    w.prestressed = true;
+    w.loadFactor = loadFactor;
+    w.who = "mfh_modes_prestressed";
+    w.masked = !c->fixedVars.empty();
+    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
+    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
+    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid;
+    if (!w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    LoopOut lo;
+    lobpcg_run(w, nev, false, rtol, maxit, tsetup, lambda, Xout, residuals, lo, X0);
+    int nNeg = 0;
+    for (int j = 0; j < nev; ++j) nNeg += lambda[j] < 0.0 ? 1 : 0;
+    if (nNeg > 0) note(std::to_string(nNeg) + " of the " + std::to_string(nev) + " eigenvalues are negative: the prestressed state is unstable at this load factor");
+    if (info) {
+        info->converged = lo.done ? 1 : 0;
+        info->iterations = lo.iterations;
+        info->nLocked = lo.locked;
+        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
+        info->blockSize = lo.blockSize;
+        info->restarts = lo.restarts;
+        info->maxResidual = lo.maxResidual;
+        info->solve_ms = lo.solveMs;
+        info->setup_ms = lo.setupMs;
+        info->note = c->modesNote.c_str();
+    }
+    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    MFH_CATCH(c)
+}
+
+// y = (K + loadFactor Kg) x on displacement vectors, unmasked: the context's operator, then the accumulate pass on the geometric buffer
+mfh_status mfh_tangent_apply(mfh_ctx *c, double loadFactor, const double *x, double *y, int32_t flags) {
+    MFH_TRY(c)
+    require(c && x && y && std::isfinite(loadFactor), MFH_ERR_INVALID, "mfh_tangent_apply: null argument or a load factor that is not finite");
+    require((flags & ~MFH_LOAD_ON_DEVICE) == 0, MFH_ERR_INVALID, "flags: 0 | MFH_LOAD_ON_DEVICE");
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the tangent stiffness needs a mesh on a device");
+    prepare_pencil(c, "mfh_tangent_apply");
+    require(c->havePrestress, MFH_ERR_STATE, "mfh_tangent_apply: no prestress field set (mfh_set_prestress / mfh_prestress_from_displacement)");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    ensure_precond(c);                 // (K assembled, the fixed-variable mask on the device)
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_tangent_apply: unpartitioned contexts only");
+    ensure_geometric(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_tangent_apply");
+    const bool onDevice = (flags & MFH_LOAD_ON_DEVICE) != 0;
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    DBuf<double> dx, dy;
+    const double *xin = x;
+    double *yout = y;
+    if (!onDevice) {
+        dx.alloc((size_t)n); dy.alloc((size_t)n);
+        upload(dx.p, x, n, s);
+        xin = dx.p; yout = dy.p;
+    }
+    apply_operator(c, false, xin, yout, nullptr);
+    k::launch_spmv_kron_acc(geom_spmv_args(c, false), true, 1.0, loadFactor, xin, yout, nullptr, k::DynGate{nullptr, 0, nullptr}, s);
+    if (!onDevice) MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// test hook (meshfem_hip_extras.h): the pair product as the prestressed loop launches it, on host vectors; twoPass forces the two-launch form
+mfh_status mfh_debug_kron_pair(mfh_ctx *c, double sG, double rho, int32_t masked, int32_t twoPass, const double *x, double *yA, double *yB) {
+    MFH_TRY(c)
+    require(c && x && yA && yB && std::isfinite(sG) && std::isfinite(rho), MFH_ERR_INVALID, "mfh_debug_kron_pair: arguments");
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the pair product needs a mesh on a device");
+    prepare_pencil(c, "mfh_debug_kron_pair");
+    require(c->havePrestress, MFH_ERR_STATE, "mfh_debug_kron_pair: no prestress field set");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    ensure_fixed_uploaded(c);
+    ensure_mass(c);
+    ensure_geometric(c);
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    const bool m = masked != 0 && !c->fixedVars.empty();
+    DBuf<double> dx, da, db;
+    dx.alloc((size_t)n); da.alloc((size_t)n); db.alloc((size_t)n);
+    upload(dx.p, x, n, s);
+    upload(da.p, yA, n, s);
+    k::launch_spmv_kron_pair(mass_spmv_args(c, m), c->dGeomVals.p, c->dMassVals.p, sG, rho, dx.p, da.p, db.p, n, twoPass != 0, s);
+    MFH_HIP(hipMemcpyAsync(yA, da.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(yB, db.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// measurement (meshfem_hip_extras.h): average device time of `reps` pair products on hashed vectors in the single pass and in the two-launch form
+// (density 1, the default of every facade: the two-launch form then pays no scaling kernel), in alternating groups after a warm-up of both
+mfh_status mfh_time_kron_pair(mfh_ctx *c, int32_t reps, double *pair_ms, double *separate_ms) {
+    MFH_TRY(c)
+    require(c && pair_ms && separate_ms && reps > 0, MFH_ERR_INVALID, "bad arguments");
+    require(c->haveMesh && !c->hostOnly && !c->external, MFH_ERR_STATE, "the pair product needs a mesh on a device");
+    prepare_pencil(c, "mfh_time_kron_pair");
+    require(c->havePrestress, MFH_ERR_STATE, "mfh_time_kron_pair: no prestress field set");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    ensure_fixed_uploaded(c);
+    ensure_mass(c);
+    ensure_geometric(c);
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    const k::SpmvArgs a = mass_spmv_args(c, !c->fixedVars.empty());
+    DBuf<double> v;
+    v.alloc((size_t)3 * n);
+    k::launch_fill_hash(3 * n, v.p, s);
+    double *x = v.p, *yA = v.p + n, *yB = v.p + 2 * n;
+    const int groups = 4, per = (reps + groups - 1) / groups;
+    double t[2] = {0.0, 0.0};
+    for (int g = -1; g < groups; ++g)          // (g == -1: the warm-up)
+        for (int form = 0; form < 2; ++form) {
+            EventTimer tm(s);
+            for (int r = 0; r < per; ++r) k::launch_spmv_kron_pair(a, c->dGeomVals.p, c->dMassVals.p, 1e-3, 1.0, x, yA, yB, n, form == 1, s);
+            const double ms = tm.stop();
+            if (g >= 0) t[form] += ms;
+        }
+    *pair_ms = t[0] / (groups * per);
+    *separate_ms = t[1] / (groups * per);
     MFH_CATCH(c)
 }
 

@@ -1,7 +1,8 @@
 // The pieces of the pencil operator A = cK K + cM M that mfh_dynamics.hip (real coefficients, PCG) and mfh_harmonic.hip (complex coefficients,
 // COCG) both build on: the iteration gate, the two-stage ordered sums, the accumulating mass product, the inverse diagonal blocks of the pencil
 // and the context conditions. Everything here has internal linkage (anonymous namespaces): each of the two translation units carries its own
-// copy of the kernels, which is what keeps this header a move of code and not a new layer. Not part of the ABI.
+// copy of the kernels, which is what keeps this header a move of code and not a new layer. Not part of the ABI. mfh_modes.hip includes it too, for
+// the accumulate pass of its prestressed pencil (K + s Kg: k_spmv_kron_acc on the geometric buffer) and the LDS limit of its pair kernel.
 //   k_spmv_kron_acc    y = cK y + cM (M (x) I) x: k_spmv_kron's chunks and LDS partials, ADDING into the K product that apply_operator left in y
 //                      (cK == 0: y is not read), the fixed rows zeroed, x . y summed per workgroup in the same pass
 //   k_pencil_dinv      inverse diagonal blocks of A: cK K_ii + cM m_ii I (fixed rows / columns replaced by the identity), symmetric-packed
@@ -22,6 +23,8 @@ namespace {
 constexpr int DYN_GRID_CAP = 2048;      // workgroups of k_spmv_kron_acc (k_spmv_kron's cap) and of the PCG's vector kernels at most = rows of the partials buffer
 constexpr int DYN_STEP_CAP = 256;       // workgroups of the three step kernels (once per step: one workgroup per CU is plenty)
 constexpr int DYN_NV = 4;               // sums a kernel may emit (stride of the partials)
+constexpr size_t HARM_LDS_MAX = 160 * 1024;     // what a workgroup of gfx950 can be granted (launch_k asks for anything above 64 KB): the two-plane
+                                                // kernels (k_spmv_kron_cacc, k_spmv_kron_pair) fall back to two launches above it
 
 struct DynGate { const double *scal; int it; const double *stop; };
 DEV bool dyn_closed(const DynGate &g) {

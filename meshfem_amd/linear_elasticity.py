@@ -281,6 +281,39 @@ class Simulator:
             X = X[:, dof, :]
         return fac, X, u
 
+    # ---- prestressed vibration (docs/design/04_18_prestressed_modes.md)
+    def prestressedModes(self, nev, load=None, factors=(1.0,), density=1.0, rtol=1e-6, maxit=500):
+        """(lam, modes, u): solves the static problem as buckling() does (load: a per-DoF vector, None = neumannLoad()), makes the element-average
+        stress of its displacement u the prestress on the device, and returns for every multiple s in `factors` of that load, in order, the nev
+        smallest eigenvalues of (K + s Kg) x = lam M x (mfh_modes_prestressed; frequencies sqrt(lam) / 2 pi while lam > 0, negative beyond the
+        critical load): lam [nFactors, nev], the shapes as nodal fields [nFactors, nev, nNode, N] and u [nNode, N]. Every factor after the first
+        starts from the shapes of the one before it. density as in vibrational_modes; the Dirichlet variables of the applied conditions are
+        the clamp. self.prestressed_modes_info holds the solver's record of every factor."""
+        ctx = self.ctx
+        factors = [float(s) for s in np.atleast_1d(np.asarray(factors, dtype=np.float64))]
+        rho = self._density_scalar(density)
+        u = self.solve(None if load is None else np.asarray(load, dtype=np.float64).reshape(ctx.n_dof, self.N))
+        ctx.prestress_from_displacement(u)
+        v, _ = ctx.bc_dirichlet_vars()
+        ctx.clear_fixed()
+        if len(v):
+            ctx.fix_variables(v)
+        lams, shapes, X = [], [], None
+        self.prestressed_modes_info = []
+        for s in factors:
+            try:
+                lam, X, info = ctx.modes_prestressed(nev, s, density=rho, x0=X, rtol=rtol, maxit=maxit)
+            finally:
+                last = getattr(ctx, "last_modes_prestressed", None)
+                self.prestressed_modes_info.append(last[2] if last else None)
+            lams.append(lam)
+            shapes.append(X.reshape(len(lam), ctx.n_dof, self.N))
+        shapes = np.array(shapes)
+        if ctx.n_dof != ctx.n_node:                         # a DoF map (periodic conditions): every node takes its DoF's value
+            dof, _ = ctx.get_dof_map()
+            shapes = shapes[:, :, dof, :]
+        return np.array(lams), shapes, u
+
     def transient(self, dt, n_steps, amplitude=None, u0=None, v0=None, density=1.0, damping=(0, 0), beta=0.25, gamma=0.5, probes=None,
                   snapshot_stride=0, a0=None, energies=False, rtol=None, maxit=None, load=None):
         """The response to the load history amplitude[n] x f, f = neumannLoad() or the per-DoF vector `load` (a volume load, a sum of loads), by implicit Newmark time stepping on the device (mfh_newmark):
