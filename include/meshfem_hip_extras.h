@@ -108,6 +108,26 @@ mfh_status mfh_debug_pencil_apply(mfh_ctx* ctx, double cK, double cM, int32_t ma
  * {Re, Im} of the unconjugated x^T y from the kernel's partials. zK == 0 skips the K products */
 mfh_status mfh_debug_harmonic_apply(mfh_ctx* ctx, double zKre, double zKim, double zMre, double zMim, int32_t masked, const double* xRe, const double* xIm,
                                     double* yRe, double* yIm, double* dot);
+/* test hooks: the two iterative loops on the pencil (NewmarkWork::solve of mfh_dynamics.hip, HarmonicWork::solve of mfh_harmonic.hip) and their
+ * block-Jacobi preconditioner, on host vectors of dim * nDoF doubles, M with density 1, the context's fixed variables and preconditioner choice as
+ * mfh_newmark / mfh_harmonic make it (tests/test_gpu_pencil_iterates.py).
+ * precond: z = Dinv r with the inverse diagonal blocks the loops build for cK K + cM M (k_pencil_dinv; the rows and columns of fixed variables
+ *   replaced by the identity; cK == 0 does not read K). The harmonic loop builds its blocks with cK = 1, cM = w^2 density */
+mfh_status mfh_debug_pencil_precond(mfh_ctx* ctx, double cK, double cM, const double* r, double* z);
+/* newmark_pcg: the PCG on cK K + cM M for the right-hand side b (its fixed rows are zeroed, the threshold is rtol^2 b . b) from the start vector x0
+ *   (NULL: zero; zero on the fixed variables). cK == 0 runs the block-Jacobi of cM M whatever the context's preconditioner, as the solve for the
+ *   initial acceleration does. x = the iterate the loop ends on, ALWAYS written; history: 4 (maxit + 1) doubles, the rows {r.z, p.Ap, r.r, -} of
+ *   iterations 0 .. maxit as the loop left them (r.z stays 0 in the block-Jacobi-free form until the preconditioner ran); *its = the loop's return
+ *   value: the iteration that met the threshold, -1 at maxit, -2 on a breakdown. Status MFH_ERR_NOT_CONVERGED with *its < 0 */
+mfh_status mfh_debug_newmark_pcg(mfh_ctx* ctx, double cK, double cM, double rtol, int32_t maxit, const double* b, const double* x0, double* x, double* history,
+                                 int32_t* its);
+/* harmonic_cocg: the COCG on zK K + zM M (zK, zM: {re, im}) for the load fRe + i fIm (fIm may be NULL) from x0 (either plane may be NULL: zero),
+ *   without the continuations from the true residual mfh_harmonic adds. jacobiCM: the cM of the block-Jacobi blocks K + cM M, used where the context's
+ *   choice is block-Jacobi. history as above (its r.r the Hermitian one); chistory: 4 (maxit + 1) doubles, {Re r^T z, Im r^T z, Re p^T Z p, Im p^T Z p}
+ *   per iteration; *its and the status as above */
+mfh_status mfh_debug_harmonic_cocg(mfh_ctx* ctx, const double* zK, const double* zM, double jacobiCM, double rtol, int32_t maxit, const double* fRe,
+                                   const double* fIm, const double* x0Re, const double* x0Im, double* xRe, double* xIm, double* history, double* chistory,
+                                   int32_t* its);
 /* the pair product of mfh_modes_prestressed through the launcher its loop uses: yA (in: any vector, out: yA + s Kg x) and yB = rho M x (M with the
  * density field in force), rows of fixed variables zeroed in both if masked != 0. k_spmv_kron_pair, or, if twoPass != 0 (or where its LDS does not
  * fit), k_spmv_kron_acc on the geometric buffer followed by k_spmv_kron on the mass buffer and the density scaling */

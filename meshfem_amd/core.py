@@ -693,6 +693,51 @@ class Context:
         self._ck(self.lib.mfh_debug_pencil_apply(self.h, float(cK), float(cM), 1 if masked else 0, ptr(x), ptr(y), ptr(dot)))
         return y, float(dot[0])
 
+    def debug_pencil_precond(self, cK, cM, r):
+        """z = Dinv r with the inverse diagonal blocks the Newmark and harmonic loops build for cK K + cM M (test hook mfh_debug_pencil_precond;
+        M with density 1, the fixed variables decoupled)."""
+        r = as_f64(r).reshape(-1)
+        z = np.empty(self.bs * self.n_dof)
+        assert r.size == z.size
+        self._ck(self.lib.mfh_debug_pencil_precond(self.h, float(cK), float(cM), ptr(r), ptr(z)))
+        return z
+
+    def _ck_loop(self, st):
+        """the status of a loop hook: MFH_ERR_NOT_CONVERGED (the loop ended at maxit: its iterate is what the caller asked for) passes"""
+        if st != L.ERR_NOT_CONVERGED:
+            self._ck(st)
+
+    def debug_newmark_pcg(self, cK, cM, b, x0=None, rtol=1e-30, maxit=1):
+        """(x, history [maxit + 1, 4] = {r.z, p.Ap, r.r, -}, its) of the PCG of mfh_newmark on cK K + cM M from x0 (test hook mfh_debug_newmark_pcg;
+        M with density 1). its: the iteration that met rtol, -1 at maxit (x is then iterate maxit), -2 on a breakdown."""
+        n = self.bs * self.n_dof
+        b = as_f64(b).reshape(-1)
+        x0 = None if x0 is None else as_f64(x0).reshape(-1)
+        assert b.size == n and (x0 is None or x0.size == n)
+        x, hist, its = np.full(n, np.nan), np.zeros((int(maxit) + 1, 4)), np.zeros(1, dtype=np.int32)
+        self._ck_loop(self.lib.mfh_debug_newmark_pcg(self.h, float(cK), float(cM), float(rtol), int(maxit), ptr(b), ptr(x0), ptr(x), ptr(hist), ptr(its)))
+        return x, hist, int(its[0])
+
+    def debug_harmonic_cocg(self, zK, zM, jacobi_cM, f, x0=None, rtol=1e-30, maxit=1):
+        """(x, history [maxit + 1, 4], chistory [maxit + 1, 2] complex = {r^T z, p^T Z p}, its) of the COCG of mfh_harmonic on zK K + zM M from x0,
+        without its continuations (test hook mfh_debug_harmonic_cocg; M with density 1; jacobi_cM: the block-Jacobi blocks are those of
+        K + jacobi_cM M). its as in debug_newmark_pcg."""
+        n = self.bs * self.n_dof
+        f = np.asarray(f).reshape(-1)
+        assert f.size == n and (x0 is None or np.asarray(x0).size == n)
+        f_re = np.ascontiguousarray(f.real, dtype=np.float64)
+        f_im = np.ascontiguousarray(f.imag, dtype=np.float64) if np.iscomplexobj(f) else None
+        x0 = None if x0 is None else np.asarray(x0, dtype=np.complex128).reshape(-1)
+        x0_re = None if x0 is None else np.ascontiguousarray(x0.real)
+        x0_im = None if x0 is None else np.ascontiguousarray(x0.imag)
+        zK, zM = complex(zK), complex(zM)
+        zk, zm = np.array([zK.real, zK.imag]), np.array([zM.real, zM.imag])
+        xr, xi = np.full(n, np.nan), np.full(n, np.nan)
+        hist, chist, its = np.zeros((int(maxit) + 1, 4)), np.zeros((int(maxit) + 1, 4)), np.zeros(1, dtype=np.int32)
+        self._ck_loop(self.lib.mfh_debug_harmonic_cocg(self.h, ptr(zk), ptr(zm), float(jacobi_cM), float(rtol), int(maxit), ptr(f_re), ptr(f_im), ptr(x0_re),
+                                                       ptr(x0_im), ptr(xr), ptr(xi), ptr(hist), ptr(chist), ptr(its)))
+        return xr + 1j * xi, hist, chist[:, 0::2] + 1j * chist[:, 1::2], int(its[0])
+
     def debug_sym_gen_eig(self, A, B):
         """(w, V) of the dense pencil A v = w B v by the Rayleigh-Ritz routine of mfh_modes (test hook mfh_debug_sym_gen_eig)."""
         A, B = as_f64(A), as_f64(B)

@@ -500,7 +500,9 @@ struct WideGuard {
     mfh_ctx *c;
     bool widened = false;
     explicit WideGuard(mfh_ctx *c_) : c(c_) {
-        if (resolve_upper_storage(c)) { c->modesWide = true; widened = true; }
+        // invariant: the storage rule is in force before ensure_precond chooses a preconditioner or k_pencil_dinv reads K (so it is applied here, not by
+        // the first ensure_symbolic that happens to run)
+        if (resolve_upper_storage(c)) { c->modesWide = true; widened = true; refresh_storage_rule(c); }
     }
     ~WideGuard() {
         if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }

@@ -180,6 +180,21 @@ __global__ void __launch_bounds__(256) k_dyn_direction(int64_t n, const double *
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = first ? z[i] : fma(beta, p[i], z[i]);
 }
 
+// z = Dinv r, one lane per block row (test hook mfh_debug_pencil_precond: the blocks of k_pencil_dinv as a map; the loops apply them inside
+// k_dyn_init / k_dyn_update and their complex counterparts)
+template <int DIM>
+__global__ void __launch_bounds__(256) k_pencil_apply(int64_t nRows, const double *__restrict__ dinv, const double *__restrict__ r, double *__restrict__ z) {
+    constexpr int NS = DIM * (DIM + 1) / 2;
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < nRows; n += (int64_t)gridDim.x * 256) {
+        double rv[DIM], zv[DIM];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) rv[c] = r[n * DIM + c];
+        apply_packed<DIM>(dinv + n * NS, rv, zv);
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) z[n * DIM + c] = zv[c];
+    }
+}
+
 void launch_newmark_predict(const PredictArgs &p, const double *u, const double *v, const double *a, const uint8_t *mask, double *ut, double *vt, double *xm,
                             double *xk, hipStream_t s) {
     hipLaunchKernelGGL(k_newmark_predict, dim3(dyn_grid(p.n)), dim3(256), 0, s, p, u, v, a, mask, ut, vt, xm, xk);
@@ -351,6 +366,55 @@ struct NewmarkWork {
     }
 };
 
+// What mfh_newmark and the test hooks of its loop (mfh_debug_pencil_precond, mfh_debug_newmark_pcg) share: the state of the context the pencil
+// products and the preconditioners read, the choice between the block-Jacobi of A, the two-level and the multigrid preconditioner (note: what
+// was chosen, in words), the work vectors and the control blocks of NewmarkWork::solve. Returns whether the time steps run block-Jacobi.
+template <class Note>
+bool setup_newmark_work(mfh_ctx *c, NewmarkWork &w, const char *who, int maxit, double rtol, Note &&note) {
+    hipStream_t s = c->stream;
+    const bool masked = !c->fixedVars.empty();
+    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of A itself otherwise
+    ensure_precond(c);
+    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
+    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, (std::string(who) + ": unpartitioned contexts only").c_str());
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, ("the assembled SpMV of " + std::string(who)).c_str());
+
+    w.c = c; w.s = s; w.d = c->bs();
+    w.nRows = c->sym.nRows;
+    w.n = (int64_t)w.d * c->nDoF;
+    w.masked = masked;
+    w.mask = masked ? c->dFixedMask.p : nullptr;
+    w.maxit = maxit; w.rtol = rtol;
+    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
+    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
+    const bool stepJacobi = !(w.useMG || w.useTL);
+    if (wantCoarse && !masked) note("no fixed variables (K singular, A not): block-Jacobi of A in place of the two-level / multigrid preconditioner");
+    else if (wantCoarse && stepJacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of A") : c->precondNote + " (block-Jacobi of A)");
+    else if (!wantCoarse) note("block-Jacobi of A = cK K + cM M");
+    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K") : c->precondNote);
+    const int64_t ld = (w.n + 31) / 32 * 32;
+    w.vec.alloc((size_t)ld * 14);
+    w.vec.zero(s);
+    {
+        double *q = w.vec.p;
+        double **slots[14] = {&w.u, &w.v, &w.a, &w.ut, &w.vt, &w.xm, &w.xk, &w.f, &w.b, &w.x, &w.r, &w.z, &w.p, &w.Ap};
+        for (auto sl : slots) { *sl = q; q += ld; }
+    }
+    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
+    w.scal.alloc(((size_t)maxit + 2) * 4);
+    w.ctl.alloc(8);
+    w.ctl.zero(s);
+    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
+    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
+    c->stop.zero(s);
+    w.batch = std::max(2, std::min(8, c->checkEvery));
+    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
+    return stepJacobi;
+}
+
 void check_params(const mfh_newmark_params *p) {
     require(p != nullptr, MFH_ERR_INVALID, "mfh_newmark: params is null");
     require(p->dt > 0.0 && std::isfinite(p->dt), MFH_ERR_INVALID, "mfh_newmark: dt > 0");
@@ -415,46 +479,8 @@ mfh_status mfh_newmark(mfh_ctx *c, const mfh_newmark_params *prm, double *u, dou
     const double bdt = P.beta * P.dt;
     const double cK = 1.0 + P.gamma * P.rayleighStiff / bdt;
     const double cM = P.density * (1.0 / (bdt * P.dt) + P.gamma * P.rayleighMass / bdt);
-    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of A itself otherwise
-    ensure_precond(c);
-    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
-    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_newmark: unpartitioned contexts only");
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_newmark");
-
     NewmarkWork w;
-    w.c = c; w.s = s; w.d = c->bs();
-    w.nRows = c->sym.nRows;
-    w.n = (int64_t)w.d * c->nDoF;
-    w.masked = masked;
-    w.mask = masked ? c->dFixedMask.p : nullptr;
-    w.maxit = P.maxit; w.rtol = P.rtol;
-    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
-    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
-    const bool stepJacobi = !(w.useMG || w.useTL);
-    if (wantCoarse && !masked) note("no fixed variables (K singular, A not): block-Jacobi of A in place of the two-level / multigrid preconditioner");
-    else if (wantCoarse && stepJacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of A") : c->precondNote + " (block-Jacobi of A)");
-    else if (!wantCoarse) note("block-Jacobi of A = cK K + cM M");
-    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K") : c->precondNote);
-    const int64_t ld = (w.n + 31) / 32 * 32;
-    w.vec.alloc((size_t)ld * 14);
-    w.vec.zero(s);
-    {
-        double *q = w.vec.p;
-        double **slots[14] = {&w.u, &w.v, &w.a, &w.ut, &w.vt, &w.xm, &w.xk, &w.f, &w.b, &w.x, &w.r, &w.z, &w.p, &w.Ap};
-        for (auto sl : slots) { *sl = q; q += ld; }
-    }
-    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
-    w.scal.alloc(((size_t)P.maxit + 2) * 4);
-    w.ctl.alloc(8);
-    w.ctl.zero(s);
-    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
-    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
-    c->stop.zero(s);
-    w.batch = std::max(2, std::min(8, c->checkEvery));
-    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
+    const bool stepJacobi = setup_newmark_work(c, w, "mfh_newmark", P.maxit, P.rtol, note);
 
     const int nSteps = P.nSteps;
     const int stride = snapshots ? P.snapshotStride : 0;
@@ -723,6 +749,53 @@ mfh_status mfh_debug_pencil_apply(mfh_ctx *c, double cK, double cM, int32_t mask
     MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dot) MFH_HIP(hipMemcpyAsync(dot, dy.p + n, sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// z = Dinv r with the blocks NewmarkWork::ensure_dinv builds for (cK, cM) (HarmonicWork::ensure_dinv launches the same kernel with cK = 1)
+mfh_status mfh_debug_pencil_precond(mfh_ctx *c, double cK, double cM, const double *r, double *z) {
+    MFH_TRY(c)
+    require(c && r && z && std::isfinite(cK) && std::isfinite(cM), MFH_ERR_INVALID, "mfh_debug_pencil_precond: arguments");
+    prepare_pencil(c, "mfh_debug_pencil_precond");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    // the whole setup of the loop for one block apply, deliberately: ensure_dinv then sees the context in the state the loop's own call sees it in
+    // (storage, assembled K, mass buffer, mask)
+    NewmarkWork w;
+    setup_newmark_work(c, w, "mfh_debug_pencil_precond", 1, 0.5, [](const std::string &) {});
+    w.ensure_dinv(cK, cM);
+    upload(w.r, r, w.n, s);
+    k::with_dim(w.d, [&](auto D) {
+        k::launch_k(k::k_pencil_apply<D()>, dim3(k::dyn_grid(w.nRows)), dim3(256), 0, s, w.nRows, (const double *)w.dinv.p, (const double *)w.r, w.z);
+    });
+    CHECK_LAUNCH();
+    MFH_HIP(hipMemcpyAsync(z, w.z, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// NewmarkWork::solve on (b, x0) as a time step of mfh_newmark calls it: b masked and its threshold set by k_newmark_rhs / set_threshold, the
+// preconditioner the steps would take (cK == 0: block-Jacobi of cM M, the solve for the initial acceleration)
+mfh_status mfh_debug_newmark_pcg(mfh_ctx *c, double cK, double cM, double rtol, int32_t maxit, const double *b, const double *x0, double *x, double *history,
+                                 int32_t *its) {
+    MFH_TRY(c)
+    require(c && b && x && history && its && std::isfinite(cK) && std::isfinite(cM) && rtol > 0.0 && rtol < 1.0 && maxit > 0, MFH_ERR_INVALID,
+            "mfh_debug_newmark_pcg: arguments");
+    prepare_pencil(c, "mfh_debug_newmark_pcg");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    NewmarkWork w;
+    const bool stepJacobi = setup_newmark_work(c, w, "mfh_debug_newmark_pcg", maxit, rtol, [](const std::string &) {});
+    upload(w.f, b, w.n, s);
+    const int np = k::launch_newmark_rhs(w.n, 0.0, nullptr, w.f, w.mask, w.b, w.partials.p, s);
+    w.set_threshold(np);
+    if (x0) upload(w.x, x0, w.n, s);           // (zero on the fixed variables, as k_newmark_predict leaves the loop's start vector)
+    const int ret = w.solve(cK, cM, cK == 0.0 || stepJacobi);
+    MFH_HIP(hipMemcpyAsync(x, w.x, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(history, w.scal.p, ((size_t)maxit + 1) * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    *its = ret;
+    if (ret < 0) throw Error(MFH_ERR_NOT_CONVERGED, ret == -1 ? "mfh_debug_newmark_pcg: the PCG reached maxit" : "mfh_debug_newmark_pcg: PCG breakdown");
     MFH_CATCH(c)
 }
 

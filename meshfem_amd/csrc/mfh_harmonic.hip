@@ -435,7 +435,70 @@ struct HarmonicWork {
             step = std::max(2, std::min(8, c->checkEvery));
         }
     }
+    // |f|^2 of the load in this->f -> bb[0] and the threshold rtol^2 |f|^2 -> stop[0]
+    void set_threshold(double rtol) {
+        const int grid = vec_grid(n);
+        hipLaunchKernelGGL(k::k_harm_norm2, dim3(grid), dim3(256), 0, s, n, (const double *)f, ld, partials.p);
+        CHECK_LAUNCH();
+        const int col[2] = {0, 0};
+        const double sc[2] = {rtol * rtol, 1.0};
+        double *const dst[2] = {stop, bb};
+        reduce(grid, 2, col, sc, dst, open());
+    }
 };
+
+// What mfh_harmonic and the test hook of its loop (mfh_debug_harmonic_cocg) share: the state of the context the pencil products and the
+// preconditioners read, the choice between the block-Jacobi of K + w^2 density M, the two-level and the multigrid preconditioner (note: what was
+// chosen, in words), the work vectors, the two histories and the control block of HarmonicWork::solve. Returns whether the loop runs block-Jacobi.
+template <class Note>
+bool setup_harmonic_work(mfh_ctx *c, HarmonicWork &w, const char *who, int maxit, Note &&note) {
+    hipStream_t s = c->stream;
+    const bool masked = !c->fixedVars.empty();
+    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of K + w^2 density M otherwise
+    ensure_precond(c);
+    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
+    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, (std::string(who) + ": unpartitioned contexts only").c_str());
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, ("the assembled SpMV of " + std::string(who)).c_str());
+
+    w.c = c; w.s = s; w.d = c->bs();
+    w.nRows = c->sym.nRows;
+    w.n = (int64_t)w.d * c->nDoF;
+    w.masked = masked;
+    w.mask = masked ? c->dFixedMask.p : nullptr;
+    w.maxit = maxit;
+    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
+    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
+    const bool jacobi = !(w.useMG || w.useTL);
+    if (wantCoarse && !masked) note("no fixed variables (K singular): block-Jacobi of K + w^2 density M in place of the two-level / multigrid preconditioner");
+    else if (wantCoarse && jacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of K + w^2 density M") : c->precondNote + " (block-Jacobi of K + w^2 density M)");
+    else if (!wantCoarse) note("block-Jacobi of K + w^2 density M on both planes");
+    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K on both planes") : c->precondNote);
+    else note(w.useMG ? "multigrid V-cycle of K on both planes" : "two-level preconditioner of K on both planes");
+    if (c->harmTwoPass) note("mass product: two real passes and a combine kernel (option harmonic_two_pass)");
+    w.ld = (w.n + 31) / 32 * 32;
+    const int64_t ld = w.ld;
+    w.vec.alloc((size_t)ld * 14);
+    w.vec.zero(s);
+    {
+        double *q = w.vec.p;
+        double **slots[7] = {&w.f, &w.x, &w.r, &w.z, &w.p, &w.Ap, &w.tmp};
+        for (auto sl : slots) { *sl = q; q += 2 * ld; }
+    }
+    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
+    w.scal.alloc(((size_t)maxit + 2) * 4);
+    w.cscal.alloc(((size_t)maxit + 2) * 4);
+    w.ctl.alloc(8);
+    w.ctl.zero(s);
+    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
+    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
+    c->stop.zero(s);
+    w.batch = std::max(2, std::min(8, c->checkEvery));
+    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
+    return jacobi;
+}
 
 void check_params(const mfh_ctx *c, const mfh_harmonic_params *p, const double *omega, const double *fRe, const int64_t *probeVars, int32_t nProbe,
                   const double *probeOut) {
@@ -477,50 +540,9 @@ mfh_status mfh_harmonic(mfh_ctx *c, const mfh_harmonic_params *prm, const double
     if (guard.widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
     EventTimer tsetup(s);
     const bool masked = !c->fixedVars.empty();
-    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of K + w^2 density M otherwise
-    ensure_precond(c);
-    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
-    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_harmonic: unpartitioned contexts only");
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_harmonic");
-
     HarmonicWork w;
-    w.c = c; w.s = s; w.d = c->bs();
-    w.nRows = c->sym.nRows;
-    w.n = (int64_t)w.d * c->nDoF;
-    w.masked = masked;
-    w.mask = masked ? c->dFixedMask.p : nullptr;
-    w.maxit = P.maxit;
-    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
-    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
-    const bool jacobi = !(w.useMG || w.useTL);
-    if (wantCoarse && !masked) note("no fixed variables (K singular): block-Jacobi of K + w^2 density M in place of the two-level / multigrid preconditioner");
-    else if (wantCoarse && jacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of K + w^2 density M") : c->precondNote + " (block-Jacobi of K + w^2 density M)");
-    else if (!wantCoarse) note("block-Jacobi of K + w^2 density M on both planes");
-    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K on both planes") : c->precondNote);
-    else note(w.useMG ? "multigrid V-cycle of K on both planes" : "two-level preconditioner of K on both planes");
-    if (c->harmTwoPass) note("mass product: two real passes and a combine kernel (option harmonic_two_pass)");
-    w.ld = (w.n + 31) / 32 * 32;
+    const bool jacobi = setup_harmonic_work(c, w, "mfh_harmonic", P.maxit, note);
     const int64_t ld = w.ld;
-    w.vec.alloc((size_t)ld * 14);
-    w.vec.zero(s);
-    {
-        double *q = w.vec.p;
-        double **slots[7] = {&w.f, &w.x, &w.r, &w.z, &w.p, &w.Ap, &w.tmp};
-        for (auto sl : slots) { *sl = q; q += 2 * ld; }
-    }
-    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
-    w.scal.alloc(((size_t)P.maxit + 2) * 4);
-    w.cscal.alloc(((size_t)P.maxit + 2) * 4);
-    w.ctl.alloc(8);
-    w.ctl.zero(s);
-    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
-    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
-    c->stop.zero(s);
-    w.batch = std::max(2, std::min(8, c->checkEvery));
-    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
 
     const int nFreq = P.nFreq;
     const int64_t rowLen = 2 * w.n;
@@ -540,17 +562,8 @@ mfh_status mfh_harmonic(mfh_ctx *c, const mfh_harmonic_params *prm, const double
     if (fIm) upload(w.f + ld, fIm, w.n, s);
     if (masked) { k::launch_mask(w.n, w.mask, w.f, s); k::launch_mask(w.n, w.mask, w.f + ld, s); }
     double hbb = 0.0;
-    {
-        // |f|^2 -> bb[0] and the threshold rtol^2 |f|^2 -> stop[0]: the same for every frequency
-        const int grid = w.vec_grid(w.n);
-        hipLaunchKernelGGL(k::k_harm_norm2, dim3(grid), dim3(256), 0, s, w.n, (const double *)w.f, ld, w.partials.p);
-        CHECK_LAUNCH();
-        const int col[2] = {0, 0};
-        const double sc[2] = {P.rtol * P.rtol, 1.0};
-        double *const dst[2] = {w.stop, w.bb};
-        w.reduce(grid, 2, col, sc, dst, w.open());
-        MFH_HIP(hipMemcpyAsync(&hbb, w.bb, sizeof(double), hipMemcpyDeviceToHost, s));
-    }
+    w.set_threshold(P.rtol);            // the same for every frequency
+    MFH_HIP(hipMemcpyAsync(&hbb, w.bb, sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
     require(std::isfinite(hbb), MFH_ERR_INVALID, "mfh_harmonic: the load has an entry that is not finite");
     const double setupMs = tsetup.stop();
@@ -686,6 +699,36 @@ mfh_status mfh_debug_harmonic_apply(mfh_ctx *c, double zKre, double zKim, double
     MFH_HIP(hipMemcpyAsync(yIm, dy + ld, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dot) MFH_HIP(hipMemcpyAsync(dot, dd, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// HarmonicWork::solve (restart = false) on (f^, x0^) as a frequency of mfh_harmonic calls it: the load masked and its threshold set the same way
+mfh_status mfh_debug_harmonic_cocg(mfh_ctx *c, const double *zK, const double *zM, double jacobiCM, double rtol, int32_t maxit, const double *fRe, const double *fIm,
+                                   const double *x0Re, const double *x0Im, double *xRe, double *xIm, double *history, double *chistory, int32_t *its) {
+    MFH_TRY(c)
+    require(c && zK && zM && fRe && xRe && xIm && history && chistory && its && std::isfinite(jacobiCM) && rtol > 0.0 && rtol < 1.0 && maxit > 0, MFH_ERR_INVALID,
+            "mfh_debug_harmonic_cocg: arguments");
+    require(std::isfinite(zK[0]) && std::isfinite(zK[1]) && std::isfinite(zM[0]) && std::isfinite(zM[1]), MFH_ERR_INVALID, "mfh_debug_harmonic_cocg: coefficients");
+    prepare_pencil(c, "mfh_debug_harmonic_cocg");
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    HarmonicWork w;
+    const bool jacobi = setup_harmonic_work(c, w, "mfh_debug_harmonic_cocg", maxit, [](const std::string &) {});
+    const int64_t ld = w.ld;
+    upload(w.f, fRe, w.n, s);
+    if (fIm) upload(w.f + ld, fIm, w.n, s);
+    if (w.masked) { k::launch_mask(w.n, w.mask, w.f, s); k::launch_mask(w.n, w.mask, w.f + ld, s); }
+    w.set_threshold(rtol);
+    if (x0Re) upload(w.x, x0Re, w.n, s);       // (zero on the fixed variables, as a converged frequency leaves the warm start)
+    if (x0Im) upload(w.x + ld, x0Im, w.n, s);
+    const int ret = w.solve(Cx{zK[0], zK[1]}, Cx{zM[0], zM[1]}, jacobi, jacobiCM, false);
+    MFH_HIP(hipMemcpyAsync(xRe, w.x, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(xIm, w.x + ld, (size_t)w.n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(history, w.scal.p, ((size_t)maxit + 1) * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipMemcpyAsync(chistory, w.cscal.p, ((size_t)maxit + 1) * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    *its = ret;
+    if (ret < 0) throw Error(MFH_ERR_NOT_CONVERGED, ret == -1 ? "mfh_debug_harmonic_cocg: the COCG reached maxit" : "mfh_debug_harmonic_cocg: COCG breakdown");
     MFH_CATCH(c)
 }
 

@@ -1105,6 +1105,7 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
     } guard{c};
     if (resolve_upper_storage(c)) {
         c->modesWide = true;
+        refresh_storage_rule(c);          // (before ensure_precond: see WideGuard)
         note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
     }
     EventTimer tsetup(s);

@@ -169,6 +169,17 @@ __global__ void __launch_bounds__(256) k_pencil_dinv(int64_t nRows, const int32_
                 }
         }
         sym_block_inverse<DIM>(A, Inv);
+        // the identity on the fixed variables EXACTLY: with one fixed component of three, the cofactor and the determinant of its diagonal entry are
+        // the same 2 x 2 expression contracted into fmas two different ways, and their quotient came out as 1 -+ 1 ulp
+        if (fixedMask) {
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+                if (fixedMask[r * DIM + c]) {
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) { Inv[c * DIM + d] = 0.0; Inv[d * DIM + c] = 0.0; }
+                    Inv[c * DIM + c] = 1.0;
+                }
+        }
 #pragma unroll
         for (int c = 0; c < DIM; ++c)
 #pragma unroll

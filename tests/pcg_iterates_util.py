@@ -182,7 +182,7 @@ def exact_stop(res):
         best = min(res[:k])
         if res[k] <= 0.9 * best:
             return k, float(np.sqrt(res[k] * best))
-    raise AssertionError("no iteration falls 10 % below its predecessors: %s" % (res,))
+    raise AssertionError("no iteration falls 10 %% below its predecessors: %s" % (res,))
 
 
 def block_jacobi_blocks(K, bs, fixed):
