@@ -4,19 +4,11 @@
 //   A u+ = b,   A = cK K + cM M  (the "pencil operator"),   cK = 1 + gamma bR / (beta dt),  cM = density (1 / (beta dt^2) + gamma aR / (beta dt))
 // by a PCG loop of this file on the context's operator (apply_operator) and preconditioners (launch of k_pencil_dinv's blocks / tl_precond /
 // mg_precond), the way mfh_modes.hip builds on them without touching the pinned loops of mfh_solver.cpp.
-//   k_spmv_kron_acc    y = cK y + cM (M (x) I) x: k_spmv_kron's chunks and LDS partials, ADDING into the K product that apply_operator left in y
-//                      (cK == 0: y is not read), the fixed rows zeroed, x . y summed per workgroup in the same pass
-//   k_pencil_dinv      inverse diagonal blocks of A: cK K_ii + cM m_ii I (fixed rows / columns replaced by the identity), symmetric-packed
 //   k_newmark_predict  u~, v~, the vector M multiplies and the vector K multiplies, one pass over (u, v, a)
 //   k_newmark_rhs      b = g f + (products), masked, with b . b
 //   k_newmark_correct  a+, v+, u+, the probe values of the step and the snapshot row
 //   k_dyn_*            the PCG's vector kernels
-// Sums: every producing kernel leaves ONE partial per workgroup and sum (plain stores); k_dyn_reduce adds them in a fixed order (runs of consecutive
-// workgroups per lane, then an ordered two-level tree) and stores the total where the loop reads it. No floating-point atomics; the grids depend on n (and option dyn_grid_cap) only, so two
-// calls add in the same order.
-// Gate: the kernels of iteration `it` are no-ops once scal[4 it + 2] = r.r has met stop[0] (the idiom of the loops in mfh_solver.cpp; the layout of
-// the history -- {r.z, p.Ap, r.r, -} per iteration -- and of the control block is theirs, so that mg_precond's kernels take the same gate).
-#include "mfh_pencil.hh"      // the gate, the ordered sums, k_spmv_kron_acc, k_pencil_dinv and prepare_pencil, shared with mfh_harmonic.hip
+#include "mfh_pencil.hh"      // shared with mfh_harmonic.hip: the gate, the ordered sums, k_spmv_kron_acc, k_pencil_dinv, and the loop's setup and host driver
 
 namespace mfh { namespace k {
 
@@ -223,67 +215,26 @@ using k::DYN_NV;
 
 namespace {
 
-struct NewmarkWork {
-    mfh_ctx *c;
-    hipStream_t s;
-    int d;
-    int64_t n, nRows;
-    bool masked, useMG = false, useTL = false;
-    const uint8_t *mask = nullptr;
-    DBuf<double> vec, partials, scal, ctl, dinv;
+struct NewmarkWork : PencilWork {
     double *u, *v, *a, *ut, *vt, *xm, *xk, *f, *b, *x, *r, *z, *p, *Ap;
-    double *stop, *bb;                 // ctl: [0..3] the control block {threshold, -, -, iteration base}, [4] b . b
-    int maxit = 0, batch = 8;
-    double rtol = 0;
-    double dinvCK = -1, dinvCM = -1;   // the pencil the inverse diagonal blocks were built for
-    // per-phase device time (scripts/probe_dynamics.py: env MFH_DYN_TIMING=1 puts a synchronisation at every phase boundary)
-    bool timing = false;
-    double tPhase[7] = {0, 0, 0, 0, 0, 0, 0};   // K products, M products + p.Ap, residual update (+ block-Jacobi), coarse preconditioner + r.z, direction, read-back, step kernels
-    double tMark = 0;
-    void lap(int phase) {
-        if (!timing) return;
-        MFH_HIP(hipStreamSynchronize(s));
-        const double t = now_ms();
-        if (phase >= 0) tPhase[phase] += t - tMark;
-        tMark = t;
-    }
+    double rtol = 0, cK = 0, cM = 0;   // the tolerance set_threshold applies; the pencil of the solve under way
 
-    DynGate gate(int it) const { return DynGate{scal.p, it, stop}; }
-    DynGate open() const { return DynGate{nullptr, 0, nullptr}; }
-    void reduce(int nPart, int nv, const int *col, const double *scale, double *const *dst, const DynGate &g) {
-        k::launch_reduce(nPart, nv, col, scale, dst, partials.p, g, s);
-    }
     // y = cK K x + cM M x on the free variables; dst (may be null) = x . y
-    void pencil(double cK, double cM, const double *xin, double *y, double *dotDst, const DynGate &g) {
+    void pencil(const double *xin, double *y, double *dotDst, const DynGate &g) {
         lap(-1);
         if (cK != 0.0) apply_operator(c, masked, xin, y, nullptr);
         lap(0);
         const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, masked), cK != 0.0, cK, cM, xin, y, dotDst ? partials.p : nullptr, g, s, c->dynGridCap);
-        if (dotDst) {
-            const int col[1] = {0};
-            const double sc[1] = {1.0};
-            double *const dst[1] = {dotDst};
-            reduce(np, 1, col, sc, dst, g);
-        }
+        if (dotDst) sum_to(np, g, dotDst);
         lap(1);
     }
-    void ensure_dinv(double cK, double cM) {
-        if (dinvCK == cK && dinvCM == cM) return;
-        dinv.alloc((size_t)nRows * (size_t)(d * (d + 1) / 2));
-        k::launch_pencil_dinv(d, nRows, c->dRowPtr.p, c->dColIdx.p, cK != 0.0 ? c->dVals.p : nullptr, c->dMassVals.p, cK, cM, mask, dinv.p, s);
-        dinvCK = cK; dinvCM = cM;
-    }
-    int vec_grid(int64_t count) const { return k::dyn_grid(count, std::max(1, std::min(c->dynGridCap, k::DYN_GRID_CAP))); }
     template <bool BJ> void launch_init() {
         const int grid = vec_grid(nRows);
         k::with_dim(d, [&](auto D) {
             k::launch_k(k::k_dyn_init<D(), BJ>, dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)b, (const double *)Ap, (const double *)bb, x, r, z, p, partials.p);
         });
         CHECK_LAUNCH();
-        const int col[2] = {0, 1};
-        const double sc[2] = {1.0, 1.0};
-        double *const dst[2] = {BJ ? scal.p : nullptr, scal.p + 2};
-        reduce(grid, 2, col, sc, dst, open());
+        sum_to(grid, k::dyn_open(), BJ ? scal.p : nullptr, scal.p + 2);
     }
     template <bool BJ> void launch_update(int it) {
         const int grid = vec_grid(nRows);
@@ -292,126 +243,62 @@ struct NewmarkWork {
             k::launch_k(k::k_dyn_update<D(), BJ>, dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)Ap, (const double *)p, x, r, z, g, partials.p);
         });
         CHECK_LAUNCH();
-        const int col[2] = {0, 1};
-        const double sc[2] = {1.0, 1.0};
-        double *const dst[2] = {BJ ? scal.p + (size_t)(it + 1) * 4 : nullptr, scal.p + (size_t)(it + 1) * 4 + 2};
-        reduce(grid, 2, col, sc, dst, g);
+        sum_to(grid, g, BJ ? scal.p + (size_t)(it + 1) * 4 : nullptr, scal.p + (size_t)(it + 1) * 4 + 2);
     }
     // z = B r with the hierarchy of K (B ~ K^-1: its scaling by 1 / cK changes no PCG iterate and is left out), then r . z of iteration it + 1
     void coarse_precond(int it) {
-        const DynGate g = it >= 0 ? gate(it) : open();
+        const DynGate g = it >= 0 ? gate(it) : k::dyn_open();
         if (useMG) mg_precond(c, r, z, it >= 0 ? scal.p : nullptr, it, it >= 0 ? stop : nullptr);
         else tl_precond(c, r, z, nullptr, -1);
         const int grid = vec_grid(n);
         hipLaunchKernelGGL(k::k_dyn_rz, dim3(grid), dim3(256), 0, s, n, (const double *)r, z, mask, g, partials.p);
         CHECK_LAUNCH();
-        const int col[1] = {0};
-        const double sc[1] = {1.0};
-        double *const dst[1] = {scal.p + (size_t)(it + 1) * 4};
-        reduce(grid, 1, col, sc, dst, g);
+        sum_to(grid, g, scal.p + (size_t)(it + 1) * 4);
     }
     void direction(int it, bool first) {
-        hipLaunchKernelGGL(k::k_dyn_direction, dim3(vec_grid(n)), dim3(256), 0, s, n, (const double *)z, p, first ? open() : gate(it), first ? 1 : 0);
+        hipLaunchKernelGGL(k::k_dyn_direction, dim3(vec_grid(n)), dim3(256), 0, s, n, (const double *)z, p, first ? k::dyn_open() : gate(it), first ? 1 : 0);
         CHECK_LAUNCH();
     }
 
+    // the two halves of a PCG solve that pencil_loop calls: r = b - A x with the first z and p, and iteration `it`
+    void start(bool jacobi) {
+        if (jacobi) ensure_dinv(cK, cM);
+        pencil(x, Ap, nullptr, k::dyn_open());
+        if (jacobi) launch_init<true>();
+        else { launch_init<false>(); coarse_precond(-1); direction(-1, true); }
+    }
+    void iterate(int it, bool jacobi) {
+        pencil(p, Ap, scal.p + (size_t)it * 4 + 1, gate(it));
+        if (jacobi) { launch_update<true>(it); lap(2); }
+        else { launch_update<false>(it); lap(2); coarse_precond(it); lap(3); }
+        direction(it, false);
+        lap(4);
+    }
     // PCG on A = cK K + cM M: b in this->b with b . b in bb[0] and the threshold in stop[0] (set_threshold), the start vector in x. Returns the
     // iterations taken, -1: maxit reached (x then holds the last iterate), -2: breakdown (a residual norm is not finite).
     int solve(double cK, double cM, bool jacobi) {
-        MFH_HIP(hipMemsetAsync(scal.p, 0, scal.n * sizeof(double), s));
-        if (jacobi) ensure_dinv(cK, cM);
-        pencil(cK, cM, x, Ap, nullptr, open());
-        if (jacobi) launch_init<true>();
-        else {
-            launch_init<false>();
-            coarse_precond(-1);
-            direction(-1, true);
-        }
-        std::vector<double> hs;
-        double hctl[5];
-        int it = 0, lastChecked = 0;
-        for (;;) {
-            const int itEnd = std::min(maxit, it + batch);
-            for (; it < itEnd; ++it) {
-                pencil(cK, cM, p, Ap, scal.p + (size_t)it * 4 + 1, gate(it));
-                if (jacobi) { launch_update<true>(it); lap(2); }
-                else { launch_update<false>(it); lap(2); coarse_precond(it); lap(3); }
-                direction(it, false);
-                lap(4);
-            }
-            hs.resize((size_t)(it - lastChecked + 1) * 4);
-            MFH_HIP(hipMemcpyAsync(hs.data(), scal.p + (size_t)lastChecked * 4, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            MFH_HIP(hipMemcpyAsync(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost, s));
-            MFH_HIP(hipStreamSynchronize(s));
-            lap(5);
-            for (int q = lastChecked; q <= it; ++q) {
-                const double rr = hs[(size_t)(q - lastChecked) * 4 + 2];
-                if (!std::isfinite(rr)) return -2;
-                if (rr <= hctl[0]) {
-                    batch = std::max(2, std::min(q + 1, c->checkEvery));      // the next solve of the run needs about as many: one read-back
-                    return q;
-                }
-            }
-            if (it >= maxit) return -1;
-            lastChecked = it;
-            batch = std::max(2, std::min(2 * batch, c->checkEvery));
-        }
+        this->cK = cK; this->cM = cM;
+        return pencil_loop(*this, jacobi, batch, [&] { return batch = std::max(2, std::min(2 * batch, c->checkEvery)); }, true);
     }
     // b . b of the right-hand side just formed (the partials of k_newmark_rhs) -> bb[0] and the threshold rtol^2 b . b -> stop[0]
     void set_threshold(int nPart) {
         const int col[2] = {0, 0};
         const double sc[2] = {rtol * rtol, 1.0};
         double *const dst[2] = {stop, bb};
-        reduce(nPart, 2, col, sc, dst, open());
+        reduce(nPart, 2, col, sc, dst, k::dyn_open());
     }
 };
 
-// What mfh_newmark and the test hooks of its loop (mfh_debug_pencil_precond, mfh_debug_newmark_pcg) share: the state of the context the pencil
-// products and the preconditioners read, the choice between the block-Jacobi of A, the two-level and the multigrid preconditioner (note: what
-// was chosen, in words), the work vectors and the control blocks of NewmarkWork::solve. Returns whether the time steps run block-Jacobi.
-template <class Note>
-bool setup_newmark_work(mfh_ctx *c, NewmarkWork &w, const char *who, int maxit, double rtol, Note &&note) {
-    hipStream_t s = c->stream;
-    const bool masked = !c->fixedVars.empty();
-    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of A itself otherwise
-    ensure_precond(c);
-    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
-    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, (std::string(who) + ": unpartitioned contexts only").c_str());
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, ("the assembled SpMV of " + std::string(who)).c_str());
-
-    w.c = c; w.s = s; w.d = c->bs();
-    w.nRows = c->sym.nRows;
-    w.n = (int64_t)w.d * c->nDoF;
-    w.masked = masked;
-    w.mask = masked ? c->dFixedMask.p : nullptr;
-    w.maxit = maxit; w.rtol = rtol;
-    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
-    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
-    const bool stepJacobi = !(w.useMG || w.useTL);
-    if (wantCoarse && !masked) note("no fixed variables (K singular, A not): block-Jacobi of A in place of the two-level / multigrid preconditioner");
-    else if (wantCoarse && stepJacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of A") : c->precondNote + " (block-Jacobi of A)");
-    else if (!wantCoarse) note("block-Jacobi of A = cK K + cM M");
-    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K") : c->precondNote);
-    const int64_t ld = (w.n + 31) / 32 * 32;
-    w.vec.alloc((size_t)ld * 14);
-    w.vec.zero(s);
-    {
-        double *q = w.vec.p;
-        double **slots[14] = {&w.u, &w.v, &w.a, &w.ut, &w.vt, &w.xm, &w.xk, &w.f, &w.b, &w.x, &w.r, &w.z, &w.p, &w.Ap};
-        for (auto sl : slots) { *sl = q; q += ld; }
-    }
-    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
-    w.scal.alloc(((size_t)maxit + 2) * 4);
-    w.ctl.alloc(8);
-    w.ctl.zero(s);
-    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
-    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
-    c->stop.zero(s);
-    w.batch = std::max(2, std::min(8, c->checkEvery));
-    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
+// What mfh_newmark and the test hooks of its loop (mfh_debug_pencil_precond, mfh_debug_newmark_pcg) share: setup_pencil_work and the work vectors
+// of NewmarkWork::solve. Returns whether the time steps run block-Jacobi.
+bool setup_newmark_work(mfh_ctx *c, NewmarkWork &w, const char *who, int maxit, double rtol) {
+    const bool stepJacobi = setup_pencil_work(c, w, who, maxit);
+    w.rtol = rtol;
+    w.vec.alloc((size_t)w.ld * 14);
+    w.vec.zero(w.s);
+    double *q = w.vec.p;
+    double **slots[14] = {&w.u, &w.v, &w.a, &w.ut, &w.vt, &w.xm, &w.xk, &w.f, &w.b, &w.x, &w.r, &w.z, &w.p, &w.Ap};
+    for (auto sl : slots) { *sl = q; q += w.ld; }
     return stepJacobi;
 }
 
@@ -441,7 +328,7 @@ void kron_apply(mfh_ctx *c, const k::SpmvArgs &args, const double *x, double *y,
         upload(dx.p, x, n, s);
         xin = dx.p; yout = dy.p;
     }
-    k::launch_spmv_kron_acc(args, false, 0.0, 1.0, xin, yout, nullptr, DynGate{nullptr, 0, nullptr}, s, c->dynGridCap);
+    k::launch_spmv_kron_acc(args, false, 0.0, 1.0, xin, yout, nullptr, k::dyn_open(), s, c->dynGridCap);
     if (!onDevice) MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
 }
@@ -480,7 +367,11 @@ mfh_status mfh_newmark(mfh_ctx *c, const mfh_newmark_params *prm, double *u, dou
     const double cK = 1.0 + P.gamma * P.rayleighStiff / bdt;
     const double cM = P.density * (1.0 / (bdt * P.dt) + P.gamma * P.rayleighMass / bdt);
     NewmarkWork w;
-    const bool stepJacobi = setup_newmark_work(c, w, "mfh_newmark", P.maxit, P.rtol, note);
+    const bool stepJacobi = setup_newmark_work(c, w, "mfh_newmark", P.maxit, P.rtol);
+    if (w.wantCoarse && !masked) note("no fixed variables (K singular, A not): block-Jacobi of A in place of the two-level / multigrid preconditioner");
+    else if (w.wantCoarse && stepJacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of A") : c->precondNote + " (block-Jacobi of A)");
+    else if (!w.wantCoarse) note("block-Jacobi of A = cK K + cM M");
+    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K") : c->precondNote);
 
     const int nSteps = P.nSteps;
     const int stride = snapshots ? P.snapshotStride : 0;
@@ -528,13 +419,13 @@ mfh_status mfh_newmark(mfh_ctx *c, const mfh_newmark_params *prm, double *u, dou
             const double g = amplitude ? amplitude[step] : 1.0;
             double *row = dEnergy.p + (size_t)step * 3;
             // kinetic: 1/2 v . (density M) v through the accumulate kernel's dot; strain and work: K u, then {u . K u, f . u}
-            const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, masked), false, 0.0, P.density, w.v, w.r, w.partials.p, w.open(), s, c->dynGridCap);
-            { const int col[1] = {0}; const double sc[1] = {0.5}; double *const dst[1] = {row}; w.reduce(np, 1, col, sc, dst, w.open()); }
+            const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, masked), false, 0.0, P.density, w.v, w.r, w.partials.p, k::dyn_open(), s, c->dynGridCap);
+            { const int col[1] = {0}; const double sc[1] = {0.5}; double *const dst[1] = {row}; w.reduce(np, 1, col, sc, dst, k::dyn_open()); }
             apply_operator(c, masked, w.u, w.r, nullptr);
             const int grid = w.vec_grid(w.n);
             hipLaunchKernelGGL(k::k_dyn_dot2, dim3(grid), dim3(256), 0, s, w.n, (const double *)w.u, (const double *)w.r, f ? (const double *)w.f : (const double *)nullptr, w.partials.p);
             CHECK_LAUNCH();
-            { const int col[2] = {0, 1}; const double sc[2] = {0.5, g}; double *const dst[2] = {row + 1, row + 2}; w.reduce(grid, 2, col, sc, dst, w.open()); }
+            { const int col[2] = {0, 1}; const double sc[2] = {0.5, g}; double *const dst[2] = {row + 1, row + 2}; w.reduce(grid, 2, col, sc, dst, k::dyn_open()); }
         }
     };
     mfh_status failure = MFH_OK;
@@ -549,7 +440,7 @@ mfh_status mfh_newmark(mfh_ctx *c, const mfh_newmark_params *prm, double *u, dou
         MFH_HIP(hipMemcpyAsync(w.xk, w.u, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice, s));
         k::launch_axpby(w.n, -P.rayleighStiff, w.v, -1.0, w.xk, s);
         apply_operator(c, masked, w.xk, w.Ap, nullptr);
-        k::launch_spmv_kron_acc(mass_spmv_args(c, masked), true, 1.0, 1.0, w.xm, w.Ap, nullptr, w.open(), s, c->dynGridCap);
+        k::launch_spmv_kron_acc(mass_spmv_args(c, masked), true, 1.0, 1.0, w.xm, w.Ap, nullptr, k::dyn_open(), s, c->dynGridCap);
         const int np = k::launch_newmark_rhs(w.n, g0, f ? w.f : nullptr, w.Ap, w.mask, w.b, w.partials.p, s);
         w.set_threshold(np);
         MFH_HIP(hipMemsetAsync(w.x, 0, (size_t)w.n * sizeof(double), s));
@@ -574,7 +465,7 @@ mfh_status mfh_newmark(mfh_ctx *c, const mfh_newmark_params *prm, double *u, dou
             w.lap(-1);
             k::launch_newmark_predict(pa, w.u, w.v, w.a, w.mask, w.ut, w.vt, w.xm, haveCK ? w.xk : nullptr, s);
             if (haveCK) apply_operator(c, masked, w.xk, w.Ap, nullptr);
-            k::launch_spmv_kron_acc(mass_spmv_args(c, masked), haveCK, 1.0, 1.0, w.xm, w.Ap, nullptr, w.open(), s, c->dynGridCap);
+            k::launch_spmv_kron_acc(mass_spmv_args(c, masked), haveCK, 1.0, 1.0, w.xm, w.Ap, nullptr, k::dyn_open(), s, c->dynGridCap);
             const int np = k::launch_newmark_rhs(w.n, g, f ? w.f : nullptr, w.Ap, w.mask, w.b, w.partials.p, s);
             w.set_threshold(np);
             MFH_HIP(hipMemcpyAsync(w.x, w.ut, (size_t)w.n * sizeof(double), hipMemcpyDeviceToDevice, s));      // warm start
@@ -660,10 +551,7 @@ mfh_status mfh_debug_newmark_rhs(mfh_ctx *c, int64_t n, double g, const double *
     if (f) upload(in.p + n, f, n, s);
     if (mask) dm.upload(mask, (size_t)n, s);
     const int np = k::launch_newmark_rhs(n, g, f ? in.p + n : nullptr, in.p, mask ? dm.p : nullptr, out.p, part.p, s);
-    const int col[1] = {0};
-    const double sc[1] = {1.0};
-    double *const dst[1] = {out.p + n};
-    k::launch_reduce(np, 1, col, sc, dst, part.p, DynGate{nullptr, 0, nullptr}, s);
+    k::launch_sum(np, part.p, k::dyn_open(), s, out.p + n);
     MFH_HIP(hipMemcpyAsync(b, out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipMemcpyAsync(bb, out.p + n, sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
@@ -731,28 +619,22 @@ mfh_status mfh_debug_pencil_apply(mfh_ctx *c, double cK, double cM, int32_t mask
     prepare_pencil(c, "mfh_debug_pencil_apply");
     hipStream_t s = c->stream;
     WideGuard guard(c);
-    ensure_precond(c);                 // (K assembled, the fixed-variable mask on the device)
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_debug_pencil_apply");
+    prepare_pencil_state(c, "mfh_debug_pencil_apply", false);
     const int64_t n = (int64_t)c->bs() * c->nDoF;
     const bool m = masked != 0 && !c->fixedVars.empty();
     DBuf<double> dx, dy, part;
     dx.alloc((size_t)n); dy.alloc((size_t)n + 1); part.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
     upload(dx.p, x, n, s);
     if (cK != 0.0) apply_operator(c, m, dx.p, dy.p, nullptr);
-    const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, m), cK != 0.0, cK, cM, dx.p, dy.p, part.p, DynGate{nullptr, 0, nullptr}, s, c->dynGridCap);
-    const int col[1] = {0};
-    const double sc[1] = {1.0};
-    double *const dst[1] = {dy.p + n};
-    k::launch_reduce(np, 1, col, sc, dst, part.p, DynGate{nullptr, 0, nullptr}, s);
+    const int np = k::launch_spmv_kron_acc(mass_spmv_args(c, m), cK != 0.0, cK, cM, dx.p, dy.p, part.p, k::dyn_open(), s, c->dynGridCap);
+    k::launch_sum(np, part.p, k::dyn_open(), s, dy.p + n);
     MFH_HIP(hipMemcpyAsync(y, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dot) MFH_HIP(hipMemcpyAsync(dot, dy.p + n, sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
     MFH_CATCH(c)
 }
 
-// z = Dinv r with the blocks NewmarkWork::ensure_dinv builds for (cK, cM) (HarmonicWork::ensure_dinv launches the same kernel with cK = 1)
+// z = Dinv r with the blocks PencilWork::ensure_dinv builds for (cK, cM) (the Newmark loop's call; the harmonic loop asks for cK = 1)
 mfh_status mfh_debug_pencil_precond(mfh_ctx *c, double cK, double cM, const double *r, double *z) {
     MFH_TRY(c)
     require(c && r && z && std::isfinite(cK) && std::isfinite(cM), MFH_ERR_INVALID, "mfh_debug_pencil_precond: arguments");
@@ -762,7 +644,7 @@ mfh_status mfh_debug_pencil_precond(mfh_ctx *c, double cK, double cM, const doub
     // the whole setup of the loop for one block apply, deliberately: ensure_dinv then sees the context in the state the loop's own call sees it in
     // (storage, assembled K, mass buffer, mask)
     NewmarkWork w;
-    setup_newmark_work(c, w, "mfh_debug_pencil_precond", 1, 0.5, [](const std::string &) {});
+    setup_newmark_work(c, w, "mfh_debug_pencil_precond", 1, 0.5);
     w.ensure_dinv(cK, cM);
     upload(w.r, r, w.n, s);
     k::with_dim(w.d, [&](auto D) {
@@ -785,7 +667,7 @@ mfh_status mfh_debug_newmark_pcg(mfh_ctx *c, double cK, double cM, double rtol, 
     hipStream_t s = c->stream;
     WideGuard guard(c);
     NewmarkWork w;
-    const bool stepJacobi = setup_newmark_work(c, w, "mfh_debug_newmark_pcg", maxit, rtol, [](const std::string &) {});
+    const bool stepJacobi = setup_newmark_work(c, w, "mfh_debug_newmark_pcg", maxit, rtol);
     upload(w.f, b, w.n, s);
     const int np = k::launch_newmark_rhs(w.n, 0.0, nullptr, w.f, w.mask, w.b, w.partials.p, s);
     w.set_threshold(np);

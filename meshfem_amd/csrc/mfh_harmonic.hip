@@ -285,38 +285,14 @@ using k::DYN_NV;
 
 namespace {
 
-struct HarmonicWork {
-    mfh_ctx *c;
-    hipStream_t s;
-    int d;
-    int64_t n, nRows, ld;
-    bool masked, useMG = false, useTL = false;
-    const uint8_t *mask = nullptr;
-    DBuf<double> vec, partials, scal, cscal, ctl, dinv;
+struct HarmonicWork : PencilWork {
+    DBuf<double> cscal;                        // the complex scalars of the history (the Hermitian r . r, which the gate reads, is in scal; bb[0] = |f|^2)
     double *f, *x, *r, *z, *p, *Ap, *tmp;      // two planes each: re at v, im at v + ld
-    double *stop, *bb;                         // ctl: [0..3] the control block {threshold, -, -, iteration base}, [4] |f|^2
-    int maxit = 0, batch = 8;
-    double dinvCM = -1;                        // the pencil K + dinvCM M the inverse diagonal blocks were built for
-    // per-phase device time (scripts/probe_harmonic.py: env MFH_DYN_TIMING=1 puts a synchronisation at every phase boundary, as in mfh_newmark)
-    bool timing = false;
-    double tPhase[6] = {0, 0, 0, 0, 0, 0};     // K products, M product + p^T Z p, residual update (+ block-Jacobi), coarse preconditioner + r^T z, direction, read-back
-    double tMark = 0;
-    void lap(int phase) {
-        if (!timing) return;
-        MFH_HIP(hipStreamSynchronize(s));
-        const double t = now_ms();
-        if (phase >= 0) tPhase[phase] += t - tMark;
-        tMark = t;
-    }
+    Cx zK{0, 0}, zM{0, 0};                     // the pencil of the solve under way
+    double jacobiCM = 0;                       // and the K + jacobiCM M its block-Jacobi takes
 
-    DynGate gate(int it) const { return DynGate{scal.p, it, stop}; }
-    DynGate open() const { return DynGate{nullptr, 0, nullptr}; }
-    void reduce(int nPart, int nv, const int *col, const double *scale, double *const *dst, const DynGate &g) {
-        k::launch_reduce(nPart, nv, col, scale, dst, partials.p, g, s);
-    }
-    int vec_grid(int64_t count) const { return k::dyn_grid(count, std::max(1, std::min(c->dynGridCap, k::DYN_GRID_CAP))); }
     // y = zK K x + zM M x on the free variables; dotDst (may be null): {Re, Im} of x^T y
-    void pencil(Cx zK, Cx zM, const double *xin, double *y, double *dotDst, const DynGate &g) {
+    void pencil(const double *xin, double *y, double *dotDst, const DynGate &g) {
         const bool haveK = zK.re != 0.0 || zK.im != 0.0;
         lap(-1);
         if (haveK) {
@@ -326,19 +302,8 @@ struct HarmonicWork {
         lap(0);
         const int np = k::launch_spmv_kron_cacc(mass_spmv_args(c, masked), haveK, zK, zM, xin, y, ld, n, tmp, dotDst ? partials.p : nullptr, g, s,
                                                 c->dynGridCap, c->harmTwoPass);
-        if (dotDst) {
-            const int col[2] = {0, 1};
-            const double sc[2] = {1.0, 1.0};
-            double *const dst[2] = {dotDst, dotDst + 1};
-            reduce(np, 2, col, sc, dst, g);
-        }
+        if (dotDst) sum_to(np, g, dotDst, dotDst + 1);
         lap(1);
-    }
-    void ensure_dinv(double cM) {
-        if (dinvCM == cM) return;
-        dinv.alloc((size_t)nRows * (size_t)(d * (d + 1) / 2));
-        k::launch_pencil_dinv(d, nRows, c->dRowPtr.p, c->dColIdx.p, c->dVals.p, c->dMassVals.p, 1.0, cM, mask, dinv.p, s);
-        dinvCM = cM;
     }
     template <bool BJ> void launch_init() {
         const int grid = vec_grid(nRows);
@@ -346,10 +311,7 @@ struct HarmonicWork {
             k::launch_k(k::k_harm_init<D(), BJ>, dim3(grid), dim3(256), 0, s, nRows, (const double *)dinv.p, (const double *)f, (const double *)Ap, r, z, p, ld, partials.p);
         });
         CHECK_LAUNCH();
-        const int col[3] = {0, 1, 2};
-        const double sc[3] = {1.0, 1.0, 1.0};
-        double *const dst[3] = {BJ ? cscal.p : nullptr, BJ ? cscal.p + 1 : nullptr, scal.p + 2};
-        reduce(grid, 3, col, sc, dst, open());
+        sum_to(grid, k::dyn_open(), BJ ? cscal.p : nullptr, BJ ? cscal.p + 1 : nullptr, scal.p + 2);
     }
     template <bool BJ> void launch_update(int it) {
         const int grid = vec_grid(nRows);
@@ -359,15 +321,12 @@ struct HarmonicWork {
                         (const double *)cscal.p, partials.p);
         });
         CHECK_LAUNCH();
-        const int col[3] = {0, 1, 2};
-        const double sc[3] = {1.0, 1.0, 1.0};
         double *const cn = cscal.p + (size_t)(it + 1) * 4;
-        double *const dst[3] = {BJ ? cn : nullptr, BJ ? cn + 1 : nullptr, scal.p + (size_t)(it + 1) * 4 + 2};
-        reduce(grid, 3, col, sc, dst, g);
+        sum_to(grid, g, BJ ? cn : nullptr, BJ ? cn + 1 : nullptr, scal.p + (size_t)(it + 1) * 4 + 2);
     }
     // z = B r on both planes with the hierarchy of K, then r^T z of iteration it + 1
     void coarse_precond(int it) {
-        const DynGate g = it >= 0 ? gate(it) : open();
+        const DynGate g = it >= 0 ? gate(it) : k::dyn_open();
         for (int plane = 0; plane < 2; ++plane) {
             const double *rp = r + plane * ld;
             double *zp = z + plane * ld;
@@ -377,63 +336,38 @@ struct HarmonicWork {
         const int grid = vec_grid(n);
         hipLaunchKernelGGL(k::k_harm_rz, dim3(grid), dim3(256), 0, s, n, (const double *)r, z, ld, mask, g, partials.p);
         CHECK_LAUNCH();
-        const int col[2] = {0, 1};
-        const double sc[2] = {1.0, 1.0};
         double *const cn = cscal.p + (size_t)(it + 1) * 4;
-        double *const dst[2] = {cn, cn + 1};
-        reduce(grid, 2, col, sc, dst, g);
+        sum_to(grid, g, cn, cn + 1);
     }
     void direction(int it, bool first) {
-        hipLaunchKernelGGL(k::k_harm_direction, dim3(vec_grid(n)), dim3(256), 0, s, n, (const double *)z, p, ld, first ? open() : gate(it), (const double *)cscal.p,
+        hipLaunchKernelGGL(k::k_harm_direction, dim3(vec_grid(n)), dim3(256), 0, s, n, (const double *)z, p, ld, first ? k::dyn_open() : gate(it), (const double *)cscal.p,
                            first ? 1 : 0);
         CHECK_LAUNCH();
     }
 
+    // the two halves of a COCG solve that pencil_loop calls: r = f - Z x with the first z and p, and iteration `it`
+    void start(bool jacobi) {
+        MFH_HIP(hipMemsetAsync(cscal.p, 0, cscal.n * sizeof(double), s));
+        if (jacobi) ensure_dinv(1.0, jacobiCM);
+        pencil(x, Ap, nullptr, k::dyn_open());
+        if (jacobi) launch_init<true>();
+        else { launch_init<false>(); coarse_precond(-1); direction(-1, true); }
+    }
+    void iterate(int it, bool jacobi) {
+        pencil(p, Ap, cscal.p + (size_t)it * 4 + 2, gate(it));
+        if (jacobi) { launch_update<true>(it); lap(2); }
+        else { launch_update<false>(it); lap(2); coarse_precond(it); lap(3); }
+        direction(it, false);
+        lap(4);
+    }
     // COCG on Z = zK K + zM M: the right-hand side in f with the threshold in stop[0], the start vector in x. Returns the iterations taken,
     // -1: maxit reached (x then holds the last iterate), -2: breakdown (a residual norm is not finite). restart: a continuation from the true
     // residual of a converged iterate (a few iterations: short batches, and the guess for the next frequency stays).
+    // Batches: the first read-back comes after as many iterations as the previous frequency took; where that was not enough the next ones come in
+    // short batches: an iteration past convergence still pays for its two (ungated) K products, ten times what a read-back costs.
     int solve(Cx zK, Cx zM, bool jacobi, double jacobiCM, bool restart) {
-        MFH_HIP(hipMemsetAsync(scal.p, 0, scal.n * sizeof(double), s));
-        MFH_HIP(hipMemsetAsync(cscal.p, 0, cscal.n * sizeof(double), s));
-        if (jacobi) ensure_dinv(jacobiCM);
-        pencil(zK, zM, x, Ap, nullptr, open());
-        if (jacobi) launch_init<true>();
-        else {
-            launch_init<false>();
-            coarse_precond(-1);
-            direction(-1, true);
-        }
-        std::vector<double> hs;
-        double hctl[5];
-        // the first read-back comes after as many iterations as the previous frequency took; where that was not enough the next ones come in short
-        // batches: an iteration past convergence still pays for its two (ungated) K products, ten times what a read-back costs
-        int it = 0, lastChecked = 0, step = restart ? std::max(2, std::min(8, c->checkEvery)) : batch;
-        for (;;) {
-            const int itEnd = std::min(maxit, it + step);
-            for (; it < itEnd; ++it) {
-                pencil(zK, zM, p, Ap, cscal.p + (size_t)it * 4 + 2, gate(it));
-                if (jacobi) { launch_update<true>(it); lap(2); }
-                else { launch_update<false>(it); lap(2); coarse_precond(it); lap(3); }
-                direction(it, false);
-                lap(4);
-            }
-            hs.resize((size_t)(it - lastChecked + 1) * 4);
-            MFH_HIP(hipMemcpyAsync(hs.data(), scal.p + (size_t)lastChecked * 4, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            MFH_HIP(hipMemcpyAsync(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost, s));
-            MFH_HIP(hipStreamSynchronize(s));
-            lap(5);
-            for (int q = lastChecked; q <= it; ++q) {
-                const double rr = hs[(size_t)(q - lastChecked) * 4 + 2];
-                if (!std::isfinite(rr)) return -2;
-                if (rr <= hctl[0]) {
-                    if (!restart) batch = std::max(2, std::min(q + 1, c->checkEvery));      // the next frequency needs about as many: one read-back
-                    return q;
-                }
-            }
-            if (it >= maxit) return -1;
-            lastChecked = it;
-            step = std::max(2, std::min(8, c->checkEvery));
-        }
+        this->zK = zK; this->zM = zM; this->jacobiCM = jacobiCM;
+        return pencil_loop(*this, jacobi, restart ? short_batch() : batch, [&] { return short_batch(); }, !restart);
     }
     // |f|^2 of the load in this->f -> bb[0] and the threshold rtol^2 |f|^2 -> stop[0]
     void set_threshold(double rtol) {
@@ -443,60 +377,20 @@ struct HarmonicWork {
         const int col[2] = {0, 0};
         const double sc[2] = {rtol * rtol, 1.0};
         double *const dst[2] = {stop, bb};
-        reduce(grid, 2, col, sc, dst, open());
+        reduce(grid, 2, col, sc, dst, k::dyn_open());
     }
 };
 
-// What mfh_harmonic and the test hook of its loop (mfh_debug_harmonic_cocg) share: the state of the context the pencil products and the
-// preconditioners read, the choice between the block-Jacobi of K + w^2 density M, the two-level and the multigrid preconditioner (note: what was
-// chosen, in words), the work vectors, the two histories and the control block of HarmonicWork::solve. Returns whether the loop runs block-Jacobi.
-template <class Note>
-bool setup_harmonic_work(mfh_ctx *c, HarmonicWork &w, const char *who, int maxit, Note &&note) {
-    hipStream_t s = c->stream;
-    const bool masked = !c->fixedVars.empty();
-    // ---- preconditioner: K's hierarchy where K is definite on the free variables, the diagonal blocks of K + w^2 density M otherwise
-    ensure_precond(c);
-    const bool wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
-    if (wantCoarse && masked) ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, (std::string(who) + ": unpartitioned contexts only").c_str());
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, ("the assembled SpMV of " + std::string(who)).c_str());
-
-    w.c = c; w.s = s; w.d = c->bs();
-    w.nRows = c->sym.nRows;
-    w.n = (int64_t)w.d * c->nDoF;
-    w.masked = masked;
-    w.mask = masked ? c->dFixedMask.p : nullptr;
-    w.maxit = maxit;
-    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
-    w.useTL = masked && !w.useMG && wantCoarse && c->tl.valid;
-    const bool jacobi = !(w.useMG || w.useTL);
-    if (wantCoarse && !masked) note("no fixed variables (K singular): block-Jacobi of K + w^2 density M in place of the two-level / multigrid preconditioner");
-    else if (wantCoarse && jacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of K + w^2 density M") : c->precondNote + " (block-Jacobi of K + w^2 density M)");
-    else if (!wantCoarse) note("block-Jacobi of K + w^2 density M on both planes");
-    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K on both planes") : c->precondNote);
-    else note(w.useMG ? "multigrid V-cycle of K on both planes" : "two-level preconditioner of K on both planes");
-    if (c->harmTwoPass) note("mass product: two real passes and a combine kernel (option harmonic_two_pass)");
-    w.ld = (w.n + 31) / 32 * 32;
-    const int64_t ld = w.ld;
-    w.vec.alloc((size_t)ld * 14);
-    w.vec.zero(s);
-    {
-        double *q = w.vec.p;
-        double **slots[7] = {&w.f, &w.x, &w.r, &w.z, &w.p, &w.Ap, &w.tmp};
-        for (auto sl : slots) { *sl = q; q += 2 * ld; }
-    }
-    w.partials.alloc((size_t)k::DYN_GRID_CAP * DYN_NV);
-    w.scal.alloc(((size_t)maxit + 2) * 4);
+// What mfh_harmonic and the test hook of its loop (mfh_debug_harmonic_cocg) share: setup_pencil_work, the work vectors and the complex history of
+// HarmonicWork::solve. Returns whether the loop runs block-Jacobi.
+bool setup_harmonic_work(mfh_ctx *c, HarmonicWork &w, const char *who, int maxit) {
+    const bool jacobi = setup_pencil_work(c, w, who, maxit);
+    w.vec.alloc((size_t)w.ld * 14);
+    w.vec.zero(w.s);
+    double *q = w.vec.p;
+    double **slots[7] = {&w.f, &w.x, &w.r, &w.z, &w.p, &w.Ap, &w.tmp};
+    for (auto sl : slots) { *sl = q; q += 2 * w.ld; }
     w.cscal.alloc(((size_t)maxit + 2) * 4);
-    w.ctl.alloc(8);
-    w.ctl.zero(s);
-    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
-    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
-    c->stop.zero(s);
-    w.batch = std::max(2, std::min(8, c->checkEvery));
-    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
     return jacobi;
 }
 
@@ -541,7 +435,13 @@ mfh_status mfh_harmonic(mfh_ctx *c, const mfh_harmonic_params *prm, const double
     EventTimer tsetup(s);
     const bool masked = !c->fixedVars.empty();
     HarmonicWork w;
-    const bool jacobi = setup_harmonic_work(c, w, "mfh_harmonic", P.maxit, note);
+    const bool jacobi = setup_harmonic_work(c, w, "mfh_harmonic", P.maxit);
+    if (w.wantCoarse && !masked) note("no fixed variables (K singular): block-Jacobi of K + w^2 density M in place of the two-level / multigrid preconditioner");
+    else if (w.wantCoarse && jacobi) note(c->precondNote.empty() ? std::string("two-level / multigrid preconditioner unavailable: block-Jacobi of K + w^2 density M") : c->precondNote + " (block-Jacobi of K + w^2 density M)");
+    else if (!w.wantCoarse) note("block-Jacobi of K + w^2 density M on both planes");
+    else if (w.useTL && c->precond == MFH_PRECOND_MULTIGRID) note(c->precondNote.empty() ? std::string("multigrid hierarchy unavailable: two-level preconditioner of K on both planes") : c->precondNote);
+    else note(w.useMG ? "multigrid V-cycle of K on both planes" : "two-level preconditioner of K on both planes");
+    if (c->harmTwoPass) note("mass product: two real passes and a combine kernel (option harmonic_two_pass)");
     const int64_t ld = w.ld;
 
     const int nFreq = P.nFreq;
@@ -607,15 +507,12 @@ mfh_status mfh_harmonic(mfh_ctx *c, const mfh_harmonic_params *prm, const double
                 if (its < 0) break;
                 itsFreq += its;
                 if (attempt > 0) ++restarts;
-                w.pencil(zK, zM, w.x, w.Ap, nullptr, w.open());
+                w.pencil(w.x, w.Ap, nullptr, k::dyn_open());      // (the pencil of the solve)
                 const int grid = w.vec_grid(w.n);
                 hipLaunchKernelGGL(k::k_harm_finish, dim3(grid), dim3(256), 0, s, w.n, (const double *)w.f, (const double *)w.Ap, (const double *)w.x, ld, (int)nProbe,
                                    (const int64_t *)dProbeVars.p, nProbe ? dProbe.p + (size_t)k2 * (size_t)nProbe * 2 : nullptr, fieldRow, w.partials.p);
                 CHECK_LAUNCH();
-                const int col[1] = {0};
-                const double sc[1] = {1.0};
-                double *const dst[1] = {dRes.p + k2};
-                w.reduce(grid, 1, col, sc, dst, w.open());
+                w.sum_to(grid, k::dyn_open(), dRes.p + k2);
                 double hr = 0.0;
                 MFH_HIP(hipMemcpyAsync(&hr, dRes.p + k2, sizeof(double), hipMemcpyDeviceToHost, s));
                 MFH_HIP(hipStreamSynchronize(s));
@@ -674,10 +571,7 @@ mfh_status mfh_debug_harmonic_apply(mfh_ctx *c, double zKre, double zKim, double
     prepare_pencil(c, "mfh_debug_harmonic_apply");
     hipStream_t s = c->stream;
     WideGuard guard(c);
-    ensure_precond(c);                 // (K assembled, the fixed-variable mask on the device)
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_debug_harmonic_apply");
+    prepare_pencil_state(c, "mfh_debug_harmonic_apply", false);
     const int64_t n = (int64_t)c->bs() * c->nDoF, ld = (n + 31) / 32 * 32;
     const bool m = masked != 0 && !c->fixedVars.empty();
     DBuf<double> v, part;
@@ -689,12 +583,8 @@ mfh_status mfh_debug_harmonic_apply(mfh_ctx *c, double zKre, double zKim, double
     const Cx zK{zKre, zKim}, zM{zMre, zMim};
     const bool haveK = zKre != 0.0 || zKim != 0.0;
     if (haveK) { apply_operator(c, m, dx, dy, nullptr); apply_operator(c, m, dx + ld, dy + ld, nullptr); }
-    const DynGate open{nullptr, 0, nullptr};
-    const int np = k::launch_spmv_kron_cacc(mass_spmv_args(c, m), haveK, zK, zM, dx, dy, ld, n, dt, part.p, open, s, c->dynGridCap, c->harmTwoPass);
-    const int col[2] = {0, 1};
-    const double sc[2] = {1.0, 1.0};
-    double *const dst[2] = {dd, dd + 1};
-    k::launch_reduce(np, 2, col, sc, dst, part.p, open, s);
+    const int np = k::launch_spmv_kron_cacc(mass_spmv_args(c, m), haveK, zK, zM, dx, dy, ld, n, dt, part.p, k::dyn_open(), s, c->dynGridCap, c->harmTwoPass);
+    k::launch_sum(np, part.p, k::dyn_open(), s, dd, dd + 1);
     MFH_HIP(hipMemcpyAsync(yRe, dy, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipMemcpyAsync(yIm, dy + ld, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dot) MFH_HIP(hipMemcpyAsync(dot, dd, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -713,7 +603,7 @@ mfh_status mfh_debug_harmonic_cocg(mfh_ctx *c, const double *zK, const double *z
     hipStream_t s = c->stream;
     WideGuard guard(c);
     HarmonicWork w;
-    const bool jacobi = setup_harmonic_work(c, w, "mfh_debug_harmonic_cocg", maxit, [](const std::string &) {});
+    const bool jacobi = setup_harmonic_work(c, w, "mfh_debug_harmonic_cocg", maxit);
     const int64_t ld = w.ld;
     upload(w.f, fRe, w.n, s);
     if (fIm) upload(w.f + ld, fIm, w.n, s);

@@ -1,8 +1,10 @@
-// The pieces of the pencil operator A = cK K + cM M that mfh_dynamics.hip (real coefficients, PCG) and mfh_harmonic.hip (complex coefficients,
-// COCG) both build on: the iteration gate, the two-stage ordered sums, the accumulating mass product, the inverse diagonal blocks of the pencil
-// and the context conditions. Everything here has internal linkage (anonymous namespaces): each of the two translation units carries its own
-// copy of the kernels, which is what keeps this header a move of code and not a new layer. Not part of the ABI. mfh_modes.hip includes it too, for
-// the accumulate pass of its prestressed pencil (K + s Kg: k_spmv_kron_acc on the geometric buffer) and the LDS limit of its pair kernel.
+// What the loops of mfh_dynamics.hip (real coefficients, PCG) and mfh_harmonic.hip (complex coefficients, COCG) on the pencil operator A = cK K + cM M
+// share. Device side: the iteration gate, the two-stage ordered sums, the accumulating mass product and the inverse diagonal blocks of the pencil.
+// Host side: the context conditions and device state (prepare_pencil, prepare_pencil_state), the base of the two work structs with its setup and
+// choice of preconditioner (PencilWork, setup_pencil_work), and the driver of both loops: batches, read-back, stopping rule (pencil_loop).
+// Everything here has internal linkage (anonymous namespaces): each translation unit carries its own copy of the kernels. Not part of the ABI.
+// mfh_modes.hip includes it too, for the accumulate pass of its prestressed pencil (K + s Kg: k_spmv_kron_acc on the geometric buffer) and the LDS
+// limit of its pair kernel; it takes none of the host side.
 //   k_spmv_kron_acc    y = cK y + cM (M (x) I) x: k_spmv_kron's chunks and LDS partials, ADDING into the K product that apply_operator left in y
 //                      (cK == 0: y is not read), the fixed rows zeroed, x . y summed per workgroup in the same pass
 //   k_pencil_dinv      inverse diagonal blocks of A: cK K_ii + cM m_ii I (fixed rows / columns replaced by the identity), symmetric-packed
@@ -27,6 +29,7 @@ constexpr size_t HARM_LDS_MAX = 160 * 1024;     // what a workgroup of gfx950 ca
                                                 // kernels (k_spmv_kron_cacc, k_spmv_kron_pair) fall back to two launches above it
 
 struct DynGate { const double *scal; int it; const double *stop; };
+DynGate dyn_open() { return DynGate{nullptr, 0, nullptr}; }       // the gate of a launch outside the iterations: never closed
 DEV bool dyn_closed(const DynGate &g) {
     if (!g.scal) return false;
     const int it = g.it + (int)g.stop[3];
@@ -211,6 +214,14 @@ void launch_reduce(int nPart, int nv, const int *col, const double *scale, doubl
     CHECK_LAUNCH();
 }
 
+// the usual sums: the totals of columns 0[, 1[, 2]] as they are, to dst0[, dst1[, dst2]] (a null destination is skipped)
+void launch_sum(int nPart, const double *partials, const DynGate &g, hipStream_t s, double *dst0, double *dst1 = nullptr, double *dst2 = nullptr) {
+    const int col[3] = {0, 1, 2};
+    const double scale[3] = {1.0, 1.0, 1.0};
+    double *const dst[3] = {dst0, dst1, dst2};
+    launch_reduce(nPart, dst2 ? 3 : (dst1 ? 2 : 1), col, scale, dst, partials, g, s);
+}
+
 // y = cK y + cM M x (acc) or cM M x; the workgroups' x . y in partials[.][0] (null: not wanted). Returns the number of partials.
 int launch_spmv_kron_acc(const SpmvArgs &a, bool acc, double cK, double cM, const double *x, double *y, double *partials, const DynGate &g, hipStream_t s,
                          int cap = DYN_GRID_CAP) {
@@ -250,5 +261,121 @@ void prepare_pencil(mfh_ctx *c, const char *who) {
 }
 
 void upload(double *dst, const double *src, int64_t n, hipStream_t s) { MFH_HIP(hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s)); }
+
+// The device state both products read, after prepare_pencil and the caller's WideGuard: K assembled and the fixed-variable mask on the device
+// (ensure_precond, which also settles the preconditioner in use: BEFORE the mass buffer), the mass buffer, the lists of the matrix-free operator or
+// else both triangles of the assembled one. hierarchy: the levels of the two-level / multigrid preconditioner as well, where that is the one in use
+// (for a loop on a context with fixed variables: K's hierarchy needs K definite).
+void prepare_pencil_state(mfh_ctx *c, const char *who, bool hierarchy) {
+    ensure_precond(c);
+    if (hierarchy) ensure_coarse_levels(c, 1);
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, ("the assembled SpMV of " + std::string(who)).c_str());
+}
+
+// What NewmarkWork (mfh_dynamics.hip) and HarmonicWork (mfh_harmonic.hip) are built on: the sizes, the preconditioner chosen, the buffers of the
+// sums, the history {r.z, p.Ap, r.r, -} with its control block, the batch of the next solve and the phase clock. A work adds its vectors (slots
+// of vec, ld apart), its coefficients and the launches of its own kernels, and for pencil_loop the members start(jacobi) and iterate(it, jacobi).
+struct PencilWork {
+    mfh_ctx *c = nullptr;
+    hipStream_t s = nullptr;
+    int d = 0;
+    int64_t n = 0, nRows = 0, ld = 0;  // variables, block rows, n rounded up to 32: the stride of the slots of vec (and of the two planes of a complex vector)
+    bool masked = false, wantCoarse = false, useMG = false, useTL = false;     // wantCoarse: the context asks for a hierarchy; useMG / useTL: the loop has one
+    const uint8_t *mask = nullptr;
+    DBuf<double> vec, partials, scal, ctl, dinv;
+    double dinvCK = -1, dinvCM = -1;           // the pencil the inverse diagonal blocks in dinv were built for
+    double *stop = nullptr, *bb = nullptr;     // ctl: [0..3] the control block {threshold, -, -, iteration base}, [4] b . b of the right-hand side
+    int maxit = 0, batch = 8;
+    // per-phase device time (scripts/probe_dynamics.py, scripts/probe_harmonic.py: env MFH_DYN_TIMING=1 puts a synchronisation at every phase boundary)
+    bool timing = false;
+    double tPhase[7] = {0, 0, 0, 0, 0, 0, 0};  // K products, M products + p.Ap, residual update (+ block-Jacobi), coarse preconditioner + r.z, direction, read-back, step kernels (mfh_newmark)
+    double tMark = 0;
+    void lap(int phase) {
+        if (!timing) return;
+        MFH_HIP(hipStreamSynchronize(s));
+        const double t = now_ms();
+        if (phase >= 0) tPhase[phase] += t - tMark;
+        tMark = t;
+    }
+
+    k::DynGate gate(int it) const { return k::DynGate{scal.p, it, stop}; }
+    void reduce(int nPart, int nv, const int *col, const double *scale, double *const *dst, const k::DynGate &g) { k::launch_reduce(nPart, nv, col, scale, dst, partials.p, g, s); }
+    void sum_to(int nPart, const k::DynGate &g, double *dst0, double *dst1 = nullptr, double *dst2 = nullptr) { k::launch_sum(nPart, partials.p, g, s, dst0, dst1, dst2); }
+    int vec_grid(int64_t count) const { return k::dyn_grid(count, std::max(1, std::min(c->dynGridCap, k::DYN_GRID_CAP))); }
+    int short_batch() const { return std::max(2, std::min(8, c->checkEvery)); }
+    // the block-Jacobi of cK K + cM M, rebuilt when the pencil changes
+    void ensure_dinv(double cK, double cM) {
+        if (dinvCK == cK && dinvCM == cM) return;
+        dinv.alloc((size_t)nRows * (size_t)(d * (d + 1) / 2));
+        k::launch_pencil_dinv(d, nRows, c->dRowPtr.p, c->dColIdx.p, cK != 0.0 ? c->dVals.p : nullptr, c->dMassVals.p, cK, cM, mask, dinv.p, s);
+        dinvCK = cK; dinvCM = cM;
+    }
+};
+
+// The state of the context the pencil products and the preconditioners read, the base of the work filled in, the choice of the preconditioner (K's
+// two-level / multigrid hierarchy where the context asks for one and K is definite on the free variables, the diagonal blocks of the pencil
+// otherwise), the buffers of the sums, the history and the control blocks. Returns whether the loop runs block-Jacobi; the caller words its notes
+// from (wantCoarse, masked, useMG, useTL), and allocates vec (slots ld apart) and what else its loop keeps.
+bool setup_pencil_work(mfh_ctx *c, PencilWork &w, const char *who, int maxit) {
+    const bool masked = !c->fixedVars.empty();
+    prepare_pencil_state(c, who, masked);
+    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, (std::string(who) + ": unpartitioned contexts only").c_str());
+    w.c = c; w.s = c->stream; w.d = c->bs();
+    w.nRows = c->sym.nRows;
+    w.n = (int64_t)w.d * c->nDoF;
+    w.ld = (w.n + 31) / 32 * 32;
+    w.masked = masked;
+    w.mask = masked ? c->dFixedMask.p : nullptr;
+    w.maxit = maxit;
+    w.wantCoarse = c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID;
+    w.useMG = masked && c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
+    w.useTL = masked && !w.useMG && w.wantCoarse && c->tl.valid;
+    w.partials.alloc((size_t)k::DYN_GRID_CAP * k::DYN_NV);
+    w.scal.alloc(((size_t)maxit + 2) * 4);
+    w.ctl.alloc(8);
+    w.ctl.zero(w.s);
+    w.stop = w.ctl.p; w.bb = w.ctl.p + 4;
+    c->stop.alloc(4);                  // (the control block tl_precond hands its kernel; not read without a history)
+    c->stop.zero(w.s);
+    w.batch = w.short_batch();
+    w.timing = getenv("MFH_DYN_TIMING") != nullptr;
+    return !(w.useMG || w.useTL);
+}
+
+// The host side of one solve, for both loops: w.start(jacobi) forms the first residual and direction, then batches of w.iterate(it, jacobi); after
+// each batch the history since the last check and the control block come back (the one synchronisation) and are scanned. Returns the first q with
+// r.r of iterate q <= the threshold (the gate has made the kernels of later iterations no-ops: x is iterate q), -1: maxit reached (x then holds the
+// last iterate), -2: breakdown (a residual norm is not finite). first: iterations before the first check; later(): before each further one;
+// remember: a solve that converged at q leaves w.batch = q + 1 (within [2, check_every]) for the next -- it needs about as many: one read-back.
+template <class Work, class Later>
+int pencil_loop(Work &w, bool jacobi, int first, Later &&later, bool remember) {
+    MFH_HIP(hipMemsetAsync(w.scal.p, 0, w.scal.n * sizeof(double), w.s));
+    w.start(jacobi);
+    std::vector<double> hs;
+    double hctl[5];
+    int it = 0, lastChecked = 0, step = first;
+    for (;;) {
+        const int itEnd = std::min(w.maxit, it + step);
+        for (; it < itEnd; ++it) w.iterate(it, jacobi);
+        hs.resize((size_t)(it - lastChecked + 1) * 4);
+        MFH_HIP(hipMemcpyAsync(hs.data(), w.scal.p + (size_t)lastChecked * 4, hs.size() * sizeof(double), hipMemcpyDeviceToHost, w.s));
+        MFH_HIP(hipMemcpyAsync(hctl, w.ctl.p, sizeof(hctl), hipMemcpyDeviceToHost, w.s));
+        MFH_HIP(hipStreamSynchronize(w.s));
+        w.lap(5);
+        for (int q = lastChecked; q <= it; ++q) {
+            const double rr = hs[(size_t)(q - lastChecked) * 4 + 2];
+            if (!std::isfinite(rr)) return -2;
+            if (rr <= hctl[0]) {
+                if (remember) w.batch = std::max(2, std::min(q + 1, w.c->checkEvery));
+                return q;
+            }
+        }
+        if (it >= w.maxit) return -1;
+        lastChecked = it;
+        step = later();
+    }
+}
 
 }}   // namespace mfhi
