@@ -521,6 +521,51 @@ mfh_status mfh_modes(mfh_ctx* ctx, int32_t nev, double density, int32_t flags, d
                      double* lambda /* nev */, double* X /* nev x dim*nDoF, row per mode */, double* residuals /* nev or NULL */,
                      mfh_modes_info* info);
 
+/* More modes than one block holds (docs/design/04_19_many_modes.md): the nev smallest eigenpairs of K x = lambda M x in the M-orthogonal complement of
+ * span(Q) -- and of the rigid-body modes under MFH_MODES_FREE -- computed batch by batch. Each batch is one run of mfh_modes' loop in the complement
+ * of everything found so far: the finished batch is projected against the deflation set once more, M-orthonormalised and appended to it (hard
+ * locking); the set (Q and M Q) stays on the device for the whole call, 2 (nLocked + nev) ld 8 bytes beside the ten blocks of the loop
+ * (ld = dim nDoF rounded up to 32), and the projections run through two kernels made for "many locked columns x <= 24 active ones"
+ * (k_deflate_gram, k_deflate_update). The block's guard columns seed the next batch's start block.
+ *   Q (nLocked rows, host; NULL with nLocked 0): any full-rank set; zeroed on the fixed variables, made M-orthogonal to the rigid modes in the free
+ *     case and M-orthonormalised at entry (MFH_ERR_INVALID if its Gram matrix is not positive definite -- this one refusal is found on the device,
+ *     after the set-up; the context is left as after any other call). The X of one call as the Q of the next continues a run.
+ *   batch (0: 16): modes per batch. A batch that completes nev runs to rtol, every earlier one -- and every one when lambdaMax is set -- to
+ *     rtol lockFactor (0: 0.1): the residuals of locked vectors are a floor for the modes found after them.
+ *   lambdaMax (> 0 and finite; otherwise none): stop after the first batch that returns an eigenvalue above it and return only those <= lambdaMax
+ *     (info->nFound of them, info->bandExhausted = 1; nev reached first: bandExhausted = 0).
+ * Outputs: lambda ascending over the whole call (a mode of a later batch that sorts before an earlier batch's largest by more than rtol -- a mode
+ * the earlier batch missed, not the other member of a multiple eigenvalue -- counts in info->nOutOfOrder and is named in info->note), rows of X
+ * M-orthonormal with mfh_modes' sign rule; rows from info->nFound on are zero. residuals (may be NULL) and info->maxResidual are the FULL
+ * residuals ||r|| / (lambda ||M x||), r = K x - lambda M x recomputed from K x after the last batch and not projected against anything the call
+ * itself locked; with a Q from the caller, which need not span an invariant subspace, r is that of the restricted pencil, r - M Q (Q^T r) (an
+ * eigenvector of the restricted pencil has K x - lambda M x = M Q mu, not 0), in the loop as in the final pass. converged = all <= rtol,
+ * otherwise MFH_ERR_NOT_CONVERGED with everything filled -- also when a batch stops at maxit: then nFound counts the batches up to and including
+ * that one. info->maxLockDefect = the largest |Q^T M x| a finished batch showed before its last projection.
+ * With nLocked = 0, nev <= batch and no lambdaMax the call is mfh_modes' and returns its bits (residuals included).
+ * Refusals: what mfh_modes refuses (MFH_ERR_UNSUPPORTED / MFH_ERR_STATE); MFH_ERR_INVALID for counts out of range, nev + nLocked (+ 6 | 3 rigid
+ * modes) beyond the dimension of the pencil, an entry of Q that is not finite, lockFactor outside (0, 1], rtol <= 0, density <= 0, maxit <= 0 --
+ * all of these before any device work. */
+typedef struct mfh_modes_many_params {
+    int32_t nev;         /* modes wanted, 1 .. 256 - nLocked */
+    int32_t nLocked;     /* rows of Q, 0 .. 255 */
+    int32_t batch;       /* modes per batch, 1 .. 20; 0 = 16 */
+    int32_t flags;       /* 0 | MFH_MODES_FREE */
+    int32_t maxit;       /* per batch */
+    int32_t reserved;    /* 0 */
+    double  density, rtol;
+    double  lambdaMax;   /* stop once the band [0, lambdaMax] is exhausted; +inf or <= 0: none */
+    double  lockFactor;  /* batches that will be locked run to rtol * lockFactor; 0 = 0.1; (0, 1] */
+} mfh_modes_many_params;
+typedef struct mfh_modes_many_info {
+    int32_t converged, nFound, batches, iterations, restarts, precondUsed;
+    int32_t bandExhausted, nOutOfOrder;
+    double  maxResidual, maxLockDefect, solve_ms, setup_ms;
+    const char* note;                                                            /* owned by the context, valid until its next call */
+} mfh_modes_many_info;
+mfh_status mfh_modes_many(mfh_ctx* ctx, const mfh_modes_many_params* params, const double* Q /* nLocked x dim*nDoF, host, or NULL */,
+                          double* lambda /* nev */, double* X /* nev x dim*nDoF */, double* residuals /* nev or NULL */, mfh_modes_many_info* info);
+
 /* ---------------------------------------------------------------- transient dynamics
  * Implicit Newmark time stepping of M u'' + C u' + K u = g(t) f on the device (docs/design/04_13_dynamics.md): K the elasticity operator of the
  * context, M = density times the consistent vector-valued mass matrix of the mesh's own degree, C = rayleighMass M + rayleighStiff K, the fixed

@@ -89,6 +89,14 @@ mfh_status mfh_debug_sym_gen_eig(int64_t n, const double* A, const double* B, do
 mfh_status mfh_debug_block_gram(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, const double* A, const double* B, double* G);
 /* Y = A C through k_block_update: A n x p and Y n x q column-major, C p x q row-major */
 mfh_status mfh_debug_block_update(mfh_ctx* ctx, int64_t n, int32_t p, int32_t q, const double* A, const double* C, double* Y);
+/* test hook: the projection kernels of mfh_modes_many. BQ, Q: n x nq column-major (nq <= 262); V: n x nv column-major (nv <= 24); cols: k distinct
+ * columns of V. G (nq x k row-major) = BQ^T V(cols) through k_deflate_gram and its fixed-order second stage; Vout = V with V(cols) - Q G in the
+ * listed columns (k_deflate_update with C = G), every other column as it came */
+mfh_status mfh_debug_deflate(mfh_ctx* ctx, int64_t n, int32_t nq, int32_t nv, int32_t k, const int32_t* cols, const double* BQ, const double* Q,
+                             const double* V, double* G, double* Vout);
+/* ms per call of k_deflate_gram (+ second stage) and of k_deflate_update on nq + k columns of n rows, against a device-to-device copy of the same
+ * (nq + k) columns in the same process */
+mfh_status mfh_time_deflate(mfh_ctx* ctx, int64_t n, int32_t nq, int32_t k, int32_t reps, double* gram_ms, double* update_ms, double* copy_ms);
 
 /* test hooks: the step kernels of mfh_newmark (mfh_dynamics.hip) on host arrays of n doubles. mask: n bytes or NULL (non-zero = fixed variable).
  * predict: ut = u + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a (both 0 where masked), w = gamma / (beta dt) ut - vt,

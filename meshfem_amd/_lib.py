@@ -53,6 +53,22 @@ class ModesInfo(C.Structure):
         return d
 
 
+class ModesManyParams(C.Structure):
+    _fields_ = [("nev", C.c_int32), ("nLocked", C.c_int32), ("batch", C.c_int32), ("flags", C.c_int32), ("maxit", C.c_int32), ("reserved", C.c_int32),
+                ("density", C.c_double), ("rtol", C.c_double), ("lambdaMax", C.c_double), ("lockFactor", C.c_double)]
+
+
+class ModesManyInfo(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("nFound", C.c_int32), ("batches", C.c_int32), ("iterations", C.c_int32), ("restarts", C.c_int32),
+                ("precondUsed", C.c_int32), ("bandExhausted", C.c_int32), ("nOutOfOrder", C.c_int32), ("maxResidual", C.c_double),
+                ("maxLockDefect", C.c_double), ("solve_ms", C.c_double), ("setup_ms", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
 class BucklingInfo(C.Structure):
     _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("nLocked", C.c_int32), ("precondUsed", C.c_int32),
                 ("blockSize", C.c_int32), ("restarts", C.c_int32), ("nBuckling", C.c_int32), ("maxResidual", C.c_double),
@@ -211,6 +227,7 @@ PROTOTYPES = {
     "mfh_mass_lumped": (_i32, [_P, _P, _i32]),
     "mfh_divergence": (_i32, [_P, _P, _P]),
     "mfh_modes": (_i32, [_P, _i32, _f64, _i32, _f64, _i32, _P, _P, _P, C.POINTER(ModesInfo)]),
+    "mfh_modes_many": (_i32, [_P, C.POINTER(ModesManyParams), _P, _P, _P, _P, C.POINTER(ModesManyInfo)]),
     "mfh_set_density": (_i32, [_P, _P, _i64, _i32]),
     "mfh_mass_apply": (_i32, [_P, _P, _P, _i32]),
     "mfh_mass_properties": (_i32, [_P, _f64, C.POINTER(_f64), _P, _P, _i32]),
@@ -283,6 +300,8 @@ PROTOTYPES = {
     "mfh_debug_sym_gen_eig": (_i32, [_i64, _P, _P, _P, _P]),
     "mfh_debug_block_gram": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
     "mfh_debug_block_update": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
+    "mfh_debug_deflate": (_i32, [_P, _i64, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P]),
+    "mfh_time_deflate": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),

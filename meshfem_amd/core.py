@@ -425,6 +425,32 @@ class Context:
         self._ck(st)
         return lam, X, d
 
+    def modes_many(self, nev, density=1.0, free=False, locked=None, lambda_max=None, batch=0, rtol=1e-6, lock_factor=0.1, maxit=500):
+        """(lam, X, info): the nev (<= 256 - len(locked)) smallest eigenpairs of K x = lam M x in the M-orthogonal complement of the rows of `locked`
+        (any full-rank set, e.g. the X of an earlier call: that continues it), computed in batches of `batch` (0: 16) modes that are locked on the
+        device one after the other (mfh_modes_many). lambda_max: stop once an eigenvalue above it has been found and return those below (then
+        len(lam) = info["nFound"] and info["bandExhausted"] says whether the band is complete). lock_factor: batches that get locked run to
+        rtol * lock_factor. lam ascending, X [nFound, dim * n_dof] M-orthonormal, info["residuals"] the full residuals recomputed after the last
+        batch. Raises on MFH_ERR_NOT_CONVERGED like modes(); what was reached is then in self.last_modes_many = (lam, X, info)."""
+        nev = int(nev)
+        n = self.bs * self.n_dof
+        Q = None
+        if locked is not None:
+            Q = as_f64(np.asarray(locked, dtype=np.float64).reshape(-1, n))
+            if Q.shape[0] == 0:
+                Q = None
+        lam, X, res = np.zeros(max(nev, 0)), np.zeros((max(nev, 0), n)), np.zeros(max(nev, 0))
+        prm = L.ModesManyParams(nev, 0 if Q is None else Q.shape[0], int(batch), L.MODES_FREE if free else 0, int(maxit), 0, float(density), float(rtol),
+                                0.0 if lambda_max is None else float(lambda_max), float(lock_factor))
+        info = L.ModesManyInfo()
+        st = self.lib.mfh_modes_many(self.h, C.byref(prm), None if Q is None else ptr(Q), ptr(lam), ptr(X), ptr(res), C.byref(info))
+        d = info.as_dict()
+        k = d["nFound"] if st in (L.OK, L.ERR_NOT_CONVERGED) else 0
+        d["residuals"] = res[:k]
+        self.last_modes_many = (lam[:k], X[:k], d)
+        self._ck(st)
+        return self.last_modes_many
+
     def newmark(self, dt, n_steps, u0=None, v0=None, a0=None, f=None, amplitude=None, density=1.0, damping=(0.0, 0.0), beta=0.25, gamma=0.5,
                 rtol=1e-8, maxit=10000, probes=None, snapshot_stride=0, energies=False):
         """Implicit Newmark time stepping of M u'' + C u' + K u = g(t) f on the device (mfh_newmark): M = density x the consistent vector-valued
@@ -1249,6 +1275,26 @@ class Context:
         g, cp = C.c_double(), C.c_double()
         self._ck(self.lib.mfh_time_block_gram(self.h, int(n), int(p), int(q), int(reps), C.byref(g), C.byref(cp)))
         return g.value, cp.value
+
+    def debug_deflate(self, BQ, Q, V, cols=None):
+        """(G, Vout): G = BQ^T V[:, cols] through k_deflate_gram, Vout = V with V[:, cols] - Q G in the listed columns through k_deflate_update
+        (test hook mfh_debug_deflate). BQ, Q [n, nq], V [n, nv <= 24]; cols: distinct columns of V (None: all)."""
+        BQ, Q, V = (np.asfortranarray(a, dtype=np.float64) for a in (BQ, Q, V))
+        n, nq, nv = V.shape[0], Q.shape[1], V.shape[1]
+        if BQ.shape != Q.shape or Q.shape[0] != n:
+            raise ValueError("debug_deflate: BQ and Q need the shape [n, nq], V [n, nv]")
+        cols = np.ascontiguousarray(np.arange(nv) if cols is None else cols, dtype=np.int32)
+        G, Vout = np.empty((nq, len(cols))), np.empty((n, nv), order="F")
+        self._ck(self.lib.mfh_debug_deflate(self.h, n, nq, nv, len(cols), cols.ctypes.data_as(C.c_void_p), BQ.ctypes.data_as(C.c_void_p),
+                                            Q.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p), ptr(G), Vout.ctypes.data_as(C.c_void_p)))
+        return G, Vout
+
+    def time_deflate(self, n, nq, k, reps=10):
+        """(gram_ms, update_ms, copy_ms): k_deflate_gram and k_deflate_update on nq + k columns of n rows against a device-to-device copy of the
+        same columns (mfh_time_deflate)."""
+        g, u, cp = C.c_double(), C.c_double(), C.c_double()
+        self._ck(self.lib.mfh_time_deflate(self.h, int(n), int(nq), int(k), int(reps), C.byref(g), C.byref(u), C.byref(cp)))
+        return g.value, u.value, cp.value
 
     def time_kron_pair(self, reps=40):
         """(pair_ms, separate_ms): one pair product of the prestressed loop as k_spmv_kron_pair and as the two launches it replaces (mfh_time_kron_pair)."""

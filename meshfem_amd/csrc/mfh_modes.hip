@@ -7,6 +7,10 @@
 //   k_block_update  Y1 = [A1 A2 A3] C1, Y2 = [A1 A2 A3] C2 (row-local, so outputs may be inputs): the lanes take rows, the coefficients are
 //                   wave-uniform scalar loads. One launch serves the vectors and their K- and M-images (blockIdx.y).
 //   k_block_residual  R = KX - MX diag(lambda) with the column norms of R and MX through the same two stages
+//   k_deflate_gram / k_deflate_update  more modes than one block holds (mfh_modes_many; docs/design/04_19_many_modes.md): the projection of <= 24
+//                   active columns against a deflation set of <= 262 contiguous locked columns that stays on the device -- G = (MQ)^T V from
+//                   6 x 8 register tiles (groups of Q on blockIdx.x, slabs on blockIdx.y, k_block_partial_sum as second stage) and V -= Q C in
+//                   place (C wave-uniform scalar loads, the row's sums in registers, Q streamed once). No atomics.
 //   host            Cholesky-QR coefficients, Rayleigh-Ritz (sym_gen_eig: Cholesky reduction + cyclic Jacobi, <= 72 x 72), locking, the loop
 //   k_spmv_kron_pair  prestressed vibration (mfh_modes_prestressed; docs/design/04_18_prestressed_modes.md): yA += s (Kg (x) I) x and
 //                   yB = rho (M (x) I) x from ONE walk over the pattern -- k_spmv_kron_acc's chunks, every column index and x entry loaded once, two
@@ -23,6 +27,10 @@ constexpr int BLK_MAXC = 24;            // columns of a block vector
 constexpr int GRAM_TP = 6, GRAM_TQ = 8; // column-pair tile of one wave
 constexpr int GRAM_GRID_CAP = 512;      // workgroups of k_block_gram (= partials the second stage adds per entry)
 constexpr int UPD_GRID_CAP = 2048;
+constexpr int DEFL_MAXQ = 262;          // columns of a deflation set: 256 locked vectors and room for the 6 rigid modes
+constexpr int DEFL_TQ = 6, DEFL_TV = 8; // column-pair tile of one wave of k_deflate_gram (Q x V); 8 x 8 spills at the 168 registers of 12 waves
+constexpr int DEFL_WAVES = 12;          // waves of its workgroup: 12 / (tiles across V) tiles of Q, i.e. 24 / 36 / 72 columns of Q at <= 24 / 16 / 8 of V
+constexpr int DEFL_GRID_CAP = 256;      // workgroups of k_deflate_gram along the rows (= partials the second stage adds per entry)
 
 // the columns col[0 .. nc) of a block: column j at base + col[j] ld
 struct BlockRef {
@@ -174,6 +182,97 @@ __global__ void __launch_bounds__(256) k_block_residual(ResArgs a, double *__res
         partials[(int64_t)blockIdx.x * 2 * BLK_MAXC + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
+// ---- projection against a long deflation set (mfh_modes_many; docs/design/04_19_many_modes.md): Q and its image BQ are nq <= DEFL_MAXQ contiguous
+// columns (column i at base + i ld), V the listed columns of a block.
+// partials[(blockIdx.y nq + i) k + j] = sum over the rows of this workgroup's slabs of BQ_i V_j. blockIdx.x takes a group of qg columns of Q and
+// blockIdx.y the slabs, so the row partition depends on n only; wave w of the workgroup owns the tile (w / ntv, w % ntv) of DEFL_TQ x DEFL_TV column
+// pairs inside the group, as in k_block_gram. The waves of a workgroup walk the same slabs together: a column of Q is loaded once, a column of V
+// once per group of Q -- and the groups of one slab set are neighbours in dispatch order, so they ask for the same slab of V at about the same time.
+__global__ void __launch_bounds__(768) k_deflate_gram(int64_t n, const double *__restrict__ BQ, int64_t ldq, int nq, int qg, BlockRef V, double *__restrict__ partials) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ntv = (V.nc + DEFL_TV - 1) / DEFL_TV;
+    const int tq = wave / ntv, tv = wave - tq * ntv;
+    const int q0 = blockIdx.x * qg + tq * DEFL_TQ;
+    if (q0 >= nq) return;                                   // (wave-uniform; the kernel has no barrier)
+    const double *pa[DEFL_TQ], *pb[DEFL_TV];
+#pragma unroll
+    for (int i = 0; i < DEFL_TQ; ++i) pa[i] = BQ + (int64_t)min(q0 + i, nq - 1) * ldq;
+#pragma unroll
+    for (int j = 0; j < DEFL_TV; ++j) pb[j] = V.base + (int64_t)V.col[min(tv * DEFL_TV + j, V.nc - 1)] * V.ld;
+    double acc[DEFL_TQ][DEFL_TV];
+#pragma unroll
+    for (int i = 0; i < DEFL_TQ; ++i)
+#pragma unroll
+        for (int j = 0; j < DEFL_TV; ++j) acc[i][j] = 0.0;
+    const int64_t nSlab = (n + 63) >> 6;
+    for (int64_t sl = blockIdx.y; sl < nSlab; sl += gridDim.y) {
+        const int64_t row = (sl << 6) + lane;
+        const bool ok = row < n;
+        const int64_t r = ok ? row : 0;
+        double a[DEFL_TQ], b[DEFL_TV];
+#pragma unroll
+        for (int i = 0; i < DEFL_TQ; ++i) a[i] = pa[i][r];
+#pragma unroll
+        for (int j = 0; j < DEFL_TV; ++j) b[j] = pb[j][r];
+#pragma unroll
+        for (int i = 0; i < DEFL_TQ; ++i) a[i] = ok ? a[i] : 0.0;
+#pragma unroll
+        for (int j = 0; j < DEFL_TV; ++j) b[j] = ok ? b[j] : 0.0;
+#pragma unroll
+        for (int i = 0; i < DEFL_TQ; ++i)
+#pragma unroll
+            for (int j = 0; j < DEFL_TV; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+    }
+    double *out = partials + (int64_t)blockIdx.y * nq * V.nc;
+#pragma unroll
+    for (int i = 0; i < DEFL_TQ; ++i)
+#pragma unroll
+        for (int j = 0; j < DEFL_TV; ++j) {
+            const double v = wave_sum(acc[i][j]);
+            const int gi = q0 + i, gj = tv * DEFL_TV + j;
+            if (lane == 0 && gi < nq && gj < V.nc) out[gi * V.nc + gj] = v;
+        }
+}
+
+// V_j -= sum_i Q_i C[i][j] on the listed columns of V, in place. C: nq rows of BLK_MAXC doubles (zero-padded), wave-uniform and read-only -> scalar
+// loads, as in k_block_update. A lane keeps the NC sums of its row in registers and streams the nq columns of Q once (four loads in flight);
+// NC = the column count rounded up to 8, so a block that has shrunk to a few active columns does not pay for 24.
+template <int NC>
+__global__ void __launch_bounds__(256) k_deflate_update(int64_t n, const double *__restrict__ Q, int64_t ldq, int nq, const double *__restrict__ C, BlockRef V) {
+    double *vb = const_cast<double *>(V.base);
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.x * 256) {
+        double s[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) s[j] = 0.0;
+        const double *q = Q + row;
+        int i = 0;
+        for (; i + 4 <= nq; i += 4) {
+            const double q0 = q[(int64_t)i * ldq], q1 = q[(int64_t)(i + 1) * ldq], q2 = q[(int64_t)(i + 2) * ldq], q3 = q[(int64_t)(i + 3) * ldq];
+            const double *c = C + i * BLK_MAXC;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) s[j] = fma(q0, c[j], s[j]);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) s[j] = fma(q1, c[BLK_MAXC + j], s[j]);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) s[j] = fma(q2, c[2 * BLK_MAXC + j], s[j]);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) s[j] = fma(q3, c[3 * BLK_MAXC + j], s[j]);
+        }
+        for (; i < nq; ++i) {
+            const double q0 = q[(int64_t)i * ldq];
+            const double *c = C + i * BLK_MAXC;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) s[j] = fma(q0, c[j], s[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+            if (j < V.nc) {
+                const int64_t at = (int64_t)V.col[j] * V.ld + row;
+                vb[at] = vb[at] - s[j];
+            }
+    }
+}
+
 // flags a prestress entry that is not finite (the lanes store the flag: no atomic)
 __global__ void __launch_bounds__(256) k_prestress_finite(int64_t n, const double *__restrict__ sigma, int *__restrict__ flag) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
@@ -283,6 +382,26 @@ void launch_block_residual(const ResArgs &a, double *partials, double *norms, hi
     const int grid = grid_for(a.n, UPD_GRID_CAP);
     hipLaunchKernelGGL(k_block_residual, dim3(grid), dim3(256), 0, s, a, partials);
     hipLaunchKernelGGL(k_block_partial_sum, dim3(1), dim3(256), 0, s, grid, 2 * BLK_MAXC, (const double *)partials, norms);
+    CHECK_LAUNCH();
+}
+
+int deflate_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, DEFL_GRID_CAP)); }
+
+// G (device, nq x V.nc row-major) = BQ^T V; partials: scratch of DEFL_GRID_CAP * DEFL_MAXQ * BLK_MAXC doubles
+void launch_deflate_gram(int64_t n, const double *BQ, int64_t ldq, int nq, const BlockRef &V, double *partials, double *G, hipStream_t s) {
+    const int ntv = (V.nc + DEFL_TV - 1) / DEFL_TV, qg = DEFL_TQ * (DEFL_WAVES / ntv), ntq = (std::min(nq, qg) + DEFL_TQ - 1) / DEFL_TQ;
+    const int grid = deflate_grid(n), count = nq * V.nc;
+    hipLaunchKernelGGL(k_deflate_gram, dim3((nq + qg - 1) / qg, grid), dim3(64 * ntq * ntv), 0, s, n, BQ, ldq, nq, qg, V, partials);
+    hipLaunchKernelGGL(k_block_partial_sum, dim3((count + 255) / 256), dim3(256), 0, s, grid, count, (const double *)partials, G);
+    CHECK_LAUNCH();
+}
+
+// V (listed columns) -= Q C; C: device, nq rows of BLK_MAXC doubles
+void launch_deflate_update(int64_t n, const double *Q, int64_t ldq, int nq, const double *C, const BlockRef &V, hipStream_t s) {
+    const dim3 grid(grid_for(n, UPD_GRID_CAP)), block(256);
+    if (V.nc <= 8) hipLaunchKernelGGL(k_deflate_update<8>, grid, block, 0, s, n, Q, ldq, nq, C, V);
+    else if (V.nc <= 16) hipLaunchKernelGGL(k_deflate_update<16>, grid, block, 0, s, n, Q, ldq, nq, C, V);
+    else hipLaunchKernelGGL(k_deflate_update<BLK_MAXC>, grid, block, 0, s, n, Q, ldq, nq, C, V);
     CHECK_LAUNCH();
 }
 
@@ -492,6 +611,7 @@ struct ModesWork {
     bool pairTwoPass = !PAIR_FUSED_DEFAULT;   // the product form of apply_AB (launch_spmv_kron_pair)
     const char *who = "mfh_modes";     // the entry point, for messages
     DBuf<double> vec, zvec, gramPart, resPart, small, coef;
+    DBuf<double> deflPart, deflG, deflC;       // deflation set (mfh_modes_many): partials and Gram matrix of k_deflate_gram, coefficients of k_deflate_update
     double *X, *W, *P, *KX, *KW, *KP, *MX, *MW, *MP, *R;
     double *Z = nullptr, *KZ = nullptr, *MZ = nullptr;
     int nz = 0;
@@ -500,7 +620,7 @@ struct ModesWork {
     bool useMG = false, useTL = false;
     // per-phase device time (scripts/probe_modes.py: env MFH_MODES_TIMING=1 puts a synchronisation at every phase boundary)
     bool timing = false;
-    double tPhase[7] = {0, 0, 0, 0, 0, 0, 0};   // K products, M products, preconditioner, Gram, update, residual, host Rayleigh-Ritz incl. its synchronisation
+    double tPhase[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // K products, M products, preconditioner, Gram, update, residual, host Rayleigh-Ritz incl. its synchronisation, deflation (both kernels, the coefficients' host trip)
     double tMark = 0;
 
     void lap(int phase) {
@@ -630,6 +750,131 @@ bool chol_qr_block(ModesWork &w, double *V, double *KV, double *MV, const std::v
     return true;
 }
 
+// the staging buffers of the block kernels (sizes fixed: a second call keeps them)
+void modes_scratch(ModesWork &w) {
+    w.gramPart.alloc((size_t)k::GRAM_GRID_CAP * BLK_MAXC * BLK_MAXC);
+    w.resPart.alloc((size_t)k::UPD_GRID_CAP * 2 * BLK_MAXC);
+    w.small.alloc((size_t)4 * RR_MAX * RR_MAX);
+    w.c->stop.alloc(4);                // (control block the preconditioner kernels are handed; no gate here)
+    w.c->stop.zero(w.s);
+    w.coef.alloc((size_t)8 * RR_MAX * BLK_MAXC);
+}
+
+// The known kernel of the free body: translations and infinitesimal rotations about the centre, M-orthonormalised (w.Z, w.MZ; KZ stays zero:
+// K Z = 0 up to rounding, and the updates want a K-image of every input block). Once per ModesWork.
+void build_rigid_modes(ModesWork &w) {
+    if (w.Z) return;
+    mfh_ctx *c = w.c;
+    hipStream_t s = w.s;
+    const size_t L = (size_t)w.ld;
+    const HostMesh &hm = c->mesh;
+    const int d = w.d, nz = w.nz;
+    std::vector<int> zall;
+    for (int j = 0; j < nz; ++j) zall.push_back(j);
+    w.zvec.alloc(L * (size_t)nz * 3);
+    w.zvec.zero(s);
+    w.Z = w.zvec.p; w.KZ = w.zvec.p + L * nz; w.MZ = w.zvec.p + 2 * L * nz;
+    std::vector<double> hz(L * (size_t)nz, 0.0);
+    double cen[3] = {0, 0, 0};
+    for (int64_t nd = 0; nd < hm.nNode; ++nd)
+        for (int a = 0; a < d; ++a) cen[a] += hm.nodePos[(size_t)nd * d + a] / (double)hm.nNode;
+    for (int64_t nd = 0; nd < hm.nNode; ++nd) {
+        double x[3] = {0, 0, 0};
+        for (int a = 0; a < d; ++a) x[a] = hm.nodePos[(size_t)nd * d + a] - cen[a];
+        for (int a = 0; a < d; ++a) hz[(size_t)a * L + (size_t)nd * d + a] = 1.0;
+        if (d == 3) {
+            hz[3 * L + (size_t)nd * 3 + 1] = -x[2]; hz[3 * L + (size_t)nd * 3 + 2] = x[1];
+            hz[4 * L + (size_t)nd * 3 + 0] = x[2];  hz[4 * L + (size_t)nd * 3 + 2] = -x[0];
+            hz[5 * L + (size_t)nd * 3 + 0] = -x[1]; hz[5 * L + (size_t)nd * 3 + 1] = x[0];
+        } else {
+            hz[2 * L + (size_t)nd * 2 + 0] = -x[1]; hz[2 * L + (size_t)nd * 2 + 1] = x[0];
+        }
+    }
+    MFH_HIP(hipMemcpyAsync(w.Z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    for (int j = 0; j < nz; ++j) w.apply_B(w.col(w.Z, j), w.col(w.MZ, j));
+    if (!chol_qr_block(w, w.Z, nullptr, w.MZ, zall)) throw w.fail(MFH_ERR_STATE, "the rigid-body modes of the mesh are linearly dependent");
+}
+
+// V -= Z (MZ^T V) on the listed columns of a block (and of its M-image if given); nothing without rigid modes (the clamped case)
+void project_out_Z(ModesWork &w, double *V, double *MV, const std::vector<int> &cols) {
+    if (!w.Z || cols.empty()) return;
+    const int nz = w.nz, k2 = (int)cols.size();
+    std::vector<int> zall;
+    for (int j = 0; j < nz; ++j) zall.push_back(j);
+    w.lap(-1);
+    double *G = w.gram(w.ref(w.MZ, zall), w.ref(V, cols));
+    std::vector<double> hG((size_t)nz * k2);
+    MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, w.s));
+    w.sync();
+    w.lap(3);
+    UpdCall u;
+    u.inputs(0, zall); u.inputs(1, cols); u.outputs(0, cols);
+    u.finish();
+    for (int i = 0; i < nz; ++i)
+        for (int j = 0; j < k2; ++j) u.c1[(size_t)i * BLK_MAXC + j] = -hG[(size_t)i * k2 + j];
+    for (int j = 0; j < k2; ++j) u.c1[(size_t)(nz + j) * BLK_MAXC + j] = 1.0;
+    int f = 0;
+    u.a.fam[f].in[0] = w.Z; u.a.fam[f].in[1] = V; u.a.fam[f].out[0] = V; ++f;
+    if (MV) { u.a.fam[f].in[0] = w.MZ; u.a.fam[f].in[1] = MV; u.a.fam[f].out[0] = MV; ++f; }
+    u.a.nFam = f;
+    run_update(w, u, false);
+    w.lap(4);
+}
+
+// A deflation set on the device (mfh_modes_many): nq B-orthonormal columns Q with their images BQ, both with the blocks' column stride ld
+struct DeflationSet {
+    const double *Q = nullptr, *BQ = nullptr;
+    int nq = 0;
+    int nGiven = 0;                    // the leading columns that came from the caller and need not be eigenvectors (see project_residual)
+};
+void deflate_alloc(ModesWork &w) {
+    w.deflPart.alloc((size_t)k::DEFL_GRID_CAP * k::DEFL_MAXQ * BLK_MAXC);
+    w.deflG.alloc((size_t)k::DEFL_MAXQ * BLK_MAXC);
+    w.deflC.alloc((size_t)k::DEFL_MAXQ * BLK_MAXC);
+}
+// V -= Q (BQ^T V) on the listed columns of a block (and MV -= BQ (BQ^T V) on its B-image if given): k_deflate_gram, the coefficients through the
+// host (the set is B-orthonormal: C = G), k_deflate_update. Returns max |BQ^T V|. One synchronisation.
+double deflate_project(ModesWork &w, const DeflationSet &q, double *V, double *MV, const std::vector<int> &cols) {
+    if (q.nq == 0 || cols.empty()) return 0.0;
+    const int nq = q.nq, k2 = (int)cols.size();
+    w.lap(-1);
+    const BlockRef r = w.ref(V, cols);
+    k::launch_deflate_gram(w.n, q.BQ, w.ld, nq, r, w.deflPart.p, w.deflG.p, w.s);
+    std::vector<double> hG((size_t)nq * k2);
+    MFH_HIP(hipMemcpyAsync(hG.data(), w.deflG.p, hG.size() * sizeof(double), hipMemcpyDeviceToHost, w.s));
+    w.sync();
+    double worst = 0.0;
+    std::vector<double> hc((size_t)nq * BLK_MAXC, 0.0);
+    for (int i = 0; i < nq; ++i)
+        for (int j = 0; j < k2; ++j) {
+            const double g = hG[(size_t)i * k2 + j];
+            hc[(size_t)i * BLK_MAXC + j] = g;
+            worst = std::max(worst, std::fabs(g));
+        }
+    w.staged.push_back(std::move(hc));
+    MFH_HIP(hipMemcpyAsync(w.deflC.p, w.staged.back().data(), w.staged.back().size() * sizeof(double), hipMemcpyHostToDevice, w.s));
+    k::launch_deflate_update(w.n, q.Q, w.ld, nq, w.deflC.p, r, w.s);
+    if (MV) k::launch_deflate_update(w.n, q.BQ, w.ld, nq, w.deflC.p, w.ref(MV, cols), w.s);
+    w.lap(7);
+    return worst;
+}
+
+// The residual of the pencil RESTRICTED to the complement of the caller's columns: an eigenvector x of the restricted pencil has
+// A x - lambda B x = B Q mu with multipliers mu, not 0, unless Q spans an invariant subspace. R -= BQ (Q^T R) on the listed columns (the dual of
+// deflate_project: R lives in the image space), then the column norms of R once more: k_block_residual with lambda = 0 on R itself leaves R as it
+// is (r - 0 mx) and sums r^2. The columns the call itself locked are near-eigenvectors and stay out of this: what they leave in R is the floor
+// that mfh_modes_many's final pass measures. norms: the device slot of 2 BLK_MAXC doubles launch_block_residual filled for these columns.
+void project_residual(ModesWork &w, const DeflationSet &q, const std::vector<int> &cols, const double *MX, double *norms) {
+    if (q.nGiven == 0 || cols.empty()) return;
+    const DeflationSet dual{q.BQ, q.Q, q.nGiven, 0};
+    deflate_project(w, dual, w.R, nullptr, cols);
+    k::ResArgs ra{};
+    ra.n = w.n; ra.ld = w.ld; ra.nc = (int)cols.size(); ra.KX = w.R; ra.MX = MX; ra.R = w.R;
+    for (size_t j = 0; j < cols.size(); ++j) { ra.col[j] = (unsigned char)cols[j]; ra.lam[j] = 0.0; }
+    k::launch_block_residual(ra, w.resPart.p, norms, w.s);
+}
+
 }   // namespace
 
 extern "C" {
@@ -717,6 +962,82 @@ mfh_status mfh_debug_block_update(mfh_ctx *c, int64_t n, int32_t p, int32_t q, c
     MFH_CATCH(c)
 }
 
+mfh_status mfh_debug_deflate(mfh_ctx *c, int64_t n, int32_t nq, int32_t nv, int32_t k2, const int32_t *cols, const double *BQ, const double *Q, const double *V,
+                             double *G, double *Vout) {
+    MFH_TRY(c)
+    require(c && cols && BQ && Q && V && G && Vout && n >= 1 && nq >= 1 && nq <= k::DEFL_MAXQ && nv >= 1 && nv <= BLK_MAXC && k2 >= 1 && k2 <= nv, MFH_ERR_INVALID,
+            "mfh_debug_deflate: arguments");
+    for (int j = 0; j < k2; ++j) {
+        require(cols[j] >= 0 && cols[j] < nv, MFH_ERR_INVALID, "mfh_debug_deflate: column out of range");
+        for (int i = 0; i < j; ++i) require(cols[i] != cols[j], MFH_ERR_INVALID, "mfh_debug_deflate: column listed twice");
+    }
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    DBuf<double> bq, q, v, part, g, coef;
+    bq.alloc((size_t)ld * nq); q.alloc((size_t)ld * nq); v.alloc((size_t)ld * nv);
+    part.alloc((size_t)k::DEFL_GRID_CAP * k::DEFL_MAXQ * BLK_MAXC); g.alloc((size_t)nq * k2);
+    const size_t rowBytes = (size_t)n * sizeof(double), ldBytes = (size_t)ld * sizeof(double);
+    MFH_HIP(hipMemcpy2DAsync(bq.p, ldBytes, BQ, rowBytes, rowBytes, (size_t)nq, hipMemcpyHostToDevice, s));
+    MFH_HIP(hipMemcpy2DAsync(q.p, ldBytes, Q, rowBytes, rowBytes, (size_t)nq, hipMemcpyHostToDevice, s));
+    MFH_HIP(hipMemcpy2DAsync(v.p, ldBytes, V, rowBytes, rowBytes, (size_t)nv, hipMemcpyHostToDevice, s));
+    BlockRef rv{};
+    rv.base = v.p; rv.ld = ld; rv.nc = k2;
+    for (int j = 0; j < k2; ++j) rv.col[j] = (unsigned char)cols[j];
+    k::launch_deflate_gram(n, bq.p, ld, nq, rv, part.p, g.p, s);
+    g.download(G, (size_t)nq * k2, s);
+    std::vector<double> hc((size_t)nq * BLK_MAXC, 0.0);
+    for (int i = 0; i < nq; ++i)
+        for (int j = 0; j < k2; ++j) hc[(size_t)i * BLK_MAXC + j] = G[(size_t)i * k2 + j];
+    coef.upload(hc, s);
+    k::launch_deflate_update(n, q.p, ld, nq, coef.p, rv, s);
+    MFH_HIP(hipMemcpy2DAsync(Vout, rowBytes, v.p, ldBytes, rowBytes, (size_t)nv, hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_time_deflate(mfh_ctx *c, int64_t n, int32_t nq, int32_t k2, int32_t reps, double *gram_ms, double *update_ms, double *copy_ms) {
+    MFH_TRY(c)
+    require(c && gram_ms && update_ms && copy_ms && n >= 1 && reps >= 1 && nq >= 1 && nq <= k::DEFL_MAXQ && k2 >= 1 && k2 <= BLK_MAXC, MFH_ERR_INVALID,
+            "mfh_time_deflate: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    const size_t count = (size_t)ld * (size_t)(nq + k2);
+    DBuf<double> qv, dst, part, g, coef;
+    qv.alloc(count); dst.alloc(count); part.alloc((size_t)k::DEFL_GRID_CAP * k::DEFL_MAXQ * BLK_MAXC); g.alloc((size_t)nq * k2);
+    k::launch_fill_hash((int64_t)count, qv.p, s);
+    std::vector<double> hc((size_t)nq * BLK_MAXC, 0.0);          // zero coefficients: the update leaves V as it is, repeat after repeat
+    coef.upload(hc, s);
+    BlockRef rv{};
+    rv.base = qv.p + (size_t)ld * nq; rv.ld = ld; rv.nc = k2;
+    for (int j = 0; j < BLK_MAXC; ++j) rv.col[j] = (unsigned char)j;
+    for (int r = 0; r < 2; ++r) {      // warm-up of all three
+        k::launch_deflate_gram(n, qv.p, ld, nq, rv, part.p, g.p, s);
+        k::launch_deflate_update(n, qv.p, ld, nq, coef.p, rv, s);
+        MFH_HIP(hipMemcpyAsync(dst.p, qv.p, count * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    MFH_HIP(hipStreamSynchronize(s));
+    {
+        EventTimer t(s);
+        for (int r = 0; r < reps; ++r) k::launch_deflate_gram(n, qv.p, ld, nq, rv, part.p, g.p, s);
+        *gram_ms = t.stop() / reps;
+    }
+    {
+        EventTimer t(s);
+        for (int r = 0; r < reps; ++r) k::launch_deflate_update(n, qv.p, ld, nq, coef.p, rv, s);
+        *update_ms = t.stop() / reps;
+    }
+    {
+        EventTimer t(s);
+        for (int r = 0; r < reps; ++r) MFH_HIP(hipMemcpyAsync(dst.p, qv.p, count * sizeof(double), hipMemcpyDeviceToDevice, s));
+        *copy_ms = t.stop() / reps;
+    }
+    MFH_CATCH(c)
+}
+
 }   // extern "C"
 
 namespace {
@@ -725,17 +1046,23 @@ struct LoopOut {
     int iterations = 0, restarts = 0, locked = 0, blockSize = 0;
     bool done = false;
     double maxResidual = 0, setupMs = 0, solveMs = 0;
+    double lockDefect = 0;             // with a deflation set: max |BQ^T X| of the returned columns before their last projection
 };
 
 // The block LOBPCG loop on the pencil (A, B) of w (ModesWork::apply_A / apply_B): the nev smallest eigenpairs of A x = lambda B x, B-orthonormal
 // columns with the sign rule, the relative residuals ||A x - lambda B x|| / (|lambda| ||B x||). The caller has prepared the context (the operators'
 // buffers, the preconditioner) and the fields of w up to useTL; tsetup is its running set-up timer. Shared by mfh_modes and mfh_buckling.
+// defl (optional): a deflation set. The loop then runs in the B-orthogonal complement of its columns (and of Z): the start block is projected
+// twice and every preconditioned residual block once, nEff loses nq, and before the final orthonormalisation the returned columns and their
+// B-images are projected once more (o.lockDefect = the largest |BQ^T X| seen there). X0dev (optional): nX0dev device columns of stride ld that
+// seed the first columns of the start block as X0 does from the host. With neither, the operations are those of the loop without the arguments.
 void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, EventTimer &tsetup, double *lambda, double *Xout, double *residuals, LoopOut &o,
-                const double *X0 = nullptr) {
+                const double *X0 = nullptr, const DeflationSet *defl = nullptr, const double *X0dev = nullptr, int nX0dev = 0) {
     mfh_ctx *c = w.c;
     hipStream_t s = w.s;
     w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
-    const int64_t nEff = w.n - (int64_t)c->fixedVars.size() - w.nz;        // dimension of the space the iteration lives in
+    const int nq = defl ? defl->nq : 0;
+    const int64_t nEff = w.n - (int64_t)c->fixedVars.size() - w.nz - nq;   // dimension of the space the iteration lives in
     w.need(nev <= nEff, MFH_ERR_INVALID, "more modes asked for than the pencil has");
     const int m = (int)std::min<int64_t>(std::min(nev + std::max(2, (nev + 3) / 4), BLK_MAXC), nEff);
     w.m = m;
@@ -745,69 +1072,12 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
     double *b0 = w.vec.p;
     w.X = b0; w.W = b0 + L * m; w.P = b0 + 2 * L * m; w.KX = b0 + 3 * L * m; w.KW = b0 + 4 * L * m; w.KP = b0 + 5 * L * m;
     w.MX = b0 + 6 * L * m; w.MW = b0 + 7 * L * m; w.MP = b0 + 8 * L * m; w.R = b0 + 9 * L * m;
-    w.gramPart.alloc((size_t)k::GRAM_GRID_CAP * BLK_MAXC * BLK_MAXC);
-    w.resPart.alloc((size_t)k::UPD_GRID_CAP * 2 * BLK_MAXC);
-    w.small.alloc((size_t)4 * RR_MAX * RR_MAX);
-    c->stop.alloc(4);                  // (control block the preconditioner kernels are handed; no gate here)
-    c->stop.zero(s);
-    w.coef.alloc((size_t)8 * RR_MAX * BLK_MAXC);
+    modes_scratch(w);
     std::vector<int> all((size_t)m);
     for (int j = 0; j < m; ++j) all[(size_t)j] = j;
 
-    // ---- the known kernel of the free body: translations and infinitesimal rotations about the centre, M-orthonormalised
-    std::vector<int> zall;
-    if (freeBody) {
-        const HostMesh &hm = c->mesh;
-        const int d = w.d, nz = w.nz;
-        for (int j = 0; j < nz; ++j) zall.push_back(j);
-        w.zvec.alloc(L * (size_t)nz * 3);
-        w.zvec.zero(s);
-        w.Z = w.zvec.p; w.KZ = w.zvec.p + L * nz; w.MZ = w.zvec.p + 2 * L * nz;
-        std::vector<double> hz(L * (size_t)nz, 0.0);
-        double cen[3] = {0, 0, 0};
-        for (int64_t nd = 0; nd < hm.nNode; ++nd)
-            for (int a = 0; a < d; ++a) cen[a] += hm.nodePos[(size_t)nd * d + a] / (double)hm.nNode;
-        for (int64_t nd = 0; nd < hm.nNode; ++nd) {
-            double x[3] = {0, 0, 0};
-            for (int a = 0; a < d; ++a) x[a] = hm.nodePos[(size_t)nd * d + a] - cen[a];
-            for (int a = 0; a < d; ++a) hz[(size_t)a * L + (size_t)nd * d + a] = 1.0;
-            if (d == 3) {
-                hz[3 * L + (size_t)nd * 3 + 1] = -x[2]; hz[3 * L + (size_t)nd * 3 + 2] = x[1];
-                hz[4 * L + (size_t)nd * 3 + 0] = x[2];  hz[4 * L + (size_t)nd * 3 + 2] = -x[0];
-                hz[5 * L + (size_t)nd * 3 + 0] = -x[1]; hz[5 * L + (size_t)nd * 3 + 1] = x[0];
-            } else {
-                hz[2 * L + (size_t)nd * 2 + 0] = -x[1]; hz[2 * L + (size_t)nd * 2 + 1] = x[0];
-            }
-        }
-        MFH_HIP(hipMemcpyAsync(w.Z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        MFH_HIP(hipStreamSynchronize(s));
-        for (int j = 0; j < nz; ++j) w.apply_B(w.col(w.Z, j), w.col(w.MZ, j));
-        if (!chol_qr_block(w, w.Z, nullptr, w.MZ, zall)) throw w.fail(MFH_ERR_STATE, "the rigid-body modes of the mesh are linearly dependent");
-        // (KZ stays zero: K Z = 0 up to rounding, and the updates below want a K-image of every input block)
-    }
-    // W -= Z (MZ^T W) on the listed columns of a block (and of its M-image if given)
-    auto project_out_Z = [&](double *V, double *MV, const std::vector<int> &cols) {
-        if (!freeBody || cols.empty()) return;
-        const int nz = w.nz, k2 = (int)cols.size();
-        w.lap(-1);
-        double *G = w.gram(w.ref(w.MZ, zall), w.ref(V, cols));
-        std::vector<double> hG((size_t)nz * k2);
-        MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        w.sync();
-        w.lap(3);
-        UpdCall u;
-        u.inputs(0, zall); u.inputs(1, cols); u.outputs(0, cols);
-        u.finish();
-        for (int i = 0; i < nz; ++i)
-            for (int j = 0; j < k2; ++j) u.c1[(size_t)i * BLK_MAXC + j] = -hG[(size_t)i * k2 + j];
-        for (int j = 0; j < k2; ++j) u.c1[(size_t)(nz + j) * BLK_MAXC + j] = 1.0;
-        int f = 0;
-        u.a.fam[f].in[0] = w.Z; u.a.fam[f].in[1] = V; u.a.fam[f].out[0] = V; ++f;
-        if (MV) { u.a.fam[f].in[0] = w.MZ; u.a.fam[f].in[1] = MV; u.a.fam[f].out[0] = MV; ++f; }
-        u.a.nFam = f;
-        run_update(w, u, false);
-        w.lap(4);
-    };
+    // ---- the known kernel of the free body
+    if (freeBody) build_rigid_modes(w);
 
     // ---- start block: hashed values, smoothed once by the preconditioner, in the complement of Z, M-orthonormal; then Rayleigh-Ritz on it
     k::launch_fill_hash((int64_t)L * m, w.W, s);
@@ -821,7 +1091,11 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
             for (int j = 0; j < nev; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.X, j), s);
         MFH_HIP(hipStreamSynchronize(s));
     }
-    project_out_Z(w.X, nullptr, all);
+    if (X0dev && nX0dev > 0)           // ... or from the device (columns of stride ld, already in the space: the guard columns of an earlier batch)
+        MFH_HIP(hipMemcpyAsync(w.X, X0dev, (size_t)w.ld * std::min(nX0dev, m) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    project_out_Z(w, w.X, nullptr, all);
+    if (nq > 0)
+        for (int pass = 0; pass < 2; ++pass) deflate_project(w, *defl, w.X, nullptr, all);
     for (int j = 0; j < m; ++j) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
     if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw w.fail(MFH_ERR_STATE, "the start block is rank deficient");
     for (int j = 0; j < m; ++j) {
@@ -867,6 +1141,10 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
             for (int j = 0; j < m; ++j) { ra.col[j] = (unsigned char)j; ra.lam[j] = lam[(size_t)j]; }
             double *norms = w.small_slot(2 * BLK_MAXC);
             k::launch_block_residual(ra, w.resPart.p, norms, s);
+            if (nq > 0 && defl->nGiven > 0) {      // (one synchronisation more; the staging slot does not survive it)
+                project_residual(w, *defl, all, w.MX, w.deflG.p);
+                norms = w.deflG.p;
+            }
             double hn[2 * BLK_MAXC];
             MFH_HIP(hipMemcpyAsync(hn, norms, sizeof(hn), hipMemcpyDeviceToHost, s));
             w.sync();
@@ -887,7 +1165,8 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
             if (!conv[(size_t)j]) act.push_back(j);
         for (int j : act) w.precond(w.col(w.R, j), w.col(w.W, j));
         w.lap(2);
-        project_out_Z(w.W, nullptr, act);
+        project_out_Z(w, w.W, nullptr, act);
+        if (nq > 0) deflate_project(w, *defl, w.W, nullptr, act);
         if (w.prestressed) {
             for (int j : act) w.apply_AB(w.col(w.W, j), w.col(w.KW, j), w.col(w.MW, j), true);
         } else {
@@ -1044,6 +1323,7 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
     // more than M X ever does (X K X^T - I of 3e-12 after 200 block-Jacobi iterations at cond 7e4), so the buckling pencil takes them afresh
     if (w.buckling)
         for (int j : ret) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
+    if (nq > 0) o.lockDefect = deflate_project(w, *defl, w.X, w.MX, ret);
     if (!chol_qr_block(w, w.X, nullptr, w.MX, ret)) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the returned modes lost their rank)");
     MFH_HIP(hipMemcpy2DAsync(Xout, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nev, hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
@@ -1061,13 +1341,82 @@ void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, Ev
         if (residuals) residuals[j] = res[(size_t)j];
     }
     if (w.timing)
-        fprintf(stderr, "[%s] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f\n",
-                w.who, (long long)w.n, m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6]);
+        fprintf(stderr, "[%s] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f deflation %.3f\n",
+                w.who, (long long)w.n, m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6], w.tPhase[7]);
     int locked = 0;
     double mr = 0;
     for (int j = 0; j < m; ++j) locked += conv[(size_t)j] ? 1 : 0;
     for (int j = 0; j < nev; ++j) mr = std::max(mr, res[(size_t)j]);
     o.iterations = it; o.restarts = restarts; o.locked = locked; o.blockSize = m; o.done = done; o.maxResidual = mr; o.setupMs = setupMs; o.solveMs = solveMs;
+}
+
+}   // namespace
+
+namespace {
+
+// What mfh_modes and mfh_modes_many share: the contexts they accept, the state they hold for the duration of the call, the preconditioner.
+// the storage of the pattern for the duration of the call (see mfh_ctx::modesWide); the guard also restores the solver's singular-system switch
+struct ModesGuard {
+    mfh_ctx *c;
+    ~ModesGuard() {
+        c->tlSuppress = false;
+        if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
+    }
+};
+void modes_note(mfh_ctx *c, const std::string &t) {
+    if (!c->modesNote.empty()) c->modesNote += "; ";
+    c->modesNote += t;
+}
+// the refusals that need no device work (after require_device)
+void modes_require_context(mfh_ctx *c, bool freeBody, const std::string &who) {
+    if (!(c->op == MFH_OP_ELASTICITY && c->opDegree != 1))
+        throw Error(MFH_ERR_UNSUPPORTED, who + ": the pencil is (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
+    if (!(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF)) throw Error(MFH_ERR_UNSUPPORTED, who + ": unpartitioned contexts only");
+    if (!(c->mesh.dim == 2 || c->mesh.dim == 3)) throw Error(MFH_ERR_UNSUPPORTED, who + ": 2D / 3D meshes");
+    if (freeBody) {
+        if (!(c->fixedVars.empty() && c->dofForNode.empty())) throw Error(MFH_ERR_UNSUPPORTED, who + ": the free-free case takes no fixed variables and the identity DoF map");
+    } else {
+        const int q = free_rigid_motions(c);
+        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables, or ask for MFH_MODES_FREE)");
+    }
+}
+// both triangles of the pattern for the duration of the call (a ModesGuard undoes it); before the set-up timer starts
+void modes_widen_storage(mfh_ctx *c) {
+    c->modesNote.clear();
+    if (resolve_upper_storage(c)) {
+        c->modesWide = true;
+        refresh_storage_rule(c);          // (before ensure_precond: see WideGuard)
+        modes_note(c, "the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    }
+}
+// preconditioner, mass buffer and the fields of w up to useTL
+void modes_prepare(mfh_ctx *c, bool freeBody, double density, const std::string &who, ModesWork &w) {
+    hipStream_t s = c->stream;
+    // ---- preconditioner: what the next solve of this kind would use
+    c->tlSuppress = freeBody;
+    ensure_precond(c);
+    if (freeBody) {
+        c->precondNote.clear();
+        if (c->precond == MFH_PRECOND_MULTIGRID && ensure_multigrid(c)) modes_note(c, "multigrid preconditioner on the singular K of the free body: dense level pinned");
+        else if (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) modes_note(c, "two-level / multigrid preconditioner unavailable on the singular K of the free body: using block-Jacobi");
+    } else
+        ensure_coarse_levels(c, 1);
+    if (c->sym.nRows != c->sym.nCols) throw Error(MFH_ERR_UNSUPPORTED, who + ": unpartitioned contexts only");
+    ensure_mass(c);
+    prepare_matrix_free(c);
+    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes");
+
+    w.c = c; w.s = s; w.d = c->bs();
+    w.n = (int64_t)w.d * c->nDoF; w.ld = (w.n + 31) / 32 * 32;
+    w.density = density;
+    w.masked = !c->fixedVars.empty();
+    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
+    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
+    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
+    if (!freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) modes_note(c, c->precondNote);
+}
+int modes_precond_used(const mfh_ctx *c, const ModesWork &w) {
+    return w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
 }
 
 }   // namespace
@@ -1084,61 +1433,19 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
     require_device(c);
     MFH_HIP(hipSetDevice(c->device));
     const bool freeBody = (flags & MFH_MODES_FREE) != 0;
-    require(c->op == MFH_OP_ELASTICITY && c->opDegree != 1, MFH_ERR_UNSUPPORTED, "mfh_modes: the pencil is (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
-    require(!dist_active(c) && c->mesh.nOwned == c->mesh.nNode && c->nOwnedDoF() == c->nDoF, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
-    require(c->mesh.dim == 2 || c->mesh.dim == 3, MFH_ERR_UNSUPPORTED, "mfh_modes: 2D / 3D meshes");
-    if (freeBody) require(c->fixedVars.empty() && c->dofForNode.empty(), MFH_ERR_UNSUPPORTED, "mfh_modes: the free-free case takes no fixed variables and the identity DoF map");
-    else {
-        const int q = free_rigid_motions(c);
-        if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables, or ask for MFH_MODES_FREE)");
-    }
-    hipStream_t s = c->stream;
-    c->modesNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
-    // the storage of the pattern for the duration of the call (see mfh_ctx::modesWide); the guard also restores the solver's singular-system switch
-    struct Guard {
-        mfh_ctx *c;
-        ~Guard() {
-            c->tlSuppress = false;
-            if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
-        }
-    } guard{c};
-    if (resolve_upper_storage(c)) {
-        c->modesWide = true;
-        refresh_storage_rule(c);          // (before ensure_precond: see WideGuard)
-        note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
-    }
-    EventTimer tsetup(s);
-    // ---- preconditioner: what the next solve of this kind would use
-    c->tlSuppress = freeBody;
-    ensure_precond(c);
-    if (freeBody) {
-        c->precondNote.clear();
-        if (c->precond == MFH_PRECOND_MULTIGRID && ensure_multigrid(c)) note("multigrid preconditioner on the singular K of the free body: dense level pinned");
-        else if (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) note("two-level / multigrid preconditioner unavailable on the singular K of the free body: using block-Jacobi");
-    } else
-        ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modes: unpartitioned contexts only");
-    ensure_mass(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes");
-
+    modes_require_context(c, freeBody, "mfh_modes");
+    ModesGuard guard{c};
+    modes_widen_storage(c);
+    EventTimer tsetup(c->stream);
     ModesWork w;
-    w.c = c; w.s = s; w.d = c->bs();
-    w.n = (int64_t)w.d * c->nDoF; w.ld = (w.n + 31) / 32 * 32;
-    w.density = density;
-    w.masked = !c->fixedVars.empty();
-    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
-    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
-    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
-    if (!freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    modes_prepare(c, freeBody, density, "mfh_modes", w);
     LoopOut lo;
     lobpcg_run(w, nev, freeBody, rtol, maxit, tsetup, lambda, Xout, residuals, lo);
     if (info) {
         info->converged = lo.done ? 1 : 0;
         info->iterations = lo.iterations;
         info->nLocked = lo.locked;
-        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
+        info->precondUsed = modes_precond_used(c, w);
         info->blockSize = lo.blockSize;
         info->restarts = lo.restarts;
         info->maxResidual = lo.maxResidual;
@@ -1147,6 +1454,231 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
         info->note = c->modesNote.c_str();
     }
     if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modes_many(mfh_ctx *c, const mfh_modes_many_params *prm, const double *Qin, double *lambda, double *Xout, double *residuals,
+                          mfh_modes_many_info *info) {
+    if (info) { *info = mfh_modes_many_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c && prm && lambda && Xout, MFH_ERR_INVALID, "mfh_modes_many: context, parameters, lambda and X not null");
+    const mfh_modes_many_params p = *prm;
+    const int nLocked = p.nLocked, nev = p.nev;
+    require(nLocked >= 0 && nLocked <= 255 && nev >= 1 && nev <= 256 - nLocked && p.batch >= 0 && p.batch <= 20 && p.maxit > 0 && p.reserved == 0 &&
+                (p.flags & ~MFH_MODES_FREE) == 0,
+            MFH_ERR_INVALID, "mfh_modes_many: 0 <= nLocked <= 255, 1 <= nev <= 256 - nLocked, 0 <= batch <= 20, maxit > 0, flags 0 | MFH_MODES_FREE, reserved 0");
+    require(p.density > 0.0 && std::isfinite(p.density) && p.rtol > 0.0 && std::isfinite(p.rtol), MFH_ERR_INVALID, "mfh_modes_many: density > 0, rtol > 0");
+    const double lockFactor = p.lockFactor == 0.0 ? 0.1 : p.lockFactor;
+    require(lockFactor > 0.0 && lockFactor <= 1.0, MFH_ERR_INVALID, "mfh_modes_many: lockFactor in (0, 1] (0: the default 0.1)");
+    require(!std::isnan(p.lambdaMax), MFH_ERR_INVALID, "mfh_modes_many: lambdaMax is not a number");
+    require(nLocked == 0 || Qin, MFH_ERR_INVALID, "mfh_modes_many: nLocked > 0 needs Q");
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "mfh_modes_many: no mesh set");
+    const bool freeBody = (p.flags & MFH_MODES_FREE) != 0;
+    const bool band = p.lambdaMax > 0.0 && std::isfinite(p.lambdaMax);
+    const int batch = p.batch == 0 ? 16 : p.batch;
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    {
+        const int nz = freeBody ? (c->bs() == 3 ? 6 : 3) : 0;
+        require((int64_t)nev + nLocked + nz <= n - (int64_t)c->fixedVars.size(), MFH_ERR_INVALID, "mfh_modes_many: nev + nLocked (+ the rigid modes) exceed the dimension of the pencil");
+        for (int64_t e = 0; e < (int64_t)nLocked * n; ++e)
+            require(std::isfinite(Qin[e]), MFH_ERR_INVALID, "mfh_modes_many: Q has an entry that is not finite");
+    }
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    modes_require_context(c, freeBody, "mfh_modes_many");
+    hipStream_t s = c->stream;
+    ModesGuard guard{c};
+    modes_widen_storage(c);
+    EventTimer tsetup(s);
+    ModesWork w;
+    modes_prepare(c, freeBody, p.density, "mfh_modes_many", w);
+    w.who = "mfh_modes_many";
+    const int precondUsed = modes_precond_used(c, w);
+    LoopOut lo;
+    if (nLocked == 0 && nev <= batch && !band) {
+        // one batch and nothing to deflate: the call of mfh_modes, its bits, its residuals
+        lobpcg_run(w, nev, freeBody, p.rtol, p.maxit, tsetup, lambda, Xout, residuals, lo);
+        if (info) {
+            info->converged = lo.done ? 1 : 0;
+            info->nFound = nev; info->batches = 1; info->iterations = lo.iterations; info->restarts = lo.restarts; info->precondUsed = precondUsed;
+            info->maxResidual = lo.maxResidual; info->solve_ms = lo.solveMs; info->setup_ms = lo.setupMs;
+            info->note = c->modesNote.c_str();
+        }
+        if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+        return MFH_OK;
+    }
+    const size_t L = (size_t)w.ld;
+    const int cap = nLocked + nev;
+    // ---- the deflation set: Q and M Q, cap columns each, resident for the call
+    DBuf<double> setQ, setBQ, seed;
+    setQ.alloc(L * (size_t)cap); setBQ.alloc(L * (size_t)cap);
+    setQ.zero(s); setBQ.zero(s);
+    deflate_alloc(w);
+    modes_scratch(w);
+    w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
+    if (nLocked > 0) {
+        // M-orthonormalise the caller's Q (masked, and in the free case in the complement of Z): block Gram-Schmidt over groups of <= 24 columns --
+        // a group is projected twice against the groups before it (k_deflate_gram / k_deflate_update), then Cholesky-QR'd on the host
+        MFH_HIP(hipMemcpy2DAsync(setQ.p, L * sizeof(double), Qin, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nLocked, hipMemcpyHostToDevice, s));
+        if (w.masked)
+            for (int j = 0; j < nLocked; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(setQ.p, j), s);
+        MFH_HIP(hipStreamSynchronize(s));
+        if (freeBody) build_rigid_modes(w);
+        for (int g0 = 0; g0 < nLocked; g0 += BLK_MAXC) {
+            const int kg = std::min(BLK_MAXC, nLocked - g0);
+            std::vector<int> cols((size_t)kg);
+            for (int j = 0; j < kg; ++j) cols[(size_t)j] = j;
+            double *Vg = w.col(setQ.p, g0), *MVg = w.col(setBQ.p, g0);
+            if (freeBody) project_out_Z(w, Vg, nullptr, cols);
+            for (int j = 0; j < kg; ++j) w.apply_B(w.col(Vg, j), w.col(MVg, j));
+            auto norms2 = [&]() {
+                double *G = w.gram(w.ref(Vg, cols), w.ref(MVg, cols));
+                std::vector<double> hG((size_t)kg * kg), dd((size_t)kg);
+                MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+                w.sync();
+                for (int j = 0; j < kg; ++j) dd[(size_t)j] = hG[(size_t)j * kg + j];
+                return dd;
+            };
+            const std::vector<double> d0 = norms2();
+            if (g0 > 0) {
+                const DeflationSet prev{setQ.p, setBQ.p, g0, 0};
+                for (int pass = 0; pass < 2; ++pass) deflate_project(w, prev, Vg, MVg, cols);
+                const std::vector<double> d1 = norms2();
+                for (int j = 0; j < kg; ++j)
+                    if (!(d1[(size_t)j] > 1e-13 * d0[(size_t)j])) throw w.fail(MFH_ERR_INVALID, "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)");
+            }
+            for (int j = 0; j < kg; ++j)
+                if (!(d0[(size_t)j] > 0.0)) throw w.fail(MFH_ERR_INVALID, "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)");
+            if (!chol_qr_block(w, Vg, nullptr, MVg, cols)) throw w.fail(MFH_ERR_INVALID, "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)");
+        }
+        for (int j = 0; j < nLocked; ++j) w.apply_B(w.col(setQ.p, j), w.col(setBQ.p, j));      // the images afresh: they went through every update
+    }
+    // ---- batch by batch
+    const bool useSeed = getenv("MFH_MODES_MANY_NO_SEED") == nullptr;      // (scripts/probe_many_modes.py measures what the seeding saves)
+    int nqNow = nLocked, found = 0, batches = 0, iterations = 0, restarts = 0, nSeed = 0;
+    bool allDone = true, exhausted = false;
+    double setupMs = 0, solveMs = 0, lockDefect = 0;
+    std::vector<double> res((size_t)nev, 0.0);
+    std::vector<int> batchOf((size_t)nev, 0);
+    while (found < nev) {
+        const int nb = std::min(batch, nev - found);
+        const bool last = !band && found + nb == nev;
+        const double tol = last ? p.rtol : p.rtol * lockFactor;
+        const DeflationSet ds{setQ.p, setBQ.p, nqNow, nLocked};
+        lo = LoopOut{};
+        if (batches == 0)
+            lobpcg_run(w, nb, freeBody, tol, p.maxit, tsetup, lambda + found, Xout + (size_t)found * (size_t)n, res.data() + found, lo, nullptr, nqNow ? &ds : nullptr);
+        else {
+            EventTimer tb(s);
+            lobpcg_run(w, nb, freeBody, tol, p.maxit, tb, lambda + found, Xout + (size_t)found * (size_t)n, res.data() + found, lo, nullptr, &ds,
+                       nSeed > 0 ? seed.p : nullptr, nSeed);
+        }
+        if (w.timing || getenv("MFH_MODES_MANY_LOG")) fprintf(stderr, "[mfh_modes_many] batch %d: %d modes, set %d, seeded %d, iterations %d, setup %.3f ms, solve %.3f ms\n", batches, nb, nqNow, nSeed, lo.iterations, lo.setupMs, lo.solveMs);
+        for (int j = 0; j < nb; ++j) batchOf[(size_t)(found + j)] = batches;
+        ++batches;
+        iterations += lo.iterations; restarts += lo.restarts; setupMs += lo.setupMs; solveMs += lo.solveMs;
+        lockDefect = std::max(lockDefect, lo.lockDefect);
+        // the batch joins the set (images afresh); its guard columns seed the next start block
+        MFH_HIP(hipMemcpyAsync(w.col(setQ.p, nqNow), w.X, L * (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, s));
+        for (int j = 0; j < nb; ++j) w.apply_B(w.col(setQ.p, nqNow + j), w.col(setBQ.p, nqNow + j));
+        nSeed = useSeed ? lo.blockSize - nb : 0;
+        if (nSeed > 0) {
+            seed.reserve(L * (size_t)BLK_MAXC);
+            MFH_HIP(hipMemcpyAsync(seed.p, w.col(w.X, nb), L * (size_t)nSeed * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+        nqNow += nb; found += nb;
+        if (!lo.done) { allDone = false; break; }
+        if (band) {
+            for (int j = found - nb; j < found; ++j) exhausted = exhausted || lambda[j] > p.lambdaMax;
+            if (exhausted) break;
+        }
+    }
+    // ---- the full residuals of everything found, unprojected against what the call itself locked: K x afresh, k_block_residual in groups of the block's width
+    {
+        EventTimer tr(s);
+        const int gw = w.m;
+        for (int g0 = 0; g0 < found; g0 += gw) {
+            const int kg = std::min(gw, found - g0);
+            k::ResArgs ra{};
+            ra.n = w.n; ra.ld = w.ld; ra.nc = kg; ra.KX = w.KX; ra.MX = w.col(setBQ.p, nLocked + g0); ra.R = w.R;
+            for (int j = 0; j < kg; ++j) {
+                w.apply_A(w.col(setQ.p, nLocked + g0 + j), w.col(w.KX, j));
+                ra.col[j] = (unsigned char)j; ra.lam[j] = lambda[g0 + j];
+            }
+            double *norms = w.small_slot(2 * BLK_MAXC);
+            k::launch_block_residual(ra, w.resPart.p, norms, s);
+            if (nLocked > 0) {                     // the caller's Q need not be eigenvectors: the residual of the restricted pencil
+                std::vector<int> cols((size_t)kg);
+                for (int j = 0; j < kg; ++j) cols[(size_t)j] = j;
+                project_residual(w, DeflationSet{setQ.p, setBQ.p, nLocked, nLocked}, cols, ra.MX, w.deflG.p);
+                norms = w.deflG.p;
+            }
+            double hn[2 * BLK_MAXC];
+            MFH_HIP(hipMemcpyAsync(hn, norms, sizeof(hn), hipMemcpyDeviceToHost, s));
+            w.sync();
+            for (int j = 0; j < kg; ++j) {
+                const double den = std::fabs(lambda[g0 + j]) * std::sqrt(hn[2 * j + 1]);
+                res[(size_t)(g0 + j)] = den > 0 ? std::sqrt(hn[2 * j]) / den : (hn[2 * j] == 0.0 ? 0.0 : 1e300);
+            }
+        }
+        solveMs += tr.stop();
+    }
+    // ---- sorted by lambda; a mode of a later batch that sorts before an earlier batch's largest (by more than rtol) is counted and named
+    std::vector<int> order((size_t)found);
+    for (int j = 0; j < found; ++j) order[(size_t)j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lambda[a] < lambda[b]; });
+    int nOut = 0;
+    {
+        std::vector<double> hiOfBatch((size_t)std::max(batches, 1), -1e300);
+        for (int j = 0; j < found; ++j) hiOfBatch[(size_t)batchOf[(size_t)j]] = std::max(hiOfBatch[(size_t)batchOf[(size_t)j]], lambda[j]);
+        for (int b = 1; b < batches; ++b) hiOfBatch[(size_t)b] = std::max(hiOfBatch[(size_t)b], hiOfBatch[(size_t)b - 1]);
+        std::string names;
+        for (int j = 0; j < found; ++j)
+            if (batchOf[(size_t)j] > 0 && lambda[j] < hiOfBatch[(size_t)batchOf[(size_t)j] - 1] * (1.0 - p.rtol)) {     // (below by more than rtol: the other member of a multiple eigenvalue that a batch edge cut is no missed mode)
+                ++nOut;
+                const int pos = (int)(std::find(order.begin(), order.end(), j) - order.begin());
+                names += (names.empty() ? "" : ", ") + std::to_string(pos) + " (batch " + std::to_string(batchOf[(size_t)j]) + ")";
+            }
+        if (nOut > 0) modes_note(c, "modes out of order (a later batch found them below an earlier batch's largest; sorted position): " + names);
+    }
+    {
+        std::vector<double> lam2((size_t)found), res2((size_t)found), row((size_t)n);
+        for (int j = 0; j < found; ++j) { lam2[(size_t)j] = lambda[order[(size_t)j]]; res2[(size_t)j] = res[(size_t)order[(size_t)j]]; }
+        // rows of X in place, cycle by cycle
+        std::vector<uint8_t> seen((size_t)found, 0);
+        for (int st = 0; st < found; ++st) {
+            if (seen[(size_t)st] || order[(size_t)st] == st) { seen[(size_t)st] = 1; continue; }
+            std::copy(Xout + (size_t)st * (size_t)n, Xout + (size_t)(st + 1) * (size_t)n, row.begin());
+            int at = st;
+            for (;;) {
+                seen[(size_t)at] = 1;
+                const int from = order[(size_t)at];
+                if (from == st) { std::copy(row.begin(), row.end(), Xout + (size_t)at * (size_t)n); break; }
+                std::copy(Xout + (size_t)from * (size_t)n, Xout + (size_t)(from + 1) * (size_t)n, Xout + (size_t)at * (size_t)n);
+                at = from;
+            }
+        }
+        for (int j = 0; j < found; ++j) { lambda[j] = lam2[(size_t)j]; res[(size_t)j] = res2[(size_t)j]; }
+    }
+    int nFound = found;
+    if (band)
+        while (nFound > 0 && lambda[nFound - 1] > p.lambdaMax) --nFound;
+    // rows past nFound hold nothing: zero
+    for (int j = nFound; j < nev; ++j) { lambda[j] = 0.0; res[(size_t)j] = 0.0; }
+    std::fill(Xout + (size_t)nFound * (size_t)n, Xout + (size_t)nev * (size_t)n, 0.0);
+    double mr = 0;
+    for (int j = 0; j < nFound; ++j) mr = std::max(mr, res[(size_t)j]);
+    if (residuals) std::copy(res.begin(), res.end(), residuals);
+    const bool converged = allDone && mr <= p.rtol;
+    if (info) {
+        info->converged = converged ? 1 : 0;
+        info->nFound = nFound; info->batches = batches; info->iterations = iterations; info->restarts = restarts; info->precondUsed = precondUsed;
+        info->bandExhausted = exhausted ? 1 : 0; info->nOutOfOrder = nOut;
+        info->maxResidual = mr; info->maxLockDefect = lockDefect; info->solve_ms = solveMs; info->setup_ms = setupMs;
+        info->note = c->modesNote.c_str();
+    }
+    if (!allDone) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations (batch " + std::to_string(batches - 1) + ")");
+    if (!converged) throw Error(MFH_ERR_NOT_CONVERGED, "the full residuals of the locked modes exceed rtol (largest " + std::to_string(mr / p.rtol) + " rtol): lower lockFactor");
     MFH_CATCH(c)
 }
 

@@ -247,6 +247,71 @@ class Simulator:
             X = X[:, dof, :]
         return np.sqrt(lam) / (2.0 * np.pi), X
 
+    # ---- more modes than one block holds (docs/design/04_19_many_modes.md)
+    def _clamp_for_modes(self, free):
+        v, _ = self.ctx.bc_dirichlet_vars()
+        if free is None:
+            free = len(v) == 0
+        self.ctx.clear_fixed()
+        if not free and len(v):
+            self.ctx.fix_variables(v)
+        return free, v
+
+    def vibrational_modes_many(self, nev=None, fmax=None, density=1.0, free=None, locked=None, batch=0, rtol=1e-6, lock_factor=0.1, maxit=500):
+        """(frequencies, modes) like vibrational_modes, for up to 256 modes (mfh_modes_many: batches of `batch` modes, each locked on the device
+        before the next starts). fmax (Hz): all natural frequencies up to it -- lambdaMax = (2 pi fmax)^2; nev then defaults to the cap of
+        256 - len(locked), and self.modes_many_info["bandExhausted"] says whether the band is complete. locked: per-DoF rows [k, nDoF * N] (or
+        [k, nDoF, N]) to stay M-orthogonal to, e.g. the modes of an earlier call. The clamp is handled as in vibrational_modes."""
+        if nev is None and fmax is None:
+            raise ValueError("vibrational_modes_many: give nev, fmax or both")
+        free, _ = self._clamp_for_modes(free)
+        n = self.ctx.n_dof * self.N
+        Q = None if locked is None else np.asarray(locked, dtype=np.float64).reshape(-1, n)
+        if nev is None:
+            nev = 256 - (0 if Q is None else len(Q))
+        lam_max = None if fmax is None else (2.0 * np.pi * float(fmax)) ** 2
+        lam, X, info = self.ctx.modes_many(nev, density=self._density_scalar(density), free=free, locked=Q, lambda_max=lam_max, batch=batch, rtol=rtol,
+                                           lock_factor=lock_factor, maxit=maxit)
+        self.modes_many_info = info
+        X = X.reshape(len(lam), self.ctx.n_dof, self.N)
+        if self.ctx.n_dof != self.ctx.n_node:               # a DoF map (periodic conditions): every node takes its DoF's value
+            dof, _ = self.ctx.get_dof_map()
+            X = X[:, dof, :]
+        return np.sqrt(lam) / (2.0 * np.pi), X
+
+    def modesForMassFraction(self, fraction=0.9, nmax=256, batch=16, density=1.0, rtol=1e-6, lock_factor=0.1, maxit=500):
+        """(frequencies, modes, fractions[N]): the lowest modes of the clamped body, computed `batch` at a time until in every direction d the summed
+        modalEffectiveMass reaches `fraction` of r_f^T M_ff r_f (r_f: the unit translation in d, zeroed on the clamp; the product through
+        mass_apply) or nmax modes are there. Every call continues the one before through mfh_modes_many's locked set, so each runs to
+        rtol * lock_factor: its modes are locked for the next. modes: per-DoF rows as nodal fields [k, nDoF, N]; fractions: what was reached.
+        Clamped bodies only, without a DoF map."""
+        ctx = self.ctx
+        free, v = self._clamp_for_modes(False)
+        if len(v) == 0:
+            raise ValueError("modesForMassFraction: clamped bodies only (apply a Dirichlet condition)")
+        if ctx.n_dof != ctx.n_node:
+            raise ValueError("modesForMassFraction: not under a DoF map")
+        if not (0.0 < fraction <= 1.0) or not (1 <= int(nmax) <= 256) or not (1 <= int(batch) <= 20):
+            raise ValueError("modesForMassFraction: 0 < fraction <= 1, 1 <= nmax <= 256, 1 <= batch <= 20")
+        rho = self._density_scalar(density)
+        n = ctx.n_dof * self.N
+        total = np.empty(self.N)
+        for d in range(self.N):
+            r = np.zeros((ctx.n_dof, self.N))
+            r[:, d] = 1.0
+            r.reshape(-1)[np.asarray(v, dtype=np.int64)] = 0.0
+            total[d] = rho * float(r.reshape(-1) @ ctx.mass_apply(r).reshape(-1))
+        lam_all, X_all, reached = np.zeros(0), np.zeros((0, n)), np.zeros(self.N)
+        self.modes_many_info = None
+        while len(lam_all) < int(nmax) and np.any(reached < fraction * total):
+            nb = min(int(batch), int(nmax) - len(lam_all))
+            lam, X, info = ctx.modes_many(nb, density=rho, locked=X_all if len(X_all) else None, batch=int(batch), rtol=rtol * lock_factor, maxit=maxit)
+            self.modes_many_info = info
+            lam_all, X_all = np.concatenate([lam_all, lam]), np.concatenate([X_all, X])
+            reached = reached + rho * rho * self.modalEffectiveMass(X).sum(axis=0)
+        order = np.argsort(lam_all, kind="stable")
+        return np.sqrt(lam_all[order]) / (2.0 * np.pi), X_all[order].reshape(len(order), ctx.n_dof, self.N), reached / total
+
     # ---- linear buckling (docs/design/04_16_buckling.md)
     def setPrestress(self, stress):
         """The per-element prestress [nElem, flatLen] (tensor shear entries, the layout of averageStressField) of applyGeometricStiffness and
