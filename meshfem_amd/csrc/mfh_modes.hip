@@ -11,7 +11,12 @@
 //                   active columns against a deflation set of <= 262 contiguous locked columns that stays on the device -- G = (MQ)^T V from
 //                   6 x 8 register tiles (groups of Q on blockIdx.x, slabs on blockIdx.y, k_block_partial_sum as second stage) and V -= Q C in
 //                   place (C wave-uniform scalar loads, the row's sums in registers, Q streamed once). No atomics.
-//   host            Cholesky-QR coefficients, Rayleigh-Ritz (sym_gen_eig: Cholesky reduction + cyclic Jacobi, <= 72 x 72), locking, the loop
+//   host            Cholesky-QR coefficients (chol_qr_factor), Rayleigh-Ritz (sym_gen_eig: Cholesky reduction + cyclic Jacobi, <= 72 x 72), locking,
+//                   the loop. One loop serves the four entry points: ModesWork names the pencil (enum Pencil: vibration (K, rho M), buckling
+//                   (Kg, K), prestressed (K + s Kg, rho M)) and its product members are the only code that switches on it; lobpcg_run(LoopIn,
+//                   LoopOut) is the algorithm over the steps of struct Lobpcg (start_block, converged, new_directions, orthonormalise,
+//                   rayleigh_ritz, return_columns). The entry points share ModesGuard, modes_prepare(ModesSetup), modes_fill_info and
+//                   require_converged; mfh_modes_many adds many_orthonormalise_given, many_batches, many_full_residuals and many_sort.
 //   k_spmv_kron_pair  prestressed vibration (mfh_modes_prestressed; docs/design/04_18_prestressed_modes.md): yA += s (Kg (x) I) x and
 //                   yB = rho (M (x) I) x from ONE walk over the pattern -- k_spmv_kron_acc's chunks, every column index and x entry loaded once, two
 //                   interleaved planes of LDS partials [dim][chunkSlots][2]. No atomics.
@@ -598,6 +603,13 @@ int free_rigid_motions(const mfh_ctx *c) {
     return q;
 }
 
+// The pencil (A, B) the loop works on; only the product members of ModesWork look at it
+enum class Pencil {
+    Vibration,                         // (K, density M): mfh_modes, mfh_modes_many
+    Buckling,                          // (Kg, K), A indefinite: mfh_buckling
+    Prestressed                        // (K + loadFactor Kg, density M), A indefinite beyond the critical load: mfh_modes_prestressed
+};
+
 struct ModesWork {
     mfh_ctx *c;
     hipStream_t s;
@@ -605,8 +617,7 @@ struct ModesWork {
     int64_t n, ld;
     double density = 1.0;
     bool masked;
-    bool buckling = false;             // the pencil: (K, density M) of mfh_modes, or (Kg, K) of mfh_buckling, or ...
-    bool prestressed = false;          // ... (K + loadFactor Kg, density M) of mfh_modes_prestressed
+    Pencil pencil = Pencil::Vibration;
     double loadFactor = 0.0;
     bool pairTwoPass = !PAIR_FUSED_DEFAULT;   // the product form of apply_AB (launch_spmv_kron_pair)
     const char *who = "mfh_modes";     // the entry point, for messages
@@ -662,26 +673,44 @@ struct ModesWork {
         MFH_HIP(hipMemcpyAsync(p, staged.back().data(), staged.back().size() * sizeof(double), hipMemcpyHostToDevice, s));
         return p;
     }
-    // The pencil (A, B) the loop works on. Vibration: A = K, B = density M. Buckling: A = Kg (indefinite), B = K. Prestressed vibration:
-    // A = K + loadFactor Kg (indefinite beyond the critical load), B = density M. In the loop the blocks named K* hold the A-images and the blocks
-    // named M* the B-images; B carries the inner product, and the preconditioner approximates K^-1 in all three.
+    // The products of the pencil (A, B). In the loop the blocks named K* hold the A-images and the blocks named M* the B-images; B carries the
+    // inner product, and the preconditioner approximates K^-1 in all three pencils. These members are the only code that switches on the kind.
     void apply_A(const double *x, double *y) {
-        if (buckling) k::launch_spmv(geom_spmv_args(c, masked), x, y, nullptr, s);
-        else apply_operator(c, masked, x, y, nullptr);
-        if (prestressed) k::launch_spmv_kron_acc(geom_spmv_args(c, masked), true, 1.0, loadFactor, x, y, nullptr, k::DynGate{nullptr, 0, nullptr}, s);
+        if (pencil == Pencil::Buckling) { k::launch_spmv(geom_spmv_args(c, masked), x, y, nullptr, s); return; }
+        apply_operator(c, masked, x, y, nullptr);
+        if (pencil == Pencil::Prestressed) k::launch_spmv_kron_acc(geom_spmv_args(c, masked), true, 1.0, loadFactor, x, y, nullptr, k::DynGate{nullptr, 0, nullptr}, s);
     }
-    // both images of one column (the prestressed pencil only): K x into yA, then Kg's and M's parts from one walk over the pattern
-    // (book: under MFH_MODES_TIMING K's product goes to phase 0 and the pair product to phase 1)
-    void apply_AB(const double *x, double *yA, double *yB, bool book = false) {
+    void apply_B(const double *x, double *y) {
+        if (pencil == Pencil::Buckling) { apply_operator(c, masked, x, y, nullptr); return; }
+        k::launch_spmv(mass_spmv_args(c, masked), x, y, nullptr, s);
+        if (density != 1.0) k::launch_axpby(n, 0.0, y, density, y, s);      // the buffer holds density 1
+    }
+    // both images of one column of the prestressed pencil: K x into yA, then Kg's and M's parts from one walk over the pattern
+    void apply_AB(const double *x, double *yA, double *yB, bool book) {
         apply_operator(c, masked, x, yA, nullptr);
         if (book) lap(0);
         k::launch_spmv_kron_pair(mass_spmv_args(c, masked), c->dGeomVals.p, c->dMassVals.p, loadFactor, density, x, yA, yB, n, pairTwoPass, s);
         if (book) lap(1);
     }
-    void apply_B(const double *x, double *y) {
-        if (buckling) { apply_operator(c, masked, x, y, nullptr); return; }
-        k::launch_spmv(mass_spmv_args(c, masked), x, y, nullptr, s);
-        if (density != 1.0) k::launch_axpby(n, 0.0, y, density, y, s);      // the buffer holds density 1
+    // AV and BV = the images of the listed columns of V: all A-products, then all B-products; the prestressed pencil column by column through
+    // apply_AB. book: under MFH_MODES_TIMING the A-products (of the prestressed pencil: K's) go to phase 0 and the others to phase 1.
+    void apply_images(double *V, double *AV, double *BV, const std::vector<int> &cols, bool book) {
+        if (pencil == Pencil::Prestressed) {
+            for (int j : cols) apply_AB(col(V, j), col(AV, j), col(BV, j), book);
+            return;
+        }
+        for (int j : cols) apply_A(col(V, j), col(AV, j));
+        if (book) lap(0);
+        for (int j : cols) apply_B(col(V, j), col(BV, j));
+        if (book) lap(1);
+    }
+    // B is ill-conditioned where the mass matrix is not (B = K): the B-images carried through hundreds of block updates have drifted from K X by
+    // far more than M X ever does (X K X^T - I of 3e-12 after 200 block-Jacobi iterations at cond 7e4), so the returned columns take theirs afresh
+    bool recompute_returned_B() const { return pencil == Pencil::Buckling; }
+    // the three families of the basis [X W P]: the vectors (0), their A-images (1), their B-images (2)
+    double *block(int fam, int b) const {
+        double *const t[3][3] = {{X, W, P}, {KX, KW, KP}, {MX, MW, MP}};
+        return t[fam][b];
     }
     void need(bool cond, mfh_status code, const char *what) const { if (!cond) throw fail(code, what); }
     Error fail(mfh_status code, const char *what) const { return Error(code, std::string(who) + ": " + what); }
@@ -713,7 +742,35 @@ struct UpdCall {
         c1.assign((size_t)nInTot * BLK_MAXC, 0.0);
         c2.assign((size_t)nInTot * BLK_MAXC, 0.0);
     }
+    // one more family: input blocks in0, in1 (null: none), output block out
+    void family(const double *in0, const double *in1, double *out) {
+        k::UpdFamily &f = a.fam[a.nFam++];
+        f.in[0] = in0; f.in[1] = in1; f.out[0] = out;
+    }
+    // the three families of the loop's basis [X W P]: the first nIn blocks are the inputs, output o goes to block out0 / out1 (-1: one output)
+    void basis(const ModesWork &w, int nIn, int out0, int out1 = -1) {
+        for (int f = 0; f < 3; ++f) {
+            for (int b = 0; b < nIn; ++b) a.fam[f].in[b] = w.block(f, b);
+            a.fam[f].out[0] = w.block(f, out0);
+            if (out1 >= 0) a.fam[f].out[1] = w.block(f, out1);
+        }
+        a.nFam = 3;
+    }
 };
+
+std::vector<int> iota(int k) {
+    std::vector<int> v((size_t)k);
+    for (int j = 0; j < k; ++j) v[(size_t)j] = j;
+    return v;
+}
+
+// the arguments of k_block_residual on the listed columns: R = KX - MX diag(lambda) into w.R (lambda null: zeros)
+k::ResArgs res_args(const ModesWork &w, const std::vector<int> &cols, const double *lambda, const double *KX, const double *MX) {
+    k::ResArgs ra{};
+    ra.n = w.n; ra.ld = w.ld; ra.nc = (int)cols.size(); ra.KX = KX; ra.MX = MX; ra.R = w.R;
+    for (size_t j = 0; j < cols.size(); ++j) { ra.col[j] = (unsigned char)cols[j]; ra.lam[j] = lambda ? lambda[j] : 0.0; }
+    return ra;
+}
 
 void run_update(ModesWork &w, UpdCall &u, bool two) {
     u.a.n = w.n; u.a.ld = w.ld;
@@ -739,11 +796,9 @@ bool chol_qr_block(ModesWork &w, double *V, double *KV, double *MV, const std::v
         u.finish();
         for (int i = 0; i < k2; ++i)
             for (int j = 0; j < k2; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * k2 + j];
-        int f = 0;
-        u.a.fam[f].in[0] = V; u.a.fam[f].out[0] = V; ++f;
-        u.a.fam[f].in[0] = MV; u.a.fam[f].out[0] = MV; ++f;
-        if (KV) { u.a.fam[f].in[0] = KV; u.a.fam[f].out[0] = KV; ++f; }
-        u.a.nFam = f;
+        u.family(V, nullptr, V);
+        u.family(MV, nullptr, MV);
+        if (KV) u.family(KV, nullptr, KV);
         run_update(w, u, false);
         w.lap(4);
     }
@@ -769,8 +824,6 @@ void build_rigid_modes(ModesWork &w) {
     const size_t L = (size_t)w.ld;
     const HostMesh &hm = c->mesh;
     const int d = w.d, nz = w.nz;
-    std::vector<int> zall;
-    for (int j = 0; j < nz; ++j) zall.push_back(j);
     w.zvec.alloc(L * (size_t)nz * 3);
     w.zvec.zero(s);
     w.Z = w.zvec.p; w.KZ = w.zvec.p + L * nz; w.MZ = w.zvec.p + 2 * L * nz;
@@ -793,15 +846,14 @@ void build_rigid_modes(ModesWork &w) {
     MFH_HIP(hipMemcpyAsync(w.Z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, s));
     MFH_HIP(hipStreamSynchronize(s));
     for (int j = 0; j < nz; ++j) w.apply_B(w.col(w.Z, j), w.col(w.MZ, j));
-    if (!chol_qr_block(w, w.Z, nullptr, w.MZ, zall)) throw w.fail(MFH_ERR_STATE, "the rigid-body modes of the mesh are linearly dependent");
+    if (!chol_qr_block(w, w.Z, nullptr, w.MZ, iota(nz))) throw w.fail(MFH_ERR_STATE, "the rigid-body modes of the mesh are linearly dependent");
 }
 
 // V -= Z (MZ^T V) on the listed columns of a block (and of its M-image if given); nothing without rigid modes (the clamped case)
 void project_out_Z(ModesWork &w, double *V, double *MV, const std::vector<int> &cols) {
     if (!w.Z || cols.empty()) return;
     const int nz = w.nz, k2 = (int)cols.size();
-    std::vector<int> zall;
-    for (int j = 0; j < nz; ++j) zall.push_back(j);
+    const std::vector<int> zall = iota(nz);
     w.lap(-1);
     double *G = w.gram(w.ref(w.MZ, zall), w.ref(V, cols));
     std::vector<double> hG((size_t)nz * k2);
@@ -814,10 +866,8 @@ void project_out_Z(ModesWork &w, double *V, double *MV, const std::vector<int> &
     for (int i = 0; i < nz; ++i)
         for (int j = 0; j < k2; ++j) u.c1[(size_t)i * BLK_MAXC + j] = -hG[(size_t)i * k2 + j];
     for (int j = 0; j < k2; ++j) u.c1[(size_t)(nz + j) * BLK_MAXC + j] = 1.0;
-    int f = 0;
-    u.a.fam[f].in[0] = w.Z; u.a.fam[f].in[1] = V; u.a.fam[f].out[0] = V; ++f;
-    if (MV) { u.a.fam[f].in[0] = w.MZ; u.a.fam[f].in[1] = MV; u.a.fam[f].out[0] = MV; ++f; }
-    u.a.nFam = f;
+    u.family(w.Z, V, V);
+    if (MV) u.family(w.MZ, MV, MV);
     run_update(w, u, false);
     w.lap(4);
 }
@@ -869,10 +919,30 @@ void project_residual(ModesWork &w, const DeflationSet &q, const std::vector<int
     if (q.nGiven == 0 || cols.empty()) return;
     const DeflationSet dual{q.BQ, q.Q, q.nGiven, 0};
     deflate_project(w, dual, w.R, nullptr, cols);
-    k::ResArgs ra{};
-    ra.n = w.n; ra.ld = w.ld; ra.nc = (int)cols.size(); ra.KX = w.R; ra.MX = MX; ra.R = w.R;
-    for (size_t j = 0; j < cols.size(); ++j) { ra.col[j] = (unsigned char)cols[j]; ra.lam[j] = 0.0; }
-    k::launch_block_residual(ra, w.resPart.p, norms, w.s);
+    k::launch_block_residual(res_args(w, cols, nullptr, w.R, MX), w.resPart.p, norms, w.s);
+}
+
+// ||A x - lambda B x|| / (|lambda| ||B x||) from the squared norms k_block_residual sums
+double relative_residual(double r2, double lambda, double mx2) {
+    const double den = std::fabs(lambda) * std::sqrt(mx2);
+    return den > 0 ? std::sqrt(r2) / den : (r2 == 0.0 ? 0.0 : 1e300);
+}
+
+// R = KX - MX diag(lambda) on the columns 0 .. nc - 1 and their relative residuals (out): one download, one synchronisation. given (optional):
+// a deflation set whose leading columns came from the caller -- the residuals are then those of the restricted pencil (project_residual: one
+// synchronisation more, and the staging slot does not survive it).
+void block_residuals(ModesWork &w, const DeflationSet *given, int nc, const double *lambda, const double *KX, const double *MX, double *out) {
+    const std::vector<int> cols = iota(nc);
+    double *norms = w.small_slot(2 * BLK_MAXC);
+    k::launch_block_residual(res_args(w, cols, lambda, KX, MX), w.resPart.p, norms, w.s);
+    if (given && given->nGiven > 0) {
+        project_residual(w, *given, cols, MX, w.deflG.p);
+        norms = w.deflG.p;
+    }
+    double hn[2 * BLK_MAXC];
+    MFH_HIP(hipMemcpyAsync(hn, norms, sizeof(hn), hipMemcpyDeviceToHost, w.s));
+    w.sync();
+    for (int j = 0; j < nc; ++j) out[j] = relative_residual(hn[2 * j], lambda[j], hn[2 * j + 1]);
 }
 
 }   // namespace
@@ -1042,6 +1112,18 @@ mfh_status mfh_time_deflate(mfh_ctx *c, int64_t n, int32_t nq, int32_t k2, int32
 
 namespace {
 
+// What a run of the loop is given, beside the ModesWork its caller prepared
+struct LoopIn {
+    int nev;
+    bool freeBody;
+    double rtol;
+    int maxit;
+    double *lambda, *X, *residuals;    // the outputs on the host: nev eigenvalues, nev x n modes, nev relative residuals (optional)
+    const double *X0 = nullptr;        // a warm start (host, nev x n): its rows take the place of the first nev columns of the start block as they are, masked
+    const DeflationSet *defl = nullptr;
+    const double *X0dev = nullptr;     // ... or nX0dev columns from the device (stride ld, already in the space: the guard columns of an earlier batch)
+    int nX0dev = 0;
+};
 struct LoopOut {
     int iterations = 0, restarts = 0, locked = 0, blockSize = 0;
     bool done = false;
@@ -1049,325 +1131,274 @@ struct LoopOut {
     double lockDefect = 0;             // with a deflation set: max |BQ^T X| of the returned columns before their last projection
 };
 
-// The block LOBPCG loop on the pencil (A, B) of w (ModesWork::apply_A / apply_B): the nev smallest eigenpairs of A x = lambda B x, B-orthonormal
-// columns with the sign rule, the relative residuals ||A x - lambda B x|| / (|lambda| ||B x||). The caller has prepared the context (the operators'
-// buffers, the preconditioner) and the fields of w up to useTL; tsetup is its running set-up timer. Shared by mfh_modes and mfh_buckling.
-// defl (optional): a deflation set. The loop then runs in the B-orthogonal complement of its columns (and of Z): the start block is projected
-// twice and every preconditioned residual block once, nEff loses nq, and before the final orthonormalisation the returned columns and their
-// B-images are projected once more (o.lockDefect = the largest |BQ^T X| seen there). X0dev (optional): nX0dev device columns of stride ld that
-// seed the first columns of the start block as X0 does from the host. With neither, the operations are those of the loop without the arguments.
-void lobpcg_run(ModesWork &w, int nev, bool freeBody, double rtol, int maxit, EventTimer &tsetup, double *lambda, double *Xout, double *residuals, LoopOut &o,
-                const double *X0 = nullptr, const DeflationSet *defl = nullptr, const double *X0dev = nullptr, int nX0dev = 0) {
-    mfh_ctx *c = w.c;
-    hipStream_t s = w.s;
-    w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
-    const int nq = defl ? defl->nq : 0;
-    const int64_t nEff = w.n - (int64_t)c->fixedVars.size() - w.nz - nq;   // dimension of the space the iteration lives in
-    w.need(nev <= nEff, MFH_ERR_INVALID, "more modes asked for than the pencil has");
-    const int m = (int)std::min<int64_t>(std::min(nev + std::max(2, (nev + 3) / 4), BLK_MAXC), nEff);
-    w.m = m;
-    const size_t L = (size_t)w.ld;
-    w.vec.alloc(L * (size_t)m * 10);
-    w.vec.zero(s);
-    double *b0 = w.vec.p;
-    w.X = b0; w.W = b0 + L * m; w.P = b0 + 2 * L * m; w.KX = b0 + 3 * L * m; w.KW = b0 + 4 * L * m; w.KP = b0 + 5 * L * m;
-    w.MX = b0 + 6 * L * m; w.MW = b0 + 7 * L * m; w.MP = b0 + 8 * L * m; w.R = b0 + 9 * L * m;
-    modes_scratch(w);
-    std::vector<int> all((size_t)m);
-    for (int j = 0; j < m; ++j) all[(size_t)j] = j;
+// The state of one run of the loop and its steps. The basis of an iteration is S = [X W P]: all m columns of X, the columns wact of W (the
+// preconditioned residuals of the columns that have not converged) and the columns pact of P (the previous directions).
+struct Lobpcg {
+    ModesWork &w;
+    const LoopIn &in;
+    const int nq;                      // columns of the deflation set
+    int m = 0;                         // block size
+    std::vector<int> all, wact, pact;
+    std::vector<double> lam, res;
+    std::vector<uint8_t> conv;
+    bool haveP = false;
+    int restarts = 0;
 
-    // ---- the known kernel of the free body
-    if (freeBody) build_rigid_modes(w);
+    // block size, the ten blocks, the staging buffers
+    Lobpcg(ModesWork &w_, const LoopIn &in_) : w(w_), in(in_), nq(in_.defl ? in_.defl->nq : 0) {
+        w.nz = in.freeBody ? (w.d == 3 ? 6 : 3) : 0;
+        const int64_t nEff = w.n - (int64_t)w.c->fixedVars.size() - w.nz - nq;   // dimension of the space the iteration lives in
+        w.need(in.nev <= nEff, MFH_ERR_INVALID, "more modes asked for than the pencil has");
+        m = (int)std::min<int64_t>(std::min(in.nev + std::max(2, (in.nev + 3) / 4), BLK_MAXC), nEff);
+        w.m = m;
+        const size_t L = (size_t)w.ld;
+        w.vec.alloc(L * (size_t)m * 10);
+        w.vec.zero(w.s);
+        double *b0 = w.vec.p;
+        w.X = b0; w.W = b0 + L * m; w.P = b0 + 2 * L * m; w.KX = b0 + 3 * L * m; w.KW = b0 + 4 * L * m; w.KP = b0 + 5 * L * m;
+        w.MX = b0 + 6 * L * m; w.MW = b0 + 7 * L * m; w.MP = b0 + 8 * L * m; w.R = b0 + 9 * L * m;
+        modes_scratch(w);
+        all = iota(m);
+        lam.assign((size_t)m, 0.0);
+        res.assign((size_t)m, 0.0);
+        conv.assign((size_t)m, 0);
+    }
 
-    // ---- start block: hashed values, smoothed once by the preconditioner, in the complement of Z, M-orthonormal; then Rayleigh-Ritz on it
-    k::launch_fill_hash((int64_t)L * m, w.W, s);
-    for (int j = 0; j < m; ++j) {
-        if (w.masked) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.W, j), s);
-        w.precond(w.col(w.W, j), w.col(w.X, j));
-    }
-    if (X0) {                          // a warm start (host, nev x n): its rows take the place of the first nev columns as they are, masked
-        MFH_HIP(hipMemcpy2DAsync(w.X, (size_t)w.ld * sizeof(double), X0, (size_t)w.n * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nev, hipMemcpyHostToDevice, s));
-        if (w.masked)
-            for (int j = 0; j < nev; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.X, j), s);
-        MFH_HIP(hipStreamSynchronize(s));
-    }
-    if (X0dev && nX0dev > 0)           // ... or from the device (columns of stride ld, already in the space: the guard columns of an earlier batch)
-        MFH_HIP(hipMemcpyAsync(w.X, X0dev, (size_t)w.ld * std::min(nX0dev, m) * sizeof(double), hipMemcpyDeviceToDevice, s));
-    project_out_Z(w, w.X, nullptr, all);
-    if (nq > 0)
-        for (int pass = 0; pass < 2; ++pass) deflate_project(w, *defl, w.X, nullptr, all);
-    for (int j = 0; j < m; ++j) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
-    if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw w.fail(MFH_ERR_STATE, "the start block is rank deficient");
-    for (int j = 0; j < m; ++j) {
-        if (w.prestressed) w.apply_AB(w.col(w.X, j), w.col(w.KX, j), w.col(w.MX, j));
-        else { w.apply_A(w.col(w.X, j), w.col(w.KX, j)); w.apply_B(w.col(w.X, j), w.col(w.MX, j)); }
-    }
-    std::vector<double> lam((size_t)m, 0.0);
-    {
+    // start block: hashed values, smoothed once by the preconditioner (or the caller's / the earlier batch's columns), in the complement of Z and
+    // of the deflation set, M-orthonormal; then Rayleigh-Ritz on it (the generalised problem: X^T K X against X^T M X)
+    void start_block() {
+        mfh_ctx *c = w.c;
+        hipStream_t s = w.s;
+        k::launch_fill_hash((int64_t)w.ld * m, w.W, s);
+        for (int j = 0; j < m; ++j) {
+            if (w.masked) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.W, j), s);
+            w.precond(w.col(w.W, j), w.col(w.X, j));
+        }
+        if (in.X0) {
+            MFH_HIP(hipMemcpy2DAsync(w.X, (size_t)w.ld * sizeof(double), in.X0, (size_t)w.n * sizeof(double), (size_t)w.n * sizeof(double), (size_t)in.nev, hipMemcpyHostToDevice, s));
+            if (w.masked)
+                for (int j = 0; j < in.nev; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.X, j), s);
+            MFH_HIP(hipStreamSynchronize(s));
+        }
+        if (in.X0dev && in.nX0dev > 0)
+            MFH_HIP(hipMemcpyAsync(w.X, in.X0dev, (size_t)w.ld * std::min(in.nX0dev, m) * sizeof(double), hipMemcpyDeviceToDevice, s));
+        project_out_Z(w, w.X, nullptr, all);
+        if (nq > 0)
+            for (int pass = 0; pass < 2; ++pass) deflate_project(w, *in.defl, w.X, nullptr, all);
+        for (int j = 0; j < m; ++j) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
+        if (!chol_qr_block(w, w.X, nullptr, w.MX, all)) throw w.fail(MFH_ERR_STATE, "the start block is rank deficient");
+        w.apply_images(w.X, w.KX, w.MX, all, false);
         double *GK = w.gram(w.ref(w.X, all), w.ref(w.KX, all));
         double *GM = w.gram(w.ref(w.X, all), w.ref(w.MX, all));
-        std::vector<double> hK((size_t)m * m), hM((size_t)m * m), ev((size_t)m), V((size_t)m * m);
+        std::vector<double> hK((size_t)m * m), hM((size_t)m * m), V((size_t)m * m);
         MFH_HIP(hipMemcpyAsync(hK.data(), GK, hK.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         MFH_HIP(hipMemcpyAsync(hM.data(), GM, hM.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         w.sync();
-        if (!sym_gen_eig(m, hK.data(), hM.data(), ev.data(), V.data())) throw w.fail(MFH_ERR_STATE, "the start block lost its M-orthonormality");
+        if (!sym_gen_eig(m, hK.data(), hM.data(), lam.data(), V.data())) throw w.fail(MFH_ERR_STATE, "the start block lost its M-orthonormality");
         UpdCall u;
         u.inputs(0, all); u.outputs(0, all);
         u.finish();
         for (int i = 0; i < m; ++i)
             for (int j = 0; j < m; ++j) u.c1[(size_t)i * BLK_MAXC + j] = V[(size_t)i * m + j];
-        u.a.fam[0].in[0] = w.X; u.a.fam[0].out[0] = w.X;
-        u.a.fam[1].in[0] = w.KX; u.a.fam[1].out[0] = w.KX;
-        u.a.fam[2].in[0] = w.MX; u.a.fam[2].out[0] = w.MX;
-        u.a.nFam = 3;
+        u.basis(w, 1, 0);
         run_update(w, u, false);
-        lam = ev;
     }
-    MFH_HIP(hipStreamSynchronize(s));
-    const double setupMs = tsetup.stop();
 
-    // ---- the iteration
-    EventTimer tsolve(s);
-    std::vector<double> res((size_t)m, 0.0);
-    std::vector<uint8_t> conv((size_t)m, 0);
-    bool haveP = false, done = false;
-    int it = 0, restarts = 0;
-    w.lap(-1);
-    for (;; ++it) {
-        // residuals of all columns (R, ||R||, ||MX||): one download
-        {
-            k::ResArgs ra{};
-            ra.n = w.n; ra.ld = w.ld; ra.nc = m; ra.KX = w.KX; ra.MX = w.MX; ra.R = w.R;
-            for (int j = 0; j < m; ++j) { ra.col[j] = (unsigned char)j; ra.lam[j] = lam[(size_t)j]; }
-            double *norms = w.small_slot(2 * BLK_MAXC);
-            k::launch_block_residual(ra, w.resPart.p, norms, s);
-            if (nq > 0 && defl->nGiven > 0) {      // (one synchronisation more; the staging slot does not survive it)
-                project_residual(w, *defl, all, w.MX, w.deflG.p);
-                norms = w.deflG.p;
-            }
-            double hn[2 * BLK_MAXC];
-            MFH_HIP(hipMemcpyAsync(hn, norms, sizeof(hn), hipMemcpyDeviceToHost, s));
-            w.sync();
-            w.lap(5);
-            for (int j = 0; j < m; ++j) {
-                const double den = std::fabs(lam[(size_t)j]) * std::sqrt(hn[2 * j + 1]);
-                res[(size_t)j] = den > 0 ? std::sqrt(hn[2 * j]) / den : (hn[2 * j] == 0.0 ? 0.0 : 1e300);
-                if (!std::isfinite(res[(size_t)j])) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (a residual is not finite)");
-                conv[(size_t)j] = res[(size_t)j] <= rtol;
-            }
+    // residuals of all columns (R, ||R||, ||MX||): one download. true: the first nev columns have converged.
+    bool converged() {
+        block_residuals(w, in.defl, m, lam.data(), w.KX, w.MX, res.data());
+        w.lap(5);
+        for (int j = 0; j < m; ++j) {
+            if (!std::isfinite(res[(size_t)j])) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (a residual is not finite)");
+            conv[(size_t)j] = res[(size_t)j] <= in.rtol;
         }
-        done = true;
-        for (int j = 0; j < nev; ++j) done = done && conv[(size_t)j];
-        if (done || it >= maxit) break;
-        // soft locking: converged columns stay in X, their W and P columns leave the basis
+        bool done = true;
+        for (int j = 0; j < in.nev; ++j) done = done && conv[(size_t)j];
+        return done;
+    }
+
+    // W = the preconditioned residuals of the active columns, in the complement of Z and of the deflation set, with their images. Soft locking:
+    // converged columns stay in X, their W and P columns leave the basis.
+    void new_directions() {
         std::vector<int> act;
         for (int j = 0; j < m; ++j)
             if (!conv[(size_t)j]) act.push_back(j);
         for (int j : act) w.precond(w.col(w.R, j), w.col(w.W, j));
         w.lap(2);
         project_out_Z(w, w.W, nullptr, act);
-        if (nq > 0) deflate_project(w, *defl, w.W, nullptr, act);
-        if (w.prestressed) {
-            for (int j : act) w.apply_AB(w.col(w.W, j), w.col(w.KW, j), w.col(w.MW, j), true);
-        } else {
-            for (int j : act) w.apply_A(w.col(w.W, j), w.col(w.KW, j));
-            w.lap(0);
-            for (int j : act) w.apply_B(w.col(w.W, j), w.col(w.MW, j));
-            w.lap(1);
+        if (nq > 0) deflate_project(w, *in.defl, w.W, nullptr, act);
+        w.apply_images(w.W, w.KW, w.MW, act, true);
+        pact = haveP ? act : std::vector<int>();
+        wact = std::move(act);
+    }
+
+    // host Gram matrix S^T (img S) of the basis, kb x kb row-major, against its A-images (img 1) or B-images (img 2): the block Grams of the upper
+    // block triangle, downloaded and mirrored. One synchronisation.
+    std::vector<double> basis_gram(int img) {
+        const std::vector<int> *cl[3] = {&all, &wact, &pact};
+        const int kb = m + (int)wact.size() + (int)pact.size();
+        const int off[3] = {0, m, m + (int)wact.size()};
+        struct Part { int bi, bj; double *dev; std::vector<double> host; };
+        std::vector<Part> parts;
+        parts.reserve(6);              // (asynchronous downloads point into the elements: no reallocation)
+        for (int bi = 0; bi < 3; ++bi)
+            for (int bj = bi; bj < 3; ++bj)
+                if (!cl[bi]->empty() && !cl[bj]->empty())
+                    parts.push_back(Part{bi, bj, w.gram(w.ref(w.block(0, bi), *cl[bi]), w.ref(w.block(img, bj), *cl[bj])), std::vector<double>(cl[bi]->size() * cl[bj]->size())});
+        for (Part &p : parts) MFH_HIP(hipMemcpyAsync(p.host.data(), p.dev, p.host.size() * sizeof(double), hipMemcpyDeviceToHost, w.s));
+        w.sync();
+        w.lap(3);
+        std::vector<double> G((size_t)kb * kb, 0.0);
+        for (const Part &p : parts) {
+            const int ni = (int)cl[p.bi]->size(), nj = (int)cl[p.bj]->size();
+            for (int i = 0; i < ni; ++i)
+                for (int j = 0; j < nj; ++j) {
+                    G[(size_t)(off[p.bi] + i) * kb + off[p.bj] + j] = p.host[(size_t)i * nj + j];
+                    if (p.bi != p.bj) G[(size_t)(off[p.bj] + j) * kb + off[p.bi] + i] = p.host[(size_t)i * nj + j];
+                }
         }
-        std::vector<int> pact = haveP ? act : std::vector<int>();
-        // Cholesky-QR of the basis S = [X W P], twice: Gram-Schmidt in that order, so W leaves M-orthogonal to X
-        std::vector<int> wact = act;
-        for (int pass = 0; pass < 2; ++pass) {
+        return G;
+    }
+
+    // Cholesky-QR of the basis, twice: Gram-Schmidt in the order X, W, P, so W leaves M-orthogonal to X. A pivot that fails in P restarts (P leaves
+    // the basis for this iteration); one that fails in W drops that column of W, and P with it; one in X is a breakdown.
+    void orthonormalise() {
+        for (int pass = 0; pass < 2; ++pass)
             for (int attempt = 0;; ++attempt) {
                 w.need(attempt < 2 * BLK_MAXC + 2, MFH_ERR_NOT_CONVERGED, "breakdown (the basis cannot be orthonormalised)");
-                const int nx = m, nw = (int)wact.size(), np = (int)pact.size(), kb = nx + nw + np;
-                const double *blk[3] = {w.X, w.W, w.P}, *mblk[3] = {w.MX, w.MW, w.MP};
-                const std::vector<int> *cl[3] = {&all, &wact, &pact};
-                const int off[4] = {0, nx, nx + nw, kb};
-                double *dG[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-                for (int bi = 0; bi < 3; ++bi)
-                    for (int bj = bi; bj < 3; ++bj)
-                        if (!cl[bi]->empty() && !cl[bj]->empty()) dG[bi][bj] = w.gram(w.ref(blk[bi], *cl[bi]), w.ref(mblk[bj], *cl[bj]));
-                std::vector<double> G((size_t)kb * kb, 0.0);
-                std::vector<std::vector<double>> parts;
-                parts.reserve(6);          // (asynchronous downloads point into the elements: no reallocation)
-                for (int bi = 0; bi < 3; ++bi)
-                    for (int bj = bi; bj < 3; ++bj)
-                        if (dG[bi][bj]) {
-                            parts.emplace_back(cl[bi]->size() * cl[bj]->size());
-                            MFH_HIP(hipMemcpyAsync(parts.back().data(), dG[bi][bj], parts.back().size() * sizeof(double), hipMemcpyDeviceToHost, s));
-                        }
-                w.sync();
-                w.lap(3);
-                size_t pi = 0;
-                for (int bi = 0; bi < 3; ++bi)
-                    for (int bj = bi; bj < 3; ++bj)
-                        if (dG[bi][bj]) {
-                            const std::vector<double> &pp = parts[pi++];
-                            const int ni = (int)cl[bi]->size(), nj = (int)cl[bj]->size();
-                            for (int i = 0; i < ni; ++i)
-                                for (int j = 0; j < nj; ++j) {
-                                    G[(size_t)(off[bi] + i) * kb + off[bj] + j] = pp[(size_t)i * nj + j];
-                                    if (bi != bj) G[(size_t)(off[bj] + j) * kb + off[bi] + i] = pp[(size_t)i * nj + j];
-                                }
-                        }
+                const int nw = (int)wact.size(), np = (int)pact.size(), kb = m + nw + np;
+                const std::vector<double> G = basis_gram(2);
                 std::vector<double> U;
                 const int bad = chol_qr_factor(kb, G, 1e-12, U);
-                if (bad >= 0) {
-                    if (bad >= off[2]) { pact.clear(); haveP = false; ++restarts; continue; }       // restart: P leaves the basis for this iteration
-                    if (bad >= off[1]) { wact.erase(wact.begin() + (bad - off[1])); if (!pact.empty()) { pact.clear(); haveP = false; ++restarts; } continue; }
-                    throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the Ritz block lost its rank)");
-                }
+                if (bad >= m + nw) { pact.clear(); haveP = false; ++restarts; continue; }
+                if (bad >= m) { wact.erase(wact.begin() + (bad - m)); if (!pact.empty()) { pact.clear(); haveP = false; ++restarts; } continue; }
+                if (bad >= 0) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the Ritz block lost its rank)");
                 // S <- S U, images alike: first W and P (they read the old X), then X
-                const double *kblk[3] = {w.KX, w.KW, w.KP};
-                {
+                if (nw + np > 0) {
                     UpdCall u;
                     u.inputs(0, all); u.inputs(1, wact); u.inputs(2, pact);
                     u.outputs(0, wact); u.outputs(1, pact);
                     u.finish();
                     for (int i = 0; i < kb; ++i) {
-                        for (int j = 0; j < nw; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + off[1] + j];
-                        for (int j = 0; j < np; ++j) u.c2[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + off[2] + j];
+                        for (int j = 0; j < nw; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + m + j];
+                        for (int j = 0; j < np; ++j) u.c2[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + m + nw + j];
                     }
                     u.a.skip2 = 0;
-                    for (int f = 0; f < 3; ++f) {
-                        const double *const *src = f == 0 ? blk : (f == 1 ? kblk : mblk);
-                        for (int b = 0; b < 3; ++b) u.a.fam[f].in[b] = src[b];
-                        u.a.fam[f].out[0] = const_cast<double *>(src[1]);
-                        u.a.fam[f].out[1] = const_cast<double *>(src[2]);
-                    }
-                    u.a.nFam = 3;
-                    if (nw + np > 0) run_update(w, u, np > 0);
+                    u.basis(w, 3, 1, 2);
+                    run_update(w, u, np > 0);
                 }
-                {
-                    UpdCall u;
-                    u.inputs(0, all); u.outputs(0, all);
-                    u.finish();
-                    for (int i = 0; i < nx; ++i)
-                        for (int j = 0; j < nx; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + j];
-                    for (int f = 0; f < 3; ++f) {
-                        const double *const *src = f == 0 ? blk : (f == 1 ? kblk : mblk);
-                        u.a.fam[f].in[0] = src[0];
-                        u.a.fam[f].out[0] = const_cast<double *>(src[0]);
-                    }
-                    u.a.nFam = 3;
-                    run_update(w, u, false);
-                }
+                UpdCall u;
+                u.inputs(0, all); u.outputs(0, all);
+                u.finish();
+                for (int i = 0; i < m; ++i)
+                    for (int j = 0; j < m; ++j) u.c1[(size_t)i * BLK_MAXC + j] = U[(size_t)i * kb + j];
+                u.basis(w, 1, 0);
+                run_update(w, u, false);
                 w.lap(4);
                 break;
             }
-        }
-        // Rayleigh-Ritz on the M-orthonormal basis: S^T K S, standard problem
-        {
-            const int nx = m, nw = (int)wact.size(), np = (int)pact.size(), kb = nx + nw + np;
-            const double *blk[3] = {w.X, w.W, w.P}, *kblk[3] = {w.KX, w.KW, w.KP}, *mblk[3] = {w.MX, w.MW, w.MP};
-            const std::vector<int> *cl[3] = {&all, &wact, &pact};
-            const int off[4] = {0, nx, nx + nw, kb};
-            std::vector<double> G((size_t)kb * kb, 0.0);
-            std::vector<std::vector<double>> parts;
-            parts.reserve(6);
-            std::vector<std::array<int, 2>> which;
-            for (int bi = 0; bi < 3; ++bi)
-                for (int bj = bi; bj < 3; ++bj)
-                    if (!cl[bi]->empty() && !cl[bj]->empty()) {
-                        double *dG = w.gram(w.ref(blk[bi], *cl[bi]), w.ref(kblk[bj], *cl[bj]));
-                        parts.emplace_back(cl[bi]->size() * cl[bj]->size());
-                        which.push_back({bi, bj});
-                        MFH_HIP(hipMemcpyAsync(parts.back().data(), dG, parts.back().size() * sizeof(double), hipMemcpyDeviceToHost, s));
-                    }
-            w.lap(3);
-            w.sync();
-            for (size_t pi = 0; pi < parts.size(); ++pi) {
-                const int bi = which[pi][0], bj = which[pi][1];
-                const int ni = (int)cl[bi]->size(), nj = (int)cl[bj]->size();
-                for (int i = 0; i < ni; ++i)
-                    for (int j = 0; j < nj; ++j) {
-                        G[(size_t)(off[bi] + i) * kb + off[bj] + j] = parts[pi][(size_t)i * nj + j];
-                        if (bi != bj) G[(size_t)(off[bj] + j) * kb + off[bi] + i] = parts[pi][(size_t)i * nj + j];
-                    }
-            }
-            for (int i = 0; i < kb; ++i)
-                for (int j = i + 1; j < kb; ++j) G[(size_t)i * kb + j] = G[(size_t)j * kb + i] = 0.5 * (G[(size_t)i * kb + j] + G[(size_t)j * kb + i]);
-            std::vector<double> ev((size_t)kb), V((size_t)kb * kb);
-            sym_gen_eig(kb, G.data(), nullptr, ev.data(), V.data());
-            w.lap(6);
-            // X+ = S C, P+ = [W P] C' (C' = the W and P rows of C), and the same combinations of the K- and M-images
-            UpdCall u;
-            u.inputs(0, all); u.inputs(1, wact); u.inputs(2, pact);
-            u.outputs(0, all); u.outputs(1, all);
-            u.finish();
-            for (int i = 0; i < kb; ++i)
-                for (int j = 0; j < m; ++j) {
-                    u.c1[(size_t)i * BLK_MAXC + j] = V[(size_t)i * kb + j];
-                    if (i >= nx) u.c2[(size_t)i * BLK_MAXC + j] = V[(size_t)i * kb + j];
-                }
-            u.a.skip2 = nx;
-            for (int f = 0; f < 3; ++f) {
-                const double *const *src = f == 0 ? blk : (f == 1 ? kblk : mblk);
-                for (int b = 0; b < 3; ++b) u.a.fam[f].in[b] = src[b];
-                u.a.fam[f].out[0] = const_cast<double *>(src[0]);
-                u.a.fam[f].out[1] = const_cast<double *>(src[2]);
-            }
-            u.a.nFam = 3;
-            run_update(w, u, true);
-            w.lap(4);
-            for (int j = 0; j < m; ++j) lam[(size_t)j] = ev[(size_t)j];
-            haveP = nw > 0;
-        }
     }
-    // ---- the returned columns: one final M-orthonormalisation, sign rule, download
-    std::vector<int> ret;
-    for (int j = 0; j < nev; ++j) ret.push_back(j);
-    // B = K is ill-conditioned where the mass matrix is not: the B-images carried through hundreds of block updates have drifted from K X by far
-    // more than M X ever does (X K X^T - I of 3e-12 after 200 block-Jacobi iterations at cond 7e4), so the buckling pencil takes them afresh
-    if (w.buckling)
-        for (int j : ret) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
-    if (nq > 0) o.lockDefect = deflate_project(w, *defl, w.X, w.MX, ret);
-    if (!chol_qr_block(w, w.X, nullptr, w.MX, ret)) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the returned modes lost their rank)");
-    MFH_HIP(hipMemcpy2DAsync(Xout, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nev, hipMemcpyDeviceToHost, s));
-    MFH_HIP(hipStreamSynchronize(s));
-    const double solveMs = tsolve.stop();
-    for (int j = 0; j < nev; ++j) {
-        double *x = Xout + (size_t)j * (size_t)w.n;
-        int64_t at = 0;
-        for (int64_t i = 1; i < w.n; ++i)
-            if (std::fabs(x[i]) > std::fabs(x[at])) at = i;
-        if (x[at] < 0)
-            for (int64_t i = 0; i < w.n; ++i) x[i] = -x[i];
-        if (w.masked)
-            for (int64_t fv : c->fixedVars) x[(size_t)fv] = 0.0;       // (exactly +0.0: the iteration keeps them at +-0.0)
-        lambda[j] = lam[(size_t)j];
-        if (residuals) residuals[j] = res[(size_t)j];
+
+    // Rayleigh-Ritz on the M-orthonormal basis (S^T K S, a standard problem): X+ = S C, P+ = [W P] C' (C' = the W and P rows of C), and the same
+    // combinations of the K- and M-images
+    void rayleigh_ritz() {
+        const int nw = (int)wact.size(), kb = m + nw + (int)pact.size();
+        std::vector<double> G = basis_gram(1);
+        for (int i = 0; i < kb; ++i)
+            for (int j = i + 1; j < kb; ++j) G[(size_t)i * kb + j] = G[(size_t)j * kb + i] = 0.5 * (G[(size_t)i * kb + j] + G[(size_t)j * kb + i]);
+        std::vector<double> ev((size_t)kb), V((size_t)kb * kb);
+        sym_gen_eig(kb, G.data(), nullptr, ev.data(), V.data());
+        w.lap(6);
+        UpdCall u;
+        u.inputs(0, all); u.inputs(1, wact); u.inputs(2, pact);
+        u.outputs(0, all); u.outputs(1, all);
+        u.finish();
+        for (int i = 0; i < kb; ++i)
+            for (int j = 0; j < m; ++j) {
+                u.c1[(size_t)i * BLK_MAXC + j] = V[(size_t)i * kb + j];
+                if (i >= m) u.c2[(size_t)i * BLK_MAXC + j] = V[(size_t)i * kb + j];
+            }
+        u.a.skip2 = m;
+        u.basis(w, 3, 0, 2);
+        run_update(w, u, true);
+        w.lap(4);
+        for (int j = 0; j < m; ++j) lam[(size_t)j] = ev[(size_t)j];
+        haveP = nw > 0;
     }
-    if (w.timing)
-        fprintf(stderr, "[%s] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f deflation %.3f\n",
-                w.who, (long long)w.n, m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6], w.tPhase[7]);
-    int locked = 0;
-    double mr = 0;
-    for (int j = 0; j < m; ++j) locked += conv[(size_t)j] ? 1 : 0;
-    for (int j = 0; j < nev; ++j) mr = std::max(mr, res[(size_t)j]);
-    o.iterations = it; o.restarts = restarts; o.locked = locked; o.blockSize = m; o.done = done; o.maxResidual = mr; o.setupMs = setupMs; o.solveMs = solveMs;
-}
 
-}   // namespace
-
-namespace {
-
-// What mfh_modes and mfh_modes_many share: the contexts they accept, the state they hold for the duration of the call, the preconditioner.
-// the storage of the pattern for the duration of the call (see mfh_ctx::modesWide); the guard also restores the solver's singular-system switch
-struct ModesGuard {
-    mfh_ctx *c;
-    ~ModesGuard() {
-        c->tlSuppress = false;
-        if (c->modesWide) { c->modesWide = false; refresh_storage_rule(c); }
+    // the returned columns: in the complement of the deflation set once more, one final M-orthonormalisation, download (where the solve timer
+    // stops); on the host the sign rule and exact zeros on the fixed variables
+    void return_columns(EventTimer &tsolve, LoopOut &o) {
+        const std::vector<int> ret = iota(in.nev);
+        if (w.recompute_returned_B())
+            for (int j : ret) w.apply_B(w.col(w.X, j), w.col(w.MX, j));
+        if (nq > 0) o.lockDefect = deflate_project(w, *in.defl, w.X, w.MX, ret);
+        if (!chol_qr_block(w, w.X, nullptr, w.MX, ret)) throw w.fail(MFH_ERR_NOT_CONVERGED, "breakdown (the returned modes lost their rank)");
+        MFH_HIP(hipMemcpy2DAsync(in.X, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)in.nev, hipMemcpyDeviceToHost, w.s));
+        MFH_HIP(hipStreamSynchronize(w.s));
+        o.solveMs = tsolve.stop();
+        for (int j = 0; j < in.nev; ++j) {
+            double *x = in.X + (size_t)j * (size_t)w.n;
+            int64_t at = 0;
+            for (int64_t i = 1; i < w.n; ++i)
+                if (std::fabs(x[i]) > std::fabs(x[at])) at = i;
+            if (x[at] < 0)
+                for (int64_t i = 0; i < w.n; ++i) x[i] = -x[i];
+            if (w.masked)
+                for (int64_t fv : w.c->fixedVars) x[(size_t)fv] = 0.0;       // (exactly +0.0: the iteration keeps them at +-0.0)
+            in.lambda[j] = lam[(size_t)j];
+            if (in.residuals) in.residuals[j] = res[(size_t)j];
+        }
     }
 };
+
+// The block LOBPCG loop on the pencil (A, B) of w (the product members of ModesWork): the nev smallest eigenpairs of A x = lambda B x, B-orthonormal
+// columns with the sign rule, the relative residuals ||A x - lambda B x|| / (|lambda| ||B x||). The caller has prepared the context and w
+// (modes_prepare); tsetup is its running set-up timer. Shared by mfh_modes, mfh_modes_many, mfh_buckling and mfh_modes_prestressed.
+// in.defl (optional): a deflation set. The loop then runs in the B-orthogonal complement of its columns (and of Z): the start block is projected
+// twice and every preconditioned residual block once, nEff loses nq, and before the final orthonormalisation the returned columns and their
+// B-images are projected once more (o.lockDefect = the largest |BQ^T X| seen there). Without a set, a warm start or a device seed the operations
+// are those of the loop without them.
+void lobpcg_run(ModesWork &w, const LoopIn &in, EventTimer &tsetup, LoopOut &o) {
+    Lobpcg L(w, in);
+    if (in.freeBody) build_rigid_modes(w);         // the known kernel of the free body
+    L.start_block();
+    MFH_HIP(hipStreamSynchronize(w.s));
+    o.setupMs = tsetup.stop();
+    EventTimer tsolve(w.s);
+    w.lap(-1);
+    int it = 0;
+    for (;; ++it) {
+        o.done = L.converged();
+        if (o.done || it >= in.maxit) break;
+        L.new_directions();
+        L.orthonormalise();
+        L.rayleigh_ritz();
+    }
+    L.return_columns(tsolve, o);
+    if (w.timing)
+        fprintf(stderr, "[%s] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f deflation %.3f\n",
+                w.who, (long long)w.n, L.m, it, w.tPhase[0], w.tPhase[1], w.tPhase[2], w.tPhase[3], w.tPhase[4], w.tPhase[5], w.tPhase[6], w.tPhase[7]);
+    o.iterations = it; o.restarts = L.restarts; o.blockSize = L.m;
+    for (int j = 0; j < L.m; ++j) o.locked += L.conv[(size_t)j] ? 1 : 0;
+    for (int j = 0; j < in.nev; ++j) o.maxResidual = std::max(o.maxResidual, L.res[(size_t)j]);
+}
+
+// ---- what the four entry points share: the state they hold for the duration of the call, the contexts they accept, the set-up, the finish
 void modes_note(mfh_ctx *c, const std::string &t) {
     if (!c->modesNote.empty()) c->modesNote += "; ";
     c->modesNote += t;
 }
-// the refusals that need no device work (after require_device)
+// WideGuard (both triangles of the pattern for the duration of the call, in force before ensure_precond runs) with the call's note started and,
+// at the end, the solver's singular-system switch restored. Before the set-up timer starts.
+struct ModesGuard : WideGuard {
+    explicit ModesGuard(mfh_ctx *c_) : WideGuard(c_) {
+        c->modesNote.clear();
+        if (widened) modes_note(c, "the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+    }
+    ~ModesGuard() { c->tlSuppress = false; }
+};
+// the refusals of mfh_modes and mfh_modes_many that need no device work (after require_device)
 void modes_require_context(mfh_ctx *c, bool freeBody, const std::string &who) {
     if (!(c->op == MFH_OP_ELASTICITY && c->opDegree != 1))
         throw Error(MFH_ERR_UNSUPPORTED, who + ": the pencil is (elasticity, mass) on the mesh's own degree: select MFH_OP_ELASTICITY and leave the forced-degree-1 view");
@@ -1380,43 +1411,210 @@ void modes_require_context(mfh_ctx *c, bool freeBody, const std::string &who) {
         if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: the clamped pencil is singular (fix more variables, or ask for MFH_MODES_FREE)");
     }
 }
-// both triangles of the pattern for the duration of the call (a ModesGuard undoes it); before the set-up timer starts
-void modes_widen_storage(mfh_ctx *c) {
-    c->modesNote.clear();
-    if (resolve_upper_storage(c)) {
-        c->modesWide = true;
-        refresh_storage_rule(c);          // (before ensure_precond: see WideGuard)
-        modes_note(c, "the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
-    }
-}
-// preconditioner, mass buffer and the fields of w up to useTL
-void modes_prepare(mfh_ctx *c, bool freeBody, double density, const std::string &who, ModesWork &w) {
-    hipStream_t s = c->stream;
-    // ---- preconditioner: what the next solve of this kind would use
-    c->tlSuppress = freeBody;
+struct ModesSetup {
+    const char *who;                   // the entry point, for messages
+    Pencil pencil;
+    bool freeBody;
+    double density, loadFactor;
+    bool mass, geometric;              // the one-double-per-block buffers the pencil's products read (assembled in this order; none is started that is not asked for)
+};
+// The preconditioner of K (what the next solve of this kind would use; it plays the part of the inverse in every pencil), the pencil's buffers
+// and the fields of w up to useTL. Under a ModesGuard.
+void modes_prepare(mfh_ctx *c, const ModesSetup &su, ModesWork &w) {
+    const std::string who = su.who;
+    c->tlSuppress = su.freeBody;
     ensure_precond(c);
-    if (freeBody) {
+    if (su.freeBody) {
         c->precondNote.clear();
         if (c->precond == MFH_PRECOND_MULTIGRID && ensure_multigrid(c)) modes_note(c, "multigrid preconditioner on the singular K of the free body: dense level pinned");
         else if (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) modes_note(c, "two-level / multigrid preconditioner unavailable on the singular K of the free body: using block-Jacobi");
     } else
         ensure_coarse_levels(c, 1);
     if (c->sym.nRows != c->sym.nCols) throw Error(MFH_ERR_UNSUPPORTED, who + ": unpartitioned contexts only");
-    ensure_mass(c);
+    if (su.mass) ensure_mass(c);
+    if (su.geometric) ensure_geometric(c);
     prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes");
+    if (!c->use_mf()) require_full_storage(c, ("the assembled SpMV of " + who).c_str());
 
-    w.c = c; w.s = s; w.d = c->bs();
+    w.c = c; w.s = c->stream; w.d = c->bs();
     w.n = (int64_t)w.d * c->nDoF; w.ld = (w.n + 31) / 32 * 32;
-    w.density = density;
+    w.pencil = su.pencil;
+    w.density = su.density;
+    w.loadFactor = su.loadFactor;
+    w.who = su.who;
     w.masked = !c->fixedVars.empty();
     w.timing = getenv("MFH_MODES_TIMING") != nullptr;
     w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && c->mg.singular == c->tlSuppress;
     w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid && !c->tlSuppress;
-    if (!freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) modes_note(c, c->precondNote);
+    if (!su.freeBody && !w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) modes_note(c, c->precondNote);
 }
 int modes_precond_used(const mfh_ctx *c, const ModesWork &w) {
     return w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
+}
+// the fields mfh_modes_info and mfh_buckling_info share
+template <class Info>
+void modes_fill_info(Info *info, const mfh_ctx *c, const ModesWork &w, const LoopOut &lo) {
+    if (!info) return;
+    info->converged = lo.done ? 1 : 0;
+    info->iterations = lo.iterations;
+    info->nLocked = lo.locked;
+    info->precondUsed = modes_precond_used(c, w);
+    info->blockSize = lo.blockSize;
+    info->restarts = lo.restarts;
+    info->maxResidual = lo.maxResidual;
+    info->solve_ms = lo.solveMs;
+    info->setup_ms = lo.setupMs;
+    info->note = c->modesNote.c_str();
+}
+void require_converged(const LoopOut &lo) {
+    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+}
+
+// ---- the steps of mfh_modes_many. Its deflation set is Q and M Q (device, stride ld), resident for the call: the caller's nLocked columns, then what the batches found.
+// M-orthonormalise the caller's Q (masked, and in the free case in the complement of Z): block Gram-Schmidt over groups of <= 24 columns -- a group
+// is projected twice against the groups before it (k_deflate_gram / k_deflate_update), then Cholesky-QR'd on the host
+void many_orthonormalise_given(ModesWork &w, bool freeBody, const double *Qin, int nLocked, double *Q, double *BQ) {
+    hipStream_t s = w.s;
+    const char *deficient = "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)";
+    MFH_HIP(hipMemcpy2DAsync(Q, (size_t)w.ld * sizeof(double), Qin, (size_t)w.n * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nLocked, hipMemcpyHostToDevice, s));
+    if (w.masked)
+        for (int j = 0; j < nLocked; ++j) k::launch_mask(w.n, w.c->dFixedMask.p, w.col(Q, j), s);
+    MFH_HIP(hipStreamSynchronize(s));
+    if (freeBody) build_rigid_modes(w);
+    for (int g0 = 0; g0 < nLocked; g0 += BLK_MAXC) {
+        const int kg = std::min(BLK_MAXC, nLocked - g0);
+        const std::vector<int> cols = iota(kg);
+        double *Vg = w.col(Q, g0), *MVg = w.col(BQ, g0);
+        if (freeBody) project_out_Z(w, Vg, nullptr, cols);
+        for (int j = 0; j < kg; ++j) w.apply_B(w.col(Vg, j), w.col(MVg, j));
+        auto norms2 = [&]() {
+            double *G = w.gram(w.ref(Vg, cols), w.ref(MVg, cols));
+            std::vector<double> hG((size_t)kg * kg), dd((size_t)kg);
+            MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            w.sync();
+            for (int j = 0; j < kg; ++j) dd[(size_t)j] = hG[(size_t)j * kg + j];
+            return dd;
+        };
+        const std::vector<double> d0 = norms2();
+        if (g0 > 0) {
+            const DeflationSet prev{Q, BQ, g0, 0};
+            for (int pass = 0; pass < 2; ++pass) deflate_project(w, prev, Vg, MVg, cols);
+            const std::vector<double> d1 = norms2();
+            for (int j = 0; j < kg; ++j)
+                if (!(d1[(size_t)j] > 1e-13 * d0[(size_t)j])) throw w.fail(MFH_ERR_INVALID, deficient);
+        }
+        for (int j = 0; j < kg; ++j)
+            if (!(d0[(size_t)j] > 0.0)) throw w.fail(MFH_ERR_INVALID, deficient);
+        if (!chol_qr_block(w, Vg, nullptr, MVg, cols)) throw w.fail(MFH_ERR_INVALID, deficient);
+    }
+    for (int j = 0; j < nLocked; ++j) w.apply_B(w.col(Q, j), w.col(BQ, j));      // the images afresh: they went through every update
+}
+
+struct ManyRun {
+    int found = 0, batches = 0, iterations = 0, restarts = 0;
+    bool allDone = true, exhausted = false;
+    double setupMs = 0, solveMs = 0, lockDefect = 0;
+    std::vector<double> res;           // per mode found, in the order found
+    std::vector<int> batchOf;
+};
+// Batch by batch: each runs the loop in the complement of the set (to rtol lockFactor, the last one of a sweep without a band to rtol), joins the
+// set with fresh images, and its guard columns seed the next start block. Ends at nev modes, at a batch that did not converge, or past the band.
+void many_batches(ModesWork &w, const mfh_modes_many_params &p, int batch, double lockFactor, bool band, EventTimer &tsetup, double *Q, double *BQ,
+                  double *lambda, double *Xout, ManyRun &r) {
+    hipStream_t s = w.s;
+    const size_t L = (size_t)w.ld;
+    const int nev = p.nev;
+    const bool useSeed = getenv("MFH_MODES_MANY_NO_SEED") == nullptr;      // (scripts/probe_many_modes.py measures what the seeding saves)
+    DBuf<double> seed;
+    int nqNow = p.nLocked, nSeed = 0;
+    r.res.assign((size_t)nev, 0.0);
+    r.batchOf.assign((size_t)nev, 0);
+    while (r.found < nev) {
+        const int nb = std::min(batch, nev - r.found);
+        const bool last = !band && r.found + nb == nev;
+        const DeflationSet ds{Q, BQ, nqNow, p.nLocked};
+        LoopIn in{nb, (p.flags & MFH_MODES_FREE) != 0, last ? p.rtol : p.rtol * lockFactor, p.maxit, lambda + r.found, Xout + (size_t)r.found * (size_t)w.n, r.res.data() + r.found};
+        LoopOut lo;
+        if (r.batches == 0) {
+            if (nqNow) in.defl = &ds;
+            lobpcg_run(w, in, tsetup, lo);
+        } else {
+            in.defl = &ds;
+            in.X0dev = nSeed > 0 ? seed.p : nullptr;
+            in.nX0dev = nSeed;
+            EventTimer tb(s);
+            lobpcg_run(w, in, tb, lo);
+        }
+        if (w.timing || getenv("MFH_MODES_MANY_LOG")) fprintf(stderr, "[mfh_modes_many] batch %d: %d modes, set %d, seeded %d, iterations %d, setup %.3f ms, solve %.3f ms\n", r.batches, nb, nqNow, nSeed, lo.iterations, lo.setupMs, lo.solveMs);
+        for (int j = 0; j < nb; ++j) r.batchOf[(size_t)(r.found + j)] = r.batches;
+        ++r.batches;
+        r.iterations += lo.iterations; r.restarts += lo.restarts; r.setupMs += lo.setupMs; r.solveMs += lo.solveMs;
+        r.lockDefect = std::max(r.lockDefect, lo.lockDefect);
+        MFH_HIP(hipMemcpyAsync(w.col(Q, nqNow), w.X, L * (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, s));
+        for (int j = 0; j < nb; ++j) w.apply_B(w.col(Q, nqNow + j), w.col(BQ, nqNow + j));
+        nSeed = useSeed ? lo.blockSize - nb : 0;
+        if (nSeed > 0) {
+            seed.reserve(L * (size_t)BLK_MAXC);
+            MFH_HIP(hipMemcpyAsync(seed.p, w.col(w.X, nb), L * (size_t)nSeed * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+        nqNow += nb; r.found += nb;
+        if (!lo.done) { r.allDone = false; break; }
+        if (band) {
+            for (int j = r.found - nb; j < r.found; ++j) r.exhausted = r.exhausted || lambda[j] > p.lambdaMax;
+            if (r.exhausted) break;
+        }
+    }
+}
+
+// The full residuals of everything found, unprojected against what the call itself locked: K x afresh, k_block_residual in groups of the block's
+// width. The caller's Q need not be eigenvectors: with them, the residual of the restricted pencil. Returns the device time in ms.
+double many_full_residuals(ModesWork &w, double *Q, double *BQ, int nLocked, int found, const double *lambda, double *res) {
+    EventTimer tr(w.s);
+    const DeflationSet given{Q, BQ, nLocked, nLocked};
+    for (int g0 = 0; g0 < found; g0 += w.m) {
+        const int kg = std::min(w.m, found - g0);
+        for (int j = 0; j < kg; ++j) w.apply_A(w.col(Q, nLocked + g0 + j), w.col(w.KX, j));
+        block_residuals(w, &given, kg, lambda + g0, w.KX, w.col(BQ, nLocked + g0), res + g0);
+    }
+    return tr.stop();
+}
+
+// Sorted by lambda (lambda, res and the rows of X, in place); a mode of a later batch that sorts before an earlier batch's largest (by more than
+// rtol) is counted and named in the note. Returns that count.
+int many_sort(mfh_ctx *c, int64_t n, const ManyRun &r, double rtol, double *lambda, double *res, double *Xout) {
+    const int found = r.found;
+    std::vector<int> order = iota(found);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lambda[a] < lambda[b]; });
+    int nOut = 0;
+    std::vector<double> hiOfBatch((size_t)std::max(r.batches, 1), -1e300);
+    for (int j = 0; j < found; ++j) hiOfBatch[(size_t)r.batchOf[(size_t)j]] = std::max(hiOfBatch[(size_t)r.batchOf[(size_t)j]], lambda[j]);
+    for (int b = 1; b < r.batches; ++b) hiOfBatch[(size_t)b] = std::max(hiOfBatch[(size_t)b], hiOfBatch[(size_t)b - 1]);
+    std::string names;
+    for (int j = 0; j < found; ++j)
+        if (r.batchOf[(size_t)j] > 0 && lambda[j] < hiOfBatch[(size_t)r.batchOf[(size_t)j] - 1] * (1.0 - rtol)) {     // (below by more than rtol: the other member of a multiple eigenvalue that a batch edge cut is no missed mode)
+            ++nOut;
+            const int pos = (int)(std::find(order.begin(), order.end(), j) - order.begin());
+            names += (names.empty() ? "" : ", ") + std::to_string(pos) + " (batch " + std::to_string(r.batchOf[(size_t)j]) + ")";
+        }
+    if (nOut > 0) modes_note(c, "modes out of order (a later batch found them below an earlier batch's largest; sorted position): " + names);
+    std::vector<double> lam2((size_t)found), res2((size_t)found), row((size_t)n);
+    for (int j = 0; j < found; ++j) { lam2[(size_t)j] = lambda[order[(size_t)j]]; res2[(size_t)j] = res[(size_t)order[(size_t)j]]; }
+    // rows of X in place, cycle by cycle
+    std::vector<uint8_t> seen((size_t)found, 0);
+    for (int st = 0; st < found; ++st) {
+        if (seen[(size_t)st] || order[(size_t)st] == st) { seen[(size_t)st] = 1; continue; }
+        std::copy(Xout + (size_t)st * (size_t)n, Xout + (size_t)(st + 1) * (size_t)n, row.begin());
+        int at = st;
+        for (;;) {
+            seen[(size_t)at] = 1;
+            const int from = order[(size_t)at];
+            if (from == st) { std::copy(row.begin(), row.end(), Xout + (size_t)at * (size_t)n); break; }
+            std::copy(Xout + (size_t)from * (size_t)n, Xout + (size_t)(from + 1) * (size_t)n, Xout + (size_t)at * (size_t)n);
+            at = from;
+        }
+    }
+    for (int j = 0; j < found; ++j) { lambda[j] = lam2[(size_t)j]; res[(size_t)j] = res2[(size_t)j]; }
+    return nOut;
 }
 
 }   // namespace
@@ -1434,26 +1632,15 @@ mfh_status mfh_modes(mfh_ctx *c, int32_t nev, double density, int32_t flags, dou
     MFH_HIP(hipSetDevice(c->device));
     const bool freeBody = (flags & MFH_MODES_FREE) != 0;
     modes_require_context(c, freeBody, "mfh_modes");
-    ModesGuard guard{c};
-    modes_widen_storage(c);
+    ModesGuard guard(c);
     EventTimer tsetup(c->stream);
     ModesWork w;
-    modes_prepare(c, freeBody, density, "mfh_modes", w);
+    modes_prepare(c, ModesSetup{"mfh_modes", Pencil::Vibration, freeBody, density, 0.0, true, false}, w);
+    const LoopIn in{nev, freeBody, rtol, maxit, lambda, Xout, residuals};
     LoopOut lo;
-    lobpcg_run(w, nev, freeBody, rtol, maxit, tsetup, lambda, Xout, residuals, lo);
-    if (info) {
-        info->converged = lo.done ? 1 : 0;
-        info->iterations = lo.iterations;
-        info->nLocked = lo.locked;
-        info->precondUsed = modes_precond_used(c, w);
-        info->blockSize = lo.blockSize;
-        info->restarts = lo.restarts;
-        info->maxResidual = lo.maxResidual;
-        info->solve_ms = lo.solveMs;
-        info->setup_ms = lo.setupMs;
-        info->note = c->modesNote.c_str();
-    }
-    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    lobpcg_run(w, in, tsetup, lo);
+    modes_fill_info(info, c, w, lo);
+    require_converged(lo);
     MFH_CATCH(c)
 }
 
@@ -1487,197 +1674,56 @@ mfh_status mfh_modes_many(mfh_ctx *c, const mfh_modes_many_params *prm, const do
     MFH_HIP(hipSetDevice(c->device));
     modes_require_context(c, freeBody, "mfh_modes_many");
     hipStream_t s = c->stream;
-    ModesGuard guard{c};
-    modes_widen_storage(c);
+    ModesGuard guard(c);
     EventTimer tsetup(s);
     ModesWork w;
-    modes_prepare(c, freeBody, p.density, "mfh_modes_many", w);
-    w.who = "mfh_modes_many";
+    modes_prepare(c, ModesSetup{"mfh_modes_many", Pencil::Vibration, freeBody, p.density, 0.0, true, false}, w);
     const int precondUsed = modes_precond_used(c, w);
-    LoopOut lo;
     if (nLocked == 0 && nev <= batch && !band) {
         // one batch and nothing to deflate: the call of mfh_modes, its bits, its residuals
-        lobpcg_run(w, nev, freeBody, p.rtol, p.maxit, tsetup, lambda, Xout, residuals, lo);
+        const LoopIn in{nev, freeBody, p.rtol, p.maxit, lambda, Xout, residuals};
+        LoopOut lo;
+        lobpcg_run(w, in, tsetup, lo);
         if (info) {
             info->converged = lo.done ? 1 : 0;
             info->nFound = nev; info->batches = 1; info->iterations = lo.iterations; info->restarts = lo.restarts; info->precondUsed = precondUsed;
             info->maxResidual = lo.maxResidual; info->solve_ms = lo.solveMs; info->setup_ms = lo.setupMs;
             info->note = c->modesNote.c_str();
         }
-        if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+        require_converged(lo);
         return MFH_OK;
     }
+    // ---- the deflation set: Q and M Q, nLocked + nev columns each
     const size_t L = (size_t)w.ld;
-    const int cap = nLocked + nev;
-    // ---- the deflation set: Q and M Q, cap columns each, resident for the call
-    DBuf<double> setQ, setBQ, seed;
-    setQ.alloc(L * (size_t)cap); setBQ.alloc(L * (size_t)cap);
+    DBuf<double> setQ, setBQ;
+    setQ.alloc(L * (size_t)(nLocked + nev)); setBQ.alloc(L * (size_t)(nLocked + nev));
     setQ.zero(s); setBQ.zero(s);
     deflate_alloc(w);
     modes_scratch(w);
     w.nz = freeBody ? (w.d == 3 ? 6 : 3) : 0;
-    if (nLocked > 0) {
-        // M-orthonormalise the caller's Q (masked, and in the free case in the complement of Z): block Gram-Schmidt over groups of <= 24 columns --
-        // a group is projected twice against the groups before it (k_deflate_gram / k_deflate_update), then Cholesky-QR'd on the host
-        MFH_HIP(hipMemcpy2DAsync(setQ.p, L * sizeof(double), Qin, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nLocked, hipMemcpyHostToDevice, s));
-        if (w.masked)
-            for (int j = 0; j < nLocked; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(setQ.p, j), s);
-        MFH_HIP(hipStreamSynchronize(s));
-        if (freeBody) build_rigid_modes(w);
-        for (int g0 = 0; g0 < nLocked; g0 += BLK_MAXC) {
-            const int kg = std::min(BLK_MAXC, nLocked - g0);
-            std::vector<int> cols((size_t)kg);
-            for (int j = 0; j < kg; ++j) cols[(size_t)j] = j;
-            double *Vg = w.col(setQ.p, g0), *MVg = w.col(setBQ.p, g0);
-            if (freeBody) project_out_Z(w, Vg, nullptr, cols);
-            for (int j = 0; j < kg; ++j) w.apply_B(w.col(Vg, j), w.col(MVg, j));
-            auto norms2 = [&]() {
-                double *G = w.gram(w.ref(Vg, cols), w.ref(MVg, cols));
-                std::vector<double> hG((size_t)kg * kg), dd((size_t)kg);
-                MFH_HIP(hipMemcpyAsync(hG.data(), G, hG.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-                w.sync();
-                for (int j = 0; j < kg; ++j) dd[(size_t)j] = hG[(size_t)j * kg + j];
-                return dd;
-            };
-            const std::vector<double> d0 = norms2();
-            if (g0 > 0) {
-                const DeflationSet prev{setQ.p, setBQ.p, g0, 0};
-                for (int pass = 0; pass < 2; ++pass) deflate_project(w, prev, Vg, MVg, cols);
-                const std::vector<double> d1 = norms2();
-                for (int j = 0; j < kg; ++j)
-                    if (!(d1[(size_t)j] > 1e-13 * d0[(size_t)j])) throw w.fail(MFH_ERR_INVALID, "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)");
-            }
-            for (int j = 0; j < kg; ++j)
-                if (!(d0[(size_t)j] > 0.0)) throw w.fail(MFH_ERR_INVALID, "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)");
-            if (!chol_qr_block(w, Vg, nullptr, MVg, cols)) throw w.fail(MFH_ERR_INVALID, "Q is rank deficient (its Gram matrix Q^T M Q is not positive definite)");
-        }
-        for (int j = 0; j < nLocked; ++j) w.apply_B(w.col(setQ.p, j), w.col(setBQ.p, j));      // the images afresh: they went through every update
-    }
-    // ---- batch by batch
-    const bool useSeed = getenv("MFH_MODES_MANY_NO_SEED") == nullptr;      // (scripts/probe_many_modes.py measures what the seeding saves)
-    int nqNow = nLocked, found = 0, batches = 0, iterations = 0, restarts = 0, nSeed = 0;
-    bool allDone = true, exhausted = false;
-    double setupMs = 0, solveMs = 0, lockDefect = 0;
-    std::vector<double> res((size_t)nev, 0.0);
-    std::vector<int> batchOf((size_t)nev, 0);
-    while (found < nev) {
-        const int nb = std::min(batch, nev - found);
-        const bool last = !band && found + nb == nev;
-        const double tol = last ? p.rtol : p.rtol * lockFactor;
-        const DeflationSet ds{setQ.p, setBQ.p, nqNow, nLocked};
-        lo = LoopOut{};
-        if (batches == 0)
-            lobpcg_run(w, nb, freeBody, tol, p.maxit, tsetup, lambda + found, Xout + (size_t)found * (size_t)n, res.data() + found, lo, nullptr, nqNow ? &ds : nullptr);
-        else {
-            EventTimer tb(s);
-            lobpcg_run(w, nb, freeBody, tol, p.maxit, tb, lambda + found, Xout + (size_t)found * (size_t)n, res.data() + found, lo, nullptr, &ds,
-                       nSeed > 0 ? seed.p : nullptr, nSeed);
-        }
-        if (w.timing || getenv("MFH_MODES_MANY_LOG")) fprintf(stderr, "[mfh_modes_many] batch %d: %d modes, set %d, seeded %d, iterations %d, setup %.3f ms, solve %.3f ms\n", batches, nb, nqNow, nSeed, lo.iterations, lo.setupMs, lo.solveMs);
-        for (int j = 0; j < nb; ++j) batchOf[(size_t)(found + j)] = batches;
-        ++batches;
-        iterations += lo.iterations; restarts += lo.restarts; setupMs += lo.setupMs; solveMs += lo.solveMs;
-        lockDefect = std::max(lockDefect, lo.lockDefect);
-        // the batch joins the set (images afresh); its guard columns seed the next start block
-        MFH_HIP(hipMemcpyAsync(w.col(setQ.p, nqNow), w.X, L * (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, s));
-        for (int j = 0; j < nb; ++j) w.apply_B(w.col(setQ.p, nqNow + j), w.col(setBQ.p, nqNow + j));
-        nSeed = useSeed ? lo.blockSize - nb : 0;
-        if (nSeed > 0) {
-            seed.reserve(L * (size_t)BLK_MAXC);
-            MFH_HIP(hipMemcpyAsync(seed.p, w.col(w.X, nb), L * (size_t)nSeed * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        nqNow += nb; found += nb;
-        if (!lo.done) { allDone = false; break; }
-        if (band) {
-            for (int j = found - nb; j < found; ++j) exhausted = exhausted || lambda[j] > p.lambdaMax;
-            if (exhausted) break;
-        }
-    }
-    // ---- the full residuals of everything found, unprojected against what the call itself locked: K x afresh, k_block_residual in groups of the block's width
-    {
-        EventTimer tr(s);
-        const int gw = w.m;
-        for (int g0 = 0; g0 < found; g0 += gw) {
-            const int kg = std::min(gw, found - g0);
-            k::ResArgs ra{};
-            ra.n = w.n; ra.ld = w.ld; ra.nc = kg; ra.KX = w.KX; ra.MX = w.col(setBQ.p, nLocked + g0); ra.R = w.R;
-            for (int j = 0; j < kg; ++j) {
-                w.apply_A(w.col(setQ.p, nLocked + g0 + j), w.col(w.KX, j));
-                ra.col[j] = (unsigned char)j; ra.lam[j] = lambda[g0 + j];
-            }
-            double *norms = w.small_slot(2 * BLK_MAXC);
-            k::launch_block_residual(ra, w.resPart.p, norms, s);
-            if (nLocked > 0) {                     // the caller's Q need not be eigenvectors: the residual of the restricted pencil
-                std::vector<int> cols((size_t)kg);
-                for (int j = 0; j < kg; ++j) cols[(size_t)j] = j;
-                project_residual(w, DeflationSet{setQ.p, setBQ.p, nLocked, nLocked}, cols, ra.MX, w.deflG.p);
-                norms = w.deflG.p;
-            }
-            double hn[2 * BLK_MAXC];
-            MFH_HIP(hipMemcpyAsync(hn, norms, sizeof(hn), hipMemcpyDeviceToHost, s));
-            w.sync();
-            for (int j = 0; j < kg; ++j) {
-                const double den = std::fabs(lambda[g0 + j]) * std::sqrt(hn[2 * j + 1]);
-                res[(size_t)(g0 + j)] = den > 0 ? std::sqrt(hn[2 * j]) / den : (hn[2 * j] == 0.0 ? 0.0 : 1e300);
-            }
-        }
-        solveMs += tr.stop();
-    }
-    // ---- sorted by lambda; a mode of a later batch that sorts before an earlier batch's largest (by more than rtol) is counted and named
-    std::vector<int> order((size_t)found);
-    for (int j = 0; j < found; ++j) order[(size_t)j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lambda[a] < lambda[b]; });
-    int nOut = 0;
-    {
-        std::vector<double> hiOfBatch((size_t)std::max(batches, 1), -1e300);
-        for (int j = 0; j < found; ++j) hiOfBatch[(size_t)batchOf[(size_t)j]] = std::max(hiOfBatch[(size_t)batchOf[(size_t)j]], lambda[j]);
-        for (int b = 1; b < batches; ++b) hiOfBatch[(size_t)b] = std::max(hiOfBatch[(size_t)b], hiOfBatch[(size_t)b - 1]);
-        std::string names;
-        for (int j = 0; j < found; ++j)
-            if (batchOf[(size_t)j] > 0 && lambda[j] < hiOfBatch[(size_t)batchOf[(size_t)j] - 1] * (1.0 - p.rtol)) {     // (below by more than rtol: the other member of a multiple eigenvalue that a batch edge cut is no missed mode)
-                ++nOut;
-                const int pos = (int)(std::find(order.begin(), order.end(), j) - order.begin());
-                names += (names.empty() ? "" : ", ") + std::to_string(pos) + " (batch " + std::to_string(batchOf[(size_t)j]) + ")";
-            }
-        if (nOut > 0) modes_note(c, "modes out of order (a later batch found them below an earlier batch's largest; sorted position): " + names);
-    }
-    {
-        std::vector<double> lam2((size_t)found), res2((size_t)found), row((size_t)n);
-        for (int j = 0; j < found; ++j) { lam2[(size_t)j] = lambda[order[(size_t)j]]; res2[(size_t)j] = res[(size_t)order[(size_t)j]]; }
-        // rows of X in place, cycle by cycle
-        std::vector<uint8_t> seen((size_t)found, 0);
-        for (int st = 0; st < found; ++st) {
-            if (seen[(size_t)st] || order[(size_t)st] == st) { seen[(size_t)st] = 1; continue; }
-            std::copy(Xout + (size_t)st * (size_t)n, Xout + (size_t)(st + 1) * (size_t)n, row.begin());
-            int at = st;
-            for (;;) {
-                seen[(size_t)at] = 1;
-                const int from = order[(size_t)at];
-                if (from == st) { std::copy(row.begin(), row.end(), Xout + (size_t)at * (size_t)n); break; }
-                std::copy(Xout + (size_t)from * (size_t)n, Xout + (size_t)(from + 1) * (size_t)n, Xout + (size_t)at * (size_t)n);
-                at = from;
-            }
-        }
-        for (int j = 0; j < found; ++j) { lambda[j] = lam2[(size_t)j]; res[(size_t)j] = res2[(size_t)j]; }
-    }
-    int nFound = found;
+    if (nLocked > 0) many_orthonormalise_given(w, freeBody, Qin, nLocked, setQ.p, setBQ.p);
+    ManyRun r;
+    many_batches(w, p, batch, lockFactor, band, tsetup, setQ.p, setBQ.p, lambda, Xout, r);
+    r.solveMs += many_full_residuals(w, setQ.p, setBQ.p, nLocked, r.found, lambda, r.res.data());
+    const int nOut = many_sort(c, n, r, p.rtol, lambda, r.res.data(), Xout);
+    int nFound = r.found;
     if (band)
         while (nFound > 0 && lambda[nFound - 1] > p.lambdaMax) --nFound;
     // rows past nFound hold nothing: zero
-    for (int j = nFound; j < nev; ++j) { lambda[j] = 0.0; res[(size_t)j] = 0.0; }
+    for (int j = nFound; j < nev; ++j) { lambda[j] = 0.0; r.res[(size_t)j] = 0.0; }
     std::fill(Xout + (size_t)nFound * (size_t)n, Xout + (size_t)nev * (size_t)n, 0.0);
     double mr = 0;
-    for (int j = 0; j < nFound; ++j) mr = std::max(mr, res[(size_t)j]);
-    if (residuals) std::copy(res.begin(), res.end(), residuals);
-    const bool converged = allDone && mr <= p.rtol;
+    for (int j = 0; j < nFound; ++j) mr = std::max(mr, r.res[(size_t)j]);
+    if (residuals) std::copy(r.res.begin(), r.res.end(), residuals);
+    const bool converged = r.allDone && mr <= p.rtol;
     if (info) {
         info->converged = converged ? 1 : 0;
-        info->nFound = nFound; info->batches = batches; info->iterations = iterations; info->restarts = restarts; info->precondUsed = precondUsed;
-        info->bandExhausted = exhausted ? 1 : 0; info->nOutOfOrder = nOut;
-        info->maxResidual = mr; info->maxLockDefect = lockDefect; info->solve_ms = solveMs; info->setup_ms = setupMs;
+        info->nFound = nFound; info->batches = r.batches; info->iterations = r.iterations; info->restarts = r.restarts; info->precondUsed = precondUsed;
+        info->bandExhausted = r.exhausted ? 1 : 0; info->nOutOfOrder = nOut;
+        info->maxResidual = mr; info->maxLockDefect = r.lockDefect; info->solve_ms = r.solveMs; info->setup_ms = r.setupMs;
         info->note = c->modesNote.c_str();
     }
-    if (!allDone) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations (batch " + std::to_string(batches - 1) + ")");
+    if (!r.allDone) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations (batch " + std::to_string(r.batches - 1) + ")");
     if (!converged) throw Error(MFH_ERR_NOT_CONVERGED, "the full residuals of the locked modes exceed rtol (largest " + std::to_string(mr / p.rtol) + " rtol): lower lockFactor");
     MFH_CATCH(c)
 }
@@ -1777,6 +1823,7 @@ mfh_status mfh_prestress_from_displacement(mfh_ctx *c, const double *uNodes, int
     MFH_CATCH(c)
 }
 
+// the nev smallest load factors of (K + factor Kg) x = 0: the loop of mfh_modes on the pencil (Kg, K); K's preconditioner approximates B^-1 here
 mfh_status mfh_buckling(mfh_ctx *c, int32_t nev, int32_t flags, double rtol, int32_t maxit, double *factors, double *Xout, double *residuals,
                         mfh_buckling_info *info) {
     if (info) { *info = mfh_buckling_info{}; info->note = ""; }
@@ -1789,35 +1836,15 @@ mfh_status mfh_buckling(mfh_ctx *c, int32_t nev, int32_t flags, double rtol, int
         const int q = free_rigid_motions(c);
         if (q > 0) throw Error(MFH_ERR_UNSUPPORTED, "the fixed variables leave " + std::to_string(q) + " rigid motions free: K is singular there and the pencil (Kg, K) undefined (fix more variables)");
     }
-    const int64_t nAll = (int64_t)c->bs() * c->nDoF;
-    require(nev <= nAll - (int64_t)c->fixedVars.size(), MFH_ERR_INVALID, "mfh_buckling: more modes asked for than the pencil has");
-    hipStream_t s = c->stream;
-    c->modesNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
-    WideGuard guard(c);
-    if (guard.widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
-    EventTimer tsetup(s);
-    // ---- the preconditioner of K (what the next solve would use): here it approximates B^-1
-    ensure_precond(c);
-    ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_buckling: unpartitioned contexts only");
-    ensure_geometric(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_buckling");
-
+    require(nev <= (int64_t)c->bs() * c->nDoF - (int64_t)c->fixedVars.size(), MFH_ERR_INVALID, "mfh_buckling: more modes asked for than the pencil has");
+    ModesGuard guard(c);
+    EventTimer tsetup(c->stream);
     ModesWork w;
-    w.c = c; w.s = s; w.d = c->bs();
-    w.n = nAll; w.ld = (w.n + 31) / 32 * 32;
-    w.buckling = true;
-    w.who = "mfh_buckling";
-    w.masked = !c->fixedVars.empty();
-    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
-    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
-    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid;
-    if (!w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    modes_prepare(c, ModesSetup{"mfh_buckling", Pencil::Buckling, false, 1.0, 0.0, false, true}, w);
     std::vector<double> mu((size_t)nev, 0.0);
+    const LoopIn in{nev, false, rtol, maxit, mu.data(), Xout, residuals};
     LoopOut lo;
-    lobpcg_run(w, nev, false, rtol, maxit, tsetup, mu.data(), Xout, residuals, lo);
+    lobpcg_run(w, in, tsetup, lo);
     // mu ascending; a load factor exists where mu is negative beyond rounding
     double muMax = 0.0;
     for (int j = 0; j < nev; ++j) muMax = std::max(muMax, std::fabs(mu[(size_t)j]));
@@ -1826,25 +1853,15 @@ mfh_status mfh_buckling(mfh_ctx *c, int32_t nev, int32_t flags, double rtol, int
         if (mu[(size_t)j] >= -1e-12 * muMax) factors[j] = INFINITY;
         else { factors[j] = -1.0 / mu[(size_t)j]; ++nNeg; }
     }
-    if (info) {
-        info->converged = lo.done ? 1 : 0;
-        info->iterations = lo.iterations;
-        info->nLocked = lo.locked;
-        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
-        info->blockSize = lo.blockSize;
-        info->restarts = lo.restarts;
-        info->nBuckling = nNeg;
-        info->maxResidual = lo.maxResidual;
-        info->solve_ms = lo.solveMs;
-        info->setup_ms = lo.setupMs;
-        info->note = c->modesNote.c_str();
-    }
-    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    modes_fill_info(info, c, w, lo);
+    if (info) info->nBuckling = nNeg;
+    require_converged(lo);
     MFH_CATCH(c)
 }
 
 // ---------------------------------------------------------------- prestressed vibration (docs/design/04_18_prestressed_modes.md)
-// the smallest eigenpairs of (K + loadFactor Kg) x = lambda density M x: the loop of mfh_modes on its third pencil, K's preconditioner
+// the smallest eigenpairs of (K + loadFactor Kg) x = lambda density M x: the loop of mfh_modes on its third pencil, K's preconditioner (the
+// shifted operator has none of its own)
 mfh_status mfh_modes_prestressed(mfh_ctx *c, int32_t nev, double density, double loadFactor, int32_t flags, double rtol, int32_t maxit, const double *X0,
                                  double *lambda, double *Xout, double *residuals, mfh_modes_info *info) {
     if (info) { *info = mfh_modes_info{}; info->note = ""; }
@@ -1864,51 +1881,19 @@ mfh_status mfh_modes_prestressed(mfh_ctx *c, int32_t nev, double density, double
     require(nev <= nAll - (int64_t)c->fixedVars.size(), MFH_ERR_INVALID, "mfh_modes_prestressed: more modes asked for than the pencil has");
     if (X0)
         for (int64_t q = 0; q < (int64_t)nev * nAll; ++q) require(std::isfinite(X0[q]), MFH_ERR_INVALID, "mfh_modes_prestressed: an entry of X0 is not finite");
-    hipStream_t s = c->stream;
-    c->modesNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modesNote.empty()) c->modesNote += "; "; c->modesNote += t; };
-    WideGuard guard(c);
-    if (guard.widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
-    EventTimer tsetup(s);
-    // ---- the preconditioner of K (what the next solve would use), as in mfh_modes: the shifted operator has none of its own
-    ensure_precond(c);
-    ensure_coarse_levels(c, 1);
-    require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modes_prestressed: unpartitioned contexts only");
-    ensure_mass(c);
-    ensure_geometric(c);
-    prepare_matrix_free(c);
-    if (!c->use_mf()) require_full_storage(c, "the assembled SpMV of mfh_modes_prestressed");
-
+    ModesGuard guard(c);
+    EventTimer tsetup(c->stream);
     ModesWork w;
-    w.c = c; w.s = s; w.d = c->bs();
-    w.n = nAll; w.ld = (w.n + 31) / 32 * 32;
-    w.density = density;
-    w.prestressed = true;
-    w.loadFactor = loadFactor;
-    w.who = "mfh_modes_prestressed";
-    w.masked = !c->fixedVars.empty();
-    w.timing = getenv("MFH_MODES_TIMING") != nullptr;
-    w.useMG = c->precond == MFH_PRECOND_MULTIGRID && c->mg.valid && !c->mg.singular;
-    w.useTL = !w.useMG && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && c->tl.valid;
-    if (!w.useMG && !w.useTL && (c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) && !c->precondNote.empty()) note(c->precondNote);
+    modes_prepare(c, ModesSetup{"mfh_modes_prestressed", Pencil::Prestressed, false, density, loadFactor, true, true}, w);
+    LoopIn in{nev, false, rtol, maxit, lambda, Xout, residuals};
+    in.X0 = X0;
     LoopOut lo;
-    lobpcg_run(w, nev, false, rtol, maxit, tsetup, lambda, Xout, residuals, lo, X0);
+    lobpcg_run(w, in, tsetup, lo);
     int nNeg = 0;
     for (int j = 0; j < nev; ++j) nNeg += lambda[j] < 0.0 ? 1 : 0;
-    if (nNeg > 0) note(std::to_string(nNeg) + " of the " + std::to_string(nev) + " eigenvalues are negative: the prestressed state is unstable at this load factor");
-    if (info) {
-        info->converged = lo.done ? 1 : 0;
-        info->iterations = lo.iterations;
-        info->nLocked = lo.locked;
-        info->precondUsed = w.useMG ? MFH_PRECOND_MULTIGRID : (w.useTL ? MFH_PRECOND_TWO_LEVEL : ((c->precond == MFH_PRECOND_TWO_LEVEL || c->precond == MFH_PRECOND_MULTIGRID) ? (int)MFH_PRECOND_BLOCK_JACOBI : c->precond));
-        info->blockSize = lo.blockSize;
-        info->restarts = lo.restarts;
-        info->maxResidual = lo.maxResidual;
-        info->solve_ms = lo.solveMs;
-        info->setup_ms = lo.setupMs;
-        info->note = c->modesNote.c_str();
-    }
-    if (!lo.done) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations");
+    if (nNeg > 0) modes_note(c, std::to_string(nNeg) + " of the " + std::to_string(nev) + " eigenvalues are negative: the prestressed state is unstable at this load factor");
+    modes_fill_info(info, c, w, lo);
+    require_converged(lo);
     MFH_CATCH(c)
 }
 
