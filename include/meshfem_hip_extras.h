@@ -140,6 +140,20 @@ mfh_status mfh_debug_harmonic_cocg(mfh_ctx* ctx, const double* zK, const double*
  * density field in force), rows of fixed variables zeroed in both if masked != 0. k_spmv_kron_pair, or, if twoPass != 0 (or where its LDS does not
  * fit), k_spmv_kron_acc on the geometric buffer followed by k_spmv_kron on the mass buffer and the density scaling */
 mfh_status mfh_debug_kron_pair(mfh_ctx* ctx, double s, double rho, int32_t masked, int32_t twoPass, const double* x, double* yA, double* yB);
+/* test hook: the block LOBPCG loop of mfh_modes / mfh_modes_many / mfh_buckling / mfh_modes_prestressed itself (lobpcg_run of mfh_modes.hip) with its
+ * history (tests/test_gpu_lobpcg_iterates.py). pencil: 0 vibration (K, density M), 1 buckling (Kg, K), 2 prestressed (K + loadFactor Kg, density M);
+ * the context's fixed variables, prestress and preconditioner choice as the entry point of that pencil takes them; freeBody != 0: the known-kernel
+ * variant of the vibration pencil. *blockSize = the loop's block size, nev + max(2, (nev + 3) / 4) capped by 24 and by the dimension of the space;
+ * with S0 == NULL nothing else happens. S0: the whole start block, m rows of dim * nDoF doubles, in place of the hashed and smoothed block (masked,
+ * projected and orthonormalised as that one is); m != *blockSize is refused. Q (nq rows, NULL with nq == 0): a deflation set, B-orthonormal and zero
+ * on the fixed variables as the caller gives it; the loop runs in its B-orthogonal complement and its residuals are those of the restricted pencil.
+ * X: the whole block, m rows, as the loop left it, before the returned columns are orthonormalised once more. Per call c = 0 .. maxit of the loop's
+ * convergence check: lambdaHist[c m + j], resHist[c m + j] = the Ritz value and the relative residual of column j; sets[3 c ..] = {columns of W,
+ * columns of P in the basis of the iteration before, restarts so far}; the calls a stop spared hold NaN / -1. *iterations = the loop's count where
+ * it stopped converged, else -1 with status MFH_ERR_NOT_CONVERGED (every output written). *precondUsed as in mfh_modes_info */
+mfh_status mfh_debug_lobpcg(mfh_ctx* ctx, int32_t pencil, double density, double loadFactor, int32_t freeBody, int32_t nev, double rtol, int32_t maxit,
+                            int32_t m, const double* S0, int32_t nq, const double* Q, int32_t* blockSize, double* X, double* lambdaHist, double* resHist,
+                            int32_t* sets, int32_t* iterations, int32_t* precondUsed);
 
 
 /* ---------------------------------------------------------------- device-pointer building blocks

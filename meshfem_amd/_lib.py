@@ -311,6 +311,7 @@ PROTOTYPES = {
     "mfh_debug_pencil_precond": (_i32, [_P, _f64, _f64, _P, _P]),
     "mfh_debug_newmark_pcg": (_i32, [_P, _f64, _f64, _f64, _i32, _P, _P, _P, _P, _P]),
     "mfh_debug_harmonic_cocg": (_i32, [_P, _P, _P, _f64, _f64, _i32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfh_debug_lobpcg": (_i32, [_P, _i32, _f64, _f64, _i32, _i32, _f64, _i32, _i32, _P, _i32, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 # callback types of mfh_comm_create_callbacks

@@ -764,6 +764,37 @@ class Context:
                                                        ptr(x0_im), ptr(xr), ptr(xi), ptr(hist), ptr(chist), ptr(its)))
         return xr + 1j * xi, hist, chist[:, 0::2] + 1j * chist[:, 1::2], int(its[0])
 
+    LOBPCG_PENCILS = {"vibration": 0, "buckling": 1, "prestressed": 2}
+
+    def debug_lobpcg_block_size(self, pencil, nev, free_body=False, nq=0):
+        """the block size m of the LOBPCG loop for nev modes on this context (test hook mfh_debug_lobpcg without a start block)"""
+        m = np.zeros(1, dtype=np.int32)
+        self._ck(self.lib.mfh_debug_lobpcg(self.h, self.LOBPCG_PENCILS[pencil], 1.0, 0.0, 1 if free_body else 0, int(nev), 1.0, 0, 0, None, int(nq), None,
+                                           ptr(m), None, None, None, None, None, None))
+        return int(m[0])
+
+    def debug_lobpcg(self, pencil, S0, nev, density=1.0, load_factor=0.0, free_body=False, rtol=1e-30, maxit=1, Q=None):
+        """The block LOBPCG loop of modes / modes_many / buckling / modes_prestressed itself from the start block S0 [m, n] (test hook
+        mfh_debug_lobpcg; pencil: "vibration" | "buckling" | "prestressed"; Q [nq, n]: a B-orthonormal deflation set). A dict: X [m, n] the whole
+        block as the loop left it; lam, res [maxit + 1, m] and sets [maxit + 1, 3] = {|W|, |P|, restarts} per convergence check (NaN / -1 past a
+        stop); iterations (-1 at maxit); precondUsed; m."""
+        n = self.bs * self.n_dof
+        S0 = np.ascontiguousarray(S0, dtype=np.float64)
+        assert S0.ndim == 2 and S0.shape[1] == n
+        m = S0.shape[0]
+        nq = 0
+        if Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=np.float64)
+            assert Q.ndim == 2 and Q.shape[1] == n
+            nq = Q.shape[0]
+        calls = int(maxit) + 1
+        X, lam, res = np.full((m, n), np.nan), np.full((calls, m), np.nan), np.full((calls, m), np.nan)
+        sets, its, used, bsz = np.full((calls, 3), -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        self._ck_loop(self.lib.mfh_debug_lobpcg(self.h, self.LOBPCG_PENCILS[pencil], float(density), float(load_factor), 1 if free_body else 0, int(nev),
+                                                float(rtol), int(maxit), m, ptr(S0), nq, ptr(Q), ptr(bsz), ptr(X), ptr(lam), ptr(res), ptr(sets), ptr(its),
+                                                ptr(used)))
+        return {"X": X, "lam": lam, "res": res, "sets": sets, "iterations": int(its[0]), "precondUsed": int(used[0]), "m": int(bsz[0])}
+
     def debug_sym_gen_eig(self, A, B):
         """(w, V) of the dense pencil A v = w B v by the Rayleigh-Ritz routine of mfh_modes (test hook mfh_debug_sym_gen_eig)."""
         A, B = as_f64(A), as_f64(B)

@@ -1112,6 +1112,13 @@ mfh_status mfh_time_deflate(mfh_ctx *c, int64_t n, int32_t nq, int32_t k2, int32
 
 namespace {
 
+// What mfh_debug_lobpcg sees of a run: per call of converged() the m Ritz values, the m relative residuals and {|wact|, |pact|, restarts so far} (the
+// sets are those the iteration before used), and the whole block X as the loop left it, before return_columns touches it
+struct LoopTrace {
+    std::vector<double> lam, res;
+    std::vector<int32_t> sets;
+    double *X = nullptr;               // host, m x n
+};
 // What a run of the loop is given, beside the ModesWork its caller prepared
 struct LoopIn {
     int nev;
@@ -1119,10 +1126,12 @@ struct LoopIn {
     double rtol;
     int maxit;
     double *lambda, *X, *residuals;    // the outputs on the host: nev eigenvalues, nev x n modes, nev relative residuals (optional)
-    const double *X0 = nullptr;        // a warm start (host, nev x n): its rows take the place of the first nev columns of the start block as they are, masked
+    const double *X0 = nullptr;        // a warm start (host, nX0 x n): its rows take the place of the first nX0 columns of the start block as they are, masked
+    int nX0 = -1;                      // ... its column count (-1: nev; the test hook mfh_debug_lobpcg gives the whole block, m)
     const DeflationSet *defl = nullptr;
     const double *X0dev = nullptr;     // ... or nX0dev columns from the device (stride ld, already in the space: the guard columns of an earlier batch)
     int nX0dev = 0;
+    LoopTrace *trace = nullptr;        // the history of the run (mfh_debug_lobpcg; null for every entry point: nothing is recorded, nothing launched)
 };
 struct LoopOut {
     int iterations = 0, restarts = 0, locked = 0, blockSize = 0;
@@ -1144,12 +1153,14 @@ struct Lobpcg {
     bool haveP = false;
     int restarts = 0;
 
+    static int block_size(int nev, int64_t nEff) { return (int)std::min<int64_t>(std::min(nev + std::max(2, (nev + 3) / 4), BLK_MAXC), nEff); }
+
     // block size, the ten blocks, the staging buffers
     Lobpcg(ModesWork &w_, const LoopIn &in_) : w(w_), in(in_), nq(in_.defl ? in_.defl->nq : 0) {
         w.nz = in.freeBody ? (w.d == 3 ? 6 : 3) : 0;
         const int64_t nEff = w.n - (int64_t)w.c->fixedVars.size() - w.nz - nq;   // dimension of the space the iteration lives in
         w.need(in.nev <= nEff, MFH_ERR_INVALID, "more modes asked for than the pencil has");
-        m = (int)std::min<int64_t>(std::min(in.nev + std::max(2, (in.nev + 3) / 4), BLK_MAXC), nEff);
+        m = block_size(in.nev, nEff);
         w.m = m;
         const size_t L = (size_t)w.ld;
         w.vec.alloc(L * (size_t)m * 10);
@@ -1175,9 +1186,11 @@ struct Lobpcg {
             w.precond(w.col(w.W, j), w.col(w.X, j));
         }
         if (in.X0) {
-            MFH_HIP(hipMemcpy2DAsync(w.X, (size_t)w.ld * sizeof(double), in.X0, (size_t)w.n * sizeof(double), (size_t)w.n * sizeof(double), (size_t)in.nev, hipMemcpyHostToDevice, s));
+            const int nx0 = in.nX0 < 0 ? in.nev : in.nX0;
+            w.need(nx0 >= 1 && nx0 <= m, MFH_ERR_INVALID, "the warm start has more columns than the block");
+            MFH_HIP(hipMemcpy2DAsync(w.X, (size_t)w.ld * sizeof(double), in.X0, (size_t)w.n * sizeof(double), (size_t)w.n * sizeof(double), (size_t)nx0, hipMemcpyHostToDevice, s));
             if (w.masked)
-                for (int j = 0; j < in.nev; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.X, j), s);
+                for (int j = 0; j < nx0; ++j) k::launch_mask(w.n, c->dFixedMask.p, w.col(w.X, j), s);
             MFH_HIP(hipStreamSynchronize(s));
         }
         if (in.X0dev && in.nX0dev > 0)
@@ -1215,6 +1228,18 @@ struct Lobpcg {
         bool done = true;
         for (int j = 0; j < in.nev; ++j) done = done && conv[(size_t)j];
         return done;
+    }
+
+    // (mfh_debug_lobpcg) what the call of converged() just made, and the sets of the iteration before it
+    void record(LoopTrace &t) const {
+        t.lam.insert(t.lam.end(), lam.begin(), lam.end());
+        t.res.insert(t.res.end(), res.begin(), res.end());
+        t.sets.push_back((int32_t)wact.size()); t.sets.push_back((int32_t)pact.size()); t.sets.push_back((int32_t)restarts);
+    }
+    void record_block(LoopTrace &t) const {
+        if (!t.X) return;
+        MFH_HIP(hipMemcpy2DAsync(t.X, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, w.s));
+        MFH_HIP(hipStreamSynchronize(w.s));
     }
 
     // W = the preconditioned residuals of the active columns, in the complement of Z and of the deflation set, with their images. Soft locking:
@@ -1370,11 +1395,13 @@ void lobpcg_run(ModesWork &w, const LoopIn &in, EventTimer &tsetup, LoopOut &o) 
     int it = 0;
     for (;; ++it) {
         o.done = L.converged();
+        if (in.trace) L.record(*in.trace);
         if (o.done || it >= in.maxit) break;
         L.new_directions();
         L.orthonormalise();
         L.rayleigh_ritz();
     }
+    if (in.trace) L.record_block(*in.trace);
     L.return_columns(tsolve, o);
     if (w.timing)
         fprintf(stderr, "[%s] n %lld m %d iterations %d | ms: K %.3f M %.3f precond %.3f gram %.3f update %.3f residual %.3f rayleigh-ritz(host+sync) %.3f deflation %.3f\n",
@@ -1893,6 +1920,77 @@ mfh_status mfh_modes_prestressed(mfh_ctx *c, int32_t nev, double density, double
     for (int j = 0; j < nev; ++j) nNeg += lambda[j] < 0.0 ? 1 : 0;
     if (nNeg > 0) modes_note(c, std::to_string(nNeg) + " of the " + std::to_string(nev) + " eigenvalues are negative: the prestressed state is unstable at this load factor");
     modes_fill_info(info, c, w, lo);
+    require_converged(lo);
+    MFH_CATCH(c)
+}
+
+// test hook (meshfem_hip_extras.h; tests/test_gpu_lobpcg_iterates.py): lobpcg_run itself on a pencil of the caller's choice, from a whole start
+// block of the caller's, with an optional deflation set, and its history (LoopTrace). The checks are those of the entry point of the pencil.
+mfh_status mfh_debug_lobpcg(mfh_ctx *c, int32_t pencil, double density, double loadFactor, int32_t freeBody, int32_t nev, double rtol, int32_t maxit, int32_t m,
+                            const double *S0, int32_t nq, const double *Q, int32_t *blockSize, double *X, double *lambdaHist, double *resHist, int32_t *sets,
+                            int32_t *iterations, int32_t *precondUsed) {
+    MFH_TRY(c)
+    require(c && pencil >= 0 && pencil <= 2 && nev >= 1 && nev <= 20 && density > 0.0 && std::isfinite(density) && std::isfinite(loadFactor) && rtol > 0.0 && maxit >= 0 &&
+                nq >= 0 && nq <= k::DEFL_MAXQ && blockSize,
+            MFH_ERR_INVALID, "mfh_debug_lobpcg: arguments");
+    require(c->haveMesh && !c->external, MFH_ERR_STATE, "mfh_debug_lobpcg: no mesh set");
+    const Pencil kind = pencil == 0 ? Pencil::Vibration : (pencil == 1 ? Pencil::Buckling : Pencil::Prestressed);
+    const bool fb = freeBody != 0;
+    require(kind == Pencil::Vibration || !fb, MFH_ERR_UNSUPPORTED, "mfh_debug_lobpcg: the free body is a case of the vibration pencil");
+    if (kind == Pencil::Vibration) {
+        require_device(c);
+        MFH_HIP(hipSetDevice(c->device));
+        modes_require_context(c, fb, "mfh_debug_lobpcg");
+    } else {
+        require_geometric_context(c, "mfh_debug_lobpcg");
+        MFH_HIP(hipSetDevice(c->device));
+        require(free_rigid_motions(c) == 0, MFH_ERR_UNSUPPORTED, "mfh_debug_lobpcg: the fixed variables leave rigid motions free");
+    }
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    const int64_t nEff = n - (int64_t)c->fixedVars.size() - (fb ? (c->bs() == 3 ? 6 : 3) : 0) - nq;
+    require(nev <= nEff, MFH_ERR_INVALID, "mfh_debug_lobpcg: more modes asked for than the pencil has");
+    *blockSize = Lobpcg::block_size(nev, nEff);
+    if (!S0) return MFH_OK;                        // (the question alone: how many rows does S0 take)
+    require(m == *blockSize, MFH_ERR_INVALID, "mfh_debug_lobpcg: S0 takes as many rows as the loop's block has columns (*blockSize)");
+    require(X && lambdaHist && resHist && sets && iterations && precondUsed && (nq == 0 || Q), MFH_ERR_INVALID, "mfh_debug_lobpcg: null output, or nq > 0 without Q");
+    for (int64_t q = 0; q < (int64_t)m * n; ++q) require(std::isfinite(S0[q]), MFH_ERR_INVALID, "mfh_debug_lobpcg: an entry of S0 is not finite");
+    for (int64_t q = 0; q < (int64_t)nq * n; ++q) require(std::isfinite(Q[q]), MFH_ERR_INVALID, "mfh_debug_lobpcg: an entry of Q is not finite");
+    ModesGuard guard(c);
+    EventTimer tsetup(c->stream);
+    ModesWork w;
+    const bool vib = kind == Pencil::Vibration;
+    modes_prepare(c, ModesSetup{"mfh_debug_lobpcg", kind, fb, vib || kind == Pencil::Prestressed ? density : 1.0, kind == Pencil::Prestressed ? loadFactor : 0.0,
+                                kind != Pencil::Buckling, !vib}, w);
+    *precondUsed = modes_precond_used(c, w);
+    // the deflation set as the caller gives it (B-orthonormal), with its B-image
+    DBuf<double> setQ, setBQ;
+    DeflationSet ds;
+    if (nq > 0) {
+        const size_t L = (size_t)w.ld;
+        setQ.alloc(L * (size_t)nq); setBQ.alloc(L * (size_t)nq);
+        setQ.zero(w.s); setBQ.zero(w.s);
+        deflate_alloc(w);
+        MFH_HIP(hipMemcpy2DAsync(setQ.p, L * sizeof(double), Q, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nq, hipMemcpyHostToDevice, w.s));
+        MFH_HIP(hipStreamSynchronize(w.s));
+        for (int j = 0; j < nq; ++j) w.apply_B(w.col(setQ.p, j), w.col(setBQ.p, j));
+        ds = DeflationSet{setQ.p, setBQ.p, nq, nq};
+    }
+    std::vector<double> lam((size_t)nev), Xret((size_t)nev * (size_t)n), res((size_t)nev);
+    LoopTrace trace;
+    trace.X = X;
+    LoopIn in{nev, fb, rtol, maxit, lam.data(), Xret.data(), res.data()};
+    in.X0 = S0; in.nX0 = m;
+    if (nq > 0) in.defl = &ds;
+    in.trace = &trace;
+    LoopOut lo;
+    lobpcg_run(w, in, tsetup, lo);
+    const size_t calls = trace.sets.size() / 3;
+    std::copy(trace.lam.begin(), trace.lam.end(), lambdaHist);
+    std::copy(trace.res.begin(), trace.res.end(), resHist);
+    std::copy(trace.sets.begin(), trace.sets.end(), sets);
+    for (size_t q = calls * (size_t)m; q < (size_t)(maxit + 1) * (size_t)m; ++q) lambdaHist[q] = resHist[q] = NAN;   // (the calls a stop spared)
+    for (size_t q = calls * 3; q < (size_t)(maxit + 1) * 3; ++q) sets[q] = -1;
+    *iterations = lo.done ? lo.iterations : -1;
     require_converged(lo);
     MFH_CATCH(c)
 }
