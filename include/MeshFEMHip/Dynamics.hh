@@ -16,6 +16,21 @@
 
 namespace MeshFEMHip {
 
+namespace detail {
+// the Dirichlet variables of the boundary conditions applied to the Simulator become the clamp (transient and explicitTransient)
+inline void clampDirichlet(mfh_ctx *c) {
+    check(c, mfh_clear_fixed(c));
+    int64_t nv = 0;
+    check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
+    if (nv > 0) {
+        std::vector<int64_t> vars((size_t)nv);
+        std::vector<Real> vals((size_t)nv);
+        check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
+        check(c, mfh_fix_variables(c, nv, vars.data(), nullptr));
+    }
+}
+} // namespace detail
+
 template <class VField>
 struct TransientOptions {
     Real density = 1.0, rayleighMass = 0.0, rayleighStiff = 0.0;
@@ -46,15 +61,7 @@ TransientResult<typename Sim::VField> transient(const Sim &sim, Real dt, int nSt
     using VField = typename Sim::VField;
     constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
     mfh_ctx *c = sim.ctx();
-    check(c, mfh_clear_fixed(c));
-    int64_t nv = 0;
-    check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
-    if (nv > 0) {
-        std::vector<int64_t> vars((size_t)nv);
-        std::vector<Real> vals((size_t)nv);
-        check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
-        check(c, mfh_fix_variables(c, nv, vars.data(), nullptr));
-    }
+    detail::clampDirichlet(c);
     if (!opt.elementDensity.empty()) check(c, mfh_set_density(c, opt.elementDensity.data(), (int64_t)opt.elementDensity.size(), 0));
     const size_t nDoF = sim.numDoFs(), n = nDoF * N, rows = (size_t)(nSteps > 0 ? nSteps : 0) + 1;
     auto state = [&](const VField &x, const char *name) {
@@ -95,6 +102,104 @@ TransientResult<typename Sim::VField> transient(const Sim &sim, Real dt, int nSt
     for (size_t k = 0; k < nSnap; ++k) std::copy(snaps.begin() + k * n, snaps.begin() + (k + 1) * n, &r.snapshots[k][0][0]);
     r.energies.resize(opt.energies ? rows : 0);
     for (size_t k = 0; k < r.energies.size(); ++k) r.energies[k] = {en[3 * k], en[3 * k + 1], en[3 * k + 2]};
+    return r;
+}
+
+// ---- explicit dynamics (include/meshfem_hip.h, "explicit dynamics"): central differences with the HRZ-lumped mass matrix -- one product with K per
+// step, no solve; for wave propagation, impact and short pulses.
+//   stableTimeStep(sim, density, iters)      the stability limit bracketed: dtSafe (stable for certain) and dtEst (an upper bound of the limit, close to
+//                                            it) with lambdaUpper >= lambda_max >= lambdaEst of (K, density M_L) on the free variables
+//   explicitTransient(sim, nSteps, dt, opt)  M_L u'' + opt.rayleighMass M_L u' + K u = g(t) f; dt <= 0: opt.safety x dtEst. Clamp, load, amplitude, start
+//                                            state, probes and snapshots as for transient; energies {kinetic, strain, g f.u, leapfrog invariant} at
+//                                            every opt.energyStride-th step. Throws where the C call fails: a step above the stability estimate (unless
+//                                            opt.checkDt is false) and a run that blows up included.
+template <class VField>
+struct ExplicitOptions {
+    Real density = 1.0, rayleighMass = 0.0;
+    std::vector<Real> elementDensity;                     // one value per element: becomes the context's density field; empty: the field in force
+    Real safety = 0.9;                                    // dt <= 0: the step is safety x dtEst
+    bool checkDt = true;                                  // false: MFH_EXP_NO_DT_CHECK
+    std::vector<Real> amplitude;                          // nSteps + 1 values, or empty (= 1)
+    VField u0, v0, a0;                                    // one N-vector per DoF, or empty
+    VField load;                                          // f, one N-vector per DoF; empty: neumannLoad()
+    std::vector<std::pair<size_t, int>> probes;           // (DoF, component) pairs recorded at every step
+    int snapshotStride = 0;                               // > 0: the displacement at the steps 0, stride, 2 stride, ...
+    bool energies = false;
+    int energyStride = 1;
+};
+
+template <class VField>
+struct ExplicitResult {
+    VField u, v, a;                                       // the state after the last step
+    Real dt = 0.0;                                        // the step taken
+    std::vector<std::vector<Real>> probes;                // [nSteps + 1][number of probes]
+    std::vector<VField> snapshots;
+    std::vector<std::array<Real, 4>> energies;            // [nSteps / energyStride + 1]: kinetic, strain, g f.u, the leapfrog invariant
+    mfh_explicit_info info{};
+};
+
+template <class Sim>
+mfh_explicit_dt_info stableTimeStep(const Sim &sim, Real density = 1.0, int iters = 0) {
+    mfh_ctx *c = sim.ctx();
+    detail::clampDirichlet(c);
+    mfh_explicit_dt_info info{};
+    check(c, mfh_explicit_dt(c, density, iters, nullptr, &info));
+    return info;
+}
+
+template <class Sim>
+ExplicitResult<typename Sim::VField> explicitTransient(const Sim &sim, int nSteps, Real dt = 0.0,
+                                                       const ExplicitOptions<typename Sim::VField> &opt = ExplicitOptions<typename Sim::VField>()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    mfh_ctx *c = sim.ctx();
+    detail::clampDirichlet(c);
+    if (!opt.elementDensity.empty()) check(c, mfh_set_density(c, opt.elementDensity.data(), (int64_t)opt.elementDensity.size(), 0));
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N, rows = (size_t)(nSteps > 0 ? nSteps : 0) + 1;
+    auto state = [&](const VField &x, const char *name) {
+        VField y(nDoF);
+        if (!x.empty()) {
+            if (x.size() != nDoF) throw std::runtime_error(std::string("explicitTransient: ") + name + " needs one entry per DoF");
+            y = x;
+        } else
+            for (auto &e : y) e.fill(0.0);
+        return y;
+    };
+    ExplicitResult<VField> r;
+    r.u = state(opt.u0, "u0"); r.v = state(opt.v0, "v0"); r.a = state(opt.a0, "a0");
+    if (!opt.amplitude.empty() && opt.amplitude.size() != rows) throw std::runtime_error("explicitTransient: amplitude needs nSteps + 1 values");
+    if (!opt.load.empty() && opt.load.size() != nDoF) throw std::runtime_error("explicitTransient: load needs one entry per DoF");
+    if (dt <= 0.0) {
+        mfh_explicit_dt_info di{};
+        check(c, mfh_explicit_dt(c, opt.density, 0, nullptr, &di));
+        dt = opt.safety * di.dtEst;
+    }
+    r.dt = dt;
+    const VField f = opt.load.empty() ? sim.neumannLoad() : opt.load;
+    bool loaded = false;
+    for (const auto &e : f)
+        for (size_t a = 0; a < N; ++a) loaded = loaded || e[a] != 0.0;
+    std::vector<int64_t> probeVars;
+    for (const auto &p : opt.probes) probeVars.push_back((int64_t)(p.first * N) + p.second);
+    std::vector<Real> probeOut(rows * probeVars.size()), snaps, en;
+    const size_t nSnap = opt.snapshotStride > 0 ? (rows - 1) / (size_t)opt.snapshotStride + 1 : 0;
+    const size_t eStride = (size_t)(opt.energyStride > 0 ? opt.energyStride : 1), nEn = opt.energies ? (rows - 1) / eStride + 1 : 0;
+    snaps.resize(nSnap * n);
+    en.resize(nEn * 4);
+    mfh_explicit_params prm{};
+    prm.dt = dt; prm.density = opt.density; prm.rayleighMass = opt.rayleighMass;
+    prm.nSteps = nSteps; prm.snapshotStride = nSnap ? opt.snapshotStride : 0; prm.energyStride = (int32_t)eStride;
+    prm.flags = (opt.a0.empty() ? 0 : MFH_EXP_HAVE_ACCEL) | (opt.energies ? MFH_EXP_ENERGIES : 0) | (opt.checkDt ? 0 : MFH_EXP_NO_DT_CHECK);
+    check(c, mfh_explicit(c, &prm, &r.u[0][0], &r.v[0][0], &r.a[0][0], loaded ? &f[0][0] : nullptr, opt.amplitude.empty() ? nullptr : opt.amplitude.data(),
+                          probeVars.empty() ? nullptr : probeVars.data(), (int32_t)probeVars.size(), probeVars.empty() ? nullptr : probeOut.data(),
+                          nSnap ? snaps.data() : nullptr, opt.energies ? en.data() : nullptr, &r.info));
+    r.probes.assign(rows, std::vector<Real>(probeVars.size()));
+    for (size_t k = 0; k < rows; ++k)
+        for (size_t j = 0; j < probeVars.size(); ++j) r.probes[k][j] = probeOut[k * probeVars.size() + j];
+    r.snapshots.assign(nSnap, VField(nDoF));
+    for (size_t k = 0; k < nSnap; ++k) std::copy(snaps.begin() + k * n, snaps.begin() + (k + 1) * n, &r.snapshots[k][0][0]);
+    r.energies.resize(nEn);
+    for (size_t k = 0; k < nEn; ++k) r.energies[k] = {en[4 * k], en[4 * k + 1], en[4 * k + 2], en[4 * k + 3]};
     return r;
 }
 

@@ -5,6 +5,7 @@
 //   massProperties(sim, scale)    {mass, com, secondMoment S = int rho (x - com)(x - com)^T, inertia = tr(S) I - S about the centre of mass (the tensor
 //                                 of a 3D body), polar = tr(S) (the polar moment of a 2D body)} under the field times the scalar scale
 //   applyMass(sim, x)             M x for one N-vector per DoF: the consistent mass matrix with the density field, no variables masked
+//   lumpedMassHRZ(sim)            the HRZ-lumped masses (diagonal of the element mass matrices scaled to the element's mass), one N-vector per DoF
 // Each throws std::runtime_error where the C call fails.
 #pragma once
 
@@ -51,6 +52,16 @@ typename Sim::VField applyMass(const Sim &sim, const typename Sim::VField &x) {
     typename Sim::VField y(x.size());
     check(c, mfh_mass_apply(c, &x[0][0], &y[0][0], 0));
     return y;
+}
+
+// The HRZ-lumped masses, one N-vector per DoF (the mass of a DoF repeated for its components): positive on linear and quadratic elements alike,
+// the density field inside; the mass matrix of explicitTransient (Dynamics.hh).
+template <class Sim>
+typename Sim::VField lumpedMassHRZ(const Sim &sim) {
+    mfh_ctx *c = sim.ctx();
+    typename Sim::VField m(sim.numDoFs());
+    check(c, mfh_mass_lumped_hrz(c, &m[0][0], 0));
+    return m;
 }
 
 } // namespace MeshFEMHip

@@ -605,6 +605,70 @@ mfh_status mfh_newmark(mfh_ctx* ctx, const mfh_newmark_params* params,
                        double* energies,                         /* (nSteps+1) x 3: kinetic, strain, g_n f.u_n; needs MFH_DYN_ENERGIES */
                        mfh_newmark_info* info);
 
+/* ---------------------------------------------------------------- explicit dynamics
+ * Central differences on the device (docs/design/04_20_explicit_dynamics.md) for wave propagation, impact and short pulses, where accuracy and not
+ * stability sets the time step: M_L u'' + aR M_L u' + K u = g(t) f with M_L = density x the HRZ-lumped mass matrix. One step costs one product with K
+ * and one pass over the vectors; no system is solved. Contexts as for mfh_newmark (elasticity, the mesh's own degree, unpartitioned), but the
+ * pattern keeps its storage: only the K product of the context is used.
+ *
+ *   mfh_mass_lumped_hrz  HRZ (Hinton-Rock-Zienkiewicz) lumping: m_d = sum over the (element e, local node i) pairs of DoF d of rho_e vol_e w_i with
+ *                        w_i = Mref_ii / trace(Mref) of the element type's consistent mass matrix -- the diagonal of an SPD matrix, so every mass is
+ *                        positive on every element type (the row sums of mfh_mass_lumped are zero or negative at the vertices of quadratic elements)
+ *                        and the total mass is exact. rho: the context's density field (mfh_set_density), 1 without one. diagOut: dim*nDoF values,
+ *                        the value of a DoF repeated for its components; fixed variables are not masked. flags: 0, or MFH_LOAD_ON_DEVICE (diagOut is a
+ *                        device pointer; the call returns after the context's stream is synchronised). The pairs of a DoF are added in a fixed
+ *                        order: the same call returns the same bits. Contexts and refusals as for mfh_mass_apply.
+ *   mfh_explicit_dt      the stability limit dt_crit = 2 / sqrt(lambda_max) of the pencil (K, density M_L) on the free variables, bracketed:
+ *                        lambdaUpper >= lambda_max, guaranteed: max over the free variables d of (sum over the pairs (e, i) of d of the absolute
+ *                                    row sum of row (i, c) of K_e) / m_d -- Gershgorin on M_L^-1 K, weakened by the triangle inequality;
+ *                        lambdaEst  <= lambda_max: the last Rayleigh quotient of `iters` (0: 60) steps x <- M_L^-1 K x of a power iteration, normalised
+ *                                    in M_L, from x0 (dim*nDoF, host; its fixed entries are ignored) or, with x0 NULL, from
+ *                                    x0[i] = (((i + 1) * 2654435761 mod 2^32) >> 8) / 2^24 - 1/2.
+ *                        dtSafe = 2 / sqrt(lambdaUpper) is stable for certain, dtEst = 2 / sqrt(lambdaEst) is an upper bound of dt_crit that is
+ *                        close to it after enough steps. MFH_ERR_INVALID: density <= 0, iters < 0, a start vector with no positive quotient.
+ *   mfh_explicit         the velocity-Verlet form, state (u, v, a) at integer steps so that calls chain like mfh_newmark's:
+ *                            v(n+1/2) = v(n) + dt/2 a(n),   u(n+1) = u(n) + dt v(n+1/2),
+ *                            a(n+1) = (M_L^-1 (g(n+1) f - K u(n+1)) - aR v(n+1/2)) / (1 + aR dt/2),   v(n+1) = v(n+1/2) + dt/2 a(n+1),
+ *                        a(0) = M_L^-1 (g(0) f - K u(0)) - aR v(0) unless MFH_EXP_HAVE_ACCEL passes it. The fixed variables of the context are held at
+ *                        zero (a zero in the inverse-mass vector); their set may be empty. u, v, a, f, amplitude, probeVars / probeOut and snapshots
+ *                        as for mfh_newmark. energies: with MFH_EXP_ENERGIES, at the steps 0, energyStride (0: 1), 2 energyStride, ... the row
+ *                        {1/2 v.M_L v, 1/2 u.K u, g f.u, 1/2 v(n+1/2).M_L v(n+1/2) + 1/2 u(n+1).K u(n)}: the last is the invariant the scheme
+ *                        conserves exactly without load and damping (the last row's is formed with the half step that would follow).
+ *                        Step-size policy: without MFH_EXP_NO_DT_CHECK the call runs the power iteration of mfh_explicit_dt (60 steps, default start
+ *                        vector) and refuses dt > dtEst with MFH_ERR_INVALID -- such a step is unstable for certain; info carries lambdaEst, dtEst. An
+ *                        iteration without a positive quotient (no free variable) is refused as by mfh_explicit_dt.
+ *                        Either way the step kernel raises a device flag on a value that is not finite; the host reads it every 256 steps and then
+ *                        returns MFH_ERR_NOT_CONVERGED with info->stepsDone = the last clean read, the probe and energy rows up to it, and u, v, a
+ *                        left as they were passed. MFH_ERR_INVALID before any device work: dt <= 0, density <= 0, rayleighMass < 0, a negative stride
+ *                        or step count, an unknown flag, a probe variable out of range, energies without its flag or the flag without the array.
+ * No floating-point atomics in any of the three: the same call on the same context returns the same bits where the context's K product does. */
+enum { MFH_EXP_HAVE_ACCEL = 1, MFH_EXP_ENERGIES = 2, MFH_EXP_NO_DT_CHECK = 4 };
+typedef struct mfh_explicit_dt_info {
+    double lambdaUpper, lambdaEst, dtSafe, dtEst;
+    int32_t iterations, reserved;
+    double ms;
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_explicit_dt_info;
+typedef struct mfh_explicit_params {
+    double dt, density, rayleighMass;
+    int32_t nSteps, snapshotStride, energyStride, flags;
+} mfh_explicit_params;
+typedef struct mfh_explicit_info {
+    int32_t stepsDone, reserved;
+    double lambdaEst, dtEst, solve_ms, setup_ms;                                       /* lambdaEst, dtEst: 0 under MFH_EXP_NO_DT_CHECK */
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_explicit_info;
+mfh_status mfh_mass_lumped_hrz(mfh_ctx* ctx, double* diagOut /* dim*nDoF */, int32_t flags /* 0 | MFH_LOAD_ON_DEVICE */);
+mfh_status mfh_explicit_dt(mfh_ctx* ctx, double density, int32_t iters /* 0 = 60 */, const double* x0 /* dim*nDoF or NULL */, mfh_explicit_dt_info* info);
+mfh_status mfh_explicit(mfh_ctx* ctx, const mfh_explicit_params* params,
+                        double* u, double* v, double* a,          /* dim*nDoF each; state in, state after the last step out */
+                        const double* f,                          /* dim*nDoF or NULL */
+                        const double* amplitude,                  /* nSteps+1 or NULL (= 1) */
+                        const int64_t* probeVars, int32_t nProbe, double* probeOut,  /* (nSteps+1) x nProbe */
+                        double* snapshots,                        /* (nSteps/snapshotStride + 1) x dim*nDoF or NULL */
+                        double* energies,                         /* (nSteps/energyStride + 1) x 4; needs MFH_EXP_ENERGIES */
+                        mfh_explicit_info* info);
+
 /* ---------------------------------------------------------------- frequency response
  * The steady state of M u'' + C u' + K u = Re(f^ e^{i w t}) on the device (docs/design/04_17_harmonic.md): for every frequency w of a list
  *     (K + i w C - w^2 M) u^(w) = f^,    C = rayleighMass M + rayleighStiff K,   plus the structural term i lossFactor K,

@@ -26,6 +26,10 @@ mfh_status mfh_time_geometric_assembly(mfh_ctx* ctx, int32_t reps, double* lapla
  * pass k_spmv_kron_pair, and the two launches (plus the density scaling) it replaces, in alternating groups after a warm-up of both
  * (scripts/probe_prestressed_modes.py). Needs a prestress field; holds both triangles of the pattern for its own duration. */
 mfh_status mfh_time_kron_pair(mfh_ctx* ctx, int32_t reps, double* pair_ms, double* separate_ms);
+/* average device time (ms) of `reps` launches of k_explicit_step (mfh_explicit's step kernel: five vectors read, two written) on hashed vectors of n
+ * doubles, and of `reps` device-to-device copies that move the same bytes (3.5 n doubles read and written) in the same process: the kernel's floor
+ * -- scripts/probe_explicit.py */
+mfh_status mfh_time_explicit_step(mfh_ctx* ctx, int64_t n, int32_t reps, double* step_ms, double* copy_ms);
 /* the same for one application of the operator the PCG uses (see "matrix_free") on internal scratch vectors */
 mfh_status mfh_time_spmv_kernel(mfh_ctx* ctx, int32_t reps, double* avg_ms);
 /* average device time (ms) of `reps` back-to-back k_block_gram calls (both stages) on hashed n x p and n x q blocks, and of `reps` device-to-device
@@ -108,6 +112,19 @@ mfh_status mfh_debug_newmark_rhs(mfh_ctx* ctx, int64_t n, double g, const double
 /* correct: a = (x - ut) / (beta dt^2), v = vt + gamma dt a, u = x; probeOut[j] = x[probeVars[j]]; snapshot (n doubles or NULL) = x */
 mfh_status mfh_debug_newmark_correct(mfh_ctx* ctx, int64_t n, double dt, double beta, double gamma, const double* x, const double* ut, const double* vt,
                                      double* u, double* v, double* a, const int64_t* probeVars, int32_t nProbe, double* probeOut, double* snapshot);
+/* test hooks of mfh_explicit (mfh_explicit.hip). explicit_step: k_explicit_step on host arrays of n doubles, under the context's dyn_grid_cap.
+ *   mode 0: v holds v(n-1/2); a(n) = (inv (g f - y) - alpha v) / (1 + alpha dt/2), v(n) = v + dt/2 a(n)
+ *   mode 1: v holds v(n), a(n) = inv (g f - y) - alpha v;   mode 2: v holds v(n), a(n) is read from a
+ *   then v(n+1/2) = v(n) + dt/2 a(n), u(n+1) = u + dt v(n+1/2). last == 0: u = u(n+1), v = v(n+1/2), a untouched; last != 0: u stays, v = v(n), a = a(n).
+ *   probeOut[j] = u(n)[probeVars[j]]; snapshot (n doubles or NULL) = u(n); energies (4 doubles or NULL; needs mass) = {1/2 v(n).mass v(n), 1/2 u(n).y,
+ *   g f.u(n), 1/2 v(n+1/2).mass v(n+1/2) + 1/2 u(n+1).y}; *flag = 1 if a value written is not finite. f may be NULL.
+ * elem_abs_rowsums: out[(e npe + i) dim + c] = sum_j sum_d |K_e[(i, c), (j, d)]| (k_elem_abs_rowsums), nElem * npe * dim doubles */
+mfh_status mfh_debug_explicit_step(mfh_ctx* ctx, int64_t n, double dt, double alpha, double g, int32_t mode, int32_t last, const double* y, double* u, double* v,
+                                   const double* inv, const double* mass, const double* f, double* a, const int64_t* probeVars, int32_t nProbe,
+                                   double* probeOut, double* snapshot, double* energies, int32_t* flag);
+mfh_status mfh_debug_elem_abs_rowsums(mfh_ctx* ctx, double* out);
+/* hrz_weights: the npe weights Mref_ii / trace(Mref) of the context's element type as mfh_mass_lumped_hrz takes them from the mass table */
+mfh_status mfh_debug_hrz_weights(mfh_ctx* ctx, double* w);
 /* y = cK K x + cM M x (M with density 1) through the context's operator and k_spmv_kron_acc, rows of fixed variables zeroed if masked != 0;
  * *dot (may be NULL) = x . y from the kernel's partials. cK == 0 skips the K product */
 mfh_status mfh_debug_pencil_apply(mfh_ctx* ctx, double cK, double cM, int32_t masked, const double* x, double* y, double* dot);

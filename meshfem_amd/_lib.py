@@ -21,6 +21,7 @@ LOAD_ADD, LOAD_ON_DEVICE = 1, 2
 FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE = 0, 1, 2
 MODES_FREE = 1
 DYN_HAVE_ACCEL, DYN_ENERGIES = 1, 2
+EXP_HAVE_ACCEL, EXP_ENERGIES, EXP_NO_DT_CHECK = 1, 2, 4
 HARM_WARM_START = 1
 
 
@@ -90,6 +91,31 @@ class NewmarkInfo(C.Structure):
     _fields_ = [("stepsDone", C.c_int32), ("iterationsTotal", C.c_int32), ("iterationsMax", C.c_int32), ("iterationsInit", C.c_int32),
                 ("precondUsed", C.c_int32), ("cK", C.c_double), ("cM", C.c_double), ("solve_ms", C.c_double), ("setup_ms", C.c_double),
                 ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
+class ExplicitDtInfo(C.Structure):
+    _fields_ = [("lambdaUpper", C.c_double), ("lambdaEst", C.c_double), ("dtSafe", C.c_double), ("dtEst", C.c_double), ("iterations", C.c_int32),
+                ("reserved", C.c_int32), ("ms", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
+class ExplicitParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("density", C.c_double), ("rayleighMass", C.c_double), ("nSteps", C.c_int32), ("snapshotStride", C.c_int32),
+                ("energyStride", C.c_int32), ("flags", C.c_int32)]
+
+
+class ExplicitInfo(C.Structure):
+    _fields_ = [("stepsDone", C.c_int32), ("reserved", C.c_int32), ("lambdaEst", C.c_double), ("dtEst", C.c_double), ("solve_ms", C.c_double),
+                ("setup_ms", C.c_double), ("note", C.c_char_p)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -238,6 +264,9 @@ PROTOTYPES = {
     "mfh_modes_prestressed": (_i32, [_P, _i32, _f64, _f64, _i32, _f64, _i32, _P, _P, _P, _P, C.POINTER(ModesInfo)]),
     "mfh_tangent_apply": (_i32, [_P, _f64, _P, _P, _i32]),
     "mfh_newmark": (_i32, [_P, C.POINTER(NewmarkParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(NewmarkInfo)]),
+    "mfh_mass_lumped_hrz": (_i32, [_P, _P, _i32]),
+    "mfh_explicit_dt": (_i32, [_P, _f64, _i32, _P, C.POINTER(ExplicitDtInfo)]),
+    "mfh_explicit": (_i32, [_P, C.POINTER(ExplicitParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(ExplicitInfo)]),
     "mfh_harmonic": (_i32, [_P, C.POINTER(HarmonicParams), _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(HarmonicInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
@@ -305,6 +334,10 @@ PROTOTYPES = {
     "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),
+    "mfh_debug_explicit_step": (_i32, [_P, _i64, _f64, _f64, _f64, _i32, _i32, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P]),
+    "mfh_debug_elem_abs_rowsums": (_i32, [_P, _P]),
+    "mfh_debug_hrz_weights": (_i32, [_P, _P]),
+    "mfh_time_explicit_step": (_i32, [_P, _i64, _i32, C.POINTER(_f64), C.POINTER(_f64)]),
     "mfh_debug_pencil_apply": (_i32, [_P, _f64, _f64, _i32, _P, _P, _P]),
     "mfh_debug_kron_pair": (_i32, [_P, _f64, _f64, _i32, _i32, _P, _P, _P]),
     "mfh_debug_harmonic_apply": (_i32, [_P, _f64, _f64, _f64, _f64, _i32, _P, _P, _P, _P, _P]),

@@ -492,6 +492,103 @@ class Context:
         self._ck(st)
         return out
 
+    # ---------------------------------------------------------------- explicit dynamics (docs/design/04_20_explicit_dynamics.md)
+    def mass_lumped_hrz(self):
+        """The HRZ-lumped masses, dim * n_dof values (mfh_mass_lumped_hrz): per DoF the sum over its (element, local node) pairs of
+        rho_e vol_e Mref_ii / trace(Mref), repeated for the components; positive on every element type, the context's density field inside."""
+        out = np.empty(self.dim * self.n_dof)
+        self._ck(self.lib.mfh_mass_lumped_hrz(self.h, ptr(out), 0))
+        return out
+
+    def explicit_dt(self, density=1.0, iters=0, x0=None):
+        """The stability limit of central differences on (K, density x the HRZ-lumped mass) bracketed (mfh_explicit_dt): a dict with
+        lambdaUpper >= lambda_max (Gershgorin, guaranteed), lambdaEst <= lambda_max (power iteration of `iters` steps, 0: 60, from x0 or the
+        documented default start vector), dtSafe = 2 / sqrt(lambdaUpper), dtEst = 2 / sqrt(lambdaEst), iterations, ms, note."""
+        n = self.bs * self.n_dof
+        if x0 is not None:
+            x0 = as_f64(np.asarray(x0, dtype=np.float64).reshape(-1))
+            if x0.size != n:
+                raise ValueError("explicit_dt: x0 needs dim * n_dof = %d entries, got %d" % (n, x0.size))
+        info = L.ExplicitDtInfo()
+        self._ck(self.lib.mfh_explicit_dt(self.h, float(density), int(iters), ptr(x0), C.byref(info)))
+        return info.as_dict()
+
+    def explicit(self, dt, n_steps, u0=None, v0=None, a0=None, f=None, amplitude=None, density=1.0, damping=0.0, probes=None, snapshot_stride=0,
+                 energies=False, energy_stride=1, check_dt=True):
+        """Central differences (velocity-Verlet form) on M_L u'' + damping M_L u' + K u = g(t) f on the device (mfh_explicit): M_L = density x
+        the HRZ-lumped mass, the context's fixed variables held at zero. u0 / v0 / a0, f, amplitude, probes and snapshot_stride as in newmark().
+        Returns a dict: "u", "v", "a" (the state after the last step), "probes", "snapshots", "energies" [n_steps // energy_stride + 1, 4] =
+        kinetic, strain, g f.u, the leapfrog invariant (energies=True) and "info". check_dt=False runs a step above the stability estimate all
+        the same; a run that blows up raises (MFH_ERR_NOT_CONVERGED), what was reached is then in self.last_explicit."""
+        n = self.bs * self.n_dof
+        n_steps = int(n_steps)
+        rows = max(n_steps, 0) + 1
+
+        def state(x):
+            x = np.zeros(n) if x is None else np.array(x, dtype=np.float64).reshape(-1)
+            if x.size != n:
+                raise ValueError("explicit: a state vector needs dim * n_dof = %d entries, got %d" % (n, x.size))
+            return np.ascontiguousarray(x)
+        u, v, a = state(u0), state(v0), state(a0)
+        f = None if f is None else as_f64(np.asarray(f, dtype=np.float64).reshape(-1))
+        if f is not None and f.size != n:
+            raise ValueError("explicit: f needs dim * n_dof = %d entries, got %d" % (n, f.size))
+        amp = None if amplitude is None else as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
+        if amp is not None and amp.size != rows:
+            raise ValueError("explicit: amplitude needs n_steps + 1 = %d entries, got %d" % (rows, amp.size))
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros((rows, n_probe)) if n_probe else None
+        stride, estride = int(snapshot_stride), int(energy_stride)
+        snaps = np.zeros((max(n_steps, 0) // stride + 1, n)) if stride > 0 else None
+        en = np.zeros((max(n_steps, 0) // max(estride, 1) + 1, 4)) if energies else None
+        prm = L.ExplicitParams(float(dt), float(density), float(damping), n_steps, stride, estride,
+                               (L.EXP_HAVE_ACCEL if a0 is not None else 0) | (L.EXP_ENERGIES if energies else 0) | (0 if check_dt else L.EXP_NO_DT_CHECK))
+        info = L.ExplicitInfo()
+        st = self.lib.mfh_explicit(self.h, C.byref(prm), ptr(u), ptr(v), ptr(a), ptr(f), ptr(amp), ptr(pv), n_probe, ptr(pout), ptr(snaps), ptr(en),
+                                   C.byref(info))
+        out = {"u": u, "v": v, "a": a, "probes": pout, "snapshots": snaps, "energies": en, "info": info.as_dict()}
+        self.last_explicit = out
+        self._ck(st)
+        return out
+
+    def debug_explicit_step(self, dt, alpha, g, mode, last, y, u, v, inv, mass=None, f=None, a=None, probes=None, snapshot=True, energies=True):
+        """k_explicit_step on host arrays (test hook mfh_debug_explicit_step): a dict of u, v, a after the kernel, probes, snapshot, energies[4]
+        and flag."""
+        y, inv = as_f64(y), as_f64(inv)
+        n = y.size
+        u, v = np.array(u, dtype=np.float64), np.array(v, dtype=np.float64)
+        a = np.zeros(n) if a is None else np.array(a, dtype=np.float64)
+        mass = None if mass is None else as_f64(mass)
+        f = None if f is None else as_f64(f)
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros(n_probe) if n_probe else None
+        snap = np.zeros(n) if snapshot else None
+        en = np.zeros(4) if energies else None
+        flag = np.zeros(1, dtype=np.int32)
+        self._ck(self.lib.mfh_debug_explicit_step(self.h, n, float(dt), float(alpha), float(g), int(mode), int(last), ptr(y), ptr(u), ptr(v), ptr(inv),
+                                                  ptr(mass), ptr(f), ptr(a), ptr(pv), n_probe, ptr(pout), ptr(snap), ptr(en), ptr(flag)))
+        return {"u": u, "v": v, "a": a, "probes": pout, "snapshot": snap, "energies": en, "flag": int(flag[0])}
+
+    def time_explicit_step(self, n, reps=50):
+        """(ms per launch of k_explicit_step on n variables, ms per device-to-device copy of the bytes it moves) (mfh_time_explicit_step)."""
+        step, copy = C.c_double(), C.c_double()
+        self._ck(self.lib.mfh_time_explicit_step(self.h, int(n), int(reps), C.byref(step), C.byref(copy)))
+        return step.value, copy.value
+
+    def debug_hrz_weights(self):
+        """[npe]: the HRZ weights of the element type as mass_lumped_hrz takes them from the mass table (test hook mfh_debug_hrz_weights)."""
+        out = np.zeros(self.npe)
+        self._ck(self.lib.mfh_debug_hrz_weights(self.h, ptr(out)))
+        return out
+
+    def debug_elem_abs_rowsums(self):
+        """[n_elem, npe, dim]: the absolute row sums of the element stiffness matrices (test hook mfh_debug_elem_abs_rowsums)."""
+        out = np.zeros((self.n_elem, self.npe, self.dim))
+        self._ck(self.lib.mfh_debug_elem_abs_rowsums(self.h, ptr(out)))
+        return out
+
     def harmonic(self, omega, f, f_imag=None, density=1.0, damping=(0.0, 0.0), loss_factor=0.0, rtol=1e-8, maxit=10000, probes=None, fields=True,
                  warm_start=True):
         """The frequency response (K + i w C - w^2 M) u^ = f^ at every w of omega (rad per unit time), on the device (mfh_harmonic): M = density x

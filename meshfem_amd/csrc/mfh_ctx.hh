@@ -548,6 +548,7 @@ void batch_apply(mfh_ctx *c, int NR, double *x, double *y, bool masked);        
 void tl_precond(mfh_ctx *c, const double *r, double *z, double *scal, int it);
 bool dense_inverse_device(mfh_ctx *c, const double *Ac, int64_t mm, DBuf<double> &Ainv, int64_t &ldInv);
 double device_dot(mfh_ctx *c, int64_t n, const double *a, const double *b);
+void ensure_assembled(mfh_ctx *c);     // geometry, pattern and K's values (mfh_explicit.hip: the K product alone, no inverse diagonal blocks)
 void ensure_precond(mfh_ctx *c);
 bool ensure_twolevel(mfh_ctx *c);
 bool ensure_multigrid(mfh_ctx *c);

@@ -438,6 +438,8 @@ void launch_chunk_keys(const AsmArgs &a, uint32_t *keys, hipStream_t s);
 bool launch_pack_codes(int64_t nChunk, const int64_t *contribPtr, uint32_t *contribCode, int npe, int32_t *chunkElemBase, int *flag, hipStream_t s);
 void launch_assemble_atomic(const AsmArgs &a, hipStream_t s);
 void launch_element_stiffness(const AsmArgs &a, int64_t first, int64_t count, double *KeOut, hipStream_t s);
+// out[(e npe + i) dim + c] = sum_j sum_d |K_e[(i, c), (j, d)]| with the blocks of the assembly (elasticity flavours); gridCap: workgroups at most
+void launch_elem_abs_rowsums(const AsmArgs &a, double *out, int gridCap, hipStream_t s);
 // deltaP != nullptr: the discrete shape derivative of the same quantity under the vertex perturbation deltaP
 void launch_constant_strain_load(const AsmArgs &a, const int32_t *elemNodes, const int32_t *dofForNode, const double *intGrad,
                                  const double *cstrain, const double *deltaP, double *out, hipStream_t s);

@@ -555,6 +555,33 @@ __global__ void __launch_bounds__(256) k_element_stiffness(AsmArgs a, int64_t fi
     }
 }
 
+// Absolute row sums of the element matrices (mfh_explicit_dt, mfh_explicit.hip: the Gershgorin bound on M_L^-1 K): one lane per (element, local
+// node i) walks the NPE blocks of row i with the arithmetic of the assembly (elem_block: the values K holds) and writes
+// out[(e NPE + i) DIM + c] = sum_j sum_d |K_e[(i, c), (j, d)]|. Every entry is written once, j ascending: no atomics.
+template <int DIM, int DEG, int MAT>
+__global__ void __launch_bounds__(256) k_elem_abs_rowsums(AsmArgs a, double *__restrict__ out) {
+    constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
+    const PairConst pc{a.pairConst[0], a.pairConst[1], a.pairConst[2], a.pairConst[3], a.pairConst[4], a.pairConst[5]};
+    const int64_t total = a.nElem * NPE;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < total; k += (int64_t)gridDim.x * 256) {
+        const int64_t e = k / NPE;
+        const int i = (int)(k - e * NPE);
+        double rs[DIM];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) rs[c] = 0.0;
+        for (int j = 0; j < NPE; ++j) {
+            double K[DIM * DIM];
+            elem_block<DIM, DEG, MAT>(a.geo + e * a.geoStride, a.pairTable, pc, i, j, K);
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) rs[c] += fabs(K[c * DIM + d]);
+        }
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) out[k * DIM + c] = rs[c];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K8: constantStrainLoad (LinearElasticity.hh:551-562, :135-162): l_i = (C_e : cstrain) . int grad phi_i,
 // one lane per (element, node); int grad phi_i = vol (al_i gl[s_i] + be_i gl[t_i]) with al/be the
@@ -2616,6 +2643,13 @@ void launch_assemble_atomic(const AsmArgs &a, hipStream_t s) {
 void launch_element_stiffness(const AsmArgs &a, int64_t first, int64_t count, double *KeOut, hipStream_t s) {
     const int grid = grid_for(count * a.npe * a.npe);
     with_elem_asm(a, [&](auto D, auto G, auto M) { launch_k(k_element_stiffness<D(), G(), M()>, dim3(grid), dim3(256), 0, s, a, first, count, KeOut); });
+    CHECK_LAUNCH();
+}
+
+void launch_elem_abs_rowsums(const AsmArgs &a, double *out, int gridCap, hipStream_t s) {
+    if (a.nElem <= 0) return;
+    const int grid = grid_for(a.nElem * a.npe, std::max(1, std::min(gridCap, 8192)));
+    with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_elem_abs_rowsums<D(), G(), M()>, dim3(grid), dim3(256), 0, s, a, out); });
     CHECK_LAUNCH();
 }
 

@@ -428,6 +428,73 @@ class Simulator:
         del out["info"]
         return out
 
+    # ---- explicit dynamics (docs/design/04_20_explicit_dynamics.md)
+    def _clamp_dirichlet(self):
+        v, _ = self.ctx.bc_dirichlet_vars()
+        self.ctx.clear_fixed()
+        if len(v):
+            self.ctx.fix_variables(v)
+
+    def lumpedMassHRZ(self):
+        """[nDoF, N]: the HRZ-lumped masses under the density field of setDensity (every DoF's mass repeated for its components): positive on
+        linear and quadratic elements alike, and summing to N times the mass of the body."""
+        return self.ctx.mass_lumped_hrz().reshape(self.ctx.n_dof, self.N)
+
+    def stableTimeStep(self, density=1.0, iters=0):
+        """The stability limit of transient_explicit bracketed: a dict with dtSafe (stable for certain, from a Gershgorin bound) and dtEst (an upper
+        bound of the limit 2 / sqrt(lambda_max) from `iters` power-iteration steps, 0: 60), lambdaUpper, lambdaEst. The Dirichlet variables of
+        the applied boundary conditions are the clamp; density as in transient."""
+        density = self._density_scalar(density)
+        self._clamp_dirichlet()
+        return self.ctx.explicit_dt(density=density, iters=iters)
+
+    def transient_explicit(self, n_steps, dt=None, safety=0.9, amplitude=None, u0=None, v0=None, density=1.0, damping=0.0, probes=None,
+                           snapshot_stride=0, a0=None, energies=False, energy_stride=1, load=None, check_dt=True):
+        """The response to the load history amplitude[n] x f like transient, by explicit central differences with the HRZ-lumped mass matrix
+        (mfh_explicit): one product with K per step, no solve -- for wave propagation, impact and short pulses. dt=None: safety x dtEst of
+        stableTimeStep (self.explicit_time_step holds the step taken). damping: the mass-proportional Rayleigh coefficient. Fields come back as in
+        transient; "energies" [n_steps // energy_stride + 1, 4] = kinetic, strain, g f.u, the leapfrog invariant. self.transient_info holds
+        the solver's record."""
+        ctx = self.ctx
+        density = self._density_scalar(density)
+        self._clamp_dirichlet()
+        if dt is None:
+            dt = float(safety) * ctx.explicit_dt(density=density)["dtEst"]
+        self.explicit_time_step = float(dt)
+        mapped = ctx.n_dof != ctx.n_node                   # a DoF map (periodic conditions): a DoF takes the value of its first node
+        dof = ctx.get_dof_map()[0] if mapped else None
+        if mapped:
+            first = np.full(ctx.n_dof, -1, dtype=np.int64)
+            first[dof[::-1]] = np.arange(ctx.n_node)[::-1]
+
+        def to_dofs(x):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=np.float64).reshape(ctx.n_node, self.N)
+            return x[first] if mapped else x
+
+        def to_nodes(x):
+            x = x.reshape(x.shape[:-1] + (ctx.n_dof, self.N))
+            return x[..., dof, :] if mapped else x
+        f = self.neumannLoad() if load is None else np.asarray(load, dtype=np.float64).reshape(ctx.n_dof, self.N)
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        try:
+            r = ctx.explicit(dt, n_steps, u0=to_dofs(u0), v0=to_dofs(v0), a0=to_dofs(a0), f=None if not np.any(f) else f, amplitude=amplitude,
+                             density=density, damping=damping, probes=pv, snapshot_stride=snapshot_stride, energies=energies,
+                             energy_stride=energy_stride, check_dt=check_dt)
+        finally:
+            self.transient_info = getattr(ctx, "last_explicit", {}).get("info")
+        out = dict(r)
+        for k in ("u", "v", "a"):
+            out[k] = to_nodes(r[k])
+        if r["snapshots"] is not None:
+            out["snapshots"] = to_nodes(r["snapshots"])
+        del out["info"]
+        return out
+
     def frequencyResponse(self, omegas, load=None, density=1.0, damping=(0, 0), loss_factor=0.0, probes=None, fields=True, warm_start=True,
                           rtol=None, maxit=None):
         """The steady state u^(w) of M u'' + C u' + K u = Re(f^ e^{i w t}) at every w of omegas (rad per unit time), on the device (mfh_harmonic):
