@@ -10,6 +10,7 @@
 // that does not reach opt.rtol within opt.maxit iterations included.
 #pragma once
 
+#include <algorithm>
 #include <complex>
 #include <utility>
 
@@ -77,6 +78,112 @@ frequencyResponse(const Sim &sim, const std::vector<Real> &omegas, const Harmoni
         for (size_t j = 0; j < nProbe; ++j) r.probes[k][j] = {probeOut[(k * nProbe + j) * 2], probeOut[(k * nProbe + j) * 2 + 1]};
     if (opt.fields) {
         r.u.assign(nFreq, typename HarmonicResult<N>::CField(nDoF));
+        for (size_t k = 0; k < nFreq; ++k)
+            for (size_t i = 0; i < nDoF; ++i)
+                for (size_t a = 0; a < N; ++a) r.u[k][i][a] = {fld[(2 * k) * n + i * N + a], fld[(2 * k + 1) * n + i * N + a]};
+    }
+    return r;
+}
+
+// ---- the same response by superposition of the lowest modes (include/meshfem_hip.h, "modal superposition"; docs/design/04_21_modal_superposition.md)
+//   modalFrequencyResponse(sim, omegas, opt)   u^(w) = sum_j phi_j q_j(w) + r_s / zK(w) on opt.nModes modes computed here (mfh_modes_many) and kept
+//                                              on the device (mfh_modal_set_basis), or on the eigenpairs the caller hands in (opt.lambda, opt.modes);
+//                                              system, load, clamp, damping and probes as in frequencyResponse. opt.staticCorrection: one static solve
+//                                              per load plane at opt.rtol / opt.maxit stands in for the truncated modes (clamped bodies only).
+template <class VField>
+struct ModalHarmonicOptions {
+    Real density = 1.0, rayleighMass = 0.0, rayleighStiff = 0.0, lossFactor = 0.0;
+    int nModes = 16;                                      // modes computed here when lambda is empty (1 .. 256)
+    int batch = 0;                                        // ... in batches of this many (0: the library's 16)
+    Real modesRtol = 1e-6;
+    std::vector<Real> lambda;                             // eigenpairs of (K, density M) the caller has: M-orthonormal per-DoF rows, modes[j] = one N-vector per DoF
+    std::vector<VField> modes;
+    std::vector<Real> modalDamping;                       // damping ratios per mode; empty: none
+    bool staticCorrection = true;
+    int residualStride = -1;                              // < 0: no true residuals; k >= 0: at every k-th frequency (0: every one)
+    Real rtol = 1e-8;                                     // of the static solves
+    int maxit = 10000;
+    VField load, loadImag;
+    std::vector<std::pair<size_t, int>> probes;
+    bool fields = true;
+};
+
+template <size_t N>
+struct ModalHarmonicResult {
+    using CField = std::vector<std::array<std::complex<Real>, N>>;
+    std::vector<CField> u;                                    // [nFreq][nDoF]
+    std::vector<std::vector<std::complex<Real>>> probes;      // [nFreq][number of probes]
+    std::vector<std::vector<std::complex<Real>>> modalCoords; // [nFreq][nModes]
+    std::vector<Real> trueResiduals;                          // [nFreq], -1 where none was computed
+    std::vector<Real> lambda;                                 // the basis's eigenvalues
+    mfh_modal_basis_info basisInfo{};
+    mfh_modal_harmonic_info info{};
+};
+
+template <class Sim>
+ModalHarmonicResult<std::tuple_size<typename Sim::VField::value_type>::value>
+modalFrequencyResponse(const Sim &sim, const std::vector<Real> &omegas,
+                       const ModalHarmonicOptions<typename Sim::VField> &opt = ModalHarmonicOptions<typename Sim::VField>()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    mfh_ctx *c = sim.ctx();
+    check(c, mfh_clear_fixed(c));
+    int64_t nv = 0;
+    check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
+    if (nv > 0) {
+        std::vector<int64_t> vars((size_t)nv);
+        std::vector<Real> vals((size_t)nv);
+        check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
+        check(c, mfh_fix_variables(c, nv, vars.data(), nullptr));
+    }
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N, nFreq = omegas.size();
+    if (!opt.load.empty() && opt.load.size() != nDoF) throw std::runtime_error("modalFrequencyResponse: load needs one entry per DoF");
+    if (!opt.loadImag.empty() && opt.loadImag.size() != nDoF) throw std::runtime_error("modalFrequencyResponse: loadImag needs one entry per DoF");
+    ModalHarmonicResult<N> r;
+    std::vector<Real> X;
+    if (opt.lambda.empty()) {
+        mfh_modes_many_params mp{};
+        mp.nev = opt.nModes; mp.batch = opt.batch; mp.flags = nv > 0 ? 0 : MFH_MODES_FREE; mp.maxit = 3000;
+        mp.density = opt.density; mp.rtol = opt.modesRtol;
+        r.lambda.assign((size_t)std::max(opt.nModes, 0), 0.0);
+        X.assign(r.lambda.size() * n, 0.0);
+        mfh_modes_many_info mi{};
+        check(c, mfh_modes_many(c, &mp, nullptr, r.lambda.data(), X.data(), nullptr, &mi));
+    } else {
+        if (opt.modes.size() != opt.lambda.size()) throw std::runtime_error("modalFrequencyResponse: one mode per eigenvalue");
+        r.lambda = opt.lambda;
+        X.resize(r.lambda.size() * n);
+        for (size_t j = 0; j < opt.modes.size(); ++j) {
+            if (opt.modes[j].size() != nDoF) throw std::runtime_error("modalFrequencyResponse: a mode needs one entry per DoF");
+            std::copy(&opt.modes[j][0][0], &opt.modes[j][0][0] + n, X.begin() + (std::ptrdiff_t)(j * n));
+        }
+    }
+    const size_t m = r.lambda.size();
+    if (!opt.modalDamping.empty() && opt.modalDamping.size() != m) throw std::runtime_error("modalFrequencyResponse: one damping ratio per mode");
+    check(c, mfh_modal_set_basis(c, (int32_t)m, r.lambda.data(), X.data(), opt.density, &r.basisInfo));
+    const VField f = opt.load.empty() ? sim.neumannLoad() : opt.load;
+    std::vector<int64_t> probeVars;
+    for (const auto &p : opt.probes) probeVars.push_back((int64_t)(p.first * N) + p.second);
+    const size_t nProbe = probeVars.size();
+    std::vector<Real> probeOut(nFreq * nProbe * 2), fld(opt.fields ? nFreq * 2 * n : 0), mc(nFreq * m * 2);
+    r.trueResiduals.assign(nFreq, -1.0);
+    mfh_modal_harmonic_params prm{};
+    prm.rayleighMass = opt.rayleighMass; prm.rayleighStiff = opt.rayleighStiff; prm.lossFactor = opt.lossFactor;
+    prm.rtol = opt.rtol; prm.maxit = opt.maxit; prm.nFreq = (int32_t)nFreq;
+    prm.residualStride = std::max(opt.residualStride, 0);
+    prm.flags = (opt.staticCorrection ? MFH_MODAL_STATIC_CORRECTION : 0) | (opt.residualStride >= 0 ? MFH_MODAL_RESIDUALS : 0);
+    check(c, mfh_modal_harmonic(c, &prm, omegas.data(), opt.modalDamping.empty() ? nullptr : opt.modalDamping.data(), &f[0][0],
+                                opt.loadImag.empty() ? nullptr : &opt.loadImag[0][0], nProbe ? probeVars.data() : nullptr, (int32_t)nProbe,
+                                nProbe ? probeOut.data() : nullptr, opt.fields ? fld.data() : nullptr, mc.empty() ? nullptr : mc.data(),
+                                r.trueResiduals.data(), &r.info));
+    r.probes.assign(nFreq, std::vector<std::complex<Real>>(nProbe));
+    r.modalCoords.assign(nFreq, std::vector<std::complex<Real>>(m));
+    for (size_t k = 0; k < nFreq; ++k) {
+        for (size_t j = 0; j < nProbe; ++j) r.probes[k][j] = {probeOut[(k * nProbe + j) * 2], probeOut[(k * nProbe + j) * 2 + 1]};
+        for (size_t j = 0; j < m; ++j) r.modalCoords[k][j] = {mc[(k * m + j) * 2], mc[(k * m + j) * 2 + 1]};
+    }
+    if (opt.fields) {
+        r.u.assign(nFreq, typename ModalHarmonicResult<N>::CField(nDoF));
         for (size_t k = 0; k < nFreq; ++k)
             for (size_t i = 0; i < nDoF; ++i)
                 for (size_t a = 0; a < N; ++a) r.u[k][i][a] = {fld[(2 * k) * n + i * N + a], fld[(2 * k + 1) * n + i * N + a]};

@@ -708,6 +708,62 @@ mfh_status mfh_harmonic(mfh_ctx* ctx, const mfh_harmonic_params* params,
                         double* trueResiduals,                    /* nFreq or NULL */
                         mfh_harmonic_info* info);
 
+/* ---------------------------------------------------------------- modal superposition
+ * Frequency sweeps on a mode basis that stays on the device (docs/design/04_21_modal_superposition.md). With eigenpairs (lambda_j, phi_j) of
+ * (K, density M), M-orthonormal, the response of mfh_harmonic's system is
+ *     u^(w) = sum_j phi_j q_j(w) [+ r_s / zK(w)],   q_j = (phi_j^T f^) / d_j,
+ *     d_j = lambda_j (1 + i (lossFactor + w rayleighStiff)) - w^2 + i w rayleighMass + 2 i zeta_j sqrt(lambda_j) w,
+ * exact for the full basis; a truncated basis leaves the error mfh_modal_harmonic measures on request (MFH_MODAL_RESIDUALS). r_s is the static
+ * correction (mode acceleration) u_s - sum_j phi_j (phi_j^T f^) / lambda_j with K u_s = f^, zK = 1 + i (lossFactor + w rayleighStiff).
+ *   mfh_modal_set_basis    copies nModes (1 .. 256; 0 drops the basis and its memory) modes -- rows of X, dim*nDoF each, e.g. the output of
+ *                          mfh_modes / mfh_modes_many at the same density -- to the device, zeroes their entries on the fixed variables and reports
+ *                          info->orthoDefect = max |X (density M) X^T - I|. Nothing is refused on the defect. lambda[j] >= 0 (0: a rigid mode of
+ *                          a free body). MFH_ERR_INVALID before any device work: a count out of range, density <= 0, an entry that is not
+ *                          finite, a negative lambda. The basis belongs to the mesh, vertex positions, material, density field and the set of
+ *                          fixed variables in force: after any of them changed the calls below return MFH_ERR_STATE until a basis is set again
+ *                          (clearing the fixed variables and fixing the same set again keeps it; a new mesh or DoF map drops it).
+ *   mfh_modal_coordinates  q = X (density M) u for nVec fields (rows of u): the modal coordinates of e.g. a Newmark snapshot
+ *   mfh_modal_harmonic     the sweep. omega, fRe, fIm, probeVars, probeOut, fields as in mfh_harmonic; the density is the basis's.
+ *                          modalDamping: nModes damping ratios zeta_j >= 0 or NULL; modalCoords: nFreq x nModes x {re, im} or NULL.
+ *                          MFH_MODAL_STATIC_CORRECTION: one solve K u_s = f^ per non-zero load plane with the context's solver and preconditioner
+ *                          at rtol / maxit (MFH_ERR_NOT_CONVERGED, nothing written, if one fails); needs fixed variables (MFH_ERR_UNSUPPORTED)
+ *                          and lambda_j > 0 (MFH_ERR_INVALID). MFH_MODAL_RESIDUALS: trueResiduals[k] = ||f^ - Z(w_k) u^||_2 / ||f^||_2 with the
+ *                          operator product of mfh_harmonic at every residualStride-th frequency (0: every one), -1 at the others; refused with
+ *                          modalDamping (no operator to test against). Refusals otherwise as mfh_harmonic's, plus w = 0 with a zero lambda or
+ *                          d_j = 0 and a negative zeta (MFH_ERR_INVALID), no basis or a stale one (MFH_ERR_STATE).
+ * Device memory of a sweep beside the basis ((nModes + 2) columns): with fields or residuals, staging rows for 16 frequencies (one full pass of the
+ * expansion kernel: 32 x dim*nDoF doubles, 5.7 GB at 22.3 M unknowns) or 256 MB, whichever is more; where that allocation fails the call falls back
+ * to 256 MB (one row at least) and says so in info->note. Contexts as for mfh_harmonic. */
+enum { MFH_MODAL_STATIC_CORRECTION = 1, MFH_MODAL_RESIDUALS = 2 };
+typedef struct mfh_modal_basis_info {
+    int32_t nModes, reserved;
+    int64_t ld;                                                                        /* doubles between two columns on the device */
+    double orthoDefect, deviceBytes, setupMs;
+} mfh_modal_basis_info;
+typedef struct mfh_modal_harmonic_params {
+    double rayleighMass, rayleighStiff, lossFactor, rtol;
+    int32_t maxit, nFreq, residualStride, flags;
+} mfh_modal_harmonic_params;
+typedef struct mfh_modal_harmonic_info {
+    int32_t staticSolves, staticIterations, groups, planesPerPass;
+    double worstTrueResidual, setupMs, solveMs;
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_modal_harmonic_info;
+mfh_status mfh_modal_set_basis(mfh_ctx* ctx, int32_t nModes, const double* lambda /* nModes */, const double* X /* nModes x dim*nDoF */,
+                               double density, mfh_modal_basis_info* info);
+mfh_status mfh_modal_coordinates(mfh_ctx* ctx, const double* u /* nVec x dim*nDoF */, int32_t nVec, double* q /* nVec x nModes */);
+/* *nModes = modes of the basis in place (0: none), *valid = 1 if the modal calls would accept it now (either may be NULL) */
+mfh_status mfh_modal_basis_state(mfh_ctx* ctx, int32_t* nModes, int32_t* valid);
+mfh_status mfh_modal_harmonic(mfh_ctx* ctx, const mfh_modal_harmonic_params* params,
+                              const double* omega,                      /* nFreq, rad per unit time */
+                              const double* modalDamping,               /* nModes or NULL */
+                              const double* fRe, const double* fIm,     /* dim*nDoF each; fIm may be NULL */
+                              const int64_t* probeVars, int32_t nProbe, double* probeOut,  /* nFreq x nProbe x {re, im} */
+                              double* fields,                           /* nFreq x {re plane, im plane} x dim*nDoF, or NULL */
+                              double* modalCoords,                      /* nFreq x nModes x {re, im}, or NULL */
+                              double* trueResiduals,                    /* nFreq, or NULL */
+                              mfh_modal_harmonic_info* info);
+
 /* ---------------------------------------------------------------- per-element density, the product with M, mass properties
  * (docs/design/04_15_density.md.) The mass matrix of mfh_modes and mfh_newmark is assembled from a density field of the context:
  *     M = sum_e rho_e int_e phi_i phi_j   on displacement vectors (kron with the identity of size dim),   rho = 1 until a field is set.

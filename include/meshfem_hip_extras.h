@@ -101,6 +101,18 @@ mfh_status mfh_debug_deflate(mfh_ctx* ctx, int64_t n, int32_t nq, int32_t nv, in
 /* ms per call of k_deflate_gram (+ second stage) and of k_deflate_update on nq + k columns of n rows, against a device-to-device copy of the same
  * (nq + k) columns in the same process */
 mfh_status mfh_time_deflate(mfh_ctx* ctx, int64_t n, int32_t nq, int32_t k, int32_t reps, double* gram_ms, double* update_ms, double* copy_ms);
+/* test hook: the expansion kernel of mfh_modal_harmonic (k_modal_expand, mfh_modal.hip) on host arrays, launched as the sweep launches it.
+ * B: n x nb column-major (nb <= 258), C: nb x nPlanes row-major; out: nPlanes x n, out[p][row] = sum_j B_j[row] C[j][p] as the fma chain over j
+ * ascending from +0. planesPerPass: 1 .. 32 planes a pass writes (the kernel instantiation is the smallest of 8 / 16 / 32 that holds them);
+ * 0 = the library's default */
+mfh_status mfh_debug_modal_expand(mfh_ctx* ctx, int64_t n, int32_t nb, const double* B, const double* C, int32_t nPlanes, int32_t planesPerPass,
+                                  double* out);
+/* test hook: the Gram kernel of the modal layer (k_modal_gram and its fixed-order second stage, mfh_modal.hip) on host arrays. A: n x na
+ * column-major (na <= 258), V: n x nv column-major (nv <= 8); G = A^T V, na x nv row-major */
+mfh_status mfh_debug_modal_gram(mfh_ctx* ctx, int64_t n, int32_t na, int32_t nv, const double* A, const double* V, double* G);
+/* device time (ms, one entry per repetition) of one pass of k_modal_expand<NP> (NP = planesPerPass in {8, 16, 32}; 0 = the default) on nb hashed
+ * columns of n rows; mfh_time_deflate times k_deflate_update on the same shape in the same process (scripts/probe_modal.py) */
+mfh_status mfh_time_modal_expand(mfh_ctx* ctx, int64_t n, int32_t nb, int32_t planesPerPass, int32_t reps, double* times);
 
 /* test hooks: the step kernels of mfh_newmark (mfh_dynamics.hip) on host arrays of n doubles. mask: n bytes or NULL (non-zero = fixed variable).
  * predict: ut = u + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a (both 0 where masked), w = gamma / (beta dt) ut - vt,

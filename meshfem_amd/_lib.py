@@ -23,6 +23,7 @@ MODES_FREE = 1
 DYN_HAVE_ACCEL, DYN_ENERGIES = 1, 2
 EXP_HAVE_ACCEL, EXP_ENERGIES, EXP_NO_DT_CHECK = 1, 2, 4
 HARM_WARM_START = 1
+MODAL_STATIC_CORRECTION, MODAL_RESIDUALS = 1, 2
 
 
 class SamplerGridInfo(C.Structure):
@@ -130,6 +131,29 @@ class HarmonicParams(C.Structure):
 
 class HarmonicInfo(C.Structure):
     _fields_ = [("freqsDone", C.c_int32), ("iterationsTotal", C.c_int32), ("iterationsMax", C.c_int32), ("precondUsed", C.c_int32),
+                ("worstTrueResidual", C.c_double), ("setupMs", C.c_double), ("solveMs", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
+class ModalBasisInfo(C.Structure):
+    _fields_ = [("nModes", C.c_int32), ("reserved", C.c_int32), ("ld", C.c_int64), ("orthoDefect", C.c_double), ("deviceBytes", C.c_double),
+                ("setupMs", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ModalHarmonicParams(C.Structure):
+    _fields_ = [("rayleighMass", C.c_double), ("rayleighStiff", C.c_double), ("lossFactor", C.c_double), ("rtol", C.c_double), ("maxit", C.c_int32),
+                ("nFreq", C.c_int32), ("residualStride", C.c_int32), ("flags", C.c_int32)]
+
+
+class ModalHarmonicInfo(C.Structure):
+    _fields_ = [("staticSolves", C.c_int32), ("staticIterations", C.c_int32), ("groups", C.c_int32), ("planesPerPass", C.c_int32),
                 ("worstTrueResidual", C.c_double), ("setupMs", C.c_double), ("solveMs", C.c_double), ("note", C.c_char_p)]
 
     def as_dict(self):
@@ -268,6 +292,10 @@ PROTOTYPES = {
     "mfh_explicit_dt": (_i32, [_P, _f64, _i32, _P, C.POINTER(ExplicitDtInfo)]),
     "mfh_explicit": (_i32, [_P, C.POINTER(ExplicitParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(ExplicitInfo)]),
     "mfh_harmonic": (_i32, [_P, C.POINTER(HarmonicParams), _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(HarmonicInfo)]),
+    "mfh_modal_set_basis": (_i32, [_P, _i32, _P, _P, _f64, C.POINTER(ModalBasisInfo)]),
+    "mfh_modal_coordinates": (_i32, [_P, _P, _i32, _P]),
+    "mfh_modal_basis_state": (_i32, [_P, _pi32, _pi32]),
+    "mfh_modal_harmonic": (_i32, [_P, C.POINTER(ModalHarmonicParams), _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalHarmonicInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -331,6 +359,9 @@ PROTOTYPES = {
     "mfh_debug_block_update": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
     "mfh_debug_deflate": (_i32, [_P, _i64, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "mfh_time_deflate": (_i32, [_P, _i64, _i32, _i32, _i32, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "mfh_debug_modal_expand": (_i32, [_P, _i64, _i32, _P, _P, _i32, _i32, _P]),
+    "mfh_debug_modal_gram": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
+    "mfh_time_modal_expand": (_i32, [_P, _i64, _i32, _i32, _i32, _P]),
     "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),

@@ -627,6 +627,115 @@ class Context:
         self._ck(st)
         return out
 
+    # ---------------------------------------------------------------- modal superposition (docs/design/04_21_modal_superposition.md)
+    def set_modal_basis(self, lam, X, density=1.0):
+        """Keep the modes (lam [m], X [m, dim * n_dof], M-orthonormal at this density: the output of modes() / modes_many()) on the device as the
+        basis of modal_coordinates() and modal_harmonic() (mfh_modal_set_basis). lam=None or an empty X drops the basis and its memory. Returns
+        the info dict; info["orthoDefect"] = max |X (density M) X^T - I|. The basis belongs to the mesh, vertex positions, material, density
+        field and fixed variables in force: after any of them changed the modal calls raise with code ERR_STATE."""
+        n = self.bs * self.n_dof
+        info = L.ModalBasisInfo()
+        if lam is None or np.size(lam) == 0:
+            self._ck(self.lib.mfh_modal_set_basis(self.h, 0, None, None, float(density), C.byref(info)))
+            return info.as_dict()
+        lam = as_f64(np.asarray(lam, dtype=np.float64).reshape(-1))
+        X = as_f64(np.asarray(X, dtype=np.float64).reshape(-1, n))
+        if X.shape[0] != lam.size:
+            raise ValueError("set_modal_basis: %d eigenvalues for %d modes" % (lam.size, X.shape[0]))
+        self._ck(self.lib.mfh_modal_set_basis(self.h, lam.size, ptr(lam), ptr(X), float(density), C.byref(info)))
+        return info.as_dict()
+
+    def modal_basis_state(self):
+        """(nModes, valid): the modes of the basis in place (0: none) and whether the modal calls would accept it now (mfh_modal_basis_state)."""
+        m, ok = C.c_int32(), C.c_int32()
+        self._ck(self.lib.mfh_modal_basis_state(self.h, C.byref(m), C.byref(ok)))
+        return m.value, bool(ok.value)
+
+    def modal_basis(self, nev, density=1.0, **kw):
+        """modes_many(nev, density, **kw) followed by set_modal_basis: (lam, X, info) of modes_many, info["modal_basis"] the basis's info."""
+        lam, X, info = self.modes_many(nev, density=density, **kw)
+        info["modal_basis"] = self.set_modal_basis(lam, X, density=density)
+        return lam, X, info
+
+    def modal_coordinates(self, u):
+        """q = X (density M) u, [nVec, nModes] (one row for a single field): the modal coordinates of the fields u in the basis of
+        set_modal_basis (mfh_modal_coordinates)."""
+        n = self.bs * self.n_dof
+        u = np.asarray(u, dtype=np.float64)
+        single = u.ndim == 1
+        U2 = as_f64(u.reshape(-1, n))
+        m = self.modal_basis_state()[0]
+        q = np.zeros((U2.shape[0], m))
+        self._ck(self.lib.mfh_modal_coordinates(self.h, ptr(U2), U2.shape[0], ptr(q) if q.size else None))
+        return q[0] if single else q
+
+    def modal_harmonic(self, omega, f, f_imag=None, damping=(0.0, 0.0), loss_factor=0.0, modal_damping=None, static_correction=True, residual_stride=None,
+                       rtol=1e-8, maxit=10000, probes=None, fields=True):
+        """The frequency response of harmonic() by superposition of the modes of set_modal_basis (mfh_modal_harmonic): u^(w) = sum_j phi_j q_j(w),
+        q_j = phi_j^T f^ / (lam_j (1 + i (loss_factor + w damping[1])) - w^2 + i w damping[0] + 2 i zeta_j sqrt(lam_j) w), plus, with
+        static_correction, the quasi-static response of the truncated modes from one solve K u_s = f^ per load plane at rtol / maxit. The density
+        is the basis's. modal_damping: damping ratios zeta_j per mode. residual_stride: None = no residuals; k >= 0 = the true residual
+        ||f^ - Z u^|| / ||f^|| of every k-th frequency (0: every one) through the operator of harmonic(). Returns the dict of harmonic() without
+        "iterations", plus "modal_coords" complex [nFreq, nModes]; "true_residuals" holds -1 where nothing was computed."""
+        n = self.bs * self.n_dof
+        om = as_f64(np.asarray(omega, dtype=np.float64).reshape(-1))
+        nf = om.size
+        f = np.asarray(f).reshape(-1)
+        if f.size != n:
+            raise ValueError("modal_harmonic: f needs dim * n_dof = %d entries, got %d" % (n, f.size))
+        f_re = np.ascontiguousarray(f.real, dtype=np.float64)
+        f_im = np.ascontiguousarray(f.imag, dtype=np.float64) if np.iscomplexobj(f) else None
+        if f_imag is not None:
+            fi = np.asarray(f_imag, dtype=np.float64).reshape(-1)
+            if fi.size != n:
+                raise ValueError("modal_harmonic: f_imag needs dim * n_dof = %d entries, got %d" % (n, fi.size))
+            f_im = np.ascontiguousarray(fi if f_im is None else f_im + fi)
+        m = self.modal_basis_state()[0]
+        zeta = None
+        if modal_damping is not None:
+            zeta = as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros((nf, n_probe, 2)) if n_probe else None
+        fld = np.zeros((nf, 2, n)) if fields else None
+        mc, res = np.zeros((nf, m, 2)), np.full(nf, -1.0)
+        flags = (L.MODAL_STATIC_CORRECTION if static_correction else 0) | (0 if residual_stride is None else L.MODAL_RESIDUALS)
+        prm = L.ModalHarmonicParams(float(damping[0]), float(damping[1]), float(loss_factor), float(rtol), int(maxit), nf,
+                                    0 if residual_stride is None else int(residual_stride), flags)
+        info = L.ModalHarmonicInfo()
+        st = self.lib.mfh_modal_harmonic(self.h, C.byref(prm), ptr(om), ptr(zeta), ptr(f_re), ptr(f_im), ptr(pv), n_probe, ptr(pout), ptr(fld),
+                                         ptr(mc) if mc.size else None, ptr(res), C.byref(info))
+        out = {"u": None if fld is None else fld[:, 0, :] + 1j * fld[:, 1, :],
+               "probes": np.zeros((nf, 0), dtype=np.complex128) if pout is None else pout[:, :, 0] + 1j * pout[:, :, 1],
+               "modal_coords": mc[:, :, 0] + 1j * mc[:, :, 1], "true_residuals": res, "info": info.as_dict()}
+        self.last_modal_harmonic = out
+        self._ck(st)
+        return out
+
+    def debug_modal_expand(self, B, Cm, planes_per_pass=0):
+        """out [nPlanes, n] = (B^T C)^T through k_modal_expand as the sweep launches it (test hook mfh_debug_modal_expand). B: [nb, n] (a row per
+        column of the basis), Cm: [nb, nPlanes]."""
+        B, Cm = as_f64(np.atleast_2d(B)), as_f64(np.atleast_2d(Cm))
+        nb, n = B.shape
+        assert Cm.shape[0] == nb
+        out = np.zeros((Cm.shape[1], n))
+        self._ck(self.lib.mfh_debug_modal_expand(self.h, n, nb, ptr(B), ptr(Cm), Cm.shape[1], int(planes_per_pass), ptr(out)))
+        return out
+
+    def debug_modal_gram(self, A, V):
+        """G [na, nv] = A V^T through k_modal_gram and its second stage (test hook mfh_debug_modal_gram). A: [na <= 258, n], V: [nv <= 8, n] (a row per column)."""
+        A, V = as_f64(np.atleast_2d(A)), as_f64(np.atleast_2d(V))
+        assert A.shape[1] == V.shape[1]
+        G = np.zeros((A.shape[0], V.shape[0]))
+        self._ck(self.lib.mfh_debug_modal_gram(self.h, A.shape[1], A.shape[0], V.shape[0], ptr(A), ptr(V), ptr(G)))
+        return G
+
+    def time_modal_expand(self, n, nb, planes_per_pass=0, reps=5):
+        """Device time (ms) per repetition of one pass of k_modal_expand on nb hashed columns of n rows (mfh_time_modal_expand)."""
+        t = np.zeros(int(reps))
+        self._ck(self.lib.mfh_time_modal_expand(self.h, int(n), int(nb), int(planes_per_pass), int(reps), ptr(t)))
+        return t
+
     # ---------------------------------------------------------------- per-element density (docs/design/04_15_density.md)
     def set_density(self, rho):
         """The density field of the mass matrix of modes() and newmark() (mfh_set_density): one strictly positive value per element, or

@@ -156,6 +156,22 @@ struct mfh_ctx {
     std::string modesNote;            // mfh_modes_info::note of the last mfh_modes
     std::string dynNote;              // mfh_newmark_info::note of the last mfh_newmark (mfh_dynamics.hip)
     std::string harmNote;             // mfh_harmonic_info::note of the last mfh_harmonic (mfh_harmonic.hip)
+    // The mode basis of mfh_modal_set_basis (mfh_modal.hip, docs/design/04_21_modal_superposition.md): nModes M-orthonormal columns, ld apart, zero
+    // on the fixed variables, and two more columns behind them for the static-correction vectors of a sweep. Valid for the element records
+    // (geoGen: vertex positions, material), the density field (densityGen) and the SET of fixed variables (fixedSet, sorted: re-applying the same
+    // clamp keeps the basis, a different one makes it stale) it was set under; the entry points that change the mesh or the numbering of the
+    // variables (a new mesh, a DoF map, a caller's matrix) drop it (modal_drop).
+    struct ModalBasis {
+        int nModes = 0;
+        int64_t n = 0, ld = 0;
+        double density = 1.0;
+        std::vector<double> lambda;
+        std::vector<int64_t> fixedSet;
+        DBuf<double> B;
+        int64_t geoGen = -1, densityGen = -1;
+        void reset() { nModes = 0; n = ld = 0; lambda.clear(); fixedSet.clear(); B.release(); geoGen = densityGen = -1; }
+    } modal;
+    std::string modalNote;            // mfh_modal_harmonic_info::note of the last mfh_modal_harmonic
 
     // ---- constraints (SPSDSystem state)
     std::vector<int64_t> fixedVars;
@@ -495,6 +511,11 @@ void clear_prestress(mfh_ctx *c);      // no prestress field (mfh_set_prestress(
 void ensure_geometric(mfh_ctx *c);     // dGeomVals of the current pattern, element records and prestress field (both triangles required)
 k::SpmvArgs geom_spmv_args(mfh_ctx *c, bool masked);   // k_spmv_kron on dGeomVals
 void refresh_storage_rule(mfh_ctx *c);
+inline void modal_drop(mfh_ctx *c) { c->modal.reset(); }   // the mode basis of mfh_modal_set_basis describes the previous mesh / numbering of the variables
+// mfh_harmonic.hip, for the true residual of mfh_modal_harmonic (mfh_modal.hip): y^ = zK K x^ + zM M x^ ({re, im} each; M at density 1) on the two
+// planes v, v + ld through the path of mfh_harmonic's own residual -- apply_operator per plane and k_spmv_kron_cacc, or the two-pass form --
+// after prepare_pencil_state under a WideGuard. tmp: two planes of scratch
+void harmonic_product(mfh_ctx *c, bool masked, const double *zK, const double *zM, const double *x, double *y, int64_t ld, double *tmp);
 // the storage of the pattern for the duration of a call (see mfh_ctx::modesWide): both triangles, and back
 struct WideGuard {
     mfh_ctx *c;

@@ -417,6 +417,16 @@ void check_params(const mfh_ctx *c, const mfh_harmonic_params *p, const double *
 
 }   // namespace
 
+namespace mfhi {
+void harmonic_product(mfh_ctx *c, bool masked, const double *zK, const double *zM, const double *x, double *y, int64_t ld, double *tmp) {
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    const bool haveK = zK[0] != 0.0 || zK[1] != 0.0;
+    if (haveK) { apply_operator(c, masked, x, y, nullptr); apply_operator(c, masked, x + ld, y + ld, nullptr); }
+    k::launch_spmv_kron_cacc(mass_spmv_args(c, masked), haveK, Cx{zK[0], zK[1]}, Cx{zM[0], zM[1]}, x, y, ld, n, tmp, nullptr, k::dyn_open(), c->stream,
+                             c->dynGridCap, c->harmTwoPass);
+}
+}   // namespace mfhi
+
 extern "C" {
 
 mfh_status mfh_harmonic(mfh_ctx *c, const mfh_harmonic_params *prm, const double *omega, const double *fRe, const double *fIm, const int64_t *probeVars,

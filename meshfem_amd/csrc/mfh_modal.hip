@@ -1,0 +1,645 @@
+// Modal superposition (mfh_modal_set_basis, mfh_modal_coordinates, mfh_modal_harmonic, include/meshfem_hip.h; docs/design/04_21_modal_superposition.md):
+// frequency sweeps on a mode basis that stays on the device. With M-orthonormal eigenpairs (lambda_j, phi_j) of (K, density M) the response of
+// mfh_harmonic's system Z(w) u^ = f^ is
+//     u^(w) = sum_j phi_j q_j(w) + r_s / zK(w),   q_j = g_j / d_j,   g = Phi^T f^,
+//     d_j = lambda_j zK - w^2 + i w aR + 2 i zeta_j sqrt(lambda_j) w,   zK = 1 + i (eta + w bR),
+// r_s = u_s - sum_j phi_j g_j / lambda_j the static correction with K u_s = f^ (optional). The nModes x nFreq scalars d_j, q_j are formed on the host in
+// double precision; the device holds B = [Phi | r_re | r_im] (columns ld apart, the layout of the deflation set of mfh_modes.hip) and expands.
+//   k_modal_expand<NP>  out[p][row] = sum_j B_j[row] C[j][p]: the lanes own the rows, a lane keeps the NP sums of its row in registers and streams the
+//                       nb <= 258 columns of B once (four loads in flight); C is wave-uniform and read-only, so its entries come through scalar loads
+//                       (as in k_deflate_update). The value of (row, plane) is the fma chain over j ascending from +0: its bits depend neither on
+//                       NP, nor on how the planes are grouped into passes, nor on the grid -- the probes (the same kernel on the gathered probe rows
+//                       of B) equal the field entries bit for bit. Plain vector stores, no LDS, no atomics.
+//   k_modal_gram        partials of A^T V for na <= 258 columns of A against nv <= 8 columns of V, a tile of 8 x 8 column pairs per workgroup;
+//   k_modal_gram_sum    adds the workgroups' partials in workgroup order: G = Phi^T (density M Phi), g = Phi^T [f_re f_im], q = Phi^T (density M u).
+//                       Ordered two-stage sums, no floating-point atomics; the row partition depends on n only.
+// The mass products are k_spmv_kron_acc's (mfh_pencil.hh), the true residual's operator product mfh_harmonic's own (harmonic_product, mfh_harmonic.hip).
+#include "mfh_pencil.hh"
+#include <optional>
+
+namespace mfh { namespace k {
+
+namespace {
+
+constexpr int MODAL_MAXM = 256;         // modes of a basis
+constexpr int MODAL_MAXB = MODAL_MAXM + 2;   // ... and the two static-correction columns behind them
+constexpr int MODAL_NP = 32;            // planes per pass of k_modal_expand by default: the cheapest per plane of {8, 16, 32} (profiles/r18_modal.md); a pass
+                                        // with fewer planes left takes the smallest instantiation that holds them
+constexpr int MODAL_NP_MAX = 32;
+constexpr int MODAL_GRID_CAP = 2048;    // workgroups of k_modal_expand
+constexpr int MG_TA = 8, MG_TV = 8;     // column-pair tile of a workgroup of k_modal_gram
+constexpr int MG_GRID_CAP = 256;        // its workgroups along the rows (= partials the second stage adds per entry)
+
+// out[(p0 + t) planeStride + row] = sum_j B[j ldb + row] C[j ldc + p0 + t] for t < np <= NP. C: nb rows of ldc doubles, zero-padded to p0 + NP.
+template <int NP>
+__global__ void __launch_bounds__(256) k_modal_expand(int64_t n, const double *__restrict__ B, int64_t ldb, int nb, const double *__restrict__ C, int ldc, int p0,
+                                                     int np, double *__restrict__ out, int64_t planeStride) {
+    const double *c0 = C + p0;
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.x * 256) {
+        double s[NP];
+#pragma unroll
+        for (int t = 0; t < NP; ++t) s[t] = 0.0;
+        const double *b = B + row;
+        int j = 0;
+        for (; j + 4 <= nb; j += 4) {
+            const double b0 = b[(int64_t)j * ldb], b1 = b[(int64_t)(j + 1) * ldb], b2 = b[(int64_t)(j + 2) * ldb], b3 = b[(int64_t)(j + 3) * ldb];
+            const double *c = c0 + (int64_t)j * ldc;
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b0, c[t], s[t]);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b1, c[ldc + t], s[t]);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b2, c[2 * ldc + t], s[t]);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b3, c[3 * ldc + t], s[t]);
+        }
+        for (; j < nb; ++j) {
+            const double b0 = b[(int64_t)j * ldb];
+            const double *c = c0 + (int64_t)j * ldc;
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b0, c[t], s[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < NP; ++t)
+            if (t < np) out[(int64_t)(p0 + t) * planeStride + row] = s[t];
+    }
+}
+
+// partials[(blockIdx.y na + i) nv + j] = sum over the rows of this workgroup of A_i V_j, i in the workgroup's tile of MG_TA columns of A. Columns
+// past the end are clamped to the last one (their sums are not written): the loop carries no branch.
+__global__ void __launch_bounds__(256) k_modal_gram(int64_t n, const double *__restrict__ A, int64_t lda, int na, const double *__restrict__ V, int64_t ldv, int nv,
+                                                   double *__restrict__ partials) {
+    __shared__ double red[4][MG_TA * MG_TV];
+    const int a0 = blockIdx.x * MG_TA;
+    const double *pa[MG_TA], *pv[MG_TV];
+#pragma unroll
+    for (int i = 0; i < MG_TA; ++i) pa[i] = A + (int64_t)min(a0 + i, na - 1) * lda;
+#pragma unroll
+    for (int j = 0; j < MG_TV; ++j) pv[j] = V + (int64_t)min(j, nv - 1) * ldv;
+    double acc[MG_TA][MG_TV];
+#pragma unroll
+    for (int i = 0; i < MG_TA; ++i)
+#pragma unroll
+        for (int j = 0; j < MG_TV; ++j) acc[i][j] = 0.0;
+    for (int64_t row = (int64_t)blockIdx.y * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.y * 256) {
+        double a[MG_TA], v[MG_TV];
+#pragma unroll
+        for (int i = 0; i < MG_TA; ++i) a[i] = pa[i][row];
+#pragma unroll
+        for (int j = 0; j < MG_TV; ++j) v[j] = pv[j][row];
+#pragma unroll
+        for (int i = 0; i < MG_TA; ++i)
+#pragma unroll
+            for (int j = 0; j < MG_TV; ++j) acc[i][j] = fma(a[i], v[j], acc[i][j]);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < MG_TA; ++i)
+#pragma unroll
+        for (int j = 0; j < MG_TV; ++j) {
+            const double v = wave_sum(acc[i][j]);
+            if (lane == 0) red[w][i * MG_TV + j] = v;
+        }
+    __syncthreads();
+    if (threadIdx.x < MG_TA * MG_TV) {
+        const int i = threadIdx.x / MG_TV, j = threadIdx.x - i * MG_TV;
+        if (a0 + i < na && j < nv)
+            partials[((int64_t)blockIdx.y * na + a0 + i) * nv + j] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+}
+
+// G[e] = the partials of entry e added in workgroup order
+__global__ void __launch_bounds__(256) k_modal_gram_sum(int nPart, int count, const double *__restrict__ partials, double *__restrict__ G) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    double v = 0.0;
+    for (int b = 0; b < nPart; ++b) v += partials[(int64_t)b * count + e];
+    G[e] = v;
+}
+
+// Bp[j ldp + i] = B[j ldb + vars[i]]: the probe rows of the basis
+__global__ void __launch_bounds__(256) k_modal_gather_rows(int nProbe, int nb, const int64_t *__restrict__ vars, const double *__restrict__ B, int64_t ldb,
+                                                          double *__restrict__ Bp, int64_t ldp) {
+    const int64_t total = (int64_t)nProbe * nb;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+        const int64_t j = t / nProbe, i = t - j * nProbe;
+        Bp[j * ldp + i] = B[j * ldb + vars[i]];
+    }
+}
+
+// partials {|f - y|^2} over both planes (y null: |f|^2)
+__global__ void __launch_bounds__(256) k_modal_resnorm(int64_t n, const double *__restrict__ f, const double *__restrict__ y, int64_t ld, double *__restrict__ partials) {
+    __shared__ double red[8];
+    double acc[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double a = f[i] - (y ? y[i] : 0.0), b = f[ld + i] - (y ? y[ld + i] : 0.0);
+        acc[0] = fma(a, a, fma(b, b, acc[0]));
+    }
+    store_partials<1>(acc, red, partials);
+}
+
+int modal_np_for(int planesPerPass) { return planesPerPass <= 8 ? 8 : (planesPerPass <= 16 ? 16 : 32); }
+
+// out[p planeStride + row] for the planes [0, nPlanes) in passes of planesPerPass (1 .. 32) planes; C: device, nb rows of ldc doubles, zero beyond
+// nPlanes up to ldc >= nPlanes + 32
+void launch_modal_expand(int64_t n, const double *B, int64_t ldb, int nb, const double *C, int ldc, int nPlanes, int planesPerPass, double *out, int64_t planeStride,
+                         hipStream_t s) {
+    if (n <= 0 || nPlanes <= 0) return;
+    const dim3 grid(grid_for(n, MODAL_GRID_CAP)), block(256);
+    for (int p0 = 0; p0 < nPlanes; p0 += planesPerPass) {
+        const int np = std::min(planesPerPass, nPlanes - p0);
+        with_int<8, 16, 32>(modal_np_for(np), [&](auto NP) { launch_k(k_modal_expand<NP()>, grid, block, 0, s, n, B, ldb, nb, C, ldc, p0, np, out, planeStride); });
+    }
+    CHECK_LAUNCH();
+}
+
+// G (device, na x nv row-major) = A^T V; partials: scratch of MG_GRID_CAP * na * nv doubles
+void launch_modal_gram(int64_t n, const double *A, int64_t lda, int na, const double *V, int64_t ldv, int nv, double *partials, double *G, hipStream_t s) {
+    const int rows = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, MG_GRID_CAP)), count = na * nv;
+    hipLaunchKernelGGL(k_modal_gram, dim3((na + MG_TA - 1) / MG_TA, rows), dim3(256), 0, s, n, A, lda, na, V, ldv, nv, partials);
+    hipLaunchKernelGGL(k_modal_gram_sum, dim3((count + 255) / 256), dim3(256), 0, s, rows, count, (const double *)partials, G);
+    CHECK_LAUNCH();
+}
+
+}   // namespace
+}}   // namespace mfh::k
+
+using namespace mfh;
+using namespace mfhi;
+
+namespace {
+
+constexpr int MODAL_GROUP_MAX = 128;        // frequencies of a group at most (256 planes: C stays a few hundred KB)
+
+struct Cplx { double re, im; };
+Cplx cdivh(const Cplx &a, const Cplx &b) {
+    const double d = b.re * b.re + b.im * b.im;
+    return Cplx{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+}
+
+bool all_finite(const double *v, int64_t count) {
+    std::vector<uint8_t> bad((size_t)std::max(1, host_threads()) + 1, 0);
+    parallel_ranges(count, [&](int64_t b, int64_t e, int t) {
+        for (int64_t i = b; i < e; ++i)
+            if (!std::isfinite(v[i])) { bad[(size_t)std::min<int64_t>(t, (int64_t)bad.size() - 1)] = 1; break; }
+    });
+    for (uint8_t b : bad) if (b) return false;
+    return true;
+}
+
+std::vector<int64_t> sorted_fixed(const mfh_ctx *c) {
+    std::vector<int64_t> v(c->fixedVars);
+    std::sort(v.begin(), v.end());
+    return v;
+}
+
+// a basis is set and belongs to the state in force
+void require_basis(const mfh_ctx *c, const char *who) {
+    const mfh_ctx::ModalBasis &mb = c->modal;
+    if (mb.nModes <= 0 || !mb.B.p) throw Error(MFH_ERR_STATE, std::string(who) + ": no mode basis (mfh_modal_set_basis)");
+    if (!(c->geoValid && mb.geoGen == c->geoGen && mb.densityGen == c->densityGen && mb.n == (int64_t)c->bs() * c->nDoF))
+        throw Error(MFH_ERR_STATE, std::string(who) + ": the mode basis is stale (vertex positions, material, density field or DoF map changed since mfh_modal_set_basis)");
+    if (sorted_fixed(c) != mb.fixedSet)
+        throw Error(MFH_ERR_STATE, std::string(who) + ": the mode basis is stale (the set of fixed variables changed since mfh_modal_set_basis)");
+}
+
+// G (host, na x nCols row-major) = A^T (scale M V) for nCols vectors V (device, ldv apart) in batches of MG_TV columns through k_spmv_kron_acc and
+// the Gram kernel; scale == 0: G = A^T V, no mass product
+void gram_against(mfh_ctx *c, const double *A, int64_t ld, int na, const double *V, int64_t ldv, int nCols, double scale, double *G) {
+    hipStream_t s = c->stream;
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    DBuf<double> mv, part, g;
+    if (scale != 0.0) { mv.alloc((size_t)ld * k::MG_TV); mv.zero(s); }
+    part.alloc((size_t)k::MG_GRID_CAP * na * k::MG_TV);
+    g.alloc((size_t)na * k::MG_TV);
+    std::vector<double> hg((size_t)na * k::MG_TV);
+    for (int c0 = 0; c0 < nCols; c0 += k::MG_TV) {
+        const int nv = std::min(k::MG_TV, nCols - c0);
+        const double *v = V + (int64_t)c0 * ldv;
+        int64_t lv = ldv;
+        if (scale != 0.0) {
+            for (int j = 0; j < nv; ++j) k::launch_spmv_kron_acc(mass_spmv_args(c, false), false, 0.0, scale, v + (int64_t)j * ldv, mv.p + (int64_t)j * ld, nullptr, k::dyn_open(), s, c->dynGridCap);
+            v = mv.p; lv = ld;
+        }
+        k::launch_modal_gram(n, A, ld, na, v, lv, nv, part.p, g.p, s);
+        g.download(hg.data(), (size_t)na * nv, s);
+        for (int i = 0; i < na; ++i)
+            for (int j = 0; j < nv; ++j) G[(size_t)i * nCols + c0 + j] = hg[(size_t)i * nv + j];
+    }
+}
+
+void check_sweep_params(const mfh_ctx *c, const mfh_modal_harmonic_params *p, const double *omega, const double *zeta, const double *fRe, const int64_t *probeVars,
+                        int32_t nProbe, const double *probeOut) {
+    require(p != nullptr, MFH_ERR_INVALID, "mfh_modal_harmonic: params is null");
+    require(p->nFreq >= 0 && p->maxit > 0, MFH_ERR_INVALID, "mfh_modal_harmonic: nFreq >= 0, maxit > 0");
+    require(p->rayleighMass >= 0.0 && p->rayleighStiff >= 0.0 && std::isfinite(p->rayleighMass) && std::isfinite(p->rayleighStiff), MFH_ERR_INVALID,
+            "mfh_modal_harmonic: the Rayleigh coefficients are not negative");
+    require(p->lossFactor >= 0.0 && std::isfinite(p->lossFactor), MFH_ERR_INVALID, "mfh_modal_harmonic: the loss factor is not negative");
+    require(p->rtol > 0.0 && p->rtol < 1.0, MFH_ERR_INVALID, "mfh_modal_harmonic: 0 < rtol < 1");
+    require((p->flags & ~(MFH_MODAL_STATIC_CORRECTION | MFH_MODAL_RESIDUALS)) == 0, MFH_ERR_INVALID, "mfh_modal_harmonic: unknown flag");
+    require(p->residualStride >= 0, MFH_ERR_INVALID, "mfh_modal_harmonic: residualStride >= 0");
+    require(p->nFreq == 0 || omega != nullptr, MFH_ERR_INVALID, "mfh_modal_harmonic: omega is null");
+    require(fRe != nullptr, MFH_ERR_INVALID, "mfh_modal_harmonic: fRe is null");
+    for (int32_t k2 = 0; k2 < p->nFreq; ++k2) {
+        require(std::isfinite(omega[k2]) && omega[k2] >= 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: a frequency is negative or not finite");
+        require(omega[k2] > 0.0 || !c->fixedVars.empty(), MFH_ERR_INVALID, "mfh_modal_harmonic: omega = 0 needs fixed variables (K alone is singular)");
+    }
+    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeOut)), MFH_ERR_INVALID, "mfh_modal_harmonic: probes need their variables and their output");
+    const int64_t nv = (int64_t)c->bs() * c->nDoF;
+    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_harmonic: probe variable out of range");
+    require(!((p->flags & MFH_MODAL_RESIDUALS) && zeta), MFH_ERR_INVALID, "mfh_modal_harmonic: per-mode damping has no operator to take a residual against");
+    if (zeta)
+        for (int j = 0; j < c->modal.nModes; ++j) require(std::isfinite(zeta[j]) && zeta[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: a damping ratio is negative or not finite");
+}
+
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_modal_set_basis(mfh_ctx *c, int32_t nModes, const double *lambda, const double *X, double density, mfh_modal_basis_info *info) {
+    if (info) *info = mfh_modal_basis_info{};
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_set_basis: null context");
+    require(nModes >= 0 && nModes <= k::MODAL_MAXM, MFH_ERR_INVALID, "mfh_modal_set_basis: 0 <= nModes <= 256");
+    if (nModes == 0) { modal_drop(c); return MFH_OK; }
+    require(lambda && X, MFH_ERR_INVALID, "mfh_modal_set_basis: lambda and X are needed");
+    require(density > 0.0 && std::isfinite(density), MFH_ERR_INVALID, "mfh_modal_set_basis: density > 0");
+    for (int j = 0; j < nModes; ++j) require(std::isfinite(lambda[j]) && lambda[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_set_basis: an eigenvalue is negative or not finite");
+    prepare_pencil(c, "mfh_modal_set_basis");
+    const int64_t n = (int64_t)c->bs() * c->nDoF, ld = (n + 31) / 32 * 32;
+    require(all_finite(X, (int64_t)nModes * n), MFH_ERR_INVALID, "mfh_modal_set_basis: a mode has an entry that is not finite");
+    hipStream_t s = c->stream;
+    modal_drop(c);
+    WideGuard guard(c);
+    EventTimer tsetup(s);
+    prepare_pencil_state(c, "mfh_modal_set_basis", false);
+    mfh_ctx::ModalBasis &mb = c->modal;
+    mb.B.alloc((size_t)ld * (size_t)(nModes + 2));
+    mb.B.zero(s);
+    MFH_HIP(hipMemcpy2DAsync(mb.B.p, (size_t)ld * sizeof(double), X, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nModes, hipMemcpyHostToDevice, s));
+    if (!c->fixedVars.empty())
+        for (int j = 0; j < nModes; ++j) k::launch_mask(n, c->dFixedMask.p, mb.B.p + (int64_t)j * ld, s);
+    std::vector<double> G((size_t)nModes * nModes);
+    gram_against(c, mb.B.p, ld, nModes, mb.B.p, ld, nModes, density, G.data());
+    double defect = 0.0;
+    for (int i = 0; i < nModes; ++i)
+        for (int j = 0; j < nModes; ++j) {
+            const double e = std::fabs(G[(size_t)i * nModes + j] - (i == j ? 1.0 : 0.0));
+            defect = std::isfinite(e) ? std::max(defect, e) : e;
+        }
+    mb.nModes = nModes; mb.n = n; mb.ld = ld; mb.density = density;
+    mb.lambda.assign(lambda, lambda + nModes);
+    mb.geoGen = c->geoGen; mb.densityGen = c->densityGen;
+    mb.fixedSet = sorted_fixed(c);
+    if (info) {
+        info->nModes = nModes; info->ld = ld; info->orthoDefect = defect;
+        info->deviceBytes = (double)mb.B.n * sizeof(double);
+        info->setupMs = tsetup.stop();
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modal_coordinates(mfh_ctx *c, const double *u, int32_t nVec, double *q) {
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_coordinates: null context");
+    require(nVec >= 0, MFH_ERR_INVALID, "mfh_modal_coordinates: nVec >= 0");
+    prepare_pencil(c, "mfh_modal_coordinates");
+    require_basis(c, "mfh_modal_coordinates");
+    require(nVec == 0 || (u && q), MFH_ERR_INVALID, "mfh_modal_coordinates: u and q are needed");
+    if (nVec == 0) return MFH_OK;
+    hipStream_t s = c->stream;
+    WideGuard guard(c);
+    prepare_pencil_state(c, "mfh_modal_coordinates", false);
+    require_basis(c, "mfh_modal_coordinates");
+    const mfh_ctx::ModalBasis &mb = c->modal;
+    const int m = mb.nModes;
+    DBuf<double> du;
+    du.alloc((size_t)mb.ld * k::MG_TV);
+    du.zero(s);
+    std::vector<double> G((size_t)m * k::MG_TV);
+    for (int v0 = 0; v0 < nVec; v0 += k::MG_TV) {
+        const int nv = std::min(k::MG_TV, nVec - v0);
+        MFH_HIP(hipMemcpy2DAsync(du.p, (size_t)mb.ld * sizeof(double), u + (size_t)v0 * (size_t)mb.n, (size_t)mb.n * sizeof(double), (size_t)mb.n * sizeof(double), (size_t)nv,
+                                 hipMemcpyHostToDevice, s));
+        gram_against(c, mb.B.p, mb.ld, m, du.p, mb.ld, nv, mb.density, G.data());
+        for (int j = 0; j < nv; ++j)
+            for (int i = 0; i < m; ++i) q[(size_t)(v0 + j) * m + i] = G[(size_t)i * nv + j];
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, const double *omega, const double *modalDamping, const double *fRe, const double *fIm,
+                              const int64_t *probeVars, int32_t nProbe, double *probeOut, double *fields, double *modalCoords, double *trueResiduals,
+                              mfh_modal_harmonic_info *info) {
+    if (info) { *info = mfh_modal_harmonic_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_harmonic: null context");
+    check_sweep_params(c, prm, omega, modalDamping, fRe, probeVars, nProbe, probeOut);
+    const mfh_modal_harmonic_params P = *prm;
+    prepare_pencil(c, "mfh_modal_harmonic");
+    require_basis(c, "mfh_modal_harmonic");
+    const bool correct = (P.flags & MFH_MODAL_STATIC_CORRECTION) != 0, wantRes = (P.flags & MFH_MODAL_RESIDUALS) != 0;
+    const bool masked = !c->fixedVars.empty();
+    const int m = c->modal.nModes, nFreq = P.nFreq;
+    const int64_t n = c->modal.n, ld = c->modal.ld;
+    const std::vector<double> lam = c->modal.lambda;
+    const double density = c->modal.density;
+    if (correct) {
+        require(masked, MFH_ERR_UNSUPPORTED, "mfh_modal_harmonic: the static correction needs fixed variables (K alone is singular)");
+        for (int j = 0; j < m; ++j) require(lam[(size_t)j] > 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: the static correction needs lambda_j > 0");
+    }
+    // the denominators: nModes x nFreq complex scalars, refused before any device work where one is zero
+    std::vector<Cplx> dinv((size_t)std::max(nFreq, 1) * m);
+    for (int k2 = 0; k2 < nFreq; ++k2) {
+        const double w = omega[k2];
+        const Cplx zK{1.0, P.lossFactor + w * P.rayleighStiff};
+        for (int j = 0; j < m; ++j) {
+            const double l = lam[(size_t)j];
+            require(w > 0.0 || l > 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: omega = 0 with a zero eigenvalue in the basis");
+            const Cplx d{l * zK.re - w * w, l * zK.im + w * P.rayleighMass + (modalDamping ? 2.0 * modalDamping[j] * std::sqrt(l) * w : 0.0)};
+            require(d.re != 0.0 || d.im != 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: an undamped frequency sits on an eigenfrequency of the basis (d_j = 0)");
+            dinv[(size_t)k2 * m + j] = cdivh(Cplx{1.0, 0.0}, d);
+        }
+    }
+    hipStream_t s = c->stream;
+    c->modalNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modalNote.empty()) c->modalNote += "; "; c->modalNote += t; };
+    EventTimer tsetup(s);
+
+    // ---- the static solves, as mfh_solve makes them (outside the WideGuard: the context's own storage, solver and preconditioner)
+    int staticSolves = 0, staticIts = 0;
+    std::vector<double> us[2];
+    bool planeNonZero[2] = {false, false};
+    const double *fPlane[2] = {fRe, fIm};
+    for (int pl = 0; pl < 2; ++pl) {
+        if (!fPlane[pl]) continue;
+        const uint8_t *hm = masked ? c->hFixedMask.data() : nullptr;
+        for (int64_t i = 0; i < n && !planeNonZero[pl]; ++i) planeNonZero[pl] = fPlane[pl][i] != 0.0 && !(hm && hm[i]);
+    }
+    if (correct && (planeNonZero[0] || planeNonZero[1])) {
+        ensure_precond(c);
+        ensure_coarse_levels(c, 1);
+        require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modal_harmonic: unpartitioned contexts only");
+        require_basis(c, "mfh_modal_harmonic");
+        for (int pl = 0; pl < 2; ++pl) {
+            if (!planeNonZero[pl]) continue;
+            us[pl].resize((size_t)n);
+            mfh_solve_info li{};
+            const bool savedHom = c->solveHomogeneous;
+            c->solveHomogeneous = c->anyFixedNonzero;          // (the fixed variables are held at ZERO here, whatever values mfh_solve would hold them at)
+            try { solve_one(c, fPlane[pl], us[pl].data(), P.rtol, P.maxit, &li); }
+            catch (...) { c->solveHomogeneous = savedHom; throw; }
+            c->solveHomogeneous = savedHom;
+            ++staticSolves;
+            staticIts += li.iterations;
+            if (info) { info->staticSolves = staticSolves; info->staticIterations = staticIts; }
+            if (!li.converged) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modal_harmonic: the static solve of the correction did not reach rtol within maxit iterations");
+        }
+    }
+
+    std::optional<WideGuard> guard;        // (the operator product of the residuals alone needs both triangles: a sweep without them leaves the storage alone)
+    if (wantRes) {
+        guard.emplace(c);
+        if (guard->widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+        prepare_pencil_state(c, "mfh_modal_harmonic", false);
+        if (c->harmTwoPass) note("mass product of the residuals: two real passes and a combine kernel (option harmonic_two_pass)");
+    } else if (masked) ensure_fixed_uploaded(c);
+    require_basis(c, "mfh_modal_harmonic");
+    double *const B = c->modal.B.p;
+
+    // ---- the load, its modal coordinates g = Phi^T f^ and its norm
+    DBuf<double> dF, dPart, dScal;
+    dF.alloc((size_t)ld * 2);
+    dF.zero(s);
+    upload(dF.p, fRe, n, s);
+    if (fIm) upload(dF.p + ld, fIm, n, s);
+    if (masked) { k::launch_mask(n, c->dFixedMask.p, dF.p, s); k::launch_mask(n, c->dFixedMask.p, dF.p + ld, s); }
+    dPart.alloc((size_t)k::DYN_GRID_CAP * k::DYN_NV);
+    dScal.alloc((size_t)std::max(nFreq, 1) + 1);
+    dScal.zero(s);
+    const int vgrid = k::dyn_grid(n, std::max(1, std::min(c->dynGridCap, k::DYN_GRID_CAP)));
+    hipLaunchKernelGGL(k::k_modal_resnorm, dim3(vgrid), dim3(256), 0, s, n, (const double *)dF.p, (const double *)nullptr, ld, dPart.p);
+    CHECK_LAUNCH();
+    k::launch_sum(vgrid, dPart.p, k::dyn_open(), s, dScal.p + nFreq);
+    double hbb = 0.0;
+    MFH_HIP(hipMemcpyAsync(&hbb, dScal.p + nFreq, sizeof(double), hipMemcpyDeviceToHost, s));
+    MFH_HIP(hipStreamSynchronize(s));
+    require(std::isfinite(hbb), MFH_ERR_INVALID, "mfh_modal_harmonic: the load has an entry that is not finite");
+    std::vector<double> g((size_t)m * 2);
+    gram_against(c, B, ld, m, dF.p, ld, 2, 0.0, g.data());        // g[2 j + plane]
+
+    const int nb = staticSolves ? m + 2 : m;       // the two correction columns are streamed only where they hold something
+    // ---- the static correction r_s = u_s - sum_j phi_j g_j / lambda_j into the two reserved columns, through the expansion kernel itself
+    DBuf<double> dC, dTmp;
+    if (staticSolves) {
+        MFH_HIP(hipMemsetAsync(B + (int64_t)m * ld, 0, (size_t)ld * 2 * sizeof(double), s));
+        for (int pl = 0; pl < 2; ++pl)
+            if (planeNonZero[pl]) {
+                upload(B + (int64_t)(m + pl) * ld, us[pl].data(), n, s);
+                k::launch_mask(n, c->dFixedMask.p, B + (int64_t)(m + pl) * ld, s);
+            }
+        const int ldc = 64;
+        std::vector<double> hc((size_t)nb * ldc, 0.0);
+        for (int j = 0; j < m; ++j)
+            for (int pl = 0; pl < 2; ++pl) hc[(size_t)j * ldc + pl] = planeNonZero[pl] ? -(g[(size_t)2 * j + pl] / lam[(size_t)j]) : 0.0;
+        hc[(size_t)m * ldc + 0] = 1.0;
+        hc[(size_t)(m + 1) * ldc + 1] = 1.0;
+        dC.upload(hc, s);
+        dTmp.alloc((size_t)ld * 2);
+        dTmp.zero(s);
+        k::launch_modal_expand(n, B, ld, nb, dC.p, ldc, 2, k::MODAL_NP, dTmp.p, ld, s);
+        MFH_HIP(hipMemcpyAsync(B + (int64_t)m * ld, dTmp.p, (size_t)ld * 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        note("static correction: " + std::to_string(staticSolves) + " solve(s) of K u = f, " + std::to_string(staticIts) + " iterations");
+    }
+
+    // ---- probes: the rows of B at the probe variables, gathered once
+    DBuf<double> dBp, dProbe;
+    DBuf<int64_t> dProbeVars;
+    const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
+    if (nProbe && nFreq) {
+        dProbeVars.alloc((size_t)nProbe);
+        MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        dBp.alloc((size_t)ldp * nb);
+        dBp.zero(s);
+        hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, (int)nProbe, nb, (const int64_t *)dProbeVars.p, (const double *)B, ld,
+                           dBp.p, ldp);
+        CHECK_LAUNCH();
+        dProbe.alloc((size_t)nFreq * 2 * (size_t)nProbe);
+    }
+
+    // ---- the sweep, in groups of frequencies: staging rows {re plane, im plane} of n doubles each -- 256 MB as in mfh_harmonic, but the planes of
+    // one full pass of the kernel at least (the basis is streamed once per pass: a group of one frequency would read it for two planes)
+    const int64_t rowLen = 2 * n;
+    const bool staging = fields != nullptr || wantRes;
+    const int64_t rowsIn256MB = std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(rowLen, 1));
+    int groupCap = (int)std::min<int64_t>(MODAL_GROUP_MAX, staging ? std::max<int64_t>(k::MODAL_NP / 2, rowsIn256MB) : MODAL_GROUP_MAX);
+    DBuf<double> dStage, dX, dY, dT;
+    if (staging && nFreq) {
+        // where the device has no room for the rows of a full pass (5.7 GB at 22.3 M unknowns), the group shrinks to what 256 MB hold: more
+        // passes over the basis, the same bits
+        try { dStage.alloc((size_t)std::min(groupCap, nFreq) * (size_t)rowLen); }
+        catch (const Error &) {
+            if (groupCap <= rowsIn256MB) throw;
+            groupCap = (int)rowsIn256MB;
+            dStage.alloc((size_t)std::min(groupCap, nFreq) * (size_t)rowLen);
+            note("no device memory for the staging rows of a full pass: groups of " + std::to_string(groupCap) + " frequency(ies)");
+        }
+    }
+    const int ldc = 2 * groupCap + k::MODAL_NP_MAX;
+    if (wantRes) { dX.alloc((size_t)ld * 2); dY.alloc((size_t)ld * 2); dT.alloc((size_t)ld * 2); dX.zero(s); dY.zero(s); dT.zero(s); }
+    std::vector<double> hc((size_t)nb * ldc);
+    const int stride = std::max(1, (int)P.residualStride);
+    const double setupMs = tsetup.stop();
+
+    EventTimer tsolve(s);
+    int groups = 0;
+    for (int k0 = 0; k0 < nFreq; k0 += groupCap) {
+        const int gN = std::min(groupCap, nFreq - k0);
+        std::fill(hc.begin(), hc.end(), 0.0);
+        for (int kk = 0; kk < gN; ++kk) {
+            const int k2 = k0 + kk;
+            const double w = omega[k2];
+            for (int j = 0; j < m; ++j) {
+                const Cplx di = dinv[(size_t)k2 * m + j], gj{g[(size_t)2 * j], g[(size_t)2 * j + 1]};
+                const Cplx q{gj.re * di.re - gj.im * di.im, gj.re * di.im + gj.im * di.re};
+                hc[(size_t)j * ldc + 2 * kk] = q.re;
+                hc[(size_t)j * ldc + 2 * kk + 1] = q.im;
+                if (modalCoords) { modalCoords[((size_t)k2 * m + j) * 2] = q.re; modalCoords[((size_t)k2 * m + j) * 2 + 1] = q.im; }
+            }
+            if (staticSolves) {       // the real 2 x 2 form of 1 / zK on the two correction rows
+                const Cplx iz = cdivh(Cplx{1.0, 0.0}, Cplx{1.0, P.lossFactor + w * P.rayleighStiff});
+                hc[(size_t)m * ldc + 2 * kk] = iz.re;       hc[(size_t)(m + 1) * ldc + 2 * kk] = -iz.im;
+                hc[(size_t)m * ldc + 2 * kk + 1] = iz.im;   hc[(size_t)(m + 1) * ldc + 2 * kk + 1] = iz.re;
+            }
+        }
+        dC.upload(hc, s);
+        if (staging) k::launch_modal_expand(n, B, ld, nb, dC.p, ldc, 2 * gN, k::MODAL_NP, dStage.p, n, s);
+        if (nProbe) k::launch_modal_expand(nProbe, dBp.p, ldp, nb, dC.p, ldc, 2 * gN, k::MODAL_NP, dProbe.p + (size_t)k0 * 2 * (size_t)nProbe, nProbe, s);
+        if (wantRes)
+            for (int kk = 0; kk < gN; ++kk) {
+                const int k2 = k0 + kk;
+                if (k2 % stride != 0) continue;
+                const double w = omega[k2];
+                const double zK[2] = {1.0, P.lossFactor + w * P.rayleighStiff}, zM[2] = {-density * w * w, density * w * P.rayleighMass};
+                MFH_HIP(hipMemcpyAsync(dX.p, dStage.p + (size_t)kk * (size_t)rowLen, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+                MFH_HIP(hipMemcpyAsync(dX.p + ld, dStage.p + (size_t)kk * (size_t)rowLen + (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+                harmonic_product(c, masked, zK, zM, dX.p, dY.p, ld, dT.p);
+                hipLaunchKernelGGL(k::k_modal_resnorm, dim3(vgrid), dim3(256), 0, s, n, (const double *)dF.p, (const double *)dY.p, ld, dPart.p);
+                CHECK_LAUNCH();
+                k::launch_sum(vgrid, dPart.p, k::dyn_open(), s, dScal.p + k2);
+            }
+        if (fields)       // the rows leave 256 MB at a time (one row at least)
+            for (int64_t r0 = 0; r0 < gN; r0 += rowsIn256MB) {
+                const int64_t nr = std::min<int64_t>(rowsIn256MB, gN - r0);
+                MFH_HIP(hipMemcpyAsync(fields + (size_t)(k0 + r0) * (size_t)rowLen, dStage.p + (size_t)r0 * (size_t)rowLen, (size_t)nr * (size_t)rowLen * sizeof(double),
+                                       hipMemcpyDeviceToHost, s));
+            }
+        MFH_HIP(hipStreamSynchronize(s));
+        ++groups;
+    }
+    if (nProbe && nFreq) {          // device layout [frequency][plane][probe] -> probeOut [frequency][probe][{re, im}]
+        std::vector<double> hp((size_t)nFreq * 2 * (size_t)nProbe);
+        dProbe.download(hp.data(), hp.size(), s);
+        for (int k2 = 0; k2 < nFreq; ++k2)
+            for (int j = 0; j < nProbe; ++j)
+                for (int pl = 0; pl < 2; ++pl) probeOut[((size_t)k2 * nProbe + j) * 2 + pl] = hp[((size_t)k2 * 2 + pl) * nProbe + j];
+    }
+    double worst = 0.0;
+    if (trueResiduals) std::fill(trueResiduals, trueResiduals + nFreq, -1.0);
+    if (wantRes && nFreq) {
+        std::vector<double> hr((size_t)nFreq);
+        dScal.download(hr.data(), (size_t)nFreq, s);
+        for (int k2 = 0; k2 < nFreq; k2 += stride) {
+            const double t = hbb > 0.0 ? std::sqrt(hr[(size_t)k2] / hbb) : 0.0;
+            if (trueResiduals) trueResiduals[k2] = t;
+            worst = std::isfinite(t) ? std::max(worst, t) : t;
+        }
+    }
+    const double solveMs = tsolve.stop();
+    if (info) {
+        info->staticSolves = staticSolves; info->staticIterations = staticIts;
+        info->groups = groups; info->planesPerPass = k::MODAL_NP;
+        info->worstTrueResidual = worst; info->setupMs = setupMs; info->solveMs = solveMs;
+        info->note = c->modalNote.c_str();
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modal_basis_state(mfh_ctx *c, int32_t *nModes, int32_t *valid) {
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_basis_state: null context");
+    if (nModes) *nModes = c->modal.nModes;
+    if (valid) {
+        *valid = 0;
+        if (c->modal.nModes > 0) {
+            try { require_basis(c, "mfh_modal_basis_state"); *valid = 1; } catch (const Error &) {}
+        }
+    }
+    MFH_CATCH(c)
+}
+
+// ---- hooks (include/meshfem_hip_extras.h)
+mfh_status mfh_debug_modal_gram(mfh_ctx *c, int64_t n, int32_t na, int32_t nv, const double *A, const double *V, double *G) {
+    MFH_TRY(c)
+    require(c && A && V && G && n >= 1 && na >= 1 && na <= k::MODAL_MAXB && nv >= 1 && nv <= k::MG_TV, MFH_ERR_INVALID, "mfh_debug_modal_gram: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    DBuf<double> a, v, part, g;
+    a.alloc((size_t)ld * na); v.alloc((size_t)ld * nv); part.alloc((size_t)k::MG_GRID_CAP * na * nv); g.alloc((size_t)na * nv);
+    const size_t rowBytes = (size_t)n * sizeof(double), ldBytes = (size_t)ld * sizeof(double);
+    MFH_HIP(hipMemcpy2DAsync(a.p, ldBytes, A, rowBytes, rowBytes, (size_t)na, hipMemcpyHostToDevice, s));
+    MFH_HIP(hipMemcpy2DAsync(v.p, ldBytes, V, rowBytes, rowBytes, (size_t)nv, hipMemcpyHostToDevice, s));
+    k::launch_modal_gram(n, a.p, ld, na, v.p, ld, nv, part.p, g.p, s);
+    g.download(G, (size_t)na * nv, s);
+    MFH_CATCH(c)
+}
+mfh_status mfh_debug_modal_expand(mfh_ctx *c, int64_t n, int32_t nb, const double *Bh, const double *Ch, int32_t nPlanes, int32_t planesPerPass, double *out) {
+    MFH_TRY(c)
+    require(c && Bh && Ch && out && n >= 1 && nb >= 1 && nb <= k::MODAL_MAXB && nPlanes >= 1 && nPlanes <= 4096 && planesPerPass >= 0 && planesPerPass <= k::MODAL_NP_MAX,
+            MFH_ERR_INVALID, "mfh_debug_modal_expand: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    const int ldc = nPlanes + k::MODAL_NP_MAX;
+    DBuf<double> b, cc, o;
+    b.alloc((size_t)ld * nb); o.alloc((size_t)nPlanes * (size_t)n);
+    b.zero(s);
+    const size_t rowBytes = (size_t)n * sizeof(double);
+    MFH_HIP(hipMemcpy2DAsync(b.p, (size_t)ld * sizeof(double), Bh, rowBytes, rowBytes, (size_t)nb, hipMemcpyHostToDevice, s));
+    std::vector<double> hc((size_t)nb * ldc, 0.0);
+    for (int j = 0; j < nb; ++j)
+        for (int p = 0; p < nPlanes; ++p) hc[(size_t)j * ldc + p] = Ch[(size_t)j * nPlanes + p];
+    cc.upload(hc, s);
+    k::launch_modal_expand(n, b.p, ld, nb, cc.p, ldc, nPlanes, planesPerPass ? planesPerPass : k::MODAL_NP, o.p, n, s);
+    o.download(out, (size_t)nPlanes * (size_t)n, s);
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_time_modal_expand(mfh_ctx *c, int64_t n, int32_t nb, int32_t planesPerPass, int32_t reps, double *times) {
+    MFH_TRY(c)
+    require(c && times && n >= 1 && reps >= 1 && nb >= 1 && nb <= k::MODAL_MAXB && (planesPerPass == 0 || planesPerPass == 8 || planesPerPass == 16 || planesPerPass == 32),
+            MFH_ERR_INVALID, "mfh_time_modal_expand: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int np = planesPerPass ? planesPerPass : k::MODAL_NP;
+    const int64_t ld = (n + 31) / 32 * 32;
+    const int ldc = np + k::MODAL_NP_MAX;
+    DBuf<double> b, cc, o;
+    b.alloc((size_t)ld * nb); o.alloc((size_t)ld * np); cc.alloc((size_t)nb * ldc);
+    k::launch_fill_hash((int64_t)b.n, b.p, s);
+    k::launch_fill_hash((int64_t)cc.n, cc.p, s);
+    for (int r = 0; r < 2; ++r) k::launch_modal_expand(n, b.p, ld, nb, cc.p, ldc, np, np, o.p, ld, s);      // warm-up
+    MFH_HIP(hipStreamSynchronize(s));
+    for (int r = 0; r < reps; ++r) {
+        EventTimer t(s);
+        k::launch_modal_expand(n, b.p, ld, nb, cc.p, ldc, np, np, o.p, ld, s);
+        times[r] = t.stop();
+    }
+    MFH_CATCH(c)
+}
+
+}   // extern "C"

@@ -528,6 +528,54 @@ class Simulator:
         del out["info"]
         return out
 
+    def modalFrequencyResponse(self, omegas, n_modes=None, modes=None, load=None, density=1.0, damping=(0, 0), loss_factor=0.0, modal_damping=None,
+                               static_correction=True, residual_stride=None, probes=None, fields=True, rtol=None, maxit=None, modes_rtol=1e-6,
+                               batch=0):
+        """frequencyResponse by superposition of the lowest modes (mfh_modal_harmonic, docs/design/04_21_modal_superposition.md): the same system,
+        load, clamp, damping, probes and return value, at the cost of one pass over the resident mode basis per group of frequencies. n_modes: the
+        basis is computed here (vibrational_modes_many's solver, up to 256 modes, modes_rtol / batch) and stays on the device; modes=(lam, X):
+        M-orthonormal eigenpairs the caller has, per-DoF rows [m, nDoF * N]; neither: the basis of the previous call, which must still be valid:
+        the same set of Dirichlet variables (calls in between that re-apply the same clamp, such as solve or frequencyResponse, keep it), mesh,
+        vertex positions, material and density field -- a per-element `density` array in any call in between sets the field anew and makes
+        the basis stale; the call then raises with code ERR_STATE (ctx.modal_basis_state() tells beforehand). static_correction: one static solve per load plane at rtol / maxit stands in for the truncated
+        modes (clamped bodies only). modal_damping: damping ratios per mode (a scalar or one per mode). residual_stride: None, or k >= 0 for the
+        true residual ||f^ - Z u^|| / ||f^|| at every k-th frequency (0: every one). Returns a dict: "u", "probes", "modal_coords" [nFreq, m],
+        "true_residuals" (-1 where none was computed). self.modal_info holds the solver's record, self.modal_frequencies the basis's sqrt(lam) /
+        2 pi where it was set here."""
+        ctx = self.ctx
+        density = self._density_scalar(density)
+        mapped = ctx.n_dof != ctx.n_node
+        dof = ctx.get_dof_map()[0] if mapped else None
+        if n_modes is not None or modes is not None:
+            v, _ = ctx.bc_dirichlet_vars()
+            ctx.clear_fixed()
+            if len(v):
+                ctx.fix_variables(v)
+            if modes is not None:
+                lam, X = modes
+                self.modal_basis_info = ctx.set_modal_basis(lam, np.asarray(X, dtype=np.float64).reshape(len(lam), -1), density=density)
+            else:
+                lam, X, info = ctx.modal_basis(int(n_modes), density=density, free=len(v) == 0, batch=batch, rtol=modes_rtol)
+                self.modes_many_info, self.modal_basis_info = info, info["modal_basis"]
+            self.modal_frequencies = np.sqrt(np.asarray(lam)) / (2.0 * np.pi)
+        f = self.neumannLoad() if load is None else np.asarray(load).reshape(ctx.n_dof, self.N)
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        try:
+            r = ctx.modal_harmonic(omegas, f, damping=damping, loss_factor=loss_factor, modal_damping=modal_damping, static_correction=static_correction,
+                                   residual_stride=residual_stride, rtol=self.rtol if rtol is None else rtol, maxit=self.maxit if maxit is None else maxit,
+                                   probes=pv, fields=fields)
+        finally:
+            self.modal_info = getattr(ctx, "last_modal_harmonic", {}).get("info")
+        out = dict(r)
+        if r["u"] is not None:
+            u = r["u"].reshape(len(r["u"]), ctx.n_dof, self.N)
+            out["u"] = u[:, dof, :] if mapped else u
+        del out["info"]
+        return out
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 

@@ -1,0 +1,73 @@
+"""modalFrequencyResponse of include/MeshFEMHip/Harmonic.hh compiles with plain g++ against the C ABI; on the GPU, over a quadratic Simulator clamped on
+one face and pulled on the opposite one, it returns what the Python layer's modalFrequencyResponse returns for the same mesh, conditions, mode count
+and frequencies: 1e-12 relative -- the same code path, only the call marshalling differs (both sides run with option deterministic 1, so that two
+processes add in the same order)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import meshfem_amd as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = "facade_modal"
+EXE = os.path.join(ROOT, "tests", "cpp", NAME)
+
+
+def _build():
+    src = os.path.join(ROOT, "tests", "cpp", NAME + ".cc")
+    libdir = os.path.dirname(M.LIB_PATH)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-o", EXE,
+                           "-L", libdir, "-lmeshfem_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+
+
+def test_header_compiles_and_throws_without_device():
+    _build()
+    r = subprocess.run([EXE, "-1"], capture_output=True, text=True)
+    assert r.returncode == 3 and "runtime_error" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_facade_matches_the_python_layer(tmp_path):
+    from oracle import meshfem_oracle as O
+    from meshfem_amd import _lib as L
+    from meshfem_amd.linear_elasticity import Simulator
+    _build()
+    V, T = O.grid_tet_mesh(3, 2, 2)                      # unperturbed: the clamp and the loaded face are boxes of the faces x = min / max
+    with open(tmp_path / "mesh.bin", "wb") as f:
+        np.array([len(V), len(T)], dtype=np.int64).tofile(f)
+        np.ascontiguousarray(V, dtype=np.float64).tofile(f)
+        np.ascontiguousarray(T, dtype=np.int32).tofile(f)
+    density, omegas = 2.5, [0.0, 0.05, 0.3]
+    r = subprocess.run([EXE, "0", str(tmp_path / "mesh.bin"), repr(density)] + [repr(w) for w in omegas] + [str(tmp_path / "out.bin")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0 and "modal ok" in r.stdout, r.stdout + r.stderr
+    out = np.fromfile(tmp_path / "out.bin")
+    sim = Simulator(T, V, 2)
+    sim.ctx.set_option("deterministic", 1)
+    sim.setIsotropicMaterial(1.0, 0.3)
+    sim.applyDirichletBox([-1e-9] * 3, [1e-9, 1 + 1e-9, 1 + 1e-9], [0, 0, 0], relative=True)
+    sim.applyNeumannBox([1 - 1e-9, -1e-9, -1e-9], [1 + 1e-9] * 3, [0, 0, -1.0], kind=L.NEUMANN_TRACTION, relative=True)
+    nn = sim.numNodes()
+    res = sim.modalFrequencyResponse(omegas, n_modes=8, density=density, damping=(0.05, 0.01), loss_factor=0.02, residual_stride=2,
+                                     probes=[(nn - 1, 2), (nn // 2, 0)], rtol=1e-10, maxit=10000)
+    assert sim.modal_info["staticSolves"] == 1 and sim.modal_basis_info["nModes"] == 8
+    assert res["u"].shape == (3, nn, 3) and np.iscomplexobj(res["u"]) and np.abs(res["u"].imag).max() > 0
+    assert np.array_equal(res["probes"][:, 0], res["u"][:, nn - 1, 2]) and np.array_equal(res["probes"][:, 1], res["u"][:, nn // 2, 0])
+    assert res["modal_coords"].shape == (3, 8)
+    assert res["true_residuals"][1] == -1.0 and res["true_residuals"][0] >= 0.0 and res["true_residuals"][2] >= 0.0
+    # the basis of that call serves a second sweep without being set again
+    again = sim.modalFrequencyResponse(omegas, damping=(0.05, 0.01), loss_factor=0.02, residual_stride=2, probes=[(nn - 1, 2), (nn // 2, 0)],
+                                       rtol=1e-10, maxit=10000)
+    assert np.array_equal(again["u"], res["u"])
+    lam = (2.0 * np.pi * sim.modal_frequencies) ** 2
+    parts = [res["u"].reshape(-1).view(np.float64), res["probes"].reshape(-1).view(np.float64), res["modal_coords"].reshape(-1).view(np.float64),
+             res["true_residuals"], lam]
+    assert out.size == sum(p.size for p in parts)
+    at = 0
+    for name, w in zip(("u", "probes", "modal_coords", "true_residuals", "lambda"), parts):
+        g = out[at:at + w.size]
+        at += w.size
+        assert np.abs(g - w).max() <= 1e-12 * np.abs(w).max(), name
+    sim.ctx.close()
