@@ -203,4 +203,124 @@ ExplicitResult<typename Sim::VField> explicitTransient(const Sim &sim, int nStep
     return r;
 }
 
+// ---- modal transient response (include/meshfem_hip.h, "modal superposition"; docs/design/04_22_modal_transient.md): the load history taken as piecewise
+// linear between the steps and every mode of a basis that stays on the device stepped exactly -- no stability limit, no period error.
+//   modalTransient(sim, dt, nSteps, opt)   clamp, load, amplitude, probes and snapshots as for transient. The basis: opt.nModes modes computed here
+//                                          (mfh_modes_many), or the eigenpairs the caller hands in (opt.lambda, opt.modes), or -- opt.keepBasis -- the one
+//                                          an earlier call left on the device. Start: opt.u0 / v0 (projected with mfh_modal_coordinates) or the modal
+//                                          state opt.q0 / qdot0 of an earlier result, not both; neither: rest. opt.staticCorrection: one static solve at
+//                                          opt.rtol / opt.maxit stands in for the truncated modes (clamped bodies only).
+template <class VField>
+struct ModalTransientOptions {
+    Real density = 1.0, rayleighMass = 0.0, rayleighStiff = 0.0;
+    int nModes = 16;                                      // modes computed here when lambda is empty (1 .. 256)
+    int batch = 0;
+    Real modesRtol = 1e-6;
+    bool keepBasis = false;                               // use the basis in place (of an earlier modalTransient / modalFrequencyResponse)
+    std::vector<Real> lambda;                             // eigenpairs of (K, density M) the caller has: M-orthonormal per-DoF rows
+    std::vector<VField> modes;
+    std::vector<Real> modalDamping;                       // damping ratios per mode; empty: none
+    bool staticCorrection = true;
+    Real rtol = 1e-8;                                     // of the static solve
+    int maxit = 10000;
+    std::vector<Real> amplitude;                          // nSteps + 1 values, or empty (= 1)
+    VField u0, v0;                                        // one N-vector per DoF, or empty
+    std::vector<Real> q0, qdot0;                          // the modal state of an earlier result, or empty
+    VField load;                                          // f; empty: neumannLoad()
+    std::vector<std::pair<size_t, int>> probes;
+    int snapshotStride = 0;
+    bool modalCoords = false, energies = false;
+    int chunkSteps = 0;                                   // steps per launch on the device (0: the default; a multiple of 32); changes no result
+};
+
+template <class VField>
+struct ModalTransientResult {
+    std::vector<Real> q, qdot;                            // the modal state after the last step
+    std::vector<std::vector<Real>> probes;                // [nSteps + 1][number of probes]
+    std::vector<VField> snapshots;
+    std::vector<std::vector<Real>> modalCoords;           // [nSteps + 1][nModes]
+    std::vector<std::array<Real, 3>> energies;            // [nSteps + 1]: 1/2 sum qdot^2, 1/2 sum lambda q^2, a sum g q
+    mfh_modal_transient_info info{};
+};
+
+template <class Sim>
+ModalTransientResult<typename Sim::VField> modalTransient(const Sim &sim, Real dt, int nSteps,
+                                                          const ModalTransientOptions<typename Sim::VField> &opt = ModalTransientOptions<typename Sim::VField>()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    mfh_ctx *c = sim.ctx();
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N, rows = (size_t)(nSteps > 0 ? nSteps : 0) + 1;
+    if (!opt.keepBasis) {
+        detail::clampDirichlet(c);
+        int64_t nv = 0;
+        check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
+        std::vector<Real> lambda, X;
+        if (opt.lambda.empty()) {
+            mfh_modes_many_params mp{};
+            mp.nev = opt.nModes; mp.batch = opt.batch; mp.flags = nv > 0 ? 0 : MFH_MODES_FREE; mp.maxit = 3000;
+            mp.density = opt.density; mp.rtol = opt.modesRtol;
+            lambda.assign((size_t)std::max(opt.nModes, 0), 0.0);
+            X.assign(lambda.size() * n, 0.0);
+            mfh_modes_many_info mi{};
+            check(c, mfh_modes_many(c, &mp, nullptr, lambda.data(), X.data(), nullptr, &mi));
+        } else {
+            if (opt.modes.size() != opt.lambda.size()) throw std::runtime_error("modalTransient: one mode per eigenvalue");
+            lambda = opt.lambda;
+            X.resize(lambda.size() * n);
+            for (size_t j = 0; j < opt.modes.size(); ++j) {
+                if (opt.modes[j].size() != nDoF) throw std::runtime_error("modalTransient: a mode needs one entry per DoF");
+                std::copy(&opt.modes[j][0][0], &opt.modes[j][0][0] + n, X.begin() + (std::ptrdiff_t)(j * n));
+            }
+        }
+        mfh_modal_basis_info bi{};
+        check(c, mfh_modal_set_basis(c, (int32_t)lambda.size(), lambda.data(), X.data(), opt.density, &bi));
+    }
+    int32_t mm = 0, valid = 0;
+    check(c, mfh_modal_basis_state(c, &mm, &valid));
+    const size_t m = (size_t)mm;
+    if (!opt.modalDamping.empty() && opt.modalDamping.size() != m) throw std::runtime_error("modalTransient: one damping ratio per mode");
+    if ((!opt.q0.empty() || !opt.qdot0.empty()) && (!opt.u0.empty() || !opt.v0.empty())) throw std::runtime_error("modalTransient: the start is q0 / qdot0 or u0 / v0, not both");
+    if (!opt.amplitude.empty() && opt.amplitude.size() != rows) throw std::runtime_error("modalTransient: amplitude needs nSteps + 1 values");
+    if (!opt.load.empty() && opt.load.size() != nDoF) throw std::runtime_error("modalTransient: load needs one entry per DoF");
+    ModalTransientResult<VField> r;
+    r.q.assign(m, 0.0); r.qdot.assign(m, 0.0);
+    auto modal = [&](const std::vector<Real> &x, std::vector<Real> &y, const char *name) {
+        if (x.empty()) return;
+        if (x.size() != m) throw std::runtime_error(std::string("modalTransient: ") + name + " needs one entry per mode");
+        y = x;
+    };
+    modal(opt.q0, r.q, "q0"); modal(opt.qdot0, r.qdot, "qdot0");
+    auto project = [&](const VField &x, std::vector<Real> &y, const char *name) {
+        if (x.empty()) return;
+        if (x.size() != nDoF) throw std::runtime_error(std::string("modalTransient: ") + name + " needs one entry per DoF");
+        check(c, mfh_modal_coordinates(c, &x[0][0], 1, y.data()));
+    };
+    project(opt.u0, r.q, "u0"); project(opt.v0, r.qdot, "v0");
+    const VField f = opt.load.empty() ? sim.neumannLoad() : opt.load;
+    std::vector<int64_t> probeVars;
+    for (const auto &p : opt.probes) probeVars.push_back((int64_t)(p.first * N) + p.second);
+    const size_t nProbe = probeVars.size(), nSnap = opt.snapshotStride > 0 ? (rows - 1) / (size_t)opt.snapshotStride + 1 : 0;
+    std::vector<Real> probeOut(rows * nProbe), snaps(nSnap * n), mc(opt.modalCoords ? rows * m : 0), en(opt.energies ? rows * 3 : 0);
+    mfh_modal_transient_params prm{};
+    prm.dt = dt; prm.rayleighMass = opt.rayleighMass; prm.rayleighStiff = opt.rayleighStiff; prm.rtol = opt.rtol;
+    prm.nSteps = nSteps; prm.maxit = opt.maxit; prm.snapshotStride = nSnap ? opt.snapshotStride : 0; prm.chunkSteps = opt.chunkSteps;
+    prm.flags = (opt.staticCorrection ? MFH_MODAL_TR_STATIC_CORRECTION : 0) | (opt.energies ? MFH_MODAL_TR_ENERGIES : 0);
+    check(c, mfh_modal_transient(c, &prm, opt.modalDamping.empty() ? nullptr : opt.modalDamping.data(), m ? r.q.data() : nullptr, m ? r.qdot.data() : nullptr,
+                                 &f[0][0], opt.amplitude.empty() ? nullptr : opt.amplitude.data(), nProbe ? probeVars.data() : nullptr, (int32_t)nProbe,
+                                 nProbe ? probeOut.data() : nullptr, nSnap ? snaps.data() : nullptr, mc.empty() ? nullptr : mc.data(),
+                                 opt.energies ? en.data() : nullptr, &r.info));
+    r.probes.assign(rows, std::vector<Real>(nProbe));
+    for (size_t k = 0; k < rows; ++k)
+        for (size_t j = 0; j < nProbe; ++j) r.probes[k][j] = probeOut[k * nProbe + j];
+    r.snapshots.assign(nSnap, VField(nDoF));
+    for (size_t k = 0; k < nSnap; ++k) std::copy(snaps.begin() + k * n, snaps.begin() + (k + 1) * n, &r.snapshots[k][0][0]);
+    if (opt.modalCoords) {
+        r.modalCoords.assign(rows, std::vector<Real>(m));
+        for (size_t k = 0; k < rows; ++k) std::copy(mc.begin() + k * m, mc.begin() + (k + 1) * m, r.modalCoords[k].begin());
+    }
+    r.energies.resize(opt.energies ? rows : 0);
+    for (size_t k = 0; k < r.energies.size(); ++k) r.energies[k] = {en[3 * k], en[3 * k + 1], en[3 * k + 2]};
+    return r;
+}
+
 } // namespace MeshFEMHip

@@ -763,6 +763,49 @@ mfh_status mfh_modal_harmonic(mfh_ctx* ctx, const mfh_modal_harmonic_params* par
                               double* modalCoords,                      /* nFreq x nModes x {re, im}, or NULL */
                               double* trueResiduals,                    /* nFreq, or NULL */
                               mfh_modal_harmonic_info* info);
+/* Modal transient response on the same basis (docs/design/04_22_modal_transient.md): the load g(t) f with amplitude[n] at t_n = n dt taken as piecewise
+ * linear between the steps; every mode obeys
+ *     q_j'' + c_j q_j' + lambda_j q_j = (phi_j^T f) a(t),   c_j = rayleighMass + rayleighStiff lambda_j + 2 zeta_j sqrt(lambda_j),
+ * and is stepped exactly: [q ; q']_{n+1} = A_j [q ; q']_n + g_j (b0_j a_n + b1_j (a_{n+1} - a_n) / dt). No stability limit, no period error; with the
+ * full basis the result is the exact solution of the semi-discrete system for that load. u(t_n) = sum_j phi_j q_j(n) [+ r_s a_n] with the static
+ * correction r_s of mfh_modal_harmonic (real plane; MFH_MODAL_TR_STATIC_CORRECTION: one solve K u_s = f at rtol / maxit, needs fixed variables --
+ * MFH_ERR_UNSUPPORTED -- and lambda_j > 0 -- MFH_ERR_INVALID; MFH_ERR_NOT_CONVERGED, nothing written, if it fails).
+ *   q, qdot        nModes each: the state at step 0 in, the state after the last step out; both NULL: from rest, no state returned. Two calls
+ *                  chained through them continue a run (the second call's amplitude[0] is the first's last value): row 0 of the second call equals
+ *                  the last row of the first and everything after it equals the single call bit for bit, whatever chunkSteps is.
+ *   probeOut       (nSteps+1) x nProbe, the displacement at the variables probeVars: bit for bit the snapshot entries
+ *   snapshots      every snapshotStride-th step from step 0, dim*nDoF each, or NULL; modalCoords: (nSteps+1) x nModes or NULL
+ *   energies       (nSteps+1) x {1/2 sum q_j'^2, 1/2 sum lambda_j q_j^2, a_n sum g_j q_j}: mfh_newmark's triple restricted to the retained modes; the
+ *                  array and MFH_MODAL_TR_ENERGIES come together
+ *   chunkSteps     steps the device takes per launch (0: the default; otherwise a positive multiple of 32): no influence on any result
+ * MFH_ERR_INVALID before any device work: null params, dt <= 0 or not finite, a negative count or stride, a negative Rayleigh coefficient or zeta,
+ * an unknown flag, a chunkSteps that is neither 0 nor a positive multiple of 32, only one of q / qdot, energies without their flag or the flag
+ * without the array, snapshots without a stride, a probe variable out of range, an amplitude, load or state entry that is not finite.
+ * MFH_ERR_STATE: no basis or a stale one, by the rules above. nSteps = 0 returns row 0 of every output. Contexts as for mfh_modal_harmonic. */
+enum { MFH_MODAL_TR_STATIC_CORRECTION = 1, MFH_MODAL_TR_ENERGIES = 2 };
+typedef struct mfh_modal_transient_params {
+    double dt, rayleighMass, rayleighStiff, rtol;                                      /* rtol, maxit: the static solve */
+    int32_t nSteps, maxit, snapshotStride, chunkSteps, flags, reserved;
+} mfh_modal_transient_params;
+typedef struct mfh_modal_transient_info {
+    int32_t stepsDone, staticSolves, staticIterations, chunkSteps, chunks, reserved;
+    double setupMs, marchMs, seriesMs, expandMs;
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_modal_transient_info;
+mfh_status mfh_modal_transient(mfh_ctx* ctx, const mfh_modal_transient_params* params,
+                               const double* modalDamping,               /* nModes or NULL */
+                               double* q, double* qdot,                  /* nModes each, or both NULL */
+                               const double* f,                          /* dim*nDoF */
+                               const double* amplitude,                  /* nSteps+1, or NULL (= 1) */
+                               const int64_t* probeVars, int32_t nProbe, double* probeOut,  /* (nSteps+1) x nProbe */
+                               double* snapshots,                        /* (nSteps/snapshotStride + 1) x dim*nDoF, or NULL */
+                               double* modalCoords,                      /* (nSteps+1) x nModes, or NULL */
+                               double* energies,                         /* (nSteps+1) x 3, or NULL */
+                               mfh_modal_transient_info* info);
+/* host only, no context: the eight coefficients {A11, A12, b0_q, b1_q, A21, A22, b0_v, b1_v} of one mode: the first two rows of
+ * exp(dt [[0,1,0,0],[-lambda,-c,1,0],[0,0,0,1],[0,0,0,0]]), for lambda >= 0 (0: a rigid mode), c >= 0 (under-damped, critical, over-damped) and
+ * dt > 0, each within a few ulps of its natural size (MFH_ERR_INVALID otherwise) */
+mfh_status mfh_modal_transient_coeffs(double lambda, double c, double dt, double* out8);
 
 /* ---------------------------------------------------------------- per-element density, the product with M, mass properties
  * (docs/design/04_15_density.md.) The mass matrix of mfh_modes and mfh_newmark is assembled from a density field of the context:

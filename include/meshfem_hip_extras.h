@@ -113,6 +113,17 @@ mfh_status mfh_debug_modal_gram(mfh_ctx* ctx, int64_t n, int32_t na, int32_t nv,
 /* device time (ms, one entry per repetition) of one pass of k_modal_expand<NP> (NP = planesPerPass in {8, 16, 32}; 0 = the default) on nb hashed
  * columns of n rows; mfh_time_deflate times k_deflate_update on the same shape in the same process (scripts/probe_modal.py) */
 mfh_status mfh_time_modal_expand(mfh_ctx* ctx, int64_t n, int32_t nb, int32_t planesPerPass, int32_t reps, double* times);
+/* test hook: the two kernels of mfh_modal_transient (k_modal_march, k_modal_series, mfh_modal.hip) on host arrays, run as the call runs them; needs no
+ * mesh. coef8: nModes x 8 (rows as mfh_modal_transient_coeffs writes them), g: nModes, lambda: nModes (for the energies; NULL without), amplitude:
+ * nSteps+1, chunkSteps: 0 = the default, else a positive multiple of 32; q, qdot: nModes each, state in / state after the last step out.
+ * Bp: (nModes + corr) x nProbe row-major, row j = column j of the basis at the probe variables (corr = 1: one more row, the correction column).
+ * Out (NULL: not wanted): modalCoords (nSteps+1) x nModes, probeOut (nSteps+1) x nProbe, energies (nSteps+1) x 3 */
+mfh_status mfh_debug_modal_march(mfh_ctx* ctx, int32_t nModes, const double* coef8, const double* g, const double* lambda, double dt, int32_t nSteps,
+                                 const double* amplitude, int32_t chunkSteps, double* q, double* qdot, const double* Bp, int32_t nProbe, int32_t corr,
+                                 double* modalCoords, double* probeOut, double* energies);
+/* device time (ms, one entry per repetition each) of k_modal_series and of the k_modal_expand route (the gathered probe rows as the kernel's rows, 32
+ * steps per pass) for nProbe probes of nSteps rows on nModes hashed columns, the two taking turns in every repetition */
+mfh_status mfh_time_modal_series(mfh_ctx* ctx, int32_t nModes, int32_t nProbe, int32_t nSteps, int32_t reps, double* seriesMs, double* expandMs);
 
 /* test hooks: the step kernels of mfh_newmark (mfh_dynamics.hip) on host arrays of n doubles. mask: n bytes or NULL (non-zero = fixed variable).
  * predict: ut = u + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a (both 0 where masked), w = gamma / (beta dt) ut - vt,

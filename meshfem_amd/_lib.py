@@ -24,6 +24,7 @@ DYN_HAVE_ACCEL, DYN_ENERGIES = 1, 2
 EXP_HAVE_ACCEL, EXP_ENERGIES, EXP_NO_DT_CHECK = 1, 2, 4
 HARM_WARM_START = 1
 MODAL_STATIC_CORRECTION, MODAL_RESIDUALS = 1, 2
+MODAL_TR_STATIC_CORRECTION, MODAL_TR_ENERGIES = 1, 2
 
 
 class SamplerGridInfo(C.Structure):
@@ -155,6 +156,22 @@ class ModalHarmonicParams(C.Structure):
 class ModalHarmonicInfo(C.Structure):
     _fields_ = [("staticSolves", C.c_int32), ("staticIterations", C.c_int32), ("groups", C.c_int32), ("planesPerPass", C.c_int32),
                 ("worstTrueResidual", C.c_double), ("setupMs", C.c_double), ("solveMs", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
+class ModalTransientParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("rayleighMass", C.c_double), ("rayleighStiff", C.c_double), ("rtol", C.c_double), ("nSteps", C.c_int32),
+                ("maxit", C.c_int32), ("snapshotStride", C.c_int32), ("chunkSteps", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ModalTransientInfo(C.Structure):
+    _fields_ = [("stepsDone", C.c_int32), ("staticSolves", C.c_int32), ("staticIterations", C.c_int32), ("chunkSteps", C.c_int32),
+                ("chunks", C.c_int32), ("reserved", C.c_int32), ("setupMs", C.c_double), ("marchMs", C.c_double), ("seriesMs", C.c_double),
+                ("expandMs", C.c_double), ("note", C.c_char_p)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -296,6 +313,8 @@ PROTOTYPES = {
     "mfh_modal_coordinates": (_i32, [_P, _P, _i32, _P]),
     "mfh_modal_basis_state": (_i32, [_P, _pi32, _pi32]),
     "mfh_modal_harmonic": (_i32, [_P, C.POINTER(ModalHarmonicParams), _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalHarmonicInfo)]),
+    "mfh_modal_transient": (_i32, [_P, C.POINTER(ModalTransientParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalTransientInfo)]),
+    "mfh_modal_transient_coeffs": (_i32, [_f64, _f64, _f64, _P]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -362,6 +381,8 @@ PROTOTYPES = {
     "mfh_debug_modal_expand": (_i32, [_P, _i64, _i32, _P, _P, _i32, _i32, _P]),
     "mfh_debug_modal_gram": (_i32, [_P, _i64, _i32, _i32, _P, _P, _P]),
     "mfh_time_modal_expand": (_i32, [_P, _i64, _i32, _i32, _i32, _P]),
+    "mfh_debug_modal_march": (_i32, [_P, _i32, _P, _P, _P, _f64, _i32, _P, _i32, _P, _P, _P, _i32, _i32, _P, _P, _P]),
+    "mfh_time_modal_series": (_i32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
     "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),

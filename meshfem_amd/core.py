@@ -736,6 +736,91 @@ class Context:
         self._ck(self.lib.mfh_time_modal_expand(self.h, int(n), int(nb), int(planes_per_pass), int(reps), ptr(t)))
         return t
 
+    # ---------------------------------------------------------------- modal transient response (docs/design/04_22_modal_transient.md)
+    def modal_transient(self, dt, n_steps, f, amplitude=None, q0=None, qdot0=None, u0=None, v0=None, damping=(0, 0), modal_damping=None,
+                        static_correction=True, rtol=1e-8, maxit=10000, probes=None, snapshot_stride=0, modal_coords=False, energies=False,
+                        chunk_steps=0):
+        """The response to the load amplitude(t) f by exact integration of the modes of set_modal_basis (mfh_modal_transient): every mode obeys
+        q'' + c_j q' + lam_j q = (phi_j^T f) a(t), c_j = damping[0] + damping[1] lam_j + 2 zeta_j sqrt(lam_j), with a(t) piecewise linear between
+        amplitude[n] at n dt (None: 1), and is stepped without error; u = sum_j phi_j q_j (+ r_s a_n with static_correction: one solve K u_s = f
+        at rtol / maxit, clamped bodies only). Start: q0 / qdot0 (modal) or u0 / v0 (fields, projected with modal_coordinates), not both; none:
+        rest. Returns a dict like newmark(): "q", "qdot" (the state after the last step: pass them as q0 / qdot0 of the next call, whose
+        amplitude[0] is this call's last value, to continue the run bit for bit), "probes" [n_steps + 1, len(probes)], "snapshots"
+        [n_steps // snapshot_stride + 1, dim * n_dof] (snapshot_stride > 0), "modal_coords" [n_steps + 1, nModes], "energies" [n_steps + 1, 3] =
+        1/2 sum qdot^2, 1/2 sum lam q^2, a sum g q, and "info". chunk_steps: steps per launch on the device (0: the default; a multiple of 32);
+        it changes no result."""
+        n = self.bs * self.n_dof
+        n_steps = int(n_steps)
+        rows = max(n_steps, 0) + 1
+        if (q0 is not None or qdot0 is not None) and (u0 is not None or v0 is not None):
+            raise ValueError("modal_transient: give the start as q0 / qdot0 or as u0 / v0, not both")
+        f = as_f64(np.asarray(f, dtype=np.float64).reshape(-1))
+        if f.size != n:
+            raise ValueError("modal_transient: f needs dim * n_dof = %d entries, got %d" % (n, f.size))
+        m = self.modal_basis_state()[0]
+
+        def state(x, name):
+            x = np.zeros(m) if x is None else np.array(x, dtype=np.float64).reshape(-1)
+            if x.size != m:
+                raise ValueError("modal_transient: %s needs one entry per mode (%d), got %d" % (name, m, x.size))
+            return np.ascontiguousarray(x)
+        if u0 is not None or v0 is not None:
+            q0 = None if u0 is None else self.modal_coordinates(np.asarray(u0, dtype=np.float64).reshape(-1))
+            qdot0 = None if v0 is None else self.modal_coordinates(np.asarray(v0, dtype=np.float64).reshape(-1))
+        q, qd = state(q0, "q0"), state(qdot0, "qdot0")
+        amp = None if amplitude is None else as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
+        if amp is not None and amp.size != rows:
+            raise ValueError("modal_transient: amplitude needs n_steps + 1 = %d entries, got %d" % (rows, amp.size))
+        zeta = None
+        if modal_damping is not None:
+            zeta = as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros((rows, n_probe)) if n_probe else None
+        stride = int(snapshot_stride)
+        snaps = np.zeros((max(n_steps, 0) // stride + 1, n)) if stride > 0 else None
+        mc = np.zeros((rows, m)) if modal_coords else None
+        en = np.zeros((rows, 3)) if energies else None
+        flags = (L.MODAL_TR_STATIC_CORRECTION if static_correction else 0) | (L.MODAL_TR_ENERGIES if energies else 0)
+        prm = L.ModalTransientParams(float(dt), float(damping[0]), float(damping[1]), float(rtol), n_steps, int(maxit), stride, int(chunk_steps), flags, 0)
+        info = L.ModalTransientInfo()
+        st = self.lib.mfh_modal_transient(self.h, C.byref(prm), ptr(zeta), ptr(q) if m else None, ptr(qd) if m else None, ptr(f), ptr(amp), ptr(pv), n_probe,
+                                          ptr(pout), ptr(snaps), ptr(mc) if mc is not None and mc.size else None, ptr(en), C.byref(info))
+        out = {"q": q, "qdot": qd, "probes": np.zeros((rows, 0)) if pout is None else pout, "snapshots": snaps, "modal_coords": mc, "energies": en,
+               "info": info.as_dict()}
+        self.last_modal_transient = out
+        self._ck(st)
+        return out
+
+    def debug_modal_march(self, coef8, g, amplitude, dt, q0, qdot0, chunk_steps=0, Bp=None, corr=False, lam=None, energies=False):
+        """k_modal_march and k_modal_series on caller arrays (test hook mfh_debug_modal_march; no mesh needed). coef8: [m, 8] rows of
+        modal_transient_coeffs, g: [m], amplitude: [n_steps + 1], Bp: [m + corr, nProbe] or None. Returns a dict: "q", "qdot" (after the last
+        step), "modal_coords" [n_steps + 1, m], "probes" [n_steps + 1, nProbe], "energies" [n_steps + 1, 3] or None."""
+        coef8, g, amp = as_f64(np.atleast_2d(coef8)), as_f64(np.asarray(g, dtype=np.float64).reshape(-1)), as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
+        m, rows = coef8.shape[0], amp.size
+        assert coef8.shape[1] == 8 and g.size == m
+        q, qd = np.array(q0, dtype=np.float64).reshape(-1), np.array(qdot0, dtype=np.float64).reshape(-1)
+        assert q.size == m and qd.size == m
+        n_probe = 0
+        if Bp is not None:
+            Bp = as_f64(np.atleast_2d(Bp))
+            assert Bp.shape[0] == m + int(bool(corr))
+            n_probe = Bp.shape[1]
+        lam = None if lam is None else as_f64(np.asarray(lam, dtype=np.float64).reshape(-1))
+        mc = np.zeros((rows, m))
+        pout = np.zeros((rows, n_probe)) if n_probe else None
+        en = np.zeros((rows, 3)) if energies else None
+        self._ck(self.lib.mfh_debug_modal_march(self.h, m, ptr(coef8), ptr(g), ptr(lam), float(dt), rows - 1, ptr(amp), int(chunk_steps), ptr(q), ptr(qd),
+                                                ptr(Bp) if n_probe else None, n_probe, int(bool(corr)), ptr(mc), ptr(pout), ptr(en)))
+        return {"q": q, "qdot": qd, "modal_coords": mc, "probes": np.zeros((rows, 0)) if pout is None else pout, "energies": en}
+
+    def time_modal_series(self, n_modes, n_probe, n_steps, reps=5):
+        """(series_ms, expand_ms), one entry per repetition: device time of k_modal_series and of the k_modal_expand route on the same shape, the two
+        taking turns (mfh_time_modal_series)."""
+        a, b = np.zeros(int(reps)), np.zeros(int(reps))
+        self._ck(self.lib.mfh_time_modal_series(self.h, int(n_modes), int(n_probe), int(n_steps), int(reps), ptr(a), ptr(b)))
+        return a, b
+
     # ---------------------------------------------------------------- per-element density (docs/design/04_15_density.md)
     def set_density(self, rho):
         """The density field of the mass matrix of modes() and newmark() (mfh_set_density): one strictly positive value per element, or
@@ -1633,3 +1718,19 @@ def device_arena_stats(device=0):
     lib.mfh_device_arena_stats(int(device), v)
     return dict(zip(("held_bytes", "live_bytes", "live_high_water_bytes", "segments", "free_chunks", "returned_to_driver_bytes",
                      "quarantined_bytes", "free_bound_bytes"), list(v)))
+
+
+def modal_transient_coeffs(lam, c, dt):
+    """The eight coefficients {A11, A12, b0_q, b1_q, A21, A22, b0_v, b1_v} of the exact step of q'' + c q' + lam q = a(t), a piecewise linear
+    (mfh_modal_transient_coeffs; host only, no device): one row of eight per entry of the broadcast (lam, c), a single row for scalars."""
+    lam_b, c_b = np.broadcast_arrays(np.asarray(lam, dtype=np.float64), np.asarray(c, dtype=np.float64))
+    out = np.zeros(lam_b.shape + (8,))
+    flat = out.reshape(-1, 8)
+    lib = L.load()
+    for i, (l, cc) in enumerate(zip(lam_b.reshape(-1), c_b.reshape(-1))):
+        row = np.zeros(8)
+        st = lib.mfh_modal_transient_coeffs(float(l), float(cc), float(dt), ptr(row))
+        if st != L.OK:
+            raise L.MeshFEMHipError(st, "mfh_modal_transient_coeffs: lam >= 0, c >= 0, dt > 0, all finite")
+        flat[i] = row
+    return out

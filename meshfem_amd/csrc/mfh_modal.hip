@@ -14,6 +14,8 @@
 //   k_modal_gram_sum    adds the workgroups' partials in workgroup order: G = Phi^T (density M Phi), g = Phi^T [f_re f_im], q = Phi^T (density M u).
 //                       Ordered two-stage sums, no floating-point atomics; the row partition depends on n only.
 // The mass products are k_spmv_kron_acc's (mfh_pencil.hh), the true residual's operator product mfh_harmonic's own (harmonic_product, mfh_harmonic.hip).
+// The same basis serves load histories (mfh_modal_transient; docs/design/04_22_modal_transient.md): k_modal_slope, k_modal_march, k_modal_series
+// below, the step coefficients from mfh_modal_coeffs.cpp.
 #include "mfh_pencil.hh"
 #include <optional>
 
@@ -161,6 +163,143 @@ void launch_modal_gram(int64_t n, const double *A, int64_t lda, int na, const do
     CHECK_LAUNCH();
 }
 
+// ---------------------------------------------------------------- modal transient response (mfh_modal_transient; docs/design/04_22_modal_transient.md)
+// Every mode obeys q'' + c q' + lambda q = g a(t) with a piecewise linear between the steps, for which the step is exact:
+//     [q ; v]_{r} = A [q ; v]_{r-1} + g (b0 a_{r-1} + b1 s_r),   s_r = (a_r - a_{r-1}) / dt,
+// the eight coefficients {A11, A12, b0q, b1q, A21, A22, b0v, b1v} per mode from mfh_modal_transient_coeffs (host, long double). A run is a sequence of
+// ROWS r = 0 .. nSteps (row 0: the start state), taken in chunks of rows:
+//   k_modal_slope    s_r for all rows at once (IEEE division, off the sequential path)
+//   k_modal_march    one lane per mode, the rows of a chunk in sequence; state in / out through a device buffer
+//   k_modal_series   probes and energies of all rows of a chunk: the lanes own the rows, the probe rows of the basis are wave-uniform
+// and the snapshots are k_modal_expand's on the compact coefficient matrix the march kernel writes.
+constexpr int MT_CHUNK = 4096;          // rows of a chunk by default
+constexpr int MT_PB = 8;                // probes a workgroup of k_modal_series holds per lane
+constexpr int MT_TR = 256, MT_TJ = 16;  // its tile of Q in LDS: rows x modes, rows MT_TJ + 1 doubles apart (odd: the per-lane walk over j hits 64 different banks)
+constexpr int MT_COEF_LD = MODAL_MAXM;  // the coefficient table on the device: coef[k MT_COEF_LD + j], k < 8
+
+__global__ void __launch_bounds__(256) k_modal_slope(int64_t rows, const double *__restrict__ amp, double dt, double *__restrict__ slope) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (int64_t)gridDim.x * 256) slope[r] = r > 0 ? (amp[r] - amp[r - 1]) / dt : 0.0;
+}
+
+// The rows [0, count) of a chunk; amp and slope point at the chunk's first row (amp[-1] exists unless first = 1: the chunk that holds row 0, which takes
+// no step). The operation order of a step, fixed:
+//     pq = g b0q, rq = g b1q, pv = g b0v, rv = g b1v                      (once per launch, rounded products)
+//     lq = fma(rq, s, pq a0),  lv = fma(rv, s, pv a0)                      (the load term: no state in it)
+//     q+ = fma(A11, q, fma(A12, v, lq)),  v+ = fma(A21, q, fma(A22, v, lv))  (two fma deep per component)
+// so the state after a row depends on neither the chunk length nor on where a run was cut. a0 and s are wave-uniform (scalar loads). Writes Q[i ldq + j]
+// (and V, if not null), and at the snapshot rows i = snapNext, snapNext + snapStride, ... column p = 0, 1, ... of the compact matrix Cs: rows q_j,
+// row m = a_i.
+__global__ void __launch_bounds__(256) k_modal_march(int m, const double *__restrict__ coef, const double *__restrict__ g, const double *__restrict__ amp,
+                                                    const double *__restrict__ slope, int first, int count, double *__restrict__ state, double *__restrict__ Q,
+                                                    double *__restrict__ V, int ldq, int snapNext, int snapStride, double *__restrict__ Cs, int ldcs) {
+    const int j = threadIdx.x;
+    if (j >= m) return;
+    const double A11 = coef[j], A12 = coef[MT_COEF_LD + j], A21 = coef[4 * MT_COEF_LD + j], A22 = coef[5 * MT_COEF_LD + j];
+    const double gj = g[j];
+    const double pq = gj * coef[2 * MT_COEF_LD + j], rq = gj * coef[3 * MT_COEF_LD + j], pv = gj * coef[6 * MT_COEF_LD + j], rv = gj * coef[7 * MT_COEF_LD + j];
+    double q = state[j], v = state[MODAL_MAXM + j];
+    int p = 0;
+    for (int i = 0; i < count; ++i) {
+        if (i >= first) {
+            const double a0 = amp[i - 1], s = slope[i];
+            const double lq = fma(rq, s, pq * a0), lv = fma(rv, s, pv * a0);
+            const double qn = fma(A11, q, fma(A12, v, lq)), vn = fma(A21, q, fma(A22, v, lv));
+            q = qn; v = vn;
+        }
+        Q[(int64_t)i * ldq + j] = q;
+        if (V) V[(int64_t)i * ldq + j] = v;
+        if (i == snapNext) {
+            Cs[(int64_t)j * ldcs + p] = q;
+            if (j == 0) Cs[(int64_t)m * ldcs + p] = amp[i];
+            ++p;
+            snapNext += snapStride;
+        }
+    }
+    state[j] = q;
+    state[MODAL_MAXM + j] = v;
+}
+
+// Rows [0, count) of a chunk, 256 per workgroup. blockIdx.y < ceil(nProbe / MT_PB): the probes p0 .. p0 + MT_PB - 1,
+//     probeOut[r nProbe + p] = sum_j Bp[j ldp + p] Q[r ldq + j]  (+ Bp[m ldp + p] amp[r] if corr)
+// as the fma chain over j ascending from +0.0 with the correction column last -- k_modal_expand's chain on the same numbers, so a probe equals the
+// snapshot entry of its variable bit for bit. Bp (k_modal_gather_rows' layout, zero-padded to ldp, a multiple of 32) is wave-uniform: scalar loads.
+// blockIdx.y == ceil(nProbe / MT_PB) (launched only with energies): energies[3 r] = {1/2 sum v_j^2, 1/2 sum (lambda_j q_j) q_j, amp[r] sum g_j q_j}, each
+// an fma chain over j ascending. A tile of 256 rows x 16 modes goes through LDS: the global read runs along j (16 doubles of a row at a time), the
+// per-lane walk over j reads addresses 17 doubles apart. No atomics.
+__global__ void __launch_bounds__(256) k_modal_series(int m, int count, const double *__restrict__ Q, const double *__restrict__ V, int ldq, const double *__restrict__ Bp,
+                                                     int ldp, int nProbe, int corr, const double *__restrict__ amp, const double *__restrict__ lam,
+                                                     const double *__restrict__ g, double *__restrict__ probeOut, double *__restrict__ energies) {
+    __shared__ double tile[MT_TR * (MT_TJ + 1)];
+    const int r0 = blockIdx.x * MT_TR, r = r0 + threadIdx.x;
+    const int nGroups = (nProbe + MT_PB - 1) / MT_PB;
+    auto load_tile = [&](const double *__restrict__ src, int j0) {
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < MT_TR * MT_TJ; idx += 256) {
+            const int rr = idx / MT_TJ, jj = idx - rr * MT_TJ;
+            tile[rr * (MT_TJ + 1) + jj] = (r0 + rr < count && j0 + jj < m) ? src[(int64_t)(r0 + rr) * ldq + j0 + jj] : 0.0;
+        }
+        __syncthreads();
+    };
+    const double *mine = tile + threadIdx.x * (MT_TJ + 1);
+    if ((int)blockIdx.y < nGroups) {
+        const int p0 = blockIdx.y * MT_PB;
+        double s[MT_PB];
+#pragma unroll
+        for (int t = 0; t < MT_PB; ++t) s[t] = 0.0;
+        for (int j0 = 0; j0 < m; j0 += MT_TJ) {
+            load_tile(Q, j0);
+            const int nj = min(MT_TJ, m - j0);
+            for (int jj = 0; jj < nj; ++jj) {
+                const double qv = mine[jj];
+                const double *b = Bp + (int64_t)(j0 + jj) * ldp + p0;
+#pragma unroll
+                for (int t = 0; t < MT_PB; ++t) s[t] = fma(b[t], qv, s[t]);
+            }
+        }
+        if (corr) {
+            const double a = r < count ? amp[r] : 0.0;
+            const double *b = Bp + (int64_t)m * ldp + p0;
+#pragma unroll
+            for (int t = 0; t < MT_PB; ++t) s[t] = fma(b[t], a, s[t]);
+        }
+        if (r < count) {
+#pragma unroll
+            for (int t = 0; t < MT_PB; ++t)
+                if (p0 + t < nProbe) probeOut[(int64_t)r * nProbe + p0 + t] = s[t];
+        }
+    } else {
+        double ke = 0.0, pe = 0.0, w = 0.0;
+        for (int j0 = 0; j0 < m; j0 += MT_TJ) {
+            const int nj = min(MT_TJ, m - j0);
+            load_tile(Q, j0);
+            for (int jj = 0; jj < nj; ++jj) {
+                const double qv = mine[jj], lq = lam[j0 + jj] * qv;
+                pe = fma(lq, qv, pe);
+                w = fma(g[j0 + jj], qv, w);
+            }
+            load_tile(V, j0);
+            for (int jj = 0; jj < nj; ++jj) {
+                const double vv = mine[jj];
+                ke = fma(vv, vv, ke);
+            }
+        }
+        if (r < count) {
+            energies[(int64_t)r * 3] = 0.5 * ke;
+            energies[(int64_t)r * 3 + 1] = 0.5 * pe;
+            energies[(int64_t)r * 3 + 2] = amp[r] * w;
+        }
+    }
+}
+
+void launch_modal_series(int m, int count, const double *Q, const double *V, int ldq, const double *Bp, int64_t ldp, int nProbe, bool corr, const double *amp,
+                         const double *lam, const double *g, double *probeOut, double *energies, hipStream_t s) {
+    const int nGroups = (nProbe + MT_PB - 1) / MT_PB, ny = nGroups + (energies ? 1 : 0);
+    if (count <= 0 || ny == 0) return;
+    hipLaunchKernelGGL(k_modal_series, dim3((count + MT_TR - 1) / MT_TR, ny), dim3(256), 0, s, m, count, Q, V, ldq, Bp, (int)ldp, nProbe, corr ? 1 : 0, amp, lam, g, probeOut,
+                       energies);
+    CHECK_LAUNCH();
+}
+
 }   // namespace
 }}   // namespace mfh::k
 
@@ -252,9 +391,315 @@ void check_sweep_params(const mfh_ctx *c, const mfh_modal_harmonic_params *p, co
         for (int j = 0; j < c->modal.nModes; ++j) require(std::isfinite(zeta[j]) && zeta[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: a damping ratio is negative or not finite");
 }
 
+// ---- the transient driver, shared by mfh_modal_transient and its hook. Everything on the device; the host arrays are outputs (null: not wanted).
+struct MarchRun {
+    int m = 0, nSteps = 0, chunk = k::MT_CHUNK;
+    double dt = 0.0;
+    const double *coef = nullptr, *g = nullptr, *lam = nullptr;      // device: 8 x MT_COEF_LD, m, m
+    const double *amp = nullptr;                                     // device: nSteps + 1
+    double *state = nullptr;                                         // device: 2 x MODAL_MAXM, in / out
+    const double *Bp = nullptr; int64_t ldp = 0; int nProbe = 0; bool corr = false;
+    double *probeOut = nullptr, *modalCoords = nullptr, *energies = nullptr;   // host
+    int stride = 0; const double *B = nullptr; int64_t ld = 0, n = 0; int nb = 0; double *snapshots = nullptr;   // host: snapshots of n doubles
+    double marchMs = 0.0, seriesMs = 0.0, expandMs = 0.0; int chunks = 0;
+};
+
+void run_march(hipStream_t s, MarchRun &R) {
+    const int m = R.m, chunk = R.chunk;
+    const int64_t rows = (int64_t)R.nSteps + 1;
+    const int cap = (int)std::min<int64_t>(chunk, rows);
+    const int stride = R.snapshots ? R.stride : 0;
+    const bool series = R.nProbe > 0 || R.energies;
+    DBuf<double> dSlope, dQ, dV, dCs, dProbe, dEn, dStage;
+    dSlope.alloc((size_t)rows);
+    hipLaunchKernelGGL(k::k_modal_slope, dim3(k::grid_for(rows)), dim3(256), 0, s, rows, R.amp, R.dt, dSlope.p);
+    CHECK_LAUNCH();
+    dQ.alloc((size_t)cap * m);
+    if (R.energies) { dV.alloc((size_t)cap * m); dEn.alloc((size_t)cap * 3); }
+    if (R.nProbe) dProbe.alloc((size_t)cap * R.nProbe);
+    const int ldcs = stride ? cap / stride + 1 + k::MODAL_NP_MAX : 0;
+    const int64_t snapsIn256MB = std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(R.n, 1));
+    if (stride) {
+        dCs.alloc((size_t)(m + 1) * ldcs);
+        dStage.alloc((size_t)std::min<int64_t>(snapsIn256MB, cap / stride + 1) * (size_t)R.n);
+    }
+    for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+        const int count = (int)std::min<int64_t>(chunk, rows - r0);
+        int snapNext = -1, nSnap = 0;
+        int64_t snap0 = 0;         // index of the chunk's first snapshot in the run
+        if (stride) {
+            snap0 = (r0 + stride - 1) / stride;
+            const int64_t local = snap0 * stride - r0;
+            if (local < count) { snapNext = (int)local; nSnap = (count - 1 - snapNext) / stride + 1; }
+            dCs.zero(s);
+        }
+        {
+            EventTimer t(s);
+            hipLaunchKernelGGL(k::k_modal_march, dim3(1), dim3(256), 0, s, m, R.coef, R.g, R.amp + r0, (const double *)dSlope.p + r0, r0 == 0 ? 1 : 0, count, R.state, dQ.p,
+                               dV.p, m, snapNext, std::max(stride, 1), dCs.p, ldcs);
+            CHECK_LAUNCH();
+            R.marchMs += t.stop();
+        }
+        if (series) {
+            EventTimer t(s);
+            k::launch_modal_series(m, count, dQ.p, dV.p, m, R.Bp, R.ldp, R.nProbe, R.corr, R.amp + r0, R.lam, R.g, dProbe.p, R.energies ? dEn.p : nullptr, s);
+            R.seriesMs += t.stop();
+        }
+        for (int64_t c0 = 0; c0 < nSnap; c0 += snapsIn256MB) {          // the snapshots leave 256 MB at a time (one at least)
+            const int np = (int)std::min<int64_t>(snapsIn256MB, nSnap - c0);
+            EventTimer t(s);
+            k::launch_modal_expand(R.n, R.B, R.ld, R.nb, dCs.p + c0, ldcs, np, k::MODAL_NP, dStage.p, R.n, s);
+            R.expandMs += t.stop();
+            MFH_HIP(hipMemcpyAsync(R.snapshots + (size_t)(snap0 + c0) * (size_t)R.n, dStage.p, (size_t)np * (size_t)R.n * sizeof(double), hipMemcpyDeviceToHost, s));
+            MFH_HIP(hipStreamSynchronize(s));
+        }
+        if (R.nProbe) MFH_HIP(hipMemcpyAsync(R.probeOut + (size_t)r0 * R.nProbe, dProbe.p, (size_t)count * R.nProbe * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (R.modalCoords) MFH_HIP(hipMemcpyAsync(R.modalCoords + (size_t)r0 * m, dQ.p, (size_t)count * m * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (R.energies) MFH_HIP(hipMemcpyAsync(R.energies + (size_t)r0 * 3, dEn.p, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        MFH_HIP(hipStreamSynchronize(s));
+        ++R.chunks;
+    }
+}
+
+// the coefficient table of the device, 8 x MT_COEF_LD, from rows of eight per mode
+std::vector<double> coef_table(int m, const double *coef8) {
+    std::vector<double> t((size_t)8 * k::MT_COEF_LD, 0.0);
+    for (int j = 0; j < m; ++j)
+        for (int k2 = 0; k2 < 8; ++k2) t[(size_t)k2 * k::MT_COEF_LD + j] = coef8[(size_t)j * 8 + k2];
+    return t;
+}
+
+bool chunk_ok(int32_t chunkSteps) { return chunkSteps == 0 || (chunkSteps > 0 && chunkSteps % 32 == 0); }
+
 }   // namespace
 
 extern "C" {
+
+mfh_status mfh_modal_transient(mfh_ctx *c, const mfh_modal_transient_params *prm, const double *modalDamping, double *q, double *qdot, const double *f,
+                               const double *amplitude, const int64_t *probeVars, int32_t nProbe, double *probeOut, double *snapshots, double *modalCoords,
+                               double *energies, mfh_modal_transient_info *info) {
+    if (info) { *info = mfh_modal_transient_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_transient: null context");
+    require(prm != nullptr, MFH_ERR_INVALID, "mfh_modal_transient: params is null");
+    const mfh_modal_transient_params P = *prm;
+    require(P.dt > 0.0 && std::isfinite(P.dt), MFH_ERR_INVALID, "mfh_modal_transient: dt > 0");
+    require(P.nSteps >= 0 && P.snapshotStride >= 0 && P.maxit >= 0 && nProbe >= 0, MFH_ERR_INVALID, "mfh_modal_transient: a count or the stride is negative");
+    require(P.rayleighMass >= 0.0 && P.rayleighStiff >= 0.0 && std::isfinite(P.rayleighMass) && std::isfinite(P.rayleighStiff), MFH_ERR_INVALID,
+            "mfh_modal_transient: the Rayleigh coefficients are not negative");
+    require((P.flags & ~(MFH_MODAL_TR_STATIC_CORRECTION | MFH_MODAL_TR_ENERGIES)) == 0, MFH_ERR_INVALID, "mfh_modal_transient: unknown flag");
+    require(chunk_ok(P.chunkSteps), MFH_ERR_INVALID, "mfh_modal_transient: chunkSteps is 0 or a positive multiple of 32");
+    require((q == nullptr) == (qdot == nullptr), MFH_ERR_INVALID, "mfh_modal_transient: q and qdot come together");
+    const bool correct = (P.flags & MFH_MODAL_TR_STATIC_CORRECTION) != 0, wantEn = (P.flags & MFH_MODAL_TR_ENERGIES) != 0;
+    require(wantEn == (energies != nullptr), MFH_ERR_INVALID, "mfh_modal_transient: the energies and MFH_MODAL_TR_ENERGIES come together");
+    require(!correct || (P.rtol > 0.0 && P.rtol < 1.0 && P.maxit > 0), MFH_ERR_INVALID, "mfh_modal_transient: the static solve needs 0 < rtol < 1, maxit > 0");
+    require(f != nullptr, MFH_ERR_INVALID, "mfh_modal_transient: f is null");
+    require(!snapshots || P.snapshotStride > 0, MFH_ERR_INVALID, "mfh_modal_transient: snapshots need snapshotStride > 0");
+    require(nProbe == 0 || (probeVars && probeOut), MFH_ERR_INVALID, "mfh_modal_transient: probes need their variables and their output");
+    const int64_t nv = (int64_t)c->bs() * c->nDoF;
+    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_transient: probe variable out of range");
+    if (amplitude) require(all_finite(amplitude, (int64_t)P.nSteps + 1), MFH_ERR_INVALID, "mfh_modal_transient: an amplitude is not finite");
+    if (modalDamping)       // (a basis of another length is caught below; the entries a basis could have are at most MODAL_MAXM)
+        for (int j = 0; j < c->modal.nModes; ++j)
+            require(std::isfinite(modalDamping[j]) && modalDamping[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_transient: a damping ratio is negative or not finite");
+    prepare_pencil(c, "mfh_modal_transient");
+    require_basis(c, "mfh_modal_transient");
+    const bool masked = !c->fixedVars.empty();
+    const int m = c->modal.nModes;
+    const int64_t n = c->modal.n, ld = c->modal.ld;
+    const std::vector<double> lam = c->modal.lambda;
+    if (correct) {
+        require(masked, MFH_ERR_UNSUPPORTED, "mfh_modal_transient: the static correction needs fixed variables (K alone is singular)");
+        for (int j = 0; j < m; ++j) require(lam[(size_t)j] > 0.0, MFH_ERR_INVALID, "mfh_modal_transient: the static correction needs lambda_j > 0");
+    }
+    require(all_finite(f, n), MFH_ERR_INVALID, "mfh_modal_transient: the load has an entry that is not finite");
+    if (q) require(all_finite(q, m) && all_finite(qdot, m), MFH_ERR_INVALID, "mfh_modal_transient: the start state has an entry that is not finite");
+    // the eight coefficients per mode, on the host
+    std::vector<double> coef8((size_t)m * 8);
+    for (int j = 0; j < m; ++j) {
+        const double l = lam[(size_t)j], cj = P.rayleighMass + P.rayleighStiff * l + (modalDamping ? 2.0 * modalDamping[j] * std::sqrt(l) : 0.0);
+        require(std::isfinite(cj) && mfh_modal_transient_coeffs(l, cj, P.dt, coef8.data() + (size_t)j * 8) == MFH_OK, MFH_ERR_INVALID,
+                "mfh_modal_transient: the damping of a mode is not finite");
+    }
+    hipStream_t s = c->stream;
+    c->modalNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modalNote.empty()) c->modalNote += "; "; c->modalNote += t; };
+    EventTimer tsetup(s);
+
+    // ---- the static solve, as mfh_modal_harmonic makes it (real plane only)
+    int staticSolves = 0, staticIts = 0;
+    std::vector<double> us;
+    bool loaded = false;
+    {
+        const uint8_t *hm = masked ? c->hFixedMask.data() : nullptr;
+        for (int64_t i = 0; i < n && !loaded; ++i) loaded = f[i] != 0.0 && !(hm && hm[i]);
+    }
+    if (correct && loaded) {
+        ensure_precond(c);
+        ensure_coarse_levels(c, 1);
+        require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modal_transient: unpartitioned contexts only");
+        require_basis(c, "mfh_modal_transient");
+        us.resize((size_t)n);
+        mfh_solve_info li{};
+        const bool savedHom = c->solveHomogeneous;
+        c->solveHomogeneous = c->anyFixedNonzero;
+        try { solve_one(c, f, us.data(), P.rtol, P.maxit, &li); }
+        catch (...) { c->solveHomogeneous = savedHom; throw; }
+        c->solveHomogeneous = savedHom;
+        staticSolves = 1;
+        staticIts = li.iterations;
+        if (info) { info->staticSolves = staticSolves; info->staticIterations = staticIts; }
+        if (!li.converged) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modal_transient: the static solve of the correction did not reach rtol within maxit iterations");
+    }
+    if (masked) ensure_fixed_uploaded(c);
+    require_basis(c, "mfh_modal_transient");
+    double *const B = c->modal.B.p;
+
+    // ---- g = Phi^T f
+    DBuf<double> dF;
+    dF.alloc((size_t)ld);
+    dF.zero(s);
+    upload(dF.p, f, n, s);
+    if (masked) k::launch_mask(n, c->dFixedMask.p, dF.p, s);
+    std::vector<double> g((size_t)m);
+    gram_against(c, B, ld, m, dF.p, ld, 1, 0.0, g.data());
+
+    // ---- r_s = u_s - sum_j phi_j g_j / lambda_j into the first reserved column, through the expansion kernel (mfh_modal_harmonic's, real plane)
+    const int nb = staticSolves ? m + 1 : m;
+    if (staticSolves) {
+        DBuf<double> dC, dTmp;
+        MFH_HIP(hipMemsetAsync(B + (int64_t)m * ld, 0, (size_t)ld * 2 * sizeof(double), s));
+        upload(B + (int64_t)m * ld, us.data(), n, s);
+        k::launch_mask(n, c->dFixedMask.p, B + (int64_t)m * ld, s);
+        const int ldc = 64;
+        std::vector<double> hc((size_t)nb * ldc, 0.0);
+        for (int j = 0; j < m; ++j) hc[(size_t)j * ldc] = -(g[(size_t)j] / lam[(size_t)j]);
+        hc[(size_t)m * ldc] = 1.0;
+        dC.upload(hc, s);
+        dTmp.alloc((size_t)ld);
+        dTmp.zero(s);
+        k::launch_modal_expand(n, B, ld, nb, dC.p, ldc, 1, k::MODAL_NP, dTmp.p, ld, s);
+        MFH_HIP(hipMemcpyAsync(B + (int64_t)m * ld, dTmp.p, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, s));
+        MFH_HIP(hipStreamSynchronize(s));
+        note("static correction: 1 solve of K u = f, " + std::to_string(staticIts) + " iterations");
+    }
+
+    // ---- the probe rows of B, gathered once
+    DBuf<double> dBp;
+    DBuf<int64_t> dProbeVars;
+    const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
+    if (nProbe) {
+        dProbeVars.alloc((size_t)nProbe);
+        MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        dBp.alloc((size_t)ldp * nb);
+        dBp.zero(s);
+        hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, (int)nProbe, nb, (const int64_t *)dProbeVars.p, (const double *)B, ld,
+                           dBp.p, ldp);
+        CHECK_LAUNCH();
+        MFH_HIP(hipStreamSynchronize(s));       // (probeVars is the caller's)
+    }
+
+    // ---- tables and state
+    DBuf<double> dCoef, dG, dLam, dAmp, dState;
+    dCoef.upload(coef_table(m, coef8.data()), s);
+    dG.upload(g, s);
+    dLam.upload(lam, s);
+    std::vector<double> ones;
+    if (!amplitude) ones.assign((size_t)P.nSteps + 1, 1.0);
+    dAmp.upload(amplitude ? amplitude : ones.data(), (size_t)P.nSteps + 1, s);
+    std::vector<double> hs((size_t)2 * k::MODAL_MAXM, 0.0);
+    if (q) { std::copy(q, q + m, hs.begin()); std::copy(qdot, qdot + m, hs.begin() + k::MODAL_MAXM); }
+    dState.upload(hs, s);
+    const double setupMs = tsetup.stop();
+
+    MarchRun R;
+    R.m = m; R.nSteps = P.nSteps; R.chunk = P.chunkSteps ? P.chunkSteps : k::MT_CHUNK; R.dt = P.dt;
+    R.coef = dCoef.p; R.g = dG.p; R.lam = dLam.p; R.amp = dAmp.p; R.state = dState.p;
+    R.Bp = dBp.p; R.ldp = ldp; R.nProbe = nProbe; R.corr = staticSolves != 0;
+    R.probeOut = probeOut; R.modalCoords = modalCoords; R.energies = energies;
+    R.stride = P.snapshotStride; R.B = B; R.ld = ld; R.n = n; R.nb = nb; R.snapshots = snapshots;
+    run_march(s, R);
+    if (q) {
+        dState.download(hs.data(), hs.size(), s);
+        std::copy(hs.begin(), hs.begin() + m, q);
+        std::copy(hs.begin() + k::MODAL_MAXM, hs.begin() + k::MODAL_MAXM + m, qdot);
+    }
+    if (info) {
+        info->stepsDone = P.nSteps; info->staticSolves = staticSolves; info->staticIterations = staticIts;
+        info->chunkSteps = R.chunk; info->chunks = R.chunks;
+        info->setupMs = setupMs; info->marchMs = R.marchMs; info->seriesMs = R.seriesMs; info->expandMs = R.expandMs;
+        info->note = c->modalNote.c_str();
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_modal_march(mfh_ctx *c, int32_t nModes, const double *coef8, const double *g, const double *lambda, double dt, int32_t nSteps,
+                                 const double *amplitude, int32_t chunkSteps, double *q, double *qdot, const double *Bp, int32_t nProbe, int32_t corr,
+                                 double *modalCoords, double *probeOut, double *energies) {
+    MFH_TRY(c)
+    require(c && coef8 && g && amplitude && q && qdot && nModes >= 1 && nModes <= k::MODAL_MAXM && nSteps >= 0 && dt > 0.0 && chunk_ok(chunkSteps) && nProbe >= 0 &&
+                (nProbe == 0 || (Bp && probeOut)) && (!energies || lambda) && (corr == 0 || corr == 1),
+            MFH_ERR_INVALID, "mfh_debug_modal_march: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int m = nModes, nb = m + corr;
+    const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
+    DBuf<double> dCoef, dG, dLam, dAmp, dState, dBp;
+    dCoef.upload(coef_table(m, coef8), s);
+    dG.upload(g, (size_t)m, s);
+    if (lambda) dLam.upload(lambda, (size_t)m, s);
+    dAmp.upload(amplitude, (size_t)nSteps + 1, s);
+    std::vector<double> hs((size_t)2 * k::MODAL_MAXM, 0.0);
+    std::copy(q, q + m, hs.begin());
+    std::copy(qdot, qdot + m, hs.begin() + k::MODAL_MAXM);
+    dState.upload(hs, s);
+    if (nProbe) {          // Bp: nb rows of nProbe (row j = column j of the basis at the probe variables)
+        dBp.alloc((size_t)ldp * nb);
+        dBp.zero(s);
+        MFH_HIP(hipMemcpy2DAsync(dBp.p, (size_t)ldp * sizeof(double), Bp, (size_t)nProbe * sizeof(double), (size_t)nProbe * sizeof(double), (size_t)nb, hipMemcpyHostToDevice, s));
+        MFH_HIP(hipStreamSynchronize(s));
+    }
+    MarchRun R;
+    R.m = m; R.nSteps = nSteps; R.chunk = chunkSteps ? chunkSteps : k::MT_CHUNK; R.dt = dt;
+    R.coef = dCoef.p; R.g = dG.p; R.lam = dLam.p; R.amp = dAmp.p; R.state = dState.p;
+    R.Bp = dBp.p; R.ldp = ldp; R.nProbe = nProbe; R.corr = corr != 0;
+    R.probeOut = probeOut; R.modalCoords = modalCoords; R.energies = energies;
+    run_march(s, R);
+    dState.download(hs.data(), hs.size(), s);
+    std::copy(hs.begin(), hs.begin() + m, q);
+    std::copy(hs.begin() + k::MODAL_MAXM, hs.begin() + k::MODAL_MAXM + m, qdot);
+    MFH_CATCH(c)
+}
+
+// ms per repetition of (a) k_modal_series and (b) the k_modal_expand route (the gathered rows as the kernel's rows, 32 steps per pass) for nProbe probes of
+// nSteps rows on nb hashed columns, the two taking turns
+mfh_status mfh_time_modal_series(mfh_ctx *c, int32_t nModes, int32_t nProbe, int32_t nSteps, int32_t reps, double *seriesMs, double *expandMs) {
+    MFH_TRY(c)
+    require(c && seriesMs && expandMs && nModes >= 1 && nModes <= k::MODAL_MAXM && nProbe >= 1 && nProbe <= 4096 && nSteps >= 1 && reps >= 1, MFH_ERR_INVALID,
+            "mfh_time_modal_series: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int m = nModes;
+    const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
+    const int ldc = nSteps + k::MODAL_NP_MAX;
+    DBuf<double> dQ, dCt, dBp, dAmp, dOut;
+    dQ.alloc((size_t)nSteps * m); dCt.alloc((size_t)m * ldc); dBp.alloc((size_t)ldp * m); dAmp.alloc((size_t)nSteps); dOut.alloc((size_t)nSteps * nProbe);
+    k::launch_fill_hash((int64_t)dQ.n, dQ.p, s);
+    k::launch_fill_hash((int64_t)dCt.n, dCt.p, s);
+    k::launch_fill_hash((int64_t)dBp.n, dBp.p, s);
+    k::launch_fill_hash((int64_t)dAmp.n, dAmp.p, s);
+    auto a = [&] { k::launch_modal_series(m, nSteps, dQ.p, nullptr, m, dBp.p, ldp, nProbe, false, dAmp.p, nullptr, nullptr, dOut.p, nullptr, s); };
+    auto b = [&] { k::launch_modal_expand(nProbe, dBp.p, ldp, m, dCt.p, ldc, nSteps, k::MODAL_NP, dOut.p, nProbe, s); };
+    a(); b();          // warm-up
+    MFH_HIP(hipStreamSynchronize(s));
+    for (int r = 0; r < reps; ++r) {
+        { EventTimer t(s); a(); seriesMs[r] = t.stop(); }
+        { EventTimer t(s); b(); expandMs[r] = t.stop(); }
+    }
+    MFH_CATCH(c)
+}
 
 mfh_status mfh_modal_set_basis(mfh_ctx *c, int32_t nModes, const double *lambda, const double *X, double density, mfh_modal_basis_info *info) {
     if (info) *info = mfh_modal_basis_info{};

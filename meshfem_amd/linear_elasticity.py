@@ -576,6 +576,60 @@ class Simulator:
         del out["info"]
         return out
 
+    def modalTransient(self, dt, n_steps, amplitude=None, u0=None, v0=None, n_modes=None, modes=None, load=None, density=1.0, damping=(0, 0),
+                       modal_damping=None, static_correction=True, probes=None, snapshot_stride=0, modal_coords=False, energies=False, q0=None,
+                       qdot0=None, rtol=None, maxit=None, modes_rtol=1e-6, batch=0, chunk_steps=0):
+        """transient() by exact integration of the lowest modes (mfh_modal_transient, docs/design/04_22_modal_transient.md): the same load, clamp
+        and probes as (node, component) pairs, the load history taken as piecewise linear between amplitude[n]; no stability limit and no
+        period error, one pass over the resident basis per snapshot and none at all for probes. n_modes / modes / neither: the basis, exactly
+        as in modalFrequencyResponse (the density is the basis's). u0 / v0: nodal fields [nNode, N], projected on the modes; or q0 / qdot0: the
+        "q" / "qdot" of an earlier call, to continue it. Returns a dict: "q", "qdot" (the modal state after the last step), "probes"
+        [n_steps + 1, len(probes)], "snapshots" [n_steps // snapshot_stride + 1, nNode, N] (snapshot_stride > 0), "modal_coords"
+        [n_steps + 1, m], "energies" [n_steps + 1, 3] restricted to the retained modes. self.modal_transient_info holds the solver's record."""
+        ctx = self.ctx
+        density = self._density_scalar(density)
+        mapped = ctx.n_dof != ctx.n_node
+        dof = ctx.get_dof_map()[0] if mapped else None
+        if n_modes is not None or modes is not None:
+            v, _ = ctx.bc_dirichlet_vars()
+            ctx.clear_fixed()
+            if len(v):
+                ctx.fix_variables(v)
+            if modes is not None:
+                lam, X = modes
+                self.modal_basis_info = ctx.set_modal_basis(lam, np.asarray(X, dtype=np.float64).reshape(len(lam), -1), density=density)
+            else:
+                lam, X, info = ctx.modal_basis(int(n_modes), density=density, free=len(v) == 0, batch=batch, rtol=modes_rtol)
+                self.modes_many_info, self.modal_basis_info = info, info["modal_basis"]
+            self.modal_frequencies = np.sqrt(np.asarray(lam)) / (2.0 * np.pi)
+        if mapped:
+            first = np.full(ctx.n_dof, -1, dtype=np.int64)
+            first[dof[::-1]] = np.arange(ctx.n_node)[::-1]
+
+        def to_dofs(x):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=np.float64).reshape(ctx.n_node, self.N)
+            return x[first] if mapped else x
+        f = self.neumannLoad() if load is None else np.asarray(load, dtype=np.float64).reshape(ctx.n_dof, self.N)
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        try:
+            r = ctx.modal_transient(dt, n_steps, f, amplitude=amplitude, q0=q0, qdot0=qdot0, u0=to_dofs(u0), v0=to_dofs(v0), damping=damping,
+                                    modal_damping=modal_damping, static_correction=static_correction, rtol=self.rtol if rtol is None else rtol,
+                                    maxit=self.maxit if maxit is None else maxit, probes=pv, snapshot_stride=snapshot_stride, modal_coords=modal_coords,
+                                    energies=energies, chunk_steps=chunk_steps)
+        finally:
+            self.modal_transient_info = getattr(ctx, "last_modal_transient", {}).get("info")
+        out = dict(r)
+        if r["snapshots"] is not None:
+            s = r["snapshots"].reshape(len(r["snapshots"]), ctx.n_dof, self.N)
+            out["snapshots"] = s[:, dof, :] if mapped else s
+        del out["info"]
+        return out
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 
