@@ -191,4 +191,216 @@ modalFrequencyResponse(const Sim &sim, const std::vector<Real> &omegas,
     return r;
 }
 
+// ---- random vibration and response spectra on the same basis (include/meshfem_hip.h, "Random vibration and response spectra";
+// docs/design/04_23_modal_random.md)
+//   modalRandomResponse(sim, omegas, S, opt)   the RMS displacement (velocity, acceleration on request) under the loads opt.loads (empty: the Neumann
+//                                              load) whose amplitudes have the one-sided cross-spectral density S ([nFreq][nLoad][nLoad], Hermitian) on
+//                                              the strictly ascending grid omegas; zero-crossing rates and response spectra at the probes
+//   responseSpectrum(sim, direction, Sd, opt)  the peak field sqrt(phi_i^T C phi_i), C_jk = rho_jk a_j a_k, a_j = Gamma_j Sd_j, under a base motion in
+//                                              `direction`; rule SRSS (rho = I) or CQC (mfh_cqc_matrix)
+// Basis, clamp and probes as in modalFrequencyResponse.
+namespace detail {
+// the clamp of the Dirichlet conditions and the basis: opt.nModes modes computed here, or the caller's eigenpairs
+template <class Sim, class Opt>
+void setModalBasis(const Sim &sim, const Opt &opt, const char *who, std::vector<Real> &lambda, mfh_modal_basis_info &basisInfo) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    mfh_ctx *c = sim.ctx();
+    check(c, mfh_clear_fixed(c));
+    int64_t nv = 0;
+    check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
+    if (nv > 0) {
+        std::vector<int64_t> vars((size_t)nv);
+        std::vector<Real> vals((size_t)nv);
+        check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
+        check(c, mfh_fix_variables(c, nv, vars.data(), nullptr));
+    }
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N;
+    std::vector<Real> X;
+    if (opt.lambda.empty()) {
+        mfh_modes_many_params mp{};
+        mp.nev = opt.nModes; mp.batch = opt.batch; mp.flags = nv > 0 ? 0 : MFH_MODES_FREE; mp.maxit = 3000;
+        mp.density = opt.density; mp.rtol = opt.modesRtol;
+        lambda.assign((size_t)std::max(opt.nModes, 0), 0.0);
+        X.assign(lambda.size() * n, 0.0);
+        mfh_modes_many_info mi{};
+        check(c, mfh_modes_many(c, &mp, nullptr, lambda.data(), X.data(), nullptr, &mi));
+    } else {
+        if (opt.modes.size() != opt.lambda.size()) throw std::runtime_error(std::string(who) + ": one mode per eigenvalue");
+        lambda = opt.lambda;
+        X.resize(lambda.size() * n);
+        for (size_t j = 0; j < opt.modes.size(); ++j) {
+            if (opt.modes[j].size() != nDoF) throw std::runtime_error(std::string(who) + ": a mode needs one entry per DoF");
+            std::copy(&opt.modes[j][0][0], &opt.modes[j][0][0] + n, X.begin() + (std::ptrdiff_t)(j * n));
+        }
+    }
+    check(c, mfh_modal_set_basis(c, (int32_t)lambda.size(), lambda.data(), X.data(), opt.density, &basisInfo));
+}
+} // namespace detail
+
+template <class VField>
+struct ModalRandomOptions {
+    Real density = 1.0, rayleighMass = 0.0, rayleighStiff = 0.0, lossFactor = 0.0;
+    int nModes = 16, batch = 0;                           // as in ModalHarmonicOptions
+    Real modesRtol = 1e-6;
+    std::vector<Real> lambda;
+    std::vector<VField> modes;
+    std::vector<Real> modalDamping;                       // damping ratios per mode; empty: none
+    bool staticCorrection = true;                         // at most two loads with it
+    bool velocity = false, acceleration = false;          // sigma_v, sigma_a fields as well
+    Real tol = -1.0;                                      // of the factorisation (< 0: nb eps max diag)
+    Real rtol = 1e-8;                                     // of the static solves
+    int maxit = 10000;
+    std::vector<VField> loads;                            // the load shapes; empty: the Neumann load
+    std::vector<Real> weights;                            // quadrature weights; empty: the trapezoid rule
+    std::vector<std::pair<size_t, int>> probes;
+    bool fields = true, probePsd = false;
+};
+
+template <size_t N>
+struct ModalRandomResult {
+    using Field = std::vector<std::array<Real, N>>;
+    Field sigmaU, sigmaV, sigmaA;                             // [nDoF]; empty where not asked for
+    std::vector<Real> probeSigmaU, probeSigmaV, probeSigmaA, probeNu0;   // [number of probes]
+    std::vector<std::vector<Real>> probePsd;                  // [number of probes][nFreq]
+    std::array<std::vector<Real>, 3> cov;                     // C^(0), C^(2), C^(4): nb x nb row-major
+    std::vector<Real> lambda;
+    mfh_modal_basis_info basisInfo{};
+    mfh_modal_random_info info{};
+};
+
+template <class Sim>
+ModalRandomResult<std::tuple_size<typename Sim::VField::value_type>::value>
+modalRandomResponse(const Sim &sim, const std::vector<Real> &omegas, const std::vector<std::complex<Real>> &S,
+                    const ModalRandomOptions<typename Sim::VField> &opt = ModalRandomOptions<typename Sim::VField>()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    mfh_ctx *c = sim.ctx();
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N, nFreq = omegas.size(), nLoad = std::max<size_t>(opt.loads.size(), 1);
+    if (S.size() != nFreq * nLoad * nLoad) throw std::runtime_error("modalRandomResponse: S needs nFreq x nLoad x nLoad entries");
+    if (!opt.weights.empty() && opt.weights.size() != nFreq) throw std::runtime_error("modalRandomResponse: one weight per frequency");
+    ModalRandomResult<N> r;
+    detail::setModalBasis(sim, opt, "modalRandomResponse", r.lambda, r.basisInfo);
+    const size_t m = r.lambda.size();
+    if (!opt.modalDamping.empty() && opt.modalDamping.size() != m) throw std::runtime_error("modalRandomResponse: one damping ratio per mode");
+    std::vector<Real> f(nLoad * n);
+    if (opt.loads.empty()) {
+        const VField l = sim.neumannLoad();
+        std::copy(&l[0][0], &l[0][0] + n, f.begin());
+    } else
+        for (size_t a = 0; a < nLoad; ++a) {
+            if (opt.loads[a].size() != nDoF) throw std::runtime_error("modalRandomResponse: a load needs one entry per DoF");
+            std::copy(&opt.loads[a][0][0], &opt.loads[a][0][0] + n, f.begin() + (std::ptrdiff_t)(a * n));
+        }
+    std::vector<int64_t> probeVars;
+    for (const auto &p : opt.probes) probeVars.push_back((int64_t)(p.first * N) + p.second);
+    const size_t nProbe = probeVars.size(), planes = 1 + (opt.velocity ? 1 : 0) + (opt.acceleration ? 1 : 0), nbMax = m + 2;
+    std::vector<Real> rms(4 * nProbe), psd(opt.probePsd ? nProbe * nFreq : 0), fld(opt.fields ? planes * n : 0), cov(3 * nbMax * nbMax);
+    mfh_modal_random_params prm{};
+    prm.rayleighMass = opt.rayleighMass; prm.rayleighStiff = opt.rayleighStiff; prm.lossFactor = opt.lossFactor;
+    prm.rtol = opt.rtol; prm.tol = opt.tol; prm.maxit = opt.maxit; prm.nFreq = (int32_t)nFreq; prm.nLoad = (int32_t)nLoad;
+    prm.flags = (opt.staticCorrection ? MFH_MODAL_RV_STATIC_CORRECTION : 0) | (opt.velocity ? MFH_MODAL_RV_VELOCITY : 0) |
+                (opt.acceleration ? MFH_MODAL_RV_ACCELERATION : 0);
+    check(c, mfh_modal_random(c, &prm, omegas.data(), opt.weights.empty() ? nullptr : opt.weights.data(),
+                              opt.modalDamping.empty() ? nullptr : opt.modalDamping.data(), f.data(), reinterpret_cast<const Real *>(S.data()),
+                              nProbe ? probeVars.data() : nullptr, (int32_t)nProbe, nProbe ? rms.data() : nullptr,
+                              (opt.probePsd && nProbe) ? psd.data() : nullptr, opt.fields ? fld.data() : nullptr, cov.data(), &r.info));
+    const size_t nb = (size_t)r.info.nb;
+    for (size_t q = 0; q < 3; ++q) r.cov[q].assign(cov.begin() + (std::ptrdiff_t)(q * nb * nb), cov.begin() + (std::ptrdiff_t)((q + 1) * nb * nb));
+    if (nProbe) {
+        r.probeSigmaU.assign(rms.begin(), rms.begin() + (std::ptrdiff_t)nProbe);
+        r.probeSigmaV.assign(rms.begin() + (std::ptrdiff_t)nProbe, rms.begin() + (std::ptrdiff_t)(2 * nProbe));
+        if (opt.acceleration) r.probeSigmaA.assign(rms.begin() + (std::ptrdiff_t)(2 * nProbe), rms.begin() + (std::ptrdiff_t)(3 * nProbe));
+        r.probeNu0.assign(rms.begin() + (std::ptrdiff_t)(3 * nProbe), rms.end());
+        if (opt.probePsd)
+            for (size_t p = 0; p < nProbe; ++p) r.probePsd.emplace_back(psd.begin() + (std::ptrdiff_t)(p * nFreq), psd.begin() + (std::ptrdiff_t)((p + 1) * nFreq));
+    }
+    if (opt.fields) {
+        typename ModalRandomResult<N>::Field *dst[3] = {&r.sigmaU, opt.velocity ? &r.sigmaV : nullptr, opt.acceleration ? &r.sigmaA : nullptr};
+        size_t plane = 0;
+        for (auto *d : dst) {
+            if (!d) continue;
+            d->resize(nDoF);
+            std::copy(fld.begin() + (std::ptrdiff_t)(plane * n), fld.begin() + (std::ptrdiff_t)((plane + 1) * n), &(*d)[0][0]);
+            ++plane;
+        }
+    }
+    return r;
+}
+
+template <class VField>
+struct ResponseSpectrumOptions {
+    Real density = 1.0;
+    int nModes = 16, batch = 0;
+    Real modesRtol = 1e-6;
+    std::vector<Real> lambda;
+    std::vector<VField> modes;
+    Real zeta = 0.05;                                     // damping ratio of every mode, or ...
+    std::vector<Real> modalDamping;                       // ... one per mode
+    bool cqc = true;                                      // false: SRSS
+    Real tol = -1.0;
+    std::vector<std::pair<size_t, int>> probes;
+    bool fields = true;
+};
+
+template <size_t N>
+struct ResponseSpectrumResult {
+    std::vector<std::array<Real, N>> R;                       // [nDoF]; empty without fields
+    std::vector<Real> probes, gamma, a, lambda;               // peak values at the probes; participation factors; a_j = gamma_j Sd_j
+    Real massFraction = 0.0;                                  // sum_j gamma_j^2 over the moving mass r_f^T (density M) r_f
+    mfh_modal_basis_info basisInfo{};
+    mfh_modal_quadratic_info info{};
+};
+
+// Sd: the spectral displacement as a function of (omega_j, zeta_j)
+template <class Sim, class SdFn>
+ResponseSpectrumResult<std::tuple_size<typename Sim::VField::value_type>::value>
+responseSpectrum(const Sim &sim, int direction, SdFn Sd, const ResponseSpectrumOptions<typename Sim::VField> &opt = ResponseSpectrumOptions<typename Sim::VField>()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value;
+    if (direction < 0 || direction >= (int)N) throw std::runtime_error("responseSpectrum: direction out of range");
+    mfh_ctx *c = sim.ctx();
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N;
+    ResponseSpectrumResult<N> r;
+    detail::setModalBasis(sim, opt, "responseSpectrum", r.lambda, r.basisInfo);
+    const size_t m = r.lambda.size();
+    if (!opt.modalDamping.empty() && opt.modalDamping.size() != m) throw std::runtime_error("responseSpectrum: one damping ratio per mode");
+    std::vector<Real> zeta = opt.modalDamping.empty() ? std::vector<Real>(m, opt.zeta) : opt.modalDamping;
+    std::vector<Real> rd(n, 0.0), Mr(n, 0.0);
+    for (size_t i = 0; i < nDoF; ++i) rd[i * N + (size_t)direction] = 1.0;
+    r.gamma.assign(m, 0.0);
+    check(c, mfh_modal_coordinates(c, rd.data(), 1, r.gamma.data()));
+    int64_t nv = 0;
+    check(c, mfh_bc_dirichlet_vars(c, nullptr, nullptr, &nv));
+    if (nv > 0) {
+        std::vector<int64_t> vars((size_t)nv);
+        std::vector<Real> vals((size_t)nv);
+        check(c, mfh_bc_dirichlet_vars(c, vars.data(), vals.data(), &nv));
+        for (int64_t v : vars) rd[(size_t)v] = 0.0;
+    }
+    check(c, mfh_mass_apply(c, rd.data(), Mr.data(), 0));
+    Real moving = 0.0, reached = 0.0;
+    for (size_t i = 0; i < n; ++i) moving += rd[i] * Mr[i];
+    r.a.assign(m, 0.0);
+    for (size_t j = 0; j < m; ++j) { r.a[j] = r.gamma[j] * Sd(std::sqrt(r.lambda[j]), zeta[j]); reached += r.gamma[j] * r.gamma[j]; }
+    r.massFraction = moving > 0.0 ? reached / (opt.density * moving) : 0.0;
+    std::vector<Real> C(m * m, 0.0);
+    if (opt.cqc) check(c, mfh_cqc_matrix((int32_t)m, r.lambda.data(), zeta.data(), C.data()));
+    else for (size_t j = 0; j < m; ++j) C[j * m + j] = 1.0;
+    for (size_t j = 0; j < m; ++j)
+        for (size_t k = 0; k < m; ++k) C[j * m + k] *= r.a[j] * r.a[k];
+    std::vector<int64_t> probeVars;
+    for (const auto &p : opt.probes) probeVars.push_back((int64_t)(p.first * N) + p.second);
+    const size_t nProbe = probeVars.size();
+    r.probes.assign(nProbe, 0.0);
+    std::vector<Real> fld(opt.fields ? n : 0);
+    check(c, mfh_modal_quadratic(c, 1, C.data(), opt.tol, nProbe ? probeVars.data() : nullptr, (int32_t)nProbe, nProbe ? r.probes.data() : nullptr,
+                                 opt.fields ? fld.data() : nullptr, &r.info));
+    if (opt.fields) {
+        r.R.resize(nDoF);
+        std::copy(fld.begin(), fld.end(), &r.R[0][0]);
+    }
+    return r;
+}
+
 } // namespace MeshFEMHip

@@ -563,6 +563,8 @@ typedef struct mfh_modes_many_info {
     double  maxResidual, maxLockDefect, solve_ms, setup_ms;
     const char* note;                                                            /* owned by the context, valid until its next call */
 } mfh_modes_many_info;
+/* A converged call leaves the columns it found on the device (nLocked + nev columns of dim*nDoF doubles, arena memory) for
+ * mfh_modal_set_basis_from_modes, until the context's next mfh_modes_many, a new mesh or a DoF map. */
 mfh_status mfh_modes_many(mfh_ctx* ctx, const mfh_modes_many_params* params, const double* Q /* nLocked x dim*nDoF, host, or NULL */,
                           double* lambda /* nev */, double* X /* nev x dim*nDoF */, double* residuals /* nev or NULL */, mfh_modes_many_info* info);
 
@@ -751,6 +753,12 @@ typedef struct mfh_modal_harmonic_info {
 } mfh_modal_harmonic_info;
 mfh_status mfh_modal_set_basis(mfh_ctx* ctx, int32_t nModes, const double* lambda /* nModes */, const double* X /* nModes x dim*nDoF */,
                                double density, mfh_modal_basis_info* info);
+/* the same basis without the host round trip: adopts the first nModes (1 .. what was found) modes, in ascending order of lambda, that the context's last
+ * converged mfh_modes_many left on the device -- a device-to-device copy into the modal layout with the signs of the host copy, the fixed rows zeroed, the
+ * same orthoDefect pass; every later modal result equals the round trip's bit for bit. mfh_modes_many keeps that set (nLocked + nev columns of
+ * dim*nDoF doubles, counted by the device statistics) until its next call, a new mesh or a DoF map. MFH_ERR_STATE: no such set, or one made under other
+ * vertex positions, material, density field or fixed variables (the rules of the basis itself). */
+mfh_status mfh_modal_set_basis_from_modes(mfh_ctx* ctx, int32_t nModes, double density, mfh_modal_basis_info* info);
 mfh_status mfh_modal_coordinates(mfh_ctx* ctx, const double* u /* nVec x dim*nDoF */, int32_t nVec, double* q /* nVec x nModes */);
 /* *nModes = modes of the basis in place (0: none), *valid = 1 if the modal calls would accept it now (either may be NULL) */
 mfh_status mfh_modal_basis_state(mfh_ctx* ctx, int32_t* nModes, int32_t* valid);
@@ -806,6 +814,81 @@ mfh_status mfh_modal_transient(mfh_ctx* ctx, const mfh_modal_transient_params* p
  * exp(dt [[0,1,0,0],[-lambda,-c,1,0],[0,0,0,1],[0,0,0,0]]), for lambda >= 0 (0: a rigid mode), c >= 0 (under-damped, critical, over-damped) and
  * dt > 0, each within a few ulps of its natural size (MFH_ERR_INVALID otherwise) */
 mfh_status mfh_modal_transient_coeffs(double lambda, double c, double dt, double* out8);
+
+/* Random vibration and response spectra on the same basis (docs/design/04_23_modal_random.md). Both reduce to a quadratic form per row of the basis
+ * B = [Phi | r_1 | r_2]:  v_i = phi_i^T C phi_i for a symmetric positive semi-definite nb x nb matrix C. The host factors C = F F^T (mfh_psd_factor) and
+ * the device forms v_i = sum_t (sum_j B_j[i] F_jt)^2 >= 0, one pass over the basis per 32 columns of F (kernel k_modal_sumsq).
+ * Host only, no context:
+ *   mfh_psd_factor        Cholesky with diagonal pivoting of the n x n (n <= 258) row-major matrix C, symmetry taken from the lower triangle. It stops
+ *                         when the largest remaining diagonal is <= tol (tol < 0: n eps max diag, the rule of LAPACK's dpstrf). F: n x n row-major, its
+ *                         first *rank columns written, row j belonging to row j of C (no permutation of the rows; the rows of the pivots chosen before
+ *                         column t are exactly zero from column t on); piv: n entries, the first *rank the pivots in order (or NULL);
+ *                         *truncation = the trace of the positive semi-definite remainder C - F F^T (or NULL): phi^T (C - F F^T) phi <= truncation |phi|^2.
+ *                         MFH_ERR_INVALID: n out of range, an entry that is not finite, a remaining diagonal below -tol (C is not positive
+ *                         semi-definite). A zero matrix has rank 0.
+ *   mfh_modal_covariance  C^(p) = sum_k w_k omega_k^p Re(H_k S_k H_k^H), p = 0, 2, 4: the covariances of the coordinates of displacement, velocity and
+ *                         acceleration under loads of one-sided cross-spectral density S (Hermitian, nLoad x nLoad per frequency, with respect to
+ *                         omega). H_k = [g_ja / d_j(omega_k) ; delta_ab / zK(omega_k)], nb x nLoad, the second block (nLoad rows) only with
+ *                         correction = 1; d_j, zK as for mfh_modal_harmonic. g: nModes x nLoad row-major (g = Phi^T f_a). weights: nFreq quadrature
+ *                         weights or NULL (the trapezoid rule on omega; needs nFreq >= 2). C0, C2, C4: nb x nb row-major, nb = nModes + correction nLoad,
+ *                         any may be NULL. Plain double precision; every entry is summed over k in grid order, so the bits do not depend on the number
+ *                         of host threads. MFH_ERR_INVALID: omega not strictly ascending or negative; omega = 0 with a zero lambda; d_j = 0; an S_k that
+ *                         is not Hermitian entry by entry to 8 eps max |S_k| or has a negative diagonal; a negative lambda, zeta or damping
+ *                         coefficient; an entry or a sum that is not finite. MFH_ERR_UNSUPPORTED: correction with nLoad > 2. nLoad <= 8, nModes <= 256.
+ *   mfh_cqc_matrix        rho_jk = 8 sqrt(zeta_j zeta_k) (zeta_j + r zeta_k) r^(3/2) / ((1 - r^2)^2 + 4 zeta_j zeta_k r (1 + r^2) + 4 (zeta_j^2 + zeta_k^2) r^2),
+ *                         r = omega_k / omega_j (Der Kiureghian's correlation of the CQC rule, unequal damping), m x m row-major, exactly symmetric with
+ *                         a unit diagonal. zeta_j > 0, lambda_j >= 0 (MFH_ERR_INVALID otherwise); two zero eigenvalues: 1 at equal zeta, else 0.
+ * On the basis of mfh_modal_set_basis (MFH_ERR_STATE without a valid one; contexts as for mfh_modal_harmonic):
+ *   mfh_modal_quadratic   sqrt(phi_i^T C_a phi_i) for nMat <= 4 symmetric nModes x nModes matrices (row-major, one after the other) over the modes:
+ *                         into fields (nMat x dim*nDoF, or NULL) and at the probes (probeOut nMat x nProbe), the probes bit for bit the field entries.
+ *                         The response-spectrum rules are this call with C_jk = rho_jk a_j a_k. tol: as for mfh_psd_factor. A matrix the
+ *                         factorisation refuses: MFH_ERR_INVALID, nothing written.
+ *   mfh_modal_random      the RMS response to loads sum_a A_a(t) f_a (f: nLoad x dim*nDoF real load shapes) whose amplitudes have the spectrum S.
+ *                         rmsFields: sigma_u, then sigma_v with MFH_MODAL_RV_VELOCITY, then sigma_a with MFH_MODAL_RV_ACCELERATION, dim*nDoF each, or NULL;
+ *                         probeRms: 4 x nProbe = {sigma_u, sigma_v, sigma_a (0 without its flag), nu0+ = sigma_v / (2 pi sigma_u), the rate of upward zero
+ *                         crossings}; probePsd: nProbe x nFreq, the response spectrum H_p S H_p^H of each probe, or NULL; cov: 3 x nb x nb = C^(0), C^(2),
+ *                         C^(4), or NULL. MFH_MODAL_RV_STATIC_CORRECTION: one static solve per load that is not zero, the residual vectors r_a in the two
+ *                         reserved columns of the basis as mfh_modal_harmonic writes them; at most two loads with it (MFH_ERR_UNSUPPORTED). nLoad <= 8.
+ *                         The static solves, the validity rules and the refusals are mfh_modal_harmonic's, plus those of mfh_modal_covariance. Nothing
+ *                         field-sized is done beyond the load projections when no field is asked for. */
+enum { MFH_MODAL_RV_STATIC_CORRECTION = 1, MFH_MODAL_RV_VELOCITY = 2, MFH_MODAL_RV_ACCELERATION = 4 };
+typedef struct mfh_modal_quadratic_info {
+    int32_t ranks[4], passes[4];                                                       /* per matrix: columns of F, passes over the basis */
+    double truncation[4];
+    double factorMs, solveMs;
+} mfh_modal_quadratic_info;
+typedef struct mfh_modal_random_params {
+    double rayleighMass, rayleighStiff, lossFactor, rtol, tol;                         /* rtol, maxit: the static solves; tol: mfh_psd_factor's */
+    int32_t maxit, nFreq, nLoad, flags;
+} mfh_modal_random_params;
+typedef struct mfh_modal_random_info {
+    int32_t ranks[3], passes[3];                                                       /* of C^(0), C^(2), C^(4); 0 where none was factored */
+    int32_t staticSolves, staticIterations, nb, reserved;
+    double truncation[3];
+    double covarianceMs, factorMs, solveMs;
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_modal_random_info;
+mfh_status mfh_psd_factor(int32_t n, const double* C, double tol, double* F, int32_t* rank, int32_t* piv, double* truncation);
+mfh_status mfh_modal_covariance(int32_t nModes, const double* lambda, const double* g /* nModes x nLoad */, int32_t nLoad,
+                                double rayleighMass, double rayleighStiff, double lossFactor, const double* modalDamping /* nModes or NULL */,
+                                int32_t nFreq, const double* omega, const double* weights /* nFreq or NULL */,
+                                const double* S /* nFreq x nLoad x nLoad x {re, im} */, int32_t correction,
+                                double* C0, double* C2, double* C4 /* nb x nb each, or NULL */);
+mfh_status mfh_cqc_matrix(int32_t m, const double* lambda, const double* zeta, double* rho /* m x m */);
+mfh_status mfh_modal_quadratic(mfh_ctx* ctx, int32_t nMat, const double* C /* nMat x nModes x nModes */, double tol,
+                               const int64_t* probeVars, int32_t nProbe, double* probeOut /* nMat x nProbe */,
+                               double* fields /* nMat x dim*nDoF, or NULL */, mfh_modal_quadratic_info* info);
+mfh_status mfh_modal_random(mfh_ctx* ctx, const mfh_modal_random_params* params,
+                            const double* omega,                      /* nFreq, strictly ascending */
+                            const double* weights,                    /* nFreq or NULL */
+                            const double* modalDamping,               /* nModes or NULL */
+                            const double* f,                          /* nLoad x dim*nDoF */
+                            const double* S,                          /* nFreq x nLoad x nLoad x {re, im} */
+                            const int64_t* probeVars, int32_t nProbe, double* probeRms,  /* 4 x nProbe */
+                            double* probePsd,                         /* nProbe x nFreq, or NULL */
+                            double* rmsFields,                        /* (1 + velocity + acceleration) x dim*nDoF, or NULL */
+                            double* cov,                              /* 3 x nb x nb, or NULL */
+                            mfh_modal_random_info* info);
 
 /* ---------------------------------------------------------------- per-element density, the product with M, mass properties
  * (docs/design/04_15_density.md.) The mass matrix of mfh_modes and mfh_newmark is assembled from a density field of the context:

@@ -124,6 +124,20 @@ mfh_status mfh_debug_modal_march(mfh_ctx* ctx, int32_t nModes, const double* coe
 /* device time (ms, one entry per repetition each) of k_modal_series and of the k_modal_expand route (the gathered probe rows as the kernel's rows, 32
  * steps per pass) for nProbe probes of nSteps rows on nModes hashed columns, the two taking turns in every repetition */
 mfh_status mfh_time_modal_series(mfh_ctx* ctx, int32_t nModes, int32_t nProbe, int32_t nSteps, int32_t reps, double* seriesMs, double* expandMs);
+/* test hook: the quadratic-form kernel of mfh_modal_quadratic / mfh_modal_random (k_modal_sumsq, mfh_modal.hip) on host arrays, launched as those calls
+ * launch it. B: n x nb column-major (nb <= 258), F: nb x rank row-major; out: n, out[row] = sum_t (sum_j B_j[row] F[j][t])^2 (its square root with
+ * sqrtFlag), the inner sums fma chains over j ascending from +0, the outer one fma(s_t, s_t, acc) over t ascending from +0. piv: NULL (every pass
+ * streams all nb columns) or the rank <= nb pivots of mfh_psd_factor: the pass whose first column is t0 leaves out the columns piv[0 .. t0), whose
+ * coefficients have to be exactly zero from t0 on (MFH_ERR_INVALID otherwise). planesPerPass: 1 .. 32 columns of F per pass, 0 = the default.
+ * rank 0 returns zeros without reading B */
+mfh_status mfh_debug_modal_sumsq(mfh_ctx* ctx, int64_t n, int32_t nb, const double* B, const double* F, int32_t rank, const int32_t* piv,
+                                 int32_t planesPerPass, int32_t sqrtFlag, double* out);
+/* device time (ms, one entry per repetition each) of one pass of k_modal_sumsq<NP> and of one pass of k_modal_expand<NP> on the same nb hashed columns
+ * of n rows, the two taking turns in every repetition (NP = planesPerPass in {8, 16, 32}; 0 = the default); laterMs (or NULL): the SECOND pass of a
+ * factor of rank 2 NP whose first NP pivots are the columns 0 .. NP - 1 -- it streams nc = nb - NP columns and reads the accumulator back (0 where
+ * nb <= NP) */
+mfh_status mfh_time_modal_sumsq(mfh_ctx* ctx, int64_t n, int32_t nb, int32_t planesPerPass, int32_t reps, double* sumsqMs, double* expandMs,
+                                double* laterMs);
 
 /* test hooks: the step kernels of mfh_newmark (mfh_dynamics.hip) on host arrays of n doubles. mask: n bytes or NULL (non-zero = fixed variable).
  * predict: ut = u + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a (both 0 where masked), w = gamma / (beta dt) ut - vt,

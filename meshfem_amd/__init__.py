@@ -8,6 +8,7 @@ from ._lib import (MeshFEMHipError, ASSEMBLE_GATHER, ASSEMBLE_ATOMIC, NEUMANN_TR
                    OP_ELASTICITY, OP_LAPLACIAN, OP_MASS, OP_MASS_VECTOR, SOLVE_PIN, SOLVE_NO_RIGID_MOTION, SOLVE_ALLOW_ILL_POSED,
                    FIELD_PER_VERTEX, FIELD_PER_ELEMENT, FIELD_PER_NODE)
 from .core import sym_measures, von_mises, principal_values, vertex_averaged_field, modal_transient_coeffs
+from .core import psd_factor, modal_covariance, cqc_matrix, resonance_grid
 from .core import Context, device_cache_trim, device_cache_stats, device_arena_stats, device_reserve, device_reserve_for, context_bytes_estimate
 from .linear_elasticity import Simulator
 from .tensors import ElasticityTensor, ElasticityTensor2D, ElasticityTensor3D

@@ -25,6 +25,7 @@ EXP_HAVE_ACCEL, EXP_ENERGIES, EXP_NO_DT_CHECK = 1, 2, 4
 HARM_WARM_START = 1
 MODAL_STATIC_CORRECTION, MODAL_RESIDUALS = 1, 2
 MODAL_TR_STATIC_CORRECTION, MODAL_TR_ENERGIES = 1, 2
+MODAL_RV_STATIC_CORRECTION, MODAL_RV_VELOCITY, MODAL_RV_ACCELERATION = 1, 2, 4
 
 
 class SamplerGridInfo(C.Structure):
@@ -179,6 +180,29 @@ class ModalTransientInfo(C.Structure):
         return d
 
 
+class ModalQuadraticInfo(C.Structure):
+    _fields_ = [("ranks", C.c_int32 * 4), ("passes", C.c_int32 * 4), ("truncation", C.c_double * 4), ("factorMs", C.c_double), ("solveMs", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("ranks", "passes", "truncation") else getattr(self, k)) for k, _ in self._fields_}
+
+
+class ModalRandomParams(C.Structure):
+    _fields_ = [("rayleighMass", C.c_double), ("rayleighStiff", C.c_double), ("lossFactor", C.c_double), ("rtol", C.c_double), ("tol", C.c_double),
+                ("maxit", C.c_int32), ("nFreq", C.c_int32), ("nLoad", C.c_int32), ("flags", C.c_int32)]
+
+
+class ModalRandomInfo(C.Structure):
+    _fields_ = [("ranks", C.c_int32 * 3), ("passes", C.c_int32 * 3), ("staticSolves", C.c_int32), ("staticIterations", C.c_int32), ("nb", C.c_int32),
+                ("reserved", C.c_int32), ("truncation", C.c_double * 3), ("covarianceMs", C.c_double), ("factorMs", C.c_double), ("solveMs", C.c_double),
+                ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: (list(getattr(self, k)) if k in ("ranks", "passes", "truncation") else getattr(self, k)) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
 class DistStats(C.Structure):
     _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("transport", C.c_int32), ("peer_enabled", C.c_int32),
                 ("halo_nodes_sent", C.c_int64), ("halo_nodes_received", C.c_int64), ("halo_bytes_per_exchange", C.c_int64),
@@ -311,10 +335,16 @@ PROTOTYPES = {
     "mfh_harmonic": (_i32, [_P, C.POINTER(HarmonicParams), _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(HarmonicInfo)]),
     "mfh_modal_set_basis": (_i32, [_P, _i32, _P, _P, _f64, C.POINTER(ModalBasisInfo)]),
     "mfh_modal_coordinates": (_i32, [_P, _P, _i32, _P]),
+    "mfh_modal_set_basis_from_modes": (_i32, [_P, _i32, _f64, C.POINTER(ModalBasisInfo)]),
     "mfh_modal_basis_state": (_i32, [_P, _pi32, _pi32]),
     "mfh_modal_harmonic": (_i32, [_P, C.POINTER(ModalHarmonicParams), _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalHarmonicInfo)]),
     "mfh_modal_transient": (_i32, [_P, C.POINTER(ModalTransientParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalTransientInfo)]),
     "mfh_modal_transient_coeffs": (_i32, [_f64, _f64, _f64, _P]),
+    "mfh_psd_factor": (_i32, [_i32, _P, _f64, _P, _pi32, _P, _P]),
+    "mfh_modal_covariance": (_i32, [_i32, _P, _P, _i32, _f64, _f64, _f64, _P, _i32, _P, _P, _P, _i32, _P, _P, _P]),
+    "mfh_cqc_matrix": (_i32, [_i32, _P, _P, _P]),
+    "mfh_modal_quadratic": (_i32, [_P, _i32, _P, _f64, _P, _i32, _P, _P, C.POINTER(ModalQuadraticInfo)]),
+    "mfh_modal_random": (_i32, [_P, C.POINTER(ModalRandomParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalRandomInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -383,6 +413,8 @@ PROTOTYPES = {
     "mfh_time_modal_expand": (_i32, [_P, _i64, _i32, _i32, _i32, _P]),
     "mfh_debug_modal_march": (_i32, [_P, _i32, _P, _P, _P, _f64, _i32, _P, _i32, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "mfh_time_modal_series": (_i32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
+    "mfh_debug_modal_sumsq": (_i32, [_P, _i64, _i32, _P, _P, _i32, _P, _i32, _i32, _P]),
+    "mfh_time_modal_sumsq": (_i32, [_P, _i64, _i32, _i32, _i32, _P, _P, _P]),
     "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmeshfem_hip.so")
-SOURCES = ["mfh_api.cpp", "mfh_options.cpp", "mfh_pool.cpp", "mfh_solver.cpp", "mfh_simulator.cpp", "mfh_mesh.cpp", "mfh_symbolic.cpp", "mfh_twolevel.cpp", "mfh_multigrid.cpp", "mfh_symbolic_gpu.hip", "mfh_kernels.hip", "mfh_kernels_solver.hip", "mfh_peer.hip", "mfh_sampler.hip", "mfh_modes.hip", "mfh_dynamics.hip", "mfh_harmonic.hip", "mfh_modal.hip", "mfh_modal_coeffs.cpp", "mfh_loads.hip", "mfh_mass.hip", "mfh_explicit.hip"]
+SOURCES = ["mfh_api.cpp", "mfh_options.cpp", "mfh_pool.cpp", "mfh_solver.cpp", "mfh_simulator.cpp", "mfh_mesh.cpp", "mfh_symbolic.cpp", "mfh_twolevel.cpp", "mfh_multigrid.cpp", "mfh_symbolic_gpu.hip", "mfh_kernels.hip", "mfh_kernels_solver.hip", "mfh_peer.hip", "mfh_sampler.hip", "mfh_modes.hip", "mfh_dynamics.hip", "mfh_harmonic.hip", "mfh_modal.hip", "mfh_modal_coeffs.cpp", "mfh_modal_cov.cpp", "mfh_loads.hip", "mfh_mass.hip", "mfh_explicit.hip"]
 HOST_ONLY = ["mfh_twolevel.cpp"]
 HEADERS = ["mfh_internal.hh", "mfh_ctx.hh", "mfh_device.hh", "mfh_dispatch.hh", "mfh_pencil.hh", "mfh_comm.hh", os.path.join("..", "..", "include", "meshfem_hip.h")]
 

@@ -651,10 +651,22 @@ class Context:
         self._ck(self.lib.mfh_modal_basis_state(self.h, C.byref(m), C.byref(ok)))
         return m.value, bool(ok.value)
 
+    def set_modal_basis_from_modes(self, n_modes, density=1.0):
+        """Adopt the first n_modes modes the last modes_many() of this context left on the device as the basis of the modal calls
+        (mfh_modal_set_basis_from_modes): what set_modal_basis(lam[:n_modes], X[:n_modes]) of its result sets, bit for bit, without the host round
+        trip. Raises with code ERR_STATE if there is no such set or the mesh, material, density field or fixed variables changed since."""
+        info = L.ModalBasisInfo()
+        self._ck(self.lib.mfh_modal_set_basis_from_modes(self.h, int(n_modes), float(density), C.byref(info)))
+        return info.as_dict()
+
     def modal_basis(self, nev, density=1.0, **kw):
-        """modes_many(nev, density, **kw) followed by set_modal_basis: (lam, X, info) of modes_many, info["modal_basis"] the basis's info."""
+        """modes_many(nev, density, **kw), its modes adopted on the device as the basis (set_modal_basis_from_modes; with a caller's `locked` set or
+        fewer modes found than asked for: set_modal_basis of the result): (lam, X, info) of modes_many, info["modal_basis"] the basis's info."""
         lam, X, info = self.modes_many(nev, density=density, **kw)
-        info["modal_basis"] = self.set_modal_basis(lam, X, density=density)
+        if len(lam) >= 1:
+            info["modal_basis"] = self.set_modal_basis_from_modes(len(lam), density=density)
+        else:
+            info["modal_basis"] = self.set_modal_basis(lam, X, density=density)
         return lam, X, info
 
     def modal_coordinates(self, u):
@@ -820,6 +832,115 @@ class Context:
         a, b = np.zeros(int(reps)), np.zeros(int(reps))
         self._ck(self.lib.mfh_time_modal_series(self.h, int(n_modes), int(n_probe), int(n_steps), int(reps), ptr(a), ptr(b)))
         return a, b
+
+    # ---------------------------------------------------------------- random vibration, response spectra (docs/design/04_23_modal_random.md)
+    def modal_quadratic(self, Cm, tol=-1.0, probes=None, fields=True):
+        """sqrt(phi_i^T C phi_i) per variable i for symmetric positive semi-definite matrices C over the modes of set_modal_basis
+        (mfh_modal_quadratic): Cm [m, m] or [nMat <= 4, m, m]. The host factors C = F F^T (psd_factor; tol < 0: its default) and the device sums
+        squares, so the result is never negative. Returns a dict: "fields" [nMat, dim * n_dof] (None without fields), "probes" [nMat, len(probes)]
+        (bit for bit the field entries), "info" (ranks, passes, truncation per matrix)."""
+        n = self.bs * self.n_dof
+        m = self.modal_basis_state()[0]
+        Cm = as_f64(np.asarray(Cm, dtype=np.float64))
+        if Cm.ndim == 2:
+            Cm = Cm[None]
+        if Cm.ndim != 3 or (m > 0 and Cm.shape[1:] != (m, m)):          # (no basis: the library answers with ERR_STATE)
+            raise ValueError("modal_quadratic: the matrices are %d x %d (the modes of the basis), got %s" % (m, m, Cm.shape))
+        Cm = np.ascontiguousarray(Cm)
+        n_mat = Cm.shape[0]
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        pout = np.zeros((n_mat, n_probe)) if n_probe else None
+        fld = np.zeros((n_mat, n)) if fields else None
+        info = L.ModalQuadraticInfo()
+        self._ck(self.lib.mfh_modal_quadratic(self.h, n_mat, ptr(Cm), float(tol), ptr(pv), n_probe, ptr(pout), ptr(fld), C.byref(info)))
+        d = info.as_dict()
+        for k in ("ranks", "passes", "truncation"):
+            d[k] = d[k][:n_mat]
+        return {"fields": fld, "probes": np.zeros((n_mat, 0)) if pout is None else pout, "info": d}
+
+    def modal_random(self, omega, S, f, weights=None, damping=(0.0, 0.0), loss_factor=0.0, modal_damping=None, static_correction=True, velocity=False,
+                     acceleration=False, tol=-1.0, rtol=1e-8, maxit=10000, probes=None, fields=True, probe_psd=False):
+        """The RMS response to the loads sum_a A_a(t) f_a whose amplitudes have the one-sided cross-spectral density S(omega) (mfh_modal_random),
+        on the basis of set_modal_basis. omega: strictly ascending grid [nFreq]; S: [nFreq] (one load), or [nFreq, nLoad, nLoad] Hermitian;
+        f: [dim * n_dof] or [nLoad, dim * n_dof] real load shapes; weights: quadrature weights (None: the trapezoid rule). Damping as
+        modal_harmonic. static_correction: one static solve per load (at most two loads with it). Returns a dict: "sigma_u", "sigma_v" (velocity),
+        "sigma_a" (acceleration): fields [dim * n_dof] or None; "probes": dict of "sigma_u", "sigma_v", "sigma_a", "nu0" (rate of upward zero
+        crossings sigma_v / (2 pi sigma_u)) [len(probes)] and "psd" [len(probes), nFreq] with probe_psd; "cov": [3, nb, nb] = the modal covariances
+        C^(0), C^(2), C^(4); "info"."""
+        n = self.bs * self.n_dof
+        om = as_f64(np.asarray(omega, dtype=np.float64).reshape(-1))
+        nf = om.size
+        f = as_f64(np.asarray(f, dtype=np.float64))
+        f = f.reshape(1, -1) if f.ndim == 1 else f.reshape(f.shape[0], -1)
+        if f.shape[1] != n:
+            raise ValueError("modal_random: a load needs dim * n_dof = %d entries, got %d" % (n, f.shape[1]))
+        nl = f.shape[0]
+        Sc = np.asarray(S, dtype=np.complex128)
+        if Sc.ndim == 1:
+            Sc = Sc.reshape(-1, 1, 1)
+        if Sc.shape != (nf, nl, nl):
+            raise ValueError("modal_random: S needs the shape [nFreq, nLoad, nLoad] = %s, got %s" % ((nf, nl, nl), Sc.shape))
+        Sri = np.ascontiguousarray(np.stack([Sc.real, Sc.imag], axis=-1))
+        w = None if weights is None else as_f64(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != nf:
+            raise ValueError("modal_random: %d weights for %d frequencies" % (w.size, nf))
+        m = self.modal_basis_state()[0]
+        zeta = None
+        if modal_damping is not None:
+            zeta = as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
+        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+        n_probe = 0 if pv is None else pv.size
+        prms = np.zeros((4, n_probe)) if n_probe else None
+        ppsd = np.zeros((n_probe, nf)) if n_probe and probe_psd else None
+        planes = 1 + int(bool(velocity)) + int(bool(acceleration))
+        fld = np.zeros((planes, n)) if fields else None
+        nbmax = m + 2
+        cov = np.zeros(3 * nbmax * nbmax)
+        flags = ((L.MODAL_RV_STATIC_CORRECTION if static_correction else 0) | (L.MODAL_RV_VELOCITY if velocity else 0) |
+                 (L.MODAL_RV_ACCELERATION if acceleration else 0))
+        prm = L.ModalRandomParams(float(damping[0]), float(damping[1]), float(loss_factor), float(rtol), float(tol), int(maxit), nf, nl, flags)
+        info = L.ModalRandomInfo()
+        st = self.lib.mfh_modal_random(self.h, C.byref(prm), ptr(om), ptr(w), ptr(zeta), ptr(f), ptr(Sri), ptr(pv), n_probe, ptr(prms), ptr(ppsd), ptr(fld),
+                                       ptr(cov), C.byref(info))
+        d = info.as_dict()
+        self.last_modal_random = {"info": d}
+        self._ck(st)
+        nb = d["nb"]
+        out = {"sigma_u": None, "sigma_v": None, "sigma_a": None, "cov": cov[:3 * nb * nb].reshape(3, nb, nb).copy(), "info": d}
+        if fld is not None:
+            names = ["sigma_u"] + (["sigma_v"] if velocity else []) + (["sigma_a"] if acceleration else [])
+            for i, name in enumerate(names):
+                out[name] = fld[i]
+        pr = {"sigma_u": np.zeros(0), "sigma_v": np.zeros(0), "sigma_a": np.zeros(0), "nu0": np.zeros(0), "psd": ppsd}
+        if n_probe:
+            pr.update({"sigma_u": prms[0], "sigma_v": prms[1], "sigma_a": prms[2] if acceleration else None, "nu0": prms[3]})
+        out["probes"] = pr
+        self.last_modal_random = out
+        return out
+
+    def debug_modal_sumsq(self, B, F, piv=None, planes_per_pass=0, sqrt=False):
+        """out [n] = sum_t (sum_j B[j] F[j][t])^2 through k_modal_sumsq as the calls above launch it (test hook mfh_debug_modal_sumsq). B: [nb, n]
+        (a row per column of the basis), F: [nb, rank]. piv: the pivots of psd_factor, for the shortened column lists of the later passes."""
+        B = as_f64(np.atleast_2d(B))
+        F = np.asarray(F, dtype=np.float64)
+        F = as_f64(F.reshape(B.shape[0], F.size // B.shape[0]))
+        nb, n = B.shape
+        rank = F.shape[1]
+        pv = None if piv is None else as_i32(np.asarray(piv).reshape(-1))
+        assert pv is None or pv.size == rank
+        out = np.full(n, np.nan)
+        self._ck(self.lib.mfh_debug_modal_sumsq(self.h, n, nb, ptr(B), ptr(F) if rank else None, rank, ptr(pv) if rank else None, int(planes_per_pass), int(bool(sqrt)),
+                                                ptr(out)))
+        return out
+
+    def time_modal_sumsq(self, n, nb, planes_per_pass=0, reps=5):
+        """(sumsq_ms, expand_ms, later_ms), one entry per repetition: device time of one pass of k_modal_sumsq and of one pass of k_modal_expand on
+        the same nb hashed columns of n rows, the two taking turns, and of a second pass of a rank-2 NP factor (nb - NP columns, the accumulator read
+        back; mfh_time_modal_sumsq)."""
+        a, b, l = np.zeros(int(reps)), np.zeros(int(reps)), np.zeros(int(reps))
+        self._ck(self.lib.mfh_time_modal_sumsq(self.h, int(n), int(nb), int(planes_per_pass), int(reps), ptr(a), ptr(b), ptr(l)))
+        return a, b, l
 
     # ---------------------------------------------------------------- per-element density (docs/design/04_15_density.md)
     def set_density(self, rho):
@@ -1734,3 +1855,90 @@ def modal_transient_coeffs(lam, c, dt):
             raise L.MeshFEMHipError(st, "mfh_modal_transient_coeffs: lam >= 0, c >= 0, dt > 0, all finite")
         flat[i] = row
     return out
+
+
+def psd_factor(Cm, tol=-1.0):
+    """(F [n, rank], piv [rank], truncation): the diagonally pivoted Cholesky factor C ~ F F^T of a symmetric positive semi-definite matrix (mfh_psd_factor;
+    host only, no device; n <= 258; symmetry from the lower triangle). It stops when the largest remaining diagonal is <= tol (tol < 0: n eps max diag);
+    truncation = the trace of the remainder. Rows keep their places: F[piv[s], t] == 0 for t > s. Raises with code ERR_INVALID for a matrix that is not
+    positive semi-definite or not finite."""
+    Cm = as_f64(np.atleast_2d(np.asarray(Cm, dtype=np.float64)))
+    n = Cm.shape[0]
+    if Cm.shape != (n, n):
+        raise ValueError("psd_factor: a square matrix is needed, got %s" % (Cm.shape,))
+    F, piv = np.zeros((n, n)), np.zeros(n, dtype=np.int32)
+    rank, trunc = C.c_int32(), C.c_double()
+    st = L.load().mfh_psd_factor(n, ptr(Cm), float(tol), ptr(F), C.byref(rank), ptr(piv), C.byref(trunc))
+    if st != L.OK:
+        raise L.MeshFEMHipError(st, "mfh_psd_factor: n <= 258, finite entries, a positive semi-definite matrix (no remaining diagonal below -tol)")
+    return np.ascontiguousarray(F[:, :rank.value]), piv[:rank.value].copy(), trunc.value
+
+
+def modal_covariance(lam, g, omega, S, weights=None, damping=(0.0, 0.0), loss_factor=0.0, modal_damping=None, correction=False):
+    """[3, nb, nb]: the modal covariances C^(p) = sum_k w_k omega_k^p Re(H_k S_k H_k^H), p = 0, 2, 4 (mfh_modal_covariance; host only, no device).
+    lam [m], g [m] or [m, nLoad] = Phi^T f_a, omega [nFreq] strictly ascending, S [nFreq] or [nFreq, nLoad, nLoad] Hermitian, weights [nFreq] or None
+    (trapezoid). correction: nb = m + nLoad, the rows of the static-correction columns appended (nLoad <= 2)."""
+    lam = as_f64(np.asarray(lam, dtype=np.float64).reshape(-1))
+    m = lam.size
+    g = as_f64(np.asarray(g, dtype=np.float64).reshape(m, -1))
+    nl = g.shape[1]
+    om = as_f64(np.asarray(omega, dtype=np.float64).reshape(-1))
+    nf = om.size
+    Sc = np.asarray(S, dtype=np.complex128)
+    if Sc.ndim == 1:
+        Sc = Sc.reshape(-1, 1, 1)
+    if Sc.shape != (nf, nl, nl):
+        raise ValueError("modal_covariance: S needs the shape [nFreq, nLoad, nLoad] = %s, got %s" % ((nf, nl, nl), Sc.shape))
+    Sri = np.ascontiguousarray(np.stack([Sc.real, Sc.imag], axis=-1))
+    w = None if weights is None else as_f64(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w is not None and w.size != nf:
+        raise ValueError("modal_covariance: %d weights for %d frequencies" % (w.size, nf))
+    zeta = None if modal_damping is None else as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
+    nb = m + (nl if correction else 0)
+    out = np.zeros((3, nb, nb))
+    st = L.load().mfh_modal_covariance(m, ptr(lam), ptr(g), nl, float(damping[0]), float(damping[1]), float(loss_factor), ptr(zeta), nf, ptr(om), ptr(w), ptr(Sri),
+                                       int(bool(correction)), ptr(out[0]), ptr(out[1]), ptr(out[2]))
+    if st != L.OK:
+        raise L.MeshFEMHipError(st, "mfh_modal_covariance: refused (a grid that is not strictly ascending or negative, omega = 0 with a zero eigenvalue, "
+                                    "d_j = 0, a spectrum that is not Hermitian or has a negative diagonal, an entry that is not finite, more than two loads "
+                                    "with the correction)")
+    return out
+
+
+def cqc_matrix(lam, zeta):
+    """[m, m]: the correlation coefficients of the CQC rule for modes of eigenvalues lam and damping ratios zeta > 0 (a scalar or one per mode), Der
+    Kiureghian's form for unequal damping (mfh_cqc_matrix; host only)."""
+    lam = as_f64(np.asarray(lam, dtype=np.float64).reshape(-1))
+    m = lam.size
+    z = as_f64(np.broadcast_to(np.asarray(zeta, dtype=np.float64), (m,)))
+    rho = np.zeros((m, m))
+    st = L.load().mfh_cqc_matrix(m, ptr(lam), ptr(z), ptr(rho))
+    if st != L.OK:
+        raise L.MeshFEMHipError(st, "mfh_cqc_matrix: lam >= 0, zeta > 0, finite, at most 258 modes")
+    return rho
+
+
+def resonance_grid(lam, zeta, band, per_halfpower=8, background=64):
+    """An ascending frequency grid on band = (w_lo, w_hi) for the spectra of lightly damped modes: `background` equal intervals over the band, merged,
+    for every mode with sqrt(lam_j) inside the band, with points h_j = 2 zeta_j sqrt(lam_j) / per_halfpower apart (the half-power bandwidth divided by
+    per_halfpower) over four bandwidths either side of sqrt(lam_j), and beyond them with spacings that grow by the factor 1 + 1 / per_halfpower per
+    point out to the band's ends. Every spacing of a mode's points is proportional to 1 / per_halfpower, so the trapezoid rule on the grid is second
+    order in it."""
+    lam = np.asarray(lam, dtype=np.float64).reshape(-1)
+    z = np.broadcast_to(np.asarray(zeta, dtype=np.float64), lam.shape)
+    lo, hi = float(band[0]), float(band[1])
+    p = int(per_halfpower)
+    if not (hi > lo >= 0.0) or p < 1 or background < 1:
+        raise ValueError("resonance_grid: band = (lo, hi) with 0 <= lo < hi, per_halfpower >= 1, background >= 1")
+    parts = [np.linspace(lo, hi, int(background) + 1)]
+    for l, zj in zip(lam, z):
+        wn = np.sqrt(l)
+        if not (lo <= wn <= hi) or not zj > 0.0 or not wn > 0.0:
+            continue
+        h = 2.0 * zj * wn / p
+        core = wn + h * np.arange(-4 * p, 4 * p + 1)
+        count = int(np.ceil(np.log(max((hi - lo) / h, 2.0)) / np.log1p(1.0 / p))) + 1
+        steps = np.cumsum(h * (1.0 + 1.0 / p) ** np.arange(1, count + 1))
+        parts += [core, core[-1] + steps, core[0] - steps]
+    grid = np.unique(np.concatenate(parts))
+    return grid[(grid >= lo) & (grid <= hi)]

@@ -142,7 +142,7 @@ void upload_mesh(mfh_ctx *c, bool deviceTables) {
     dist_detach(c);                  // exchange lists describe the previous mesh: mfh_dist_setup must run again
     reset_bcs(c);
     clear_fixed(c);
-    modal_drop(c);                   // a mode basis belongs to the previous mesh
+    c->modesKeep.reset(); modal_drop(c);                   // a mode basis belongs to the previous mesh
 }
 
 // default material: E = 1, nu = 0.3 (Materials.hh:408)
@@ -1554,7 +1554,7 @@ mfh_status mfh_dof_map(mfh_ctx *c, const int32_t *dofForNode, int64_t nDoF) {
     }
     invalidate_symbolic(c);
     clear_fixed(c);
-    modal_drop(c);                   // the variable numbering changed under the mode basis
+    c->modesKeep.reset(); modal_drop(c);                   // the variable numbering changed under the mode basis
     MFH_CATCH(c)
 }
 
@@ -1573,7 +1573,7 @@ mfh_status mfh_dof_map_partitioned(mfh_ctx *c, const int32_t *dofForNode, int64_
     c->dofPairsValid = false;
     invalidate_symbolic(c);
     clear_fixed(c);
-    modal_drop(c);                   // the variable numbering changed under the mode basis
+    c->modesKeep.reset(); modal_drop(c);                   // the variable numbering changed under the mode basis
     dist_detach(c);                  // exchange lists are in DoF numbers: mfh_dist_setup must run (again)
     MFH_CATCH(c)
 }
@@ -1593,7 +1593,7 @@ mfh_status mfh_apply_periodic_conditions(mfh_ctx *c, double eps, int64_t *nDoF) 
     c->dofPairsValid = false;
     invalidate_symbolic(c);
     clear_fixed(c);
-    modal_drop(c);                   // the variable numbering changed under the mode basis
+    c->modesKeep.reset(); modal_drop(c);                   // the variable numbering changed under the mode basis
     MFH_CATCH(c)
 }
 
@@ -1760,7 +1760,7 @@ mfh_status mfh_matrix_set_upper_triplets(mfh_ctx *c, int64_t n, int64_t nnz, con
     c->dinvValid = false;
     c->tl.valid = false;
     clear_fixed(c);
-    modal_drop(c);
+    c->modesKeep.reset(); modal_drop(c);
     MFH_CATCH(c)
 }
 

@@ -172,6 +172,19 @@ struct mfh_ctx {
         void reset() { nModes = 0; n = ld = 0; lambda.clear(); fixedSet.clear(); B.release(); geoGen = densityGen = -1; }
     } modal;
     std::string modalNote;            // mfh_modal_harmonic_info::note of the last mfh_modal_harmonic
+    // What the last converged mfh_modes_many left on the device for mfh_modal_set_basis_from_modes (docs/design/04_23_modal_random.md): the columns
+    // it found, ld apart, as the loop left them. Mode j of the sorted result is column src[j] times sign[j] (the sign rule is applied to the host
+    // copy only). Valid under the generations and the set of fixed variables recorded here; replaced by the next mfh_modes_many, dropped with the
+    // mode basis where the mesh or the numbering of the variables changes. Arena memory: the device statistics count it.
+    struct ModesKeep {
+        DBuf<double> Q;
+        int64_t n = 0, ld = 0;
+        std::vector<int> src;
+        std::vector<double> sign, lambda;
+        std::vector<int64_t> fixedSet;
+        int64_t geoGen = -1, densityGen = -1;
+        void reset() { Q.release(); n = ld = 0; src.clear(); sign.clear(); lambda.clear(); fixedSet.clear(); geoGen = densityGen = -1; }
+    } modesKeep;
 
     // ---- constraints (SPSDSystem state)
     std::vector<int64_t> fixedVars;

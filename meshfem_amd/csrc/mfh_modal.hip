@@ -16,7 +16,11 @@
 // The mass products are k_spmv_kron_acc's (mfh_pencil.hh), the true residual's operator product mfh_harmonic's own (harmonic_product, mfh_harmonic.hip).
 // The same basis serves load histories (mfh_modal_transient; docs/design/04_22_modal_transient.md): k_modal_slope, k_modal_march, k_modal_series
 // below, the step coefficients from mfh_modal_coeffs.cpp.
+// And quadratic forms per row, phi_i^T C phi_i, for random vibration and response spectra (mfh_modal_quadratic, mfh_modal_random;
+// docs/design/04_23_modal_random.md): k_modal_sumsq below on the factor C = F F^T that mfh_modal_cov.cpp forms on the host.
 #include "mfh_pencil.hh"
+#include <chrono>
+#include <functional>
 #include <optional>
 
 namespace mfh { namespace k {
@@ -140,6 +144,11 @@ __global__ void __launch_bounds__(256) k_modal_resnorm(int64_t n, const double *
     store_partials<1>(acc, red, partials);
 }
 
+// dst[i] = sign src[i], sign = +-1: a column mfh_modes_many left on the device, with the sign its host copy carries (exact either way)
+__global__ void __launch_bounds__(256) k_modal_adopt(int64_t n, const double *__restrict__ src, double sign, double *__restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = sign * src[i];
+}
+
 int modal_np_for(int planesPerPass) { return planesPerPass <= 8 ? 8 : (planesPerPass <= 16 ? 16 : 32); }
 
 // out[p planeStride + row] for the planes [0, nPlanes) in passes of planesPerPass (1 .. 32) planes; C: device, nb rows of ldc doubles, zero beyond
@@ -162,6 +171,95 @@ void launch_modal_gram(int64_t n, const double *A, int64_t lda, int na, const do
     hipLaunchKernelGGL(k_modal_gram_sum, dim3((count + 255) / 256), dim3(256), 0, s, rows, count, (const double *)partials, G);
     CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------- quadratic forms per row (mfh_modal_quadratic, mfh_modal_random; docs/design/04_23_modal_random.md)
+// v[row] = phi^T C phi of the row phi of B for C = F F^T, as sum_t s_t^2 with s_t = sum_j B_j[row] F[j][t]: k_modal_expand's streaming loop over the
+// columns cols[0 .. nc) (wave-uniform: the list and the coefficients come through scalar loads) with another epilogue,
+//     acc = first ? 0.0 : out[row];   acc = fma(s_t, s_t, acc) for t < np ascending;   out[row] = last && root ? sqrt(acc) : acc,
+// np <= NP the columns of F this pass takes (the sums beyond them are formed and dropped, as k_modal_expand drops the planes beyond np), so neither
+// NP nor the pass boundaries change a bit. F: rows of ldf doubles, readable (zero) up to t0 + NP. A column whose coefficients are all exactly zero in [t0, t0 + NP) may be left out of the list: fma(b, 0, s) = s for finite b.
+template <int NP>
+__global__ void __launch_bounds__(256) k_modal_sumsq(int64_t n, const double *__restrict__ B, int64_t ldb, const int32_t *__restrict__ cols, int nc,
+                                                    const double *__restrict__ F, int ldf, int t0, int np, int first, int root, double *__restrict__ out) {
+    const double *f0 = F + t0;
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.x * 256) {
+        double s[NP];
+#pragma unroll
+        for (int t = 0; t < NP; ++t) s[t] = 0.0;
+        const double *b = B + row;
+        int j = 0;
+        for (; j + 4 <= nc; j += 4) {
+            const int c0 = cols[j], c1 = cols[j + 1], c2 = cols[j + 2], c3 = cols[j + 3];
+            const double b0 = b[(int64_t)c0 * ldb], b1 = b[(int64_t)c1 * ldb], b2 = b[(int64_t)c2 * ldb], b3 = b[(int64_t)c3 * ldb];
+            const double *f_0 = f0 + (int64_t)c0 * ldf, *f_1 = f0 + (int64_t)c1 * ldf, *f_2 = f0 + (int64_t)c2 * ldf, *f_3 = f0 + (int64_t)c3 * ldf;
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b0, f_0[t], s[t]);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b1, f_1[t], s[t]);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b2, f_2[t], s[t]);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b3, f_3[t], s[t]);
+        }
+        for (; j < nc; ++j) {
+            const int c0 = cols[j];
+            const double b0 = b[(int64_t)c0 * ldb];
+            const double *f_0 = f0 + (int64_t)c0 * ldf;
+#pragma unroll
+            for (int t = 0; t < NP; ++t) s[t] = fma(b0, f_0[t], s[t]);
+        }
+        double acc = first ? 0.0 : out[row];
+#pragma unroll
+        for (int t = 0; t < NP; ++t)
+            if (t < np) acc = fma(s[t], s[t], acc);
+        out[row] = root ? sqrt(acc) : acc;
+    }
+}
+
+// The passes of one matrix, planned on the host. F: nb x rank row-major with the pivots piv (mfh_psd_factor): a pass whose first column is t0 leaves out
+// the basis columns piv[0 .. t0), whose coefficients are exactly zero from column t0 on; piv null: every pass streams all nb columns.
+struct SumsqPlan {
+    int nb = 0, rank = 0, ldf = 0, np = MODAL_NP, passes = 0;
+    std::vector<int32_t> cols;          // the lists of the passes, one after the other
+    std::vector<int> off, cnt;          // ... where each begins, and its length
+    DBuf<double> dF;
+    DBuf<int32_t> dCols;
+    void build(int nb_, const double *F, int ldFh, int rank_, const int32_t *piv, int planesPerPass, hipStream_t s) {
+        nb = nb_; rank = rank_; np = planesPerPass; ldf = rank + MODAL_NP_MAX;
+        cols.clear(); off.clear(); cnt.clear(); passes = 0;
+        if (rank <= 0) return;
+        std::vector<double> hf((size_t)nb * ldf, 0.0);
+        for (int j = 0; j < nb; ++j)
+            for (int t = 0; t < rank; ++t) hf[(size_t)j * ldf + t] = F[(size_t)j * ldFh + t];
+        std::vector<uint8_t> out((size_t)nb, 0);
+        int done = 0;
+        for (int t0 = 0; t0 < rank; t0 += np) {
+            if (piv) for (; done < t0; ++done) out[(size_t)piv[done]] = 1;
+            off.push_back((int)cols.size());
+            for (int j = 0; j < nb; ++j)
+                if (!out[(size_t)j]) cols.push_back(j);
+            cnt.push_back((int)cols.size() - off.back());
+            ++passes;
+        }
+        dF.upload(hf, s);
+        dCols.upload(cols, s);
+    }
+    // out[row] = (root ? sqrt : id)(sum_t s_t^2) for the n rows of B (columns ldb apart); rank 0: zeros, B is not read
+    // only = -1: every pass; else that pass alone (timing)
+    void run(int64_t n, const double *B, int64_t ldb, bool root, double *out, hipStream_t s, int only = -1) const {
+        if (n <= 0) return;
+        if (rank <= 0) { MFH_HIP(hipMemsetAsync(out, 0, (size_t)n * sizeof(double), s)); return; }
+        const dim3 grid(grid_for(n, MODAL_GRID_CAP)), block(256);
+        for (int p = 0; p < passes; ++p) {
+            if (only >= 0 && p != only) continue;
+            const int t0 = p * np, left = std::min(np, rank - t0), first = p == 0 ? 1 : 0, rt = (root && p == passes - 1) ? 1 : 0;
+            const int32_t *cl = dCols.p + off[(size_t)p];
+            const int nc = cnt[(size_t)p];
+            with_int<8, 16, 32>(modal_np_for(left), [&](auto NP) { launch_k(k_modal_sumsq<NP()>, grid, block, 0, s, n, B, ldb, cl, nc, (const double *)dF.p, ldf, t0, left, first, rt, out); });
+        }
+        CHECK_LAUNCH();
+    }
+};
 
 // ---------------------------------------------------------------- modal transient response (mfh_modal_transient; docs/design/04_22_modal_transient.md)
 // Every mode obeys q'' + c q' + lambda q = g a(t) with a piecewise linear between the steps, for which the step is exact:
@@ -367,6 +465,57 @@ void gram_against(mfh_ctx *c, const double *A, int64_t ld, int na, const double 
     }
 }
 
+// The static solves of the correction, shared by mfh_modal_harmonic (its load planes) and mfh_modal_random (its loads): K u = f[a] with the
+// context's solver and preconditioner for every a < na whose load is not zero off the fixed variables, the fixed variables held at ZERO whatever values
+// mfh_solve would hold them at. The counts go to the caller's info as they grow, so that a failed call reports what was done.
+void correction_solves(mfh_ctx *c, const char *who, int na, const double *const f[2], const bool nonZero[2], std::vector<double> us[2], double rtol, int maxit,
+                       int &staticSolves, int &staticIts, int32_t *infoSolves, int32_t *infoIts) {
+    if (!(nonZero[0] || nonZero[1])) return;
+    ensure_precond(c);
+    ensure_coarse_levels(c, 1);
+    if (c->sym.nRows != c->sym.nCols) throw Error(MFH_ERR_UNSUPPORTED, std::string(who) + ": unpartitioned contexts only");
+    require_basis(c, who);
+    const int64_t n = c->modal.n;
+    for (int a = 0; a < na; ++a) {
+        if (!nonZero[a]) continue;
+        us[a].resize((size_t)n);
+        mfh_solve_info li{};
+        const bool savedHom = c->solveHomogeneous;
+        c->solveHomogeneous = c->anyFixedNonzero;
+        try { solve_one(c, f[a], us[a].data(), rtol, maxit, &li); }
+        catch (...) { c->solveHomogeneous = savedHom; throw; }
+        c->solveHomogeneous = savedHom;
+        ++staticSolves;
+        staticIts += li.iterations;
+        if (infoSolves) *infoSolves = staticSolves;
+        if (infoIts) *infoIts = staticIts;
+        if (!li.converged) throw Error(MFH_ERR_NOT_CONVERGED, std::string(who) + ": the static solve of the correction did not reach rtol within maxit iterations");
+    }
+}
+
+// r_a = u_a - sum_j phi_j g_ja / lambda_j for a < na <= 2 into the two reserved columns of B (the other one zero), through the expansion kernel
+// itself; g[j na + a]. dC, dTmp: the caller's buffers (they outlive the launches).
+void correction_columns(mfh_ctx *c, double *B, int64_t n, int64_t ld, int m, int na, const std::vector<double> us[2], const bool nonZero[2], const double *g,
+                        const double *lam, DBuf<double> &dC, DBuf<double> &dTmp, hipStream_t s) {
+    MFH_HIP(hipMemsetAsync(B + (int64_t)m * ld, 0, (size_t)ld * 2 * sizeof(double), s));
+    for (int a = 0; a < na; ++a)
+        if (nonZero[a]) {
+            upload(B + (int64_t)(m + a) * ld, us[a].data(), n, s);
+            k::launch_mask(n, c->dFixedMask.p, B + (int64_t)(m + a) * ld, s);
+        }
+    const int ldc = 64;
+    std::vector<double> hc((size_t)(m + 2) * ldc, 0.0);
+    for (int j = 0; j < m; ++j)
+        for (int a = 0; a < na; ++a) hc[(size_t)j * ldc + a] = nonZero[a] ? -(g[(size_t)j * na + a] / lam[(size_t)j]) : 0.0;
+    hc[(size_t)m * ldc + 0] = 1.0;
+    hc[(size_t)(m + 1) * ldc + 1] = 1.0;
+    dC.upload(hc, s);
+    dTmp.alloc((size_t)ld * 2);
+    dTmp.zero(s);
+    k::launch_modal_expand(n, B, ld, m + 2, dC.p, ldc, 2, k::MODAL_NP, dTmp.p, ld, s);
+    MFH_HIP(hipMemcpyAsync(B + (int64_t)m * ld, dTmp.p, (size_t)ld * 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+}
+
 void check_sweep_params(const mfh_ctx *c, const mfh_modal_harmonic_params *p, const double *omega, const double *zeta, const double *fRe, const int64_t *probeVars,
                         int32_t nProbe, const double *probeOut) {
     require(p != nullptr, MFH_ERR_INVALID, "mfh_modal_harmonic: params is null");
@@ -468,6 +617,9 @@ std::vector<double> coef_table(int m, const double *coef8) {
         for (int k2 = 0; k2 < 8; ++k2) t[(size_t)k2 * k::MT_COEF_LD + j] = coef8[(size_t)j * 8 + k2];
     return t;
 }
+
+using BasisFill = std::function<void(double *, int64_t, hipStream_t)>;
+void install_basis(mfh_ctx *c, const char *who, int32_t nModes, const double *lambda, double density, mfh_modal_basis_info *info, const BasisFill &fill);
 
 bool chunk_ok(int32_t chunkSteps) { return chunkSteps == 0 || (chunkSteps > 0 && chunkSteps % 32 == 0); }
 
@@ -711,17 +863,56 @@ mfh_status mfh_modal_set_basis(mfh_ctx *c, int32_t nModes, const double *lambda,
     require(density > 0.0 && std::isfinite(density), MFH_ERR_INVALID, "mfh_modal_set_basis: density > 0");
     for (int j = 0; j < nModes; ++j) require(std::isfinite(lambda[j]) && lambda[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_set_basis: an eigenvalue is negative or not finite");
     prepare_pencil(c, "mfh_modal_set_basis");
-    const int64_t n = (int64_t)c->bs() * c->nDoF, ld = (n + 31) / 32 * 32;
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
     require(all_finite(X, (int64_t)nModes * n), MFH_ERR_INVALID, "mfh_modal_set_basis: a mode has an entry that is not finite");
+    install_basis(c, "mfh_modal_set_basis", nModes, lambda, density, info, [&](double *B, int64_t ld, hipStream_t s) {
+        MFH_HIP(hipMemcpy2DAsync(B, (size_t)ld * sizeof(double), X, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nModes, hipMemcpyHostToDevice, s));
+    });
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modal_set_basis_from_modes(mfh_ctx *c, int32_t nModes, double density, mfh_modal_basis_info *info) {
+    if (info) *info = mfh_modal_basis_info{};
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_set_basis_from_modes: null context");
+    require(nModes >= 1 && nModes <= k::MODAL_MAXM, MFH_ERR_INVALID, "mfh_modal_set_basis_from_modes: 1 <= nModes <= 256");
+    require(density > 0.0 && std::isfinite(density), MFH_ERR_INVALID, "mfh_modal_set_basis_from_modes: density > 0");
+    prepare_pencil(c, "mfh_modal_set_basis_from_modes");
+    const mfh_ctx::ModesKeep &kp = c->modesKeep;
+    const int64_t n = (int64_t)c->bs() * c->nDoF;
+    require(kp.Q.p != nullptr && !kp.src.empty(), MFH_ERR_STATE, "mfh_modal_set_basis_from_modes: no modes on the device (the context's last mfh_modes_many did not converge, or none was made)");
+    require(c->geoValid && kp.geoGen == c->geoGen && kp.densityGen == c->densityGen && kp.n == n && sorted_fixed(c) == kp.fixedSet, MFH_ERR_STATE,
+            "mfh_modal_set_basis_from_modes: the modes on the device are stale (vertex positions, material, density field, DoF map or the set of fixed variables changed since mfh_modes_many)");
+    require(nModes <= (int)kp.src.size(), MFH_ERR_INVALID, "mfh_modal_set_basis_from_modes: more modes than mfh_modes_many found");
+    const std::vector<double> lam(kp.lambda.begin(), kp.lambda.begin() + nModes);
+    for (double l : lam) require(std::isfinite(l) && l >= 0.0, MFH_ERR_INVALID, "mfh_modal_set_basis_from_modes: an eigenvalue is negative or not finite");
+    install_basis(c, "mfh_modal_set_basis_from_modes", nModes, lam.data(), density, info, [&](double *B, int64_t ld, hipStream_t s) {
+        require(ld == kp.ld, MFH_ERR_STATE, "mfh_modal_set_basis_from_modes: the column stride changed");
+        for (int j = 0; j < nModes; ++j)
+            hipLaunchKernelGGL(k::k_modal_adopt, dim3(k::grid_for(n)), dim3(256), 0, s, n, (const double *)kp.Q.p + (int64_t)kp.src[(size_t)j] * kp.ld, kp.sign[(size_t)j],
+                               B + (int64_t)j * ld);
+        CHECK_LAUNCH();
+    });
+    MFH_CATCH(c)
+}
+
+}   // extern "C"
+
+namespace {
+
+// The common part of mfh_modal_set_basis and mfh_modal_set_basis_from_modes: fill(B, ld, stream) writes the nModes columns; then the fixed rows are
+// zeroed, orthoDefect formed and the state recorded.
+void install_basis(mfh_ctx *c, const char *who, int32_t nModes, const double *lambda, double density, mfh_modal_basis_info *info, const BasisFill &fill) {
+    const int64_t n = (int64_t)c->bs() * c->nDoF, ld = (n + 31) / 32 * 32;
     hipStream_t s = c->stream;
     modal_drop(c);
     WideGuard guard(c);
     EventTimer tsetup(s);
-    prepare_pencil_state(c, "mfh_modal_set_basis", false);
+    prepare_pencil_state(c, who, false);
     mfh_ctx::ModalBasis &mb = c->modal;
     mb.B.alloc((size_t)ld * (size_t)(nModes + 2));
     mb.B.zero(s);
-    MFH_HIP(hipMemcpy2DAsync(mb.B.p, (size_t)ld * sizeof(double), X, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nModes, hipMemcpyHostToDevice, s));
+    fill(mb.B.p, ld, s);
     if (!c->fixedVars.empty())
         for (int j = 0; j < nModes; ++j) k::launch_mask(n, c->dFixedMask.p, mb.B.p + (int64_t)j * ld, s);
     std::vector<double> G((size_t)nModes * nModes);
@@ -741,8 +932,11 @@ mfh_status mfh_modal_set_basis(mfh_ctx *c, int32_t nModes, const double *lambda,
         info->deviceBytes = (double)mb.B.n * sizeof(double);
         info->setupMs = tsetup.stop();
     }
-    MFH_CATCH(c)
 }
+
+}   // namespace
+
+extern "C" {
 
 mfh_status mfh_modal_coordinates(mfh_ctx *c, const double *u, int32_t nVec, double *q) {
     MFH_TRY(c)
@@ -821,26 +1015,9 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
         const uint8_t *hm = masked ? c->hFixedMask.data() : nullptr;
         for (int64_t i = 0; i < n && !planeNonZero[pl]; ++i) planeNonZero[pl] = fPlane[pl][i] != 0.0 && !(hm && hm[i]);
     }
-    if (correct && (planeNonZero[0] || planeNonZero[1])) {
-        ensure_precond(c);
-        ensure_coarse_levels(c, 1);
-        require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modal_harmonic: unpartitioned contexts only");
-        require_basis(c, "mfh_modal_harmonic");
-        for (int pl = 0; pl < 2; ++pl) {
-            if (!planeNonZero[pl]) continue;
-            us[pl].resize((size_t)n);
-            mfh_solve_info li{};
-            const bool savedHom = c->solveHomogeneous;
-            c->solveHomogeneous = c->anyFixedNonzero;          // (the fixed variables are held at ZERO here, whatever values mfh_solve would hold them at)
-            try { solve_one(c, fPlane[pl], us[pl].data(), P.rtol, P.maxit, &li); }
-            catch (...) { c->solveHomogeneous = savedHom; throw; }
-            c->solveHomogeneous = savedHom;
-            ++staticSolves;
-            staticIts += li.iterations;
-            if (info) { info->staticSolves = staticSolves; info->staticIterations = staticIts; }
-            if (!li.converged) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modal_harmonic: the static solve of the correction did not reach rtol within maxit iterations");
-        }
-    }
+    if (correct)
+        correction_solves(c, "mfh_modal_harmonic", 2, fPlane, planeNonZero, us, P.rtol, P.maxit, staticSolves, staticIts, info ? &info->staticSolves : nullptr,
+                          info ? &info->staticIterations : nullptr);
 
     std::optional<WideGuard> guard;        // (the operator product of the residuals alone needs both triangles: a sweep without them leaves the storage alone)
     if (wantRes) {
@@ -877,23 +1054,7 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
     // ---- the static correction r_s = u_s - sum_j phi_j g_j / lambda_j into the two reserved columns, through the expansion kernel itself
     DBuf<double> dC, dTmp;
     if (staticSolves) {
-        MFH_HIP(hipMemsetAsync(B + (int64_t)m * ld, 0, (size_t)ld * 2 * sizeof(double), s));
-        for (int pl = 0; pl < 2; ++pl)
-            if (planeNonZero[pl]) {
-                upload(B + (int64_t)(m + pl) * ld, us[pl].data(), n, s);
-                k::launch_mask(n, c->dFixedMask.p, B + (int64_t)(m + pl) * ld, s);
-            }
-        const int ldc = 64;
-        std::vector<double> hc((size_t)nb * ldc, 0.0);
-        for (int j = 0; j < m; ++j)
-            for (int pl = 0; pl < 2; ++pl) hc[(size_t)j * ldc + pl] = planeNonZero[pl] ? -(g[(size_t)2 * j + pl] / lam[(size_t)j]) : 0.0;
-        hc[(size_t)m * ldc + 0] = 1.0;
-        hc[(size_t)(m + 1) * ldc + 1] = 1.0;
-        dC.upload(hc, s);
-        dTmp.alloc((size_t)ld * 2);
-        dTmp.zero(s);
-        k::launch_modal_expand(n, B, ld, nb, dC.p, ldc, 2, k::MODAL_NP, dTmp.p, ld, s);
-        MFH_HIP(hipMemcpyAsync(B + (int64_t)m * ld, dTmp.p, (size_t)ld * 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        correction_columns(c, B, n, ld, m, 2, us, planeNonZero, g.data(), lam.data(), dC, dTmp, s);
         note("static correction: " + std::to_string(staticSolves) + " solve(s) of K u = f, " + std::to_string(staticIts) + " iterations");
     }
 
@@ -1006,6 +1167,346 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
         info->groups = groups; info->planesPerPass = k::MODAL_NP;
         info->worstTrueResidual = worst; info->setupMs = setupMs; info->solveMs = solveMs;
         info->note = c->modalNote.c_str();
+    }
+    MFH_CATCH(c)
+}
+
+// ---------------------------------------------------------------- quadratic forms, random vibration (docs/design/04_23_modal_random.md)
+}   // extern "C"
+
+namespace {
+
+// the probe rows of the nb columns of B, k_modal_gather_rows' layout; synchronises (probeVars is the caller's)
+void gather_probe_rows(const double *B, int64_t ld, int nb, const int64_t *probeVars, int nProbe, DBuf<double> &dBp, int64_t ldp, hipStream_t s) {
+    DBuf<int64_t> dProbeVars;
+    dProbeVars.alloc((size_t)nProbe);
+    MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    dBp.alloc((size_t)ldp * nb);
+    dBp.zero(s);
+    hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, nProbe, nb, (const int64_t *)dProbeVars.p, B, ld, dBp.p, ldp);
+    CHECK_LAUNCH();
+    MFH_HIP(hipStreamSynchronize(s));
+}
+
+struct Factor {
+    std::vector<double> F;
+    std::vector<int32_t> piv;
+    int32_t rank = 0;
+    double truncation = 0.0;
+};
+Factor factor_or_throw(int nb, const double *C, double tol, const char *who) {
+    Factor f;
+    f.F.assign((size_t)nb * nb, 0.0);
+    f.piv.assign((size_t)nb, 0);
+    const mfh_status st = mfh_psd_factor(nb, C, tol, f.F.data(), &f.rank, f.piv.data(), &f.truncation);
+    if (st != MFH_OK) throw Error(st, std::string(who) + ": a matrix is not positive semi-definite (a remaining diagonal below -tol) or has an entry that is not finite");
+    return f;
+}
+
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_modal_quadratic(mfh_ctx *c, int32_t nMat, const double *C, double tol, const int64_t *probeVars, int32_t nProbe, double *probeOut, double *fields,
+                               mfh_modal_quadratic_info *info) {
+    if (info) *info = mfh_modal_quadratic_info{};
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_quadratic: null context");
+    require(nMat >= 1 && nMat <= 4 && C != nullptr, MFH_ERR_INVALID, "mfh_modal_quadratic: 1 <= nMat <= 4 matrices");
+    require(!std::isnan(tol), MFH_ERR_INVALID, "mfh_modal_quadratic: tol is not a number");
+    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeOut)), MFH_ERR_INVALID, "mfh_modal_quadratic: probes need their variables and their output");
+    const int64_t nv = (int64_t)c->bs() * c->nDoF;
+    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_quadratic: probe variable out of range");
+    prepare_pencil(c, "mfh_modal_quadratic");
+    require_basis(c, "mfh_modal_quadratic");
+    const int m = c->modal.nModes;
+    const int64_t n = c->modal.n, ld = c->modal.ld;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<Factor> fac;
+    for (int a = 0; a < nMat; ++a) fac.push_back(factor_or_throw(m, C + (size_t)a * m * m, tol, "mfh_modal_quadratic"));
+    const double factorMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    hipStream_t s = c->stream;
+    const double *B = c->modal.B.p;
+    DBuf<double> dBp, dOut, dPout;
+    const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
+    if (nProbe) { gather_probe_rows(B, ld, m, probeVars, nProbe, dBp, ldp, s); dPout.alloc((size_t)nProbe); }
+    if (fields) dOut.alloc((size_t)ld);
+    EventTimer tsolve(s);
+    for (int a = 0; a < nMat; ++a) {
+        k::SumsqPlan plan;
+        plan.build(m, fac[(size_t)a].F.data(), m, fac[(size_t)a].rank, fac[(size_t)a].piv.data(), k::MODAL_NP, s);
+        if (fields) {
+            plan.run(n, B, ld, true, dOut.p, s);
+            MFH_HIP(hipMemcpyAsync(fields + (size_t)a * (size_t)n, dOut.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        if (nProbe) {
+            plan.run(nProbe, dBp.p, ldp, true, dPout.p, s);
+            MFH_HIP(hipMemcpyAsync(probeOut + (size_t)a * nProbe, dPout.p, (size_t)nProbe * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        MFH_HIP(hipStreamSynchronize(s));
+        if (info) { info->ranks[a] = fac[(size_t)a].rank; info->passes[a] = plan.passes; info->truncation[a] = fac[(size_t)a].truncation; }
+    }
+    const double solveMs = tsolve.stop();
+    if (info) { info->factorMs = factorMs; info->solveMs = solveMs; }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modal_random(mfh_ctx *c, const mfh_modal_random_params *prm, const double *omega, const double *weights, const double *modalDamping, const double *f,
+                            const double *S, const int64_t *probeVars, int32_t nProbe, double *probeRms, double *probePsd, double *rmsFields, double *cov,
+                            mfh_modal_random_info *info) {
+    if (info) { *info = mfh_modal_random_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_random: null context");
+    require(prm != nullptr, MFH_ERR_INVALID, "mfh_modal_random: params is null");
+    const mfh_modal_random_params P = *prm;
+    require(P.nFreq >= 1 && P.maxit > 0, MFH_ERR_INVALID, "mfh_modal_random: nFreq >= 1, maxit > 0");
+    require(P.nLoad >= 1 && P.nLoad <= 8, MFH_ERR_INVALID, "mfh_modal_random: 1 <= nLoad <= 8");
+    require(P.rayleighMass >= 0.0 && P.rayleighStiff >= 0.0 && std::isfinite(P.rayleighMass) && std::isfinite(P.rayleighStiff), MFH_ERR_INVALID,
+            "mfh_modal_random: the Rayleigh coefficients are not negative");
+    require(P.lossFactor >= 0.0 && std::isfinite(P.lossFactor), MFH_ERR_INVALID, "mfh_modal_random: the loss factor is not negative");
+    require(P.rtol > 0.0 && P.rtol < 1.0, MFH_ERR_INVALID, "mfh_modal_random: 0 < rtol < 1");
+    require(!std::isnan(P.tol), MFH_ERR_INVALID, "mfh_modal_random: tol is not a number");
+    require((P.flags & ~(MFH_MODAL_RV_STATIC_CORRECTION | MFH_MODAL_RV_VELOCITY | MFH_MODAL_RV_ACCELERATION)) == 0, MFH_ERR_INVALID, "mfh_modal_random: unknown flag");
+    require(omega && f && S, MFH_ERR_INVALID, "mfh_modal_random: omega, f and S are needed");
+    const bool correct = (P.flags & MFH_MODAL_RV_STATIC_CORRECTION) != 0, wantV = (P.flags & MFH_MODAL_RV_VELOCITY) != 0, wantA = (P.flags & MFH_MODAL_RV_ACCELERATION) != 0;
+    require(!(correct && P.nLoad > 2), MFH_ERR_UNSUPPORTED, "mfh_modal_random: the static correction has two reserved columns: at most two loads with it");
+    const int nFreq = P.nFreq, nl = P.nLoad;
+    for (int32_t k2 = 0; k2 < nFreq; ++k2) {
+        require(std::isfinite(omega[k2]) && omega[k2] >= 0.0, MFH_ERR_INVALID, "mfh_modal_random: a frequency is negative or not finite");
+        require(k2 == 0 || omega[k2] > omega[k2 - 1], MFH_ERR_INVALID, "mfh_modal_random: the frequencies are not ascending");
+        require(omega[k2] > 0.0 || !c->fixedVars.empty(), MFH_ERR_INVALID, "mfh_modal_random: omega = 0 needs fixed variables (K alone is singular)");
+    }
+    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeRms)), MFH_ERR_INVALID, "mfh_modal_random: probes need their variables and their output");
+    require(nProbe > 0 || !probePsd, MFH_ERR_INVALID, "mfh_modal_random: the response spectra belong to probes");
+    const int64_t nv = (int64_t)c->bs() * c->nDoF;
+    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_random: probe variable out of range");
+    if (modalDamping)
+        for (int j = 0; j < c->modal.nModes; ++j) require(std::isfinite(modalDamping[j]) && modalDamping[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_random: a damping ratio is negative or not finite");
+    prepare_pencil(c, "mfh_modal_random");
+    require_basis(c, "mfh_modal_random");
+    const bool masked = !c->fixedVars.empty();
+    const int m = c->modal.nModes;
+    const int64_t n = c->modal.n, ld = c->modal.ld;
+    const std::vector<double> lam = c->modal.lambda;
+    if (correct) {
+        require(masked, MFH_ERR_UNSUPPORTED, "mfh_modal_random: the static correction needs fixed variables (K alone is singular)");
+        for (int j = 0; j < m; ++j) require(lam[(size_t)j] > 0.0, MFH_ERR_INVALID, "mfh_modal_random: the static correction needs lambda_j > 0");
+    }
+    require(all_finite(f, (int64_t)nl * n), MFH_ERR_INVALID, "mfh_modal_random: a load has an entry that is not finite");
+    hipStream_t s = c->stream;
+    c->modalNote.clear();
+    auto note = [&](const std::string &t) { if (!c->modalNote.empty()) c->modalNote += "; "; c->modalNote += t; };
+
+    // ---- the static solves, as mfh_modal_harmonic makes them: one per load that is not zero off the fixed variables
+    int staticSolves = 0, staticIts = 0;
+    std::vector<double> us[2];
+    bool loadNonZero[2] = {false, false};
+    if (correct) {
+        const uint8_t *hm = c->hFixedMask.data();
+        for (int a = 0; a < nl; ++a)
+            for (int64_t i = 0; i < n && !loadNonZero[a]; ++i) loadNonZero[a] = f[(size_t)a * n + i] != 0.0 && !hm[i];
+    }
+    if (correct) {
+        const double *fLoad[2] = {f, nl > 1 ? f + (size_t)n : nullptr};
+        correction_solves(c, "mfh_modal_random", nl, fLoad, loadNonZero, us, P.rtol, P.maxit, staticSolves, staticIts, info ? &info->staticSolves : nullptr,
+                          info ? &info->staticIterations : nullptr);
+    }
+    if (masked) ensure_fixed_uploaded(c);
+    require_basis(c, "mfh_modal_random");
+    double *const B = c->modal.B.p;
+
+    // ---- g = Phi^T f_a, m x nLoad
+    std::vector<double> g((size_t)m * nl);
+    {
+        DBuf<double> dF;
+        dF.alloc((size_t)ld * nl);
+        dF.zero(s);
+        for (int a = 0; a < nl; ++a) {
+            upload(dF.p + (int64_t)a * ld, f + (size_t)a * n, n, s);
+            if (masked) k::launch_mask(n, c->dFixedMask.p, dF.p + (int64_t)a * ld, s);
+        }
+        gram_against(c, B, ld, m, dF.p, ld, nl, 0.0, g.data());
+    }
+    // ---- r_a = u_a - sum_j phi_j g_ja / lambda_j into the two reserved columns, exactly as mfh_modal_harmonic writes r_re and r_im
+    const bool corr = staticSolves > 0;
+    const int nb = corr ? m + nl : m;
+    if (corr) {
+        DBuf<double> dC, dTmp;
+        correction_columns(c, B, n, ld, m, nl, us, loadNonZero, g.data(), lam.data(), dC, dTmp, s);
+        MFH_HIP(hipStreamSynchronize(s));
+        note("static correction: " + std::to_string(staticSolves) + " solve(s) of K u = f, " + std::to_string(staticIts) + " iterations");
+    } else if (correct) note("static correction: every load is zero off the fixed variables, nothing to correct");
+
+    // ---- the covariances of displacement, velocity and acceleration (host), and their factors
+    auto tc = std::chrono::steady_clock::now();
+    std::vector<double> Cq[3];
+    for (auto &v : Cq) v.assign((size_t)nb * nb, 0.0);
+    {
+        const mfh_status st = mfh_modal_covariance(m, lam.data(), g.data(), nl, P.rayleighMass, P.rayleighStiff, P.lossFactor, modalDamping, nFreq, omega, weights, S, corr ? 1 : 0,
+                                                   Cq[0].data(), Cq[1].data(), Cq[2].data());
+        if (st != MFH_OK)
+            throw Error(st, "mfh_modal_random: mfh_modal_covariance refused the input (omega = 0 with a zero eigenvalue, d_j = 0, a spectrum that is not Hermitian or has a "
+                            "negative diagonal, an entry that is not finite, or sums that overflow)");
+    }
+    const double covarianceMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
+    if (cov)
+        for (int q = 0; q < 3; ++q) std::copy(Cq[q].begin(), Cq[q].end(), cov + (size_t)q * nb * nb);
+    const bool need[3] = {rmsFields != nullptr || nProbe > 0, (rmsFields != nullptr && wantV) || nProbe > 0, (rmsFields != nullptr || nProbe > 0) && wantA};
+    const bool fieldOf[3] = {rmsFields != nullptr, rmsFields != nullptr && wantV, rmsFields != nullptr && wantA};
+    tc = std::chrono::steady_clock::now();
+    Factor fac[3];
+    for (int q = 0; q < 3; ++q)
+        if (need[q]) fac[q] = factor_or_throw(nb, Cq[q].data(), P.tol, "mfh_modal_random");
+    const double factorMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
+
+    // ---- the passes: fields and probes (the same kernel on the gathered rows)
+    DBuf<double> dBp, dOut, dPout;
+    const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
+    if (nProbe) { gather_probe_rows(B, ld, nb, probeVars, nProbe, dBp, ldp, s); dPout.alloc((size_t)nProbe); std::fill(probeRms, probeRms + (size_t)4 * nProbe, 0.0); }
+    if (rmsFields) dOut.alloc((size_t)ld);
+    EventTimer tsolve(s);
+    int plane = 0;
+    for (int q = 0; q < 3; ++q) {
+        if (!need[q]) continue;
+        k::SumsqPlan plan;
+        plan.build(nb, fac[q].F.data(), nb, fac[q].rank, fac[q].piv.data(), k::MODAL_NP, s);
+        if (fieldOf[q]) {
+            plan.run(n, B, ld, true, dOut.p, s);
+            MFH_HIP(hipMemcpyAsync(rmsFields + (size_t)plane * (size_t)n, dOut.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+            ++plane;
+        }
+        if (nProbe) {
+            plan.run(nProbe, dBp.p, ldp, true, dPout.p, s);
+            MFH_HIP(hipMemcpyAsync(probeRms + (size_t)q * nProbe, dPout.p, (size_t)nProbe * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        MFH_HIP(hipStreamSynchronize(s));
+        if (info) { info->ranks[q] = fac[q].rank; info->passes[q] = plan.passes; info->truncation[q] = fac[q].truncation; }
+    }
+    const double solveMs = tsolve.stop();
+    if (nProbe) {
+        const double twoPi = 6.283185307179586;
+        for (int p = 0; p < nProbe; ++p) probeRms[(size_t)3 * nProbe + p] = probeRms[p] > 0.0 ? probeRms[(size_t)nProbe + p] / (twoPi * probeRms[p]) : 0.0;
+    }
+    // ---- the response spectra of the probes: H_p S H_p^H on the gathered rows, host arithmetic on nProbe nb numbers per frequency
+    if (probePsd) {
+        std::vector<double> hb((size_t)ldp * nb);
+        dBp.download(hb.data(), hb.size(), s);
+        std::vector<Cplx> H((size_t)nb * nl), hp((size_t)nl);
+        for (int k2 = 0; k2 < nFreq; ++k2) {
+            const double w = omega[k2];
+            const Cplx zK{1.0, P.lossFactor + w * P.rayleighStiff};
+            for (int j = 0; j < m; ++j) {
+                const double l = lam[(size_t)j];
+                const Cplx d{l * zK.re - w * w, l * zK.im + w * P.rayleighMass + (modalDamping ? 2.0 * modalDamping[j] * std::sqrt(l) * w : 0.0)};
+                const Cplx di = cdivh(Cplx{1.0, 0.0}, d);
+                for (int a = 0; a < nl; ++a) H[(size_t)j * nl + a] = Cplx{g[(size_t)j * nl + a] * di.re, g[(size_t)j * nl + a] * di.im};
+            }
+            if (corr) {
+                const Cplx iz = cdivh(Cplx{1.0, 0.0}, zK);
+                for (int a = 0; a < nl; ++a)
+                    for (int b = 0; b < nl; ++b) H[(size_t)(m + a) * nl + b] = a == b ? iz : Cplx{0.0, 0.0};
+            }
+            const double *Sk = S + (size_t)k2 * nl * nl * 2;
+            for (int p = 0; p < nProbe; ++p) {
+                for (int a = 0; a < nl; ++a) {
+                    Cplx acc{0.0, 0.0};
+                    for (int j = 0; j < nb; ++j) { const double bj = hb[(size_t)j * ldp + p]; acc.re += bj * H[(size_t)j * nl + a].re; acc.im += bj * H[(size_t)j * nl + a].im; }
+                    hp[(size_t)a] = acc;
+                }
+                double v = 0.0;
+                for (int a = 0; a < nl; ++a)
+                    for (int b = 0; b < nl; ++b) {       // Re(hp_a S_ab conj(hp_b))
+                        const Cplx sab{Sk[(size_t)(a * nl + b) * 2], Sk[(size_t)(a * nl + b) * 2 + 1]};
+                        const Cplx t{hp[(size_t)a].re * sab.re - hp[(size_t)a].im * sab.im, hp[(size_t)a].re * sab.im + hp[(size_t)a].im * sab.re};
+                        v += t.re * hp[(size_t)b].re + t.im * hp[(size_t)b].im;
+                    }
+                probePsd[(size_t)p * nFreq + k2] = v;
+            }
+        }
+    }
+    if (info) {
+        info->nb = nb;
+        info->staticSolves = staticSolves; info->staticIterations = staticIts;
+        info->covarianceMs = covarianceMs; info->factorMs = factorMs; info->solveMs = solveMs;
+        info->note = c->modalNote.c_str();
+    }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_modal_sumsq(mfh_ctx *c, int64_t n, int32_t nb, const double *Bh, const double *Fh, int32_t rank, const int32_t *piv, int32_t planesPerPass,
+                                 int32_t sqrtFlag, double *out) {
+    MFH_TRY(c)
+    require(c && out && n >= 1 && nb >= 1 && nb <= k::MODAL_MAXB && rank >= 0 && rank <= 4096 && (rank == 0 || (Bh && Fh)) && planesPerPass >= 0 &&
+                planesPerPass <= k::MODAL_NP_MAX && (sqrtFlag == 0 || sqrtFlag == 1),
+            MFH_ERR_INVALID, "mfh_debug_modal_sumsq: arguments");
+    if (piv) {          // what a list leaves out has to be exactly zero from the pass's first column on
+        require(rank <= nb, MFH_ERR_INVALID, "mfh_debug_modal_sumsq: a pivot list has at most nb entries");
+        const int np = planesPerPass ? planesPerPass : k::MODAL_NP;
+        for (int t = 0; t < rank; ++t) {
+            require(piv[t] >= 0 && piv[t] < nb, MFH_ERR_INVALID, "mfh_debug_modal_sumsq: pivot out of range");
+            for (int u = (t / np + 1) * np; u < rank; ++u) require(Fh[(size_t)piv[t] * rank + u] == 0.0, MFH_ERR_INVALID, "mfh_debug_modal_sumsq: a column the list leaves out has a non-zero coefficient");
+        }
+    }
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = (n + 31) / 32 * 32;
+    DBuf<double> b, o;
+    o.alloc((size_t)ld);
+    if (rank > 0) {
+        b.alloc((size_t)ld * nb);
+        b.zero(s);
+        const size_t rowBytes = (size_t)n * sizeof(double);
+        MFH_HIP(hipMemcpy2DAsync(b.p, (size_t)ld * sizeof(double), Bh, rowBytes, rowBytes, (size_t)nb, hipMemcpyHostToDevice, s));
+    }
+    k::SumsqPlan plan;
+    plan.build(nb, Fh, rank, rank, piv, planesPerPass ? planesPerPass : k::MODAL_NP, s);
+    plan.run(n, b.p, ld, sqrtFlag != 0, o.p, s);
+    o.download(out, (size_t)n, s);
+    MFH_CATCH(c)
+}
+
+// ms per repetition of one pass of k_modal_sumsq<NP> (all nb columns) and of one pass of k_modal_expand<NP> on the same hashed columns, the two taking
+// turns; laterMs (or NULL): a second pass of a factor of rank 2 NP with pivots 0 .. NP - 1 -- nc = nb - NP columns and the accumulator read back
+mfh_status mfh_time_modal_sumsq(mfh_ctx *c, int64_t n, int32_t nb, int32_t planesPerPass, int32_t reps, double *sumsqMs, double *expandMs, double *laterMs) {
+    MFH_TRY(c)
+    require(c && sumsqMs && expandMs && n >= 1 && reps >= 1 && nb >= 1 && nb <= k::MODAL_MAXB && (planesPerPass == 0 || planesPerPass == 8 || planesPerPass == 16 || planesPerPass == 32),
+            MFH_ERR_INVALID, "mfh_time_modal_sumsq: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int np = planesPerPass ? planesPerPass : k::MODAL_NP;
+    const int64_t ld = (n + 31) / 32 * 32;
+    const int ldc = np + k::MODAL_NP_MAX;
+    DBuf<double> b, cc, o, o1;
+    b.alloc((size_t)ld * nb); o.alloc((size_t)ld * np); o1.alloc((size_t)ld); cc.alloc((size_t)nb * ldc);
+    k::launch_fill_hash((int64_t)b.n, b.p, s);
+    k::launch_fill_hash((int64_t)cc.n, cc.p, s);
+    std::vector<double> hf((size_t)nb * np);
+    for (size_t i = 0; i < hf.size(); ++i) hf[i] = 0.25 + (double)((i * 2654435761u) % 1024) / 1024.0;
+    k::SumsqPlan plan;
+    plan.build(nb, hf.data(), np, np, nullptr, np, s);
+    k::SumsqPlan plan2;
+    const bool later = laterMs != nullptr && nb > np;
+    if (later) {          // rank 2 NP, lower trapezoidal in the first NP rows: the second pass leaves the columns 0 .. NP - 1 out
+        std::vector<double> hf2((size_t)nb * 2 * np);
+        std::vector<int32_t> piv((size_t)2 * np);
+        for (int j = 0; j < nb; ++j)
+            for (int t = 0; t < 2 * np; ++t) hf2[(size_t)j * 2 * np + t] = (j < np && t > j) ? 0.0 : hf[((size_t)j * np + t % np)];
+        for (int t = 0; t < 2 * np; ++t) piv[(size_t)t] = t < nb ? t : nb - 1;
+        plan2.build(nb, hf2.data(), 2 * np, 2 * np, piv.data(), np, s);
+    }
+    auto a = [&] { plan.run(n, b.p, ld, true, o1.p, s); };
+    auto e = [&] { k::launch_modal_expand(n, b.p, ld, nb, cc.p, ldc, np, np, o.p, ld, s); };
+    auto l = [&] { plan2.run(n, b.p, ld, false, o1.p, s, 1); };
+    a(); e();          // warm-up
+    if (later) l();
+    MFH_HIP(hipStreamSynchronize(s));
+    for (int r = 0; r < reps; ++r) {
+        { EventTimer t(s); a(); sumsqMs[r] = t.stop(); }
+        { EventTimer t(s); e(); expandMs[r] = t.stop(); }
+        if (laterMs) laterMs[r] = 0.0;
+        if (later) { EventTimer t(s); l(); laterMs[r] = t.stop(); }
     }
     MFH_CATCH(c)
 }

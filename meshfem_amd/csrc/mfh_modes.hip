@@ -1134,6 +1134,7 @@ struct LoopIn {
     LoopTrace *trace = nullptr;        // the history of the run (mfh_debug_lobpcg; null for every entry point: nothing is recorded, nothing launched)
 };
 struct LoopOut {
+    std::vector<double> sign;          // per returned column: -1 where the sign rule flipped the host copy (the device column keeps its sign)
     int iterations = 0, restarts = 0, locked = 0, blockSize = 0;
     bool done = false;
     double maxResidual = 0, setupMs = 0, solveMs = 0;
@@ -1362,13 +1363,16 @@ struct Lobpcg {
         MFH_HIP(hipMemcpy2DAsync(in.X, (size_t)w.n * sizeof(double), w.X, (size_t)w.ld * sizeof(double), (size_t)w.n * sizeof(double), (size_t)in.nev, hipMemcpyDeviceToHost, w.s));
         MFH_HIP(hipStreamSynchronize(w.s));
         o.solveMs = tsolve.stop();
+        o.sign.assign((size_t)in.nev, 1.0);
         for (int j = 0; j < in.nev; ++j) {
             double *x = in.X + (size_t)j * (size_t)w.n;
             int64_t at = 0;
             for (int64_t i = 1; i < w.n; ++i)
                 if (std::fabs(x[i]) > std::fabs(x[at])) at = i;
-            if (x[at] < 0)
+            if (x[at] < 0) {
+                o.sign[(size_t)j] = -1.0;
                 for (int64_t i = 0; i < w.n; ++i) x[i] = -x[i];
+            }
             if (w.masked)
                 for (int64_t fv : w.c->fixedVars) x[(size_t)fv] = 0.0;       // (exactly +0.0: the iteration keeps them at +-0.0)
             in.lambda[j] = lam[(size_t)j];
@@ -1543,6 +1547,7 @@ struct ManyRun {
     double setupMs = 0, solveMs = 0, lockDefect = 0;
     std::vector<double> res;           // per mode found, in the order found
     std::vector<int> batchOf;
+    std::vector<double> sign;          // of every found column, in the order found (LoopOut::sign)
 };
 // Batch by batch: each runs the loop in the complement of the set (to rtol lockFactor, the last one of a sweep without a band to rtol), joins the
 // set with fresh images, and its guard columns seed the next start block. Ends at nev modes, at a batch that did not converge, or past the band.
@@ -1577,6 +1582,7 @@ void many_batches(ModesWork &w, const mfh_modes_many_params &p, int batch, doubl
         ++r.batches;
         r.iterations += lo.iterations; r.restarts += lo.restarts; r.setupMs += lo.setupMs; r.solveMs += lo.solveMs;
         r.lockDefect = std::max(r.lockDefect, lo.lockDefect);
+        r.sign.insert(r.sign.end(), lo.sign.begin(), lo.sign.end());
         MFH_HIP(hipMemcpyAsync(w.col(Q, nqNow), w.X, L * (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, s));
         for (int j = 0; j < nb; ++j) w.apply_B(w.col(Q, nqNow + j), w.col(BQ, nqNow + j));
         nSeed = useSeed ? lo.blockSize - nb : 0;
@@ -1608,9 +1614,9 @@ double many_full_residuals(ModesWork &w, double *Q, double *BQ, int nLocked, int
 
 // Sorted by lambda (lambda, res and the rows of X, in place); a mode of a later batch that sorts before an earlier batch's largest (by more than
 // rtol) is counted and named in the note. Returns that count.
-int many_sort(mfh_ctx *c, int64_t n, const ManyRun &r, double rtol, double *lambda, double *res, double *Xout) {
+int many_sort(mfh_ctx *c, int64_t n, const ManyRun &r, double rtol, double *lambda, double *res, double *Xout, std::vector<int> &order) {
     const int found = r.found;
-    std::vector<int> order = iota(found);
+    order = iota(found);
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lambda[a] < lambda[b]; });
     int nOut = 0;
     std::vector<double> hiOfBatch((size_t)std::max(r.batches, 1), -1e300);
@@ -1642,6 +1648,14 @@ int many_sort(mfh_ctx *c, int64_t n, const ManyRun &r, double rtol, double *lamb
     }
     for (int j = 0; j < found; ++j) { lambda[j] = lam2[(size_t)j]; res[(size_t)j] = res2[(size_t)j]; }
     return nOut;
+}
+
+void modes_keep_record(mfh_ctx *c, mfh_ctx::ModesKeep &kp, int64_t n, int64_t ld, const std::vector<int> &src, const std::vector<double> &sign, const double *lambda) {
+    kp.n = n; kp.ld = ld; kp.src = src; kp.sign = sign;
+    kp.lambda.assign(lambda, lambda + src.size());
+    kp.fixedSet = c->fixedVars;
+    std::sort(kp.fixedSet.begin(), kp.fixedSet.end());
+    kp.geoGen = c->geoGen; kp.densityGen = c->densityGen;
 }
 
 }   // namespace
@@ -1718,6 +1732,13 @@ mfh_status mfh_modes_many(mfh_ctx *c, const mfh_modes_many_params *prm, const do
             info->note = c->modesNote.c_str();
         }
         require_converged(lo);
+        // what mfh_modal_set_basis_from_modes adopts: the block's returned columns
+        mfh_ctx::ModesKeep &kp = c->modesKeep;
+        kp.reset();
+        kp.Q.alloc((size_t)w.ld * (size_t)nev);
+        MFH_HIP(hipMemcpyAsync(kp.Q.p, w.X, (size_t)w.ld * (size_t)nev * sizeof(double), hipMemcpyDeviceToDevice, s));
+        MFH_HIP(hipStreamSynchronize(s));
+        modes_keep_record(c, kp, n, w.ld, iota(nev), lo.sign, lambda);
         return MFH_OK;
     }
     // ---- the deflation set: Q and M Q, nLocked + nev columns each
@@ -1732,7 +1753,8 @@ mfh_status mfh_modes_many(mfh_ctx *c, const mfh_modes_many_params *prm, const do
     ManyRun r;
     many_batches(w, p, batch, lockFactor, band, tsetup, setQ.p, setBQ.p, lambda, Xout, r);
     r.solveMs += many_full_residuals(w, setQ.p, setBQ.p, nLocked, r.found, lambda, r.res.data());
-    const int nOut = many_sort(c, n, r, p.rtol, lambda, r.res.data(), Xout);
+    std::vector<int> order;
+    const int nOut = many_sort(c, n, r, p.rtol, lambda, r.res.data(), Xout, order);
     int nFound = r.found;
     if (band)
         while (nFound > 0 && lambda[nFound - 1] > p.lambdaMax) --nFound;
@@ -1752,6 +1774,16 @@ mfh_status mfh_modes_many(mfh_ctx *c, const mfh_modes_many_params *prm, const do
     }
     if (!r.allDone) throw Error(MFH_ERR_NOT_CONVERGED, "LOBPCG did not reach the requested tolerance within maxit iterations (batch " + std::to_string(r.batches - 1) + ")");
     if (!converged) throw Error(MFH_ERR_NOT_CONVERGED, "the full residuals of the locked modes exceed rtol (largest " + std::to_string(mr / p.rtol) + " rtol): lower lockFactor");
+    {   // the set stays for mfh_modal_set_basis_from_modes instead of being freed here: sorted mode j is its column nLocked + order[j]
+        mfh_ctx::ModesKeep &kp = c->modesKeep;
+        kp.reset();
+        MFH_HIP(hipStreamSynchronize(s));
+        kp.Q.swap(setQ);
+        std::vector<int> src((size_t)nFound);
+        std::vector<double> sg((size_t)nFound);
+        for (int j = 0; j < nFound; ++j) { src[(size_t)j] = nLocked + order[(size_t)j]; sg[(size_t)j] = r.sign[(size_t)order[(size_t)j]]; }
+        modes_keep_record(c, kp, n, w.ld, src, sg, lambda);
+    }
     MFH_CATCH(c)
 }
 

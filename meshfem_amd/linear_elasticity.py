@@ -630,6 +630,105 @@ class Simulator:
         del out["info"]
         return out
 
+    def _ensure_modal_basis(self, n_modes, modes, density, batch, modes_rtol):
+        """The basis of the modal calls, as modalFrequencyResponse settles it: computed here, the caller's, or the previous call's."""
+        ctx = self.ctx
+        if n_modes is None and modes is None:
+            return
+        v, _ = ctx.bc_dirichlet_vars()
+        ctx.clear_fixed()
+        if len(v):
+            ctx.fix_variables(v)
+        if modes is not None:
+            lam, X = modes
+            self.modal_basis_info = ctx.set_modal_basis(lam, np.asarray(X, dtype=np.float64).reshape(len(lam), -1), density=density)
+        else:
+            lam, X, info = ctx.modal_basis(int(n_modes), density=density, free=len(v) == 0, batch=batch, rtol=modes_rtol)
+            self.modes_many_info, self.modal_basis_info = info, info["modal_basis"]
+        self.modal_eigenvalues, self.modal_density = np.asarray(lam, dtype=np.float64).copy(), density
+        self.modal_frequencies = np.sqrt(self.modal_eigenvalues) / (2.0 * np.pi)
+
+    def randomResponse(self, omegas, psd, load=None, n_modes=None, modes=None, weights=None, density=1.0, damping=(0, 0), loss_factor=0.0,
+                       modal_damping=None, static_correction=True, velocity=False, acceleration=False, probes=None, fields=True, probe_psd=False,
+                       tol=-1.0, rtol=None, maxit=None, modes_rtol=1e-6, batch=0):
+        """The RMS response to a stationary random load (mfh_modal_random, docs/design/04_23_modal_random.md): the load shapes `load` ([nDoF, N], or
+        [nLoad, nDoF, N]; None: the Neumann load) with amplitudes of one-sided (cross-)spectral density psd ([nFreq] or [nFreq, nLoad, nLoad],
+        Hermitian) on the ascending grid omegas (resonance_grid builds one that resolves the peaks). Basis (n_modes / modes / neither), clamp,
+        damping and probes as in modalFrequencyResponse. Returns a dict: "sigma_u", "sigma_v", "sigma_a": nodal fields [nNode, N] (the latter two on
+        request), "probes": dict of "sigma_u", "sigma_v", "sigma_a", "nu0" (upward zero crossings per unit time) and "psd" [len(probes), nFreq], "cov"
+        [3, nb, nb]. self.random_info holds the solver's record."""
+        ctx = self.ctx
+        density = self._density_scalar(density)
+        mapped = ctx.n_dof != ctx.n_node
+        dof = ctx.get_dof_map()[0] if mapped else None
+        self._ensure_modal_basis(n_modes, modes, density, batch, modes_rtol)
+        f = self.neumannLoad().reshape(1, -1) if load is None else np.asarray(load, dtype=np.float64).reshape(-1, ctx.n_dof * self.N)
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        try:
+            r = ctx.modal_random(omegas, psd, f, weights=weights, damping=damping, loss_factor=loss_factor, modal_damping=modal_damping,
+                                 static_correction=static_correction, velocity=velocity, acceleration=acceleration, tol=tol,
+                                 rtol=self.rtol if rtol is None else rtol, maxit=self.maxit if maxit is None else maxit, probes=pv, fields=fields,
+                                 probe_psd=probe_psd)
+        finally:
+            self.random_info = getattr(ctx, "last_modal_random", {}).get("info")
+        out = dict(r)
+        for name in ("sigma_u", "sigma_v", "sigma_a"):
+            if r[name] is not None:
+                s = r[name].reshape(ctx.n_dof, self.N)
+                out[name] = s[dof, :] if mapped else s
+        del out["info"]
+        return out
+
+    def responseSpectrum(self, direction, Sd, modal_damping=0.05, rule="cqc", n_modes=None, modes=None, density=1.0, probes=None, fields=True,
+                         tol=-1.0, modes_rtol=1e-6, batch=0):
+        """The peak response to a design spectrum applied as a base motion in `direction` (0 .. N-1): R_i = sqrt(phi_i^T C phi_i) with
+        C_jk = rho_jk a_j a_k, a_j = Gamma_j Sd_j, Gamma = Phi^T (density M) r_d the participation factors of the unit translation r_d
+        (mfh_modal_quadratic). Sd: the spectral displacement per mode, or a callable Sd(omega, zeta) evaluated at the modes' sqrt(lam_j).
+        rule: "srss" (rho = I) or "cqc" (cqc_matrix with modal_damping, a scalar or one ratio per mode). Basis and probes as in
+        modalFrequencyResponse. Returns a dict: "R" [nNode, N] (None without fields), "probes" [len(probes)]. self.spectrum_info: "gamma",
+        "effective_mass" (gamma^2), "mass_fraction" (their sum over the moving mass r_f^T (density M_ff) r_f), "a", "rho", and the solver's record."""
+        ctx = self.ctx
+        if rule not in ("cqc", "srss"):
+            raise ValueError("responseSpectrum: rule is 'cqc' or 'srss'")
+        d = int(direction)
+        if not 0 <= d < self.N:
+            raise ValueError("responseSpectrum: direction in 0 .. %d" % (self.N - 1))
+        density = self._density_scalar(density)
+        mapped = ctx.n_dof != ctx.n_node
+        dof = ctx.get_dof_map()[0] if mapped else None
+        self._ensure_modal_basis(n_modes, modes, density, batch, modes_rtol)
+        m = ctx.modal_basis_state()[0]
+        lam = getattr(self, "modal_eigenvalues", None)
+        if lam is None or len(lam) != m:
+            raise ValueError("responseSpectrum: the basis was not set through this Simulator (pass n_modes or modes)")
+        r = np.zeros((ctx.n_dof, self.N))
+        r[:, d] = 1.0
+        gamma = ctx.modal_coordinates(r.reshape(-1))
+        zeta = np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,))
+        sd = np.asarray(Sd(np.sqrt(lam), zeta), dtype=np.float64) if callable(Sd) else np.asarray(Sd, dtype=np.float64)
+        a = gamma * np.broadcast_to(sd, (m,))
+        from .core import cqc_matrix
+        rho = np.eye(m) if rule == "srss" else cqc_matrix(lam, zeta)
+        pv = None
+        if probes is not None:
+            pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+            pv = (dof[pr[:, 0]] if mapped else pr[:, 0]) * self.N + pr[:, 1]
+        q = ctx.modal_quadratic(rho * np.outer(a, a), tol=tol, probes=pv, fields=fields)
+        v, _ = ctx.bc_dirichlet_vars()
+        rf = r.copy()
+        rf.reshape(-1)[np.asarray(v, dtype=np.int64)] = 0.0
+        moving = self.modal_density * float(rf.reshape(-1) @ ctx.mass_apply(rf).reshape(-1))
+        self.spectrum_info = {"gamma": gamma, "effective_mass": gamma ** 2, "mass_fraction": float((gamma ** 2).sum() / moving), "a": a, "rho": rho,
+                              "info": q["info"]}
+        R = None
+        if q["fields"] is not None:
+            R = q["fields"][0].reshape(ctx.n_dof, self.N)
+            R = R[dof, :] if mapped else R
+        return {"R": R, "probes": q["probes"][0]}
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 
