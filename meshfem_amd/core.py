@@ -12,6 +12,15 @@ def flat_len(dim):
     return dim * (dim + 1) // 2
 
 
+def _probe_vars(probes):             # a `probes` argument as (the variables as int64 or None, how many)
+    pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
+    return pv, 0 if pv is None else pv.size
+
+
+def _modal_zeta(modal_damping, m):   # a `modal_damping` argument (a scalar or one ratio per mode) as m doubles, or None
+    return None if modal_damping is None else as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = L.load()
@@ -476,8 +485,7 @@ class Context:
         amp = None if amplitude is None else as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
         if amp is not None and amp.size != rows:
             raise ValueError("newmark: amplitude needs n_steps + 1 = %d entries, got %d" % (rows, amp.size))
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros((rows, n_probe)) if n_probe else None
         stride = int(snapshot_stride)
         snaps = np.zeros((max(n_steps, 0) // stride + 1, n)) if stride > 0 else None
@@ -536,8 +544,7 @@ class Context:
         amp = None if amplitude is None else as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
         if amp is not None and amp.size != rows:
             raise ValueError("explicit: amplitude needs n_steps + 1 = %d entries, got %d" % (rows, amp.size))
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros((rows, n_probe)) if n_probe else None
         stride, estride = int(snapshot_stride), int(energy_stride)
         snaps = np.zeros((max(n_steps, 0) // stride + 1, n)) if stride > 0 else None
@@ -561,8 +568,7 @@ class Context:
         a = np.zeros(n) if a is None else np.array(a, dtype=np.float64)
         mass = None if mass is None else as_f64(mass)
         f = None if f is None else as_f64(f)
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros(n_probe) if n_probe else None
         snap = np.zeros(n) if snapshot else None
         en = np.zeros(4) if energies else None
@@ -610,8 +616,7 @@ class Context:
             if fi.size != n:
                 raise ValueError("harmonic: f_imag needs dim * n_dof = %d entries, got %d" % (n, fi.size))
             f_im = np.ascontiguousarray(fi if f_im is None else f_im + fi)
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros((nf, n_probe, 2)) if n_probe else None
         fld = np.zeros((nf, 2, n)) if fields else None
         its, res = np.zeros(nf, dtype=np.int32), np.zeros(nf)
@@ -703,11 +708,8 @@ class Context:
                 raise ValueError("modal_harmonic: f_imag needs dim * n_dof = %d entries, got %d" % (n, fi.size))
             f_im = np.ascontiguousarray(fi if f_im is None else f_im + fi)
         m = self.modal_basis_state()[0]
-        zeta = None
-        if modal_damping is not None:
-            zeta = as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        zeta = _modal_zeta(modal_damping, m)
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros((nf, n_probe, 2)) if n_probe else None
         fld = np.zeros((nf, 2, n)) if fields else None
         mc, res = np.zeros((nf, m, 2)), np.full(nf, -1.0)
@@ -783,11 +785,8 @@ class Context:
         amp = None if amplitude is None else as_f64(np.asarray(amplitude, dtype=np.float64).reshape(-1))
         if amp is not None and amp.size != rows:
             raise ValueError("modal_transient: amplitude needs n_steps + 1 = %d entries, got %d" % (rows, amp.size))
-        zeta = None
-        if modal_damping is not None:
-            zeta = as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        zeta = _modal_zeta(modal_damping, m)
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros((rows, n_probe)) if n_probe else None
         stride = int(snapshot_stride)
         snaps = np.zeros((max(n_steps, 0) // stride + 1, n)) if stride > 0 else None
@@ -848,8 +847,7 @@ class Context:
             raise ValueError("modal_quadratic: the matrices are %d x %d (the modes of the basis), got %s" % (m, m, Cm.shape))
         Cm = np.ascontiguousarray(Cm)
         n_mat = Cm.shape[0]
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        pv, n_probe = _probe_vars(probes)
         pout = np.zeros((n_mat, n_probe)) if n_probe else None
         fld = np.zeros((n_mat, n)) if fields else None
         info = L.ModalQuadraticInfo()
@@ -886,11 +884,8 @@ class Context:
         if w is not None and w.size != nf:
             raise ValueError("modal_random: %d weights for %d frequencies" % (w.size, nf))
         m = self.modal_basis_state()[0]
-        zeta = None
-        if modal_damping is not None:
-            zeta = as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
-        pv = None if probes is None else as_i64(np.asarray(probes).reshape(-1))
-        n_probe = 0 if pv is None else pv.size
+        zeta = _modal_zeta(modal_damping, m)
+        pv, n_probe = _probe_vars(probes)
         prms = np.zeros((4, n_probe)) if n_probe else None
         ppsd = np.zeros((n_probe, nf)) if n_probe and probe_psd else None
         planes = 1 + int(bool(velocity)) + int(bool(acceleration))
@@ -1893,7 +1888,7 @@ def modal_covariance(lam, g, omega, S, weights=None, damping=(0.0, 0.0), loss_fa
     w = None if weights is None else as_f64(np.asarray(weights, dtype=np.float64).reshape(-1))
     if w is not None and w.size != nf:
         raise ValueError("modal_covariance: %d weights for %d frequencies" % (w.size, nf))
-    zeta = None if modal_damping is None else as_f64(np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,)))
+    zeta = _modal_zeta(modal_damping, m)
     nb = m + (nl if correction else 0)
     out = np.zeros((3, nb, nb))
     st = L.load().mfh_modal_covariance(m, ptr(lam), ptr(g), nl, float(damping[0]), float(damping[1]), float(loss_factor), ptr(zeta), nf, ptr(om), ptr(w), ptr(Sri),

@@ -16,6 +16,7 @@
 // The mass products are k_spmv_kron_acc's (mfh_pencil.hh), the true residual's operator product mfh_harmonic's own (harmonic_product, mfh_harmonic.hip).
 // The same basis serves load histories (mfh_modal_transient; docs/design/04_22_modal_transient.md): k_modal_slope, k_modal_march, k_modal_series
 // below, the step coefficients from mfh_modal_coeffs.cpp.
+// The three drivers set their loads up through one path (ModalLoads): the static solves, the masked loads on the device, g and the correction columns.
 // And quadratic forms per row, phi_i^T C phi_i, for random vibration and response spectra (mfh_modal_quadratic, mfh_modal_random;
 // docs/design/04_23_modal_random.md): k_modal_sumsq below on the factor C = F F^T that mfh_modal_cov.cpp forms on the host.
 #include "mfh_pencil.hh"
@@ -413,6 +414,31 @@ Cplx cdivh(const Cplx &a, const Cplx &b) {
     const double d = b.re * b.re + b.im * b.im;
     return Cplx{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
 }
+Cplx crecip(const Cplx &b) { return cdivh(Cplx{1.0, 0.0}, b); }
+
+// The modal denominator d_j(w) = lambda zK - w^2 + i (w aR + 2 zeta_j sqrt(lambda) w) with zK = 1 + i (eta + w bR), and the two reciprocals the sweep and
+// the response spectra multiply by. (mfh_modal_cov.cpp forms its own: another translation unit, and its reciprocal is not cdivh's.)
+Cplx modal_d(double l, double w, double aR, double bR, double eta, double zetaJ) {
+    const Cplx zK{1.0, eta + w * bR};
+    return Cplx{l * zK.re - w * w, l * zK.im + w * aR + 2.0 * zetaJ * std::sqrt(l) * w};
+}
+Cplx modal_dinv(double l, double w, double aR, double bR, double eta, double zetaJ) { return crecip(modal_d(l, w, aR, bR, eta, zetaJ)); }
+Cplx inv_zK(double w, double bR, double eta) { return crecip(Cplx{1.0, eta + w * bR}); }
+
+void require_for(bool cond, mfh_status code, const char *who, const char *what) {
+    if (!cond) throw Error(code, std::string(who) + ": " + what);
+}
+
+// a line of the note a driver hands back in its info
+void modal_note(mfh_ctx *c, const std::string &t) {
+    if (!c->modalNote.empty()) c->modalNote += "; ";
+    c->modalNote += t;
+}
+
+// cols packed host columns of n doubles to device columns ld apart
+void upload_columns(double *dst, int64_t ld, const double *src, int64_t n, int64_t cols, hipStream_t s) {
+    MFH_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(double), src, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)cols, hipMemcpyHostToDevice, s));
+}
 
 bool all_finite(const double *v, int64_t count) {
     std::vector<uint8_t> bad((size_t)std::max(1, host_threads()) + 1, 0);
@@ -465,7 +491,7 @@ void gram_against(mfh_ctx *c, const double *A, int64_t ld, int na, const double 
     }
 }
 
-// The static solves of the correction, shared by mfh_modal_harmonic (its load planes) and mfh_modal_random (its loads): K u = f[a] with the
+// The static solves of the correction (ModalLoads::solve below): K u = f[a] with the
 // context's solver and preconditioner for every a < na whose load is not zero off the fixed variables, the fixed variables held at ZERO whatever values
 // mfh_solve would hold them at. The counts go to the caller's info as they grow, so that a failed call reports what was done.
 void correction_solves(mfh_ctx *c, const char *who, int na, const double *const f[2], const bool nonZero[2], std::vector<double> us[2], double rtol, int maxit,
@@ -516,13 +542,99 @@ void correction_columns(mfh_ctx *c, double *B, int64_t n, int64_t ld, int m, int
     MFH_HIP(hipMemcpyAsync(B + (int64_t)m * ld, dTmp.p, (size_t)ld * 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 
+// ---- The setup the three drivers share: the loads of a call (load planes for mfh_modal_harmonic), na <= 8 columns f[a] of n doubles (null: zero). In
+// the order of the steps:
+//   solve    which loads are not zero off the fixed variables, and the static solves of those -- on the context's own storage, solver and
+//            preconditioner, so before a caller's WideGuard. Only where a correction is wanted (then na <= 2: the basis has two reserved columns).
+//   stage    the loads masked on the device, ld apart (dF: mfh_modal_harmonic takes its norms and residuals against it)
+//   project  g = Phi^T f (g[j na + a]) and, after a solve, r_a into the reserved columns: the drivers then stream nb = m + na columns, else nb = m
+// prepare_modal_loads makes the three in a row. The counts go to the caller's info as they grow (correction_solves).
+struct ModalLoads {
+    int na = 0, nb = 0, staticSolves = 0, staticIts = 0;
+    bool corr = false;                  // the reserved columns hold corrections
+    std::vector<double> g;
+    DBuf<double> dF;
+    bool nonZero[2] = {false, false};
+    std::vector<double> us[2];
+    DBuf<double> dC, dTmp;              // correction_columns' buffers
+
+    void solve(mfh_ctx *c, const char *who, int na_, const double *const f[], bool wantCorrection, double rtol, int maxit, int32_t *infoSolves, int32_t *infoIts) {
+        na = na_;
+        if (!wantCorrection) return;
+        const uint8_t *hm = c->fixedVars.empty() ? nullptr : c->hFixedMask.data();
+        for (int a = 0; a < std::min(na, 2); ++a)
+            for (int64_t i = 0; f[a] && i < c->modal.n && !nonZero[a]; ++i) nonZero[a] = f[a][i] != 0.0 && !(hm && hm[i]);
+        correction_solves(c, who, na, f, nonZero, us, rtol, maxit, staticSolves, staticIts, infoSolves, infoIts);
+    }
+    void stage(mfh_ctx *c, const char *who, const double *const f[]) {
+        require_basis(c, who);
+        const int64_t n = c->modal.n, ld = c->modal.ld;
+        dF.alloc((size_t)ld * na);
+        dF.zero(c->stream);
+        for (int a = 0; a < na; ++a) {
+            if (f[a]) upload(dF.p + (int64_t)a * ld, f[a], n, c->stream);
+            if (!c->fixedVars.empty()) k::launch_mask(n, c->dFixedMask.p, dF.p + (int64_t)a * ld, c->stream);
+        }
+    }
+    void project(mfh_ctx *c) {
+        const mfh_ctx::ModalBasis &mb = c->modal;
+        g.resize((size_t)mb.nModes * na);
+        gram_against(c, mb.B.p, mb.ld, mb.nModes, dF.p, mb.ld, na, 0.0, g.data());
+        corr = staticSolves > 0;
+        nb = corr ? mb.nModes + na : mb.nModes;
+        if (corr) correction_columns(c, mb.B.p, mb.n, mb.ld, mb.nModes, na, us, nonZero, g.data(), mb.lambda.data(), dC, dTmp, c->stream);
+    }
+};
+
+void prepare_modal_loads(mfh_ctx *c, const char *who, ModalLoads &L, int na, const double *const f[], bool wantCorrection, double rtol, int maxit, int32_t *infoSolves,
+                         int32_t *infoIts) {
+    L.solve(c, who, na, f, wantCorrection, rtol, maxit, infoSolves, infoIts);
+    if (!c->fixedVars.empty()) ensure_fixed_uploaded(c);
+    L.stage(c, who, f);
+    L.project(c);
+    if (L.corr) MFH_HIP(hipStreamSynchronize(c->stream));
+}
+
+// the probe rows of the nb columns of B, k_modal_gather_rows' layout; synchronises (probeVars is the caller's)
+void gather_probe_rows(const double *B, int64_t ld, int nb, const int64_t *probeVars, int nProbe, DBuf<double> &dBp, int64_t ldp, hipStream_t s) {
+    DBuf<int64_t> dProbeVars;
+    dProbeVars.alloc((size_t)nProbe);
+    MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    dBp.alloc((size_t)ldp * nb);
+    dBp.zero(s);
+    hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, nProbe, nb, (const int64_t *)dProbeVars.p, B, ld, dBp.p, ldp);
+    CHECK_LAUNCH();
+    MFH_HIP(hipStreamSynchronize(s));
+}
+
+// ---- what the entry points refuse alike, each under its own name
+void check_damping(const char *who, double aR, double bR) {
+    require_for(aR >= 0.0 && bR >= 0.0 && std::isfinite(aR) && std::isfinite(bR), MFH_ERR_INVALID, who, "the Rayleigh coefficients are not negative");
+}
+void check_damping(const char *who, double aR, double bR, double eta) {
+    check_damping(who, aR, bR);
+    require_for(eta >= 0.0 && std::isfinite(eta), MFH_ERR_INVALID, who, "the loss factor is not negative");
+}
+void check_modal_damping(const char *who, const double *zeta, int m) {
+    if (zeta)
+        for (int j = 0; j < m; ++j) require_for(std::isfinite(zeta[j]) && zeta[j] >= 0.0, MFH_ERR_INVALID, who, "a damping ratio is negative or not finite");
+}
+void check_probes(const mfh_ctx *c, const char *who, const int64_t *probeVars, int32_t nProbe, const void *out) {
+    require_for(nProbe >= 0 && (nProbe == 0 || (probeVars && out)), MFH_ERR_INVALID, who, "probes need their variables and their output");
+    const int64_t nv = (int64_t)c->bs() * c->nDoF;
+    for (int32_t j = 0; j < nProbe; ++j) require_for(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, who, "probe variable out of range");
+}
+// a correction is K u = f solved: K definite (fixed variables), and the modes' share g_j / lambda_j taken out of it
+void check_correctable(const mfh_ctx *c, const char *who) {
+    require_for(!c->fixedVars.empty(), MFH_ERR_UNSUPPORTED, who, "the static correction needs fixed variables (K alone is singular)");
+    for (double l : c->modal.lambda) require_for(l > 0.0, MFH_ERR_INVALID, who, "the static correction needs lambda_j > 0");
+}
+
 void check_sweep_params(const mfh_ctx *c, const mfh_modal_harmonic_params *p, const double *omega, const double *zeta, const double *fRe, const int64_t *probeVars,
                         int32_t nProbe, const double *probeOut) {
     require(p != nullptr, MFH_ERR_INVALID, "mfh_modal_harmonic: params is null");
     require(p->nFreq >= 0 && p->maxit > 0, MFH_ERR_INVALID, "mfh_modal_harmonic: nFreq >= 0, maxit > 0");
-    require(p->rayleighMass >= 0.0 && p->rayleighStiff >= 0.0 && std::isfinite(p->rayleighMass) && std::isfinite(p->rayleighStiff), MFH_ERR_INVALID,
-            "mfh_modal_harmonic: the Rayleigh coefficients are not negative");
-    require(p->lossFactor >= 0.0 && std::isfinite(p->lossFactor), MFH_ERR_INVALID, "mfh_modal_harmonic: the loss factor is not negative");
+    check_damping("mfh_modal_harmonic", p->rayleighMass, p->rayleighStiff, p->lossFactor);
     require(p->rtol > 0.0 && p->rtol < 1.0, MFH_ERR_INVALID, "mfh_modal_harmonic: 0 < rtol < 1");
     require((p->flags & ~(MFH_MODAL_STATIC_CORRECTION | MFH_MODAL_RESIDUALS)) == 0, MFH_ERR_INVALID, "mfh_modal_harmonic: unknown flag");
     require(p->residualStride >= 0, MFH_ERR_INVALID, "mfh_modal_harmonic: residualStride >= 0");
@@ -532,12 +644,9 @@ void check_sweep_params(const mfh_ctx *c, const mfh_modal_harmonic_params *p, co
         require(std::isfinite(omega[k2]) && omega[k2] >= 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: a frequency is negative or not finite");
         require(omega[k2] > 0.0 || !c->fixedVars.empty(), MFH_ERR_INVALID, "mfh_modal_harmonic: omega = 0 needs fixed variables (K alone is singular)");
     }
-    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeOut)), MFH_ERR_INVALID, "mfh_modal_harmonic: probes need their variables and their output");
-    const int64_t nv = (int64_t)c->bs() * c->nDoF;
-    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_harmonic: probe variable out of range");
+    check_probes(c, "mfh_modal_harmonic", probeVars, nProbe, probeOut);
     require(!((p->flags & MFH_MODAL_RESIDUALS) && zeta), MFH_ERR_INVALID, "mfh_modal_harmonic: per-mode damping has no operator to take a residual against");
-    if (zeta)
-        for (int j = 0; j < c->modal.nModes; ++j) require(std::isfinite(zeta[j]) && zeta[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: a damping ratio is negative or not finite");
+    check_modal_damping("mfh_modal_harmonic", zeta, c->modal.nModes);
 }
 
 // ---- the transient driver, shared by mfh_modal_transient and its hook. Everything on the device; the host arrays are outputs (null: not wanted).
@@ -618,6 +727,28 @@ std::vector<double> coef_table(int m, const double *coef8) {
     return t;
 }
 
+// The tables and the state of a run on the device: the coefficient table, g, lambda (null: no energies asked), the rows of the amplitude and the state
+// {q, qdot} packed 2 x MODAL_MAXM (q null: rest). unpack brings the state after the run back.
+struct MarchTables {
+    DBuf<double> dCoef, dG, dLam, dAmp, dState;
+    std::vector<double> hs;
+    MarchTables(int m, const double *coef8, const double *g, const double *lam, const double *amp, int64_t rows, const double *q, const double *qdot, hipStream_t s)
+        : hs((size_t)2 * k::MODAL_MAXM, 0.0) {
+        dCoef.upload(coef_table(m, coef8), s);
+        dG.upload(g, (size_t)m, s);
+        if (lam) dLam.upload(lam, (size_t)m, s);
+        dAmp.upload(amp, (size_t)rows, s);
+        if (q) { std::copy(q, q + m, hs.begin()); std::copy(qdot, qdot + m, hs.begin() + k::MODAL_MAXM); }
+        dState.upload(hs, s);
+    }
+    void point(MarchRun &R) const { R.coef = dCoef.p; R.g = dG.p; R.lam = dLam.p; R.amp = dAmp.p; R.state = dState.p; }
+    void unpack(int m, double *q, double *qdot, hipStream_t s) {
+        dState.download(hs.data(), hs.size(), s);
+        std::copy(hs.begin(), hs.begin() + m, q);
+        std::copy(hs.begin() + k::MODAL_MAXM, hs.begin() + k::MODAL_MAXM + m, qdot);
+    }
+};
+
 using BasisFill = std::function<void(double *, int64_t, hipStream_t)>;
 void install_basis(mfh_ctx *c, const char *who, int32_t nModes, const double *lambda, double density, mfh_modal_basis_info *info, const BasisFill &fill);
 
@@ -637,8 +768,7 @@ mfh_status mfh_modal_transient(mfh_ctx *c, const mfh_modal_transient_params *prm
     const mfh_modal_transient_params P = *prm;
     require(P.dt > 0.0 && std::isfinite(P.dt), MFH_ERR_INVALID, "mfh_modal_transient: dt > 0");
     require(P.nSteps >= 0 && P.snapshotStride >= 0 && P.maxit >= 0 && nProbe >= 0, MFH_ERR_INVALID, "mfh_modal_transient: a count or the stride is negative");
-    require(P.rayleighMass >= 0.0 && P.rayleighStiff >= 0.0 && std::isfinite(P.rayleighMass) && std::isfinite(P.rayleighStiff), MFH_ERR_INVALID,
-            "mfh_modal_transient: the Rayleigh coefficients are not negative");
+    check_damping("mfh_modal_transient", P.rayleighMass, P.rayleighStiff);
     require((P.flags & ~(MFH_MODAL_TR_STATIC_CORRECTION | MFH_MODAL_TR_ENERGIES)) == 0, MFH_ERR_INVALID, "mfh_modal_transient: unknown flag");
     require(chunk_ok(P.chunkSteps), MFH_ERR_INVALID, "mfh_modal_transient: chunkSteps is 0 or a positive multiple of 32");
     require((q == nullptr) == (qdot == nullptr), MFH_ERR_INVALID, "mfh_modal_transient: q and qdot come together");
@@ -647,23 +777,15 @@ mfh_status mfh_modal_transient(mfh_ctx *c, const mfh_modal_transient_params *prm
     require(!correct || (P.rtol > 0.0 && P.rtol < 1.0 && P.maxit > 0), MFH_ERR_INVALID, "mfh_modal_transient: the static solve needs 0 < rtol < 1, maxit > 0");
     require(f != nullptr, MFH_ERR_INVALID, "mfh_modal_transient: f is null");
     require(!snapshots || P.snapshotStride > 0, MFH_ERR_INVALID, "mfh_modal_transient: snapshots need snapshotStride > 0");
-    require(nProbe == 0 || (probeVars && probeOut), MFH_ERR_INVALID, "mfh_modal_transient: probes need their variables and their output");
-    const int64_t nv = (int64_t)c->bs() * c->nDoF;
-    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_transient: probe variable out of range");
+    check_probes(c, "mfh_modal_transient", probeVars, nProbe, probeOut);
     if (amplitude) require(all_finite(amplitude, (int64_t)P.nSteps + 1), MFH_ERR_INVALID, "mfh_modal_transient: an amplitude is not finite");
-    if (modalDamping)       // (a basis of another length is caught below; the entries a basis could have are at most MODAL_MAXM)
-        for (int j = 0; j < c->modal.nModes; ++j)
-            require(std::isfinite(modalDamping[j]) && modalDamping[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_transient: a damping ratio is negative or not finite");
+    check_modal_damping("mfh_modal_transient", modalDamping, c->modal.nModes);       // (a basis of another length is caught below; the entries a basis could have are at most MODAL_MAXM)
     prepare_pencil(c, "mfh_modal_transient");
     require_basis(c, "mfh_modal_transient");
-    const bool masked = !c->fixedVars.empty();
     const int m = c->modal.nModes;
     const int64_t n = c->modal.n, ld = c->modal.ld;
     const std::vector<double> lam = c->modal.lambda;
-    if (correct) {
-        require(masked, MFH_ERR_UNSUPPORTED, "mfh_modal_transient: the static correction needs fixed variables (K alone is singular)");
-        for (int j = 0; j < m; ++j) require(lam[(size_t)j] > 0.0, MFH_ERR_INVALID, "mfh_modal_transient: the static correction needs lambda_j > 0");
-    }
+    if (correct) check_correctable(c, "mfh_modal_transient");
     require(all_finite(f, n), MFH_ERR_INVALID, "mfh_modal_transient: the load has an entry that is not finite");
     if (q) require(all_finite(q, m) && all_finite(qdot, m), MFH_ERR_INVALID, "mfh_modal_transient: the start state has an entry that is not finite");
     // the eight coefficients per mode, on the host
@@ -675,109 +797,37 @@ mfh_status mfh_modal_transient(mfh_ctx *c, const mfh_modal_transient_params *prm
     }
     hipStream_t s = c->stream;
     c->modalNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modalNote.empty()) c->modalNote += "; "; c->modalNote += t; };
     EventTimer tsetup(s);
 
-    // ---- the static solve, as mfh_modal_harmonic makes it (real plane only)
-    int staticSolves = 0, staticIts = 0;
-    std::vector<double> us;
-    bool loaded = false;
-    {
-        const uint8_t *hm = masked ? c->hFixedMask.data() : nullptr;
-        for (int64_t i = 0; i < n && !loaded; ++i) loaded = f[i] != 0.0 && !(hm && hm[i]);
-    }
-    if (correct && loaded) {
-        ensure_precond(c);
-        ensure_coarse_levels(c, 1);
-        require(c->sym.nRows == c->sym.nCols, MFH_ERR_UNSUPPORTED, "mfh_modal_transient: unpartitioned contexts only");
-        require_basis(c, "mfh_modal_transient");
-        us.resize((size_t)n);
-        mfh_solve_info li{};
-        const bool savedHom = c->solveHomogeneous;
-        c->solveHomogeneous = c->anyFixedNonzero;
-        try { solve_one(c, f, us.data(), P.rtol, P.maxit, &li); }
-        catch (...) { c->solveHomogeneous = savedHom; throw; }
-        c->solveHomogeneous = savedHom;
-        staticSolves = 1;
-        staticIts = li.iterations;
-        if (info) { info->staticSolves = staticSolves; info->staticIterations = staticIts; }
-        if (!li.converged) throw Error(MFH_ERR_NOT_CONVERGED, "mfh_modal_transient: the static solve of the correction did not reach rtol within maxit iterations");
-    }
-    if (masked) ensure_fixed_uploaded(c);
-    require_basis(c, "mfh_modal_transient");
-    double *const B = c->modal.B.p;
-
-    // ---- g = Phi^T f
-    DBuf<double> dF;
-    dF.alloc((size_t)ld);
-    dF.zero(s);
-    upload(dF.p, f, n, s);
-    if (masked) k::launch_mask(n, c->dFixedMask.p, dF.p, s);
-    std::vector<double> g((size_t)m);
-    gram_against(c, B, ld, m, dF.p, ld, 1, 0.0, g.data());
-
-    // ---- r_s = u_s - sum_j phi_j g_j / lambda_j into the first reserved column, through the expansion kernel (mfh_modal_harmonic's, real plane)
-    const int nb = staticSolves ? m + 1 : m;
-    if (staticSolves) {
-        DBuf<double> dC, dTmp;
-        MFH_HIP(hipMemsetAsync(B + (int64_t)m * ld, 0, (size_t)ld * 2 * sizeof(double), s));
-        upload(B + (int64_t)m * ld, us.data(), n, s);
-        k::launch_mask(n, c->dFixedMask.p, B + (int64_t)m * ld, s);
-        const int ldc = 64;
-        std::vector<double> hc((size_t)nb * ldc, 0.0);
-        for (int j = 0; j < m; ++j) hc[(size_t)j * ldc] = -(g[(size_t)j] / lam[(size_t)j]);
-        hc[(size_t)m * ldc] = 1.0;
-        dC.upload(hc, s);
-        dTmp.alloc((size_t)ld);
-        dTmp.zero(s);
-        k::launch_modal_expand(n, B, ld, nb, dC.p, ldc, 1, k::MODAL_NP, dTmp.p, ld, s);
-        MFH_HIP(hipMemcpyAsync(B + (int64_t)m * ld, dTmp.p, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, s));
-        MFH_HIP(hipStreamSynchronize(s));
-        note("static correction: 1 solve of K u = f, " + std::to_string(staticIts) + " iterations");
-    }
+    // ---- the load: g = Phi^T f and, with a correction, r_s = u_s - sum_j phi_j g_j / lambda_j in the first reserved column (the second one zero:
+    // the m + 1 columns streamed from here on leave it out)
+    ModalLoads L;
+    prepare_modal_loads(c, "mfh_modal_transient", L, 1, &f, correct, P.rtol, P.maxit, info ? &info->staticSolves : nullptr, info ? &info->staticIterations : nullptr);
+    if (L.corr) modal_note(c, "static correction: 1 solve of K u = f, " + std::to_string(L.staticIts) + " iterations");
+    const double *const B = c->modal.B.p;
+    const int nb = L.nb;
 
     // ---- the probe rows of B, gathered once
     DBuf<double> dBp;
-    DBuf<int64_t> dProbeVars;
     const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
-    if (nProbe) {
-        dProbeVars.alloc((size_t)nProbe);
-        MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        dBp.alloc((size_t)ldp * nb);
-        dBp.zero(s);
-        hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, (int)nProbe, nb, (const int64_t *)dProbeVars.p, (const double *)B, ld,
-                           dBp.p, ldp);
-        CHECK_LAUNCH();
-        MFH_HIP(hipStreamSynchronize(s));       // (probeVars is the caller's)
-    }
+    if (nProbe) gather_probe_rows(B, ld, nb, probeVars, nProbe, dBp, ldp, s);
 
     // ---- tables and state
-    DBuf<double> dCoef, dG, dLam, dAmp, dState;
-    dCoef.upload(coef_table(m, coef8.data()), s);
-    dG.upload(g, s);
-    dLam.upload(lam, s);
     std::vector<double> ones;
     if (!amplitude) ones.assign((size_t)P.nSteps + 1, 1.0);
-    dAmp.upload(amplitude ? amplitude : ones.data(), (size_t)P.nSteps + 1, s);
-    std::vector<double> hs((size_t)2 * k::MODAL_MAXM, 0.0);
-    if (q) { std::copy(q, q + m, hs.begin()); std::copy(qdot, qdot + m, hs.begin() + k::MODAL_MAXM); }
-    dState.upload(hs, s);
+    MarchTables T(m, coef8.data(), L.g.data(), lam.data(), amplitude ? amplitude : ones.data(), (int64_t)P.nSteps + 1, q, qdot, s);
     const double setupMs = tsetup.stop();
 
     MarchRun R;
     R.m = m; R.nSteps = P.nSteps; R.chunk = P.chunkSteps ? P.chunkSteps : k::MT_CHUNK; R.dt = P.dt;
-    R.coef = dCoef.p; R.g = dG.p; R.lam = dLam.p; R.amp = dAmp.p; R.state = dState.p;
-    R.Bp = dBp.p; R.ldp = ldp; R.nProbe = nProbe; R.corr = staticSolves != 0;
+    T.point(R);
+    R.Bp = dBp.p; R.ldp = ldp; R.nProbe = nProbe; R.corr = L.corr;
     R.probeOut = probeOut; R.modalCoords = modalCoords; R.energies = energies;
     R.stride = P.snapshotStride; R.B = B; R.ld = ld; R.n = n; R.nb = nb; R.snapshots = snapshots;
     run_march(s, R);
-    if (q) {
-        dState.download(hs.data(), hs.size(), s);
-        std::copy(hs.begin(), hs.begin() + m, q);
-        std::copy(hs.begin() + k::MODAL_MAXM, hs.begin() + k::MODAL_MAXM + m, qdot);
-    }
+    if (q) T.unpack(m, q, qdot, s);
     if (info) {
-        info->stepsDone = P.nSteps; info->staticSolves = staticSolves; info->staticIterations = staticIts;
+        info->stepsDone = P.nSteps; info->staticSolves = L.staticSolves; info->staticIterations = L.staticIts;
         info->chunkSteps = R.chunk; info->chunks = R.chunks;
         info->setupMs = setupMs; info->marchMs = R.marchMs; info->seriesMs = R.seriesMs; info->expandMs = R.expandMs;
         info->note = c->modalNote.c_str();
@@ -797,30 +847,21 @@ mfh_status mfh_debug_modal_march(mfh_ctx *c, int32_t nModes, const double *coef8
     hipStream_t s = c->stream;
     const int m = nModes, nb = m + corr;
     const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
-    DBuf<double> dCoef, dG, dLam, dAmp, dState, dBp;
-    dCoef.upload(coef_table(m, coef8), s);
-    dG.upload(g, (size_t)m, s);
-    if (lambda) dLam.upload(lambda, (size_t)m, s);
-    dAmp.upload(amplitude, (size_t)nSteps + 1, s);
-    std::vector<double> hs((size_t)2 * k::MODAL_MAXM, 0.0);
-    std::copy(q, q + m, hs.begin());
-    std::copy(qdot, qdot + m, hs.begin() + k::MODAL_MAXM);
-    dState.upload(hs, s);
+    MarchTables T(m, coef8, g, lambda, amplitude, (int64_t)nSteps + 1, q, qdot, s);
+    DBuf<double> dBp;
     if (nProbe) {          // Bp: nb rows of nProbe (row j = column j of the basis at the probe variables)
         dBp.alloc((size_t)ldp * nb);
         dBp.zero(s);
-        MFH_HIP(hipMemcpy2DAsync(dBp.p, (size_t)ldp * sizeof(double), Bp, (size_t)nProbe * sizeof(double), (size_t)nProbe * sizeof(double), (size_t)nb, hipMemcpyHostToDevice, s));
+        upload_columns(dBp.p, ldp, Bp, nProbe, nb, s);
         MFH_HIP(hipStreamSynchronize(s));
     }
     MarchRun R;
     R.m = m; R.nSteps = nSteps; R.chunk = chunkSteps ? chunkSteps : k::MT_CHUNK; R.dt = dt;
-    R.coef = dCoef.p; R.g = dG.p; R.lam = dLam.p; R.amp = dAmp.p; R.state = dState.p;
+    T.point(R);
     R.Bp = dBp.p; R.ldp = ldp; R.nProbe = nProbe; R.corr = corr != 0;
     R.probeOut = probeOut; R.modalCoords = modalCoords; R.energies = energies;
     run_march(s, R);
-    dState.download(hs.data(), hs.size(), s);
-    std::copy(hs.begin(), hs.begin() + m, q);
-    std::copy(hs.begin() + k::MODAL_MAXM, hs.begin() + k::MODAL_MAXM + m, qdot);
+    T.unpack(m, q, qdot, s);
     MFH_CATCH(c)
 }
 
@@ -865,9 +906,7 @@ mfh_status mfh_modal_set_basis(mfh_ctx *c, int32_t nModes, const double *lambda,
     prepare_pencil(c, "mfh_modal_set_basis");
     const int64_t n = (int64_t)c->bs() * c->nDoF;
     require(all_finite(X, (int64_t)nModes * n), MFH_ERR_INVALID, "mfh_modal_set_basis: a mode has an entry that is not finite");
-    install_basis(c, "mfh_modal_set_basis", nModes, lambda, density, info, [&](double *B, int64_t ld, hipStream_t s) {
-        MFH_HIP(hipMemcpy2DAsync(B, (size_t)ld * sizeof(double), X, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nModes, hipMemcpyHostToDevice, s));
-    });
+    install_basis(c, "mfh_modal_set_basis", nModes, lambda, density, info, [&](double *B, int64_t ld, hipStream_t s) { upload_columns(B, ld, X, n, nModes, s); });
     MFH_CATCH(c)
 }
 
@@ -958,8 +997,7 @@ mfh_status mfh_modal_coordinates(mfh_ctx *c, const double *u, int32_t nVec, doub
     std::vector<double> G((size_t)m * k::MG_TV);
     for (int v0 = 0; v0 < nVec; v0 += k::MG_TV) {
         const int nv = std::min(k::MG_TV, nVec - v0);
-        MFH_HIP(hipMemcpy2DAsync(du.p, (size_t)mb.ld * sizeof(double), u + (size_t)v0 * (size_t)mb.n, (size_t)mb.n * sizeof(double), (size_t)mb.n * sizeof(double), (size_t)nv,
-                                 hipMemcpyHostToDevice, s));
+        upload_columns(du.p, mb.ld, u + (size_t)v0 * (size_t)mb.n, mb.n, nv, s);
         gram_against(c, mb.B.p, mb.ld, m, du.p, mb.ld, nv, mb.density, G.data());
         for (int j = 0; j < nv; ++j)
             for (int i = 0; i < m; ++i) q[(size_t)(v0 + j) * m + i] = G[(size_t)i * nv + j];
@@ -983,59 +1021,41 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
     const int64_t n = c->modal.n, ld = c->modal.ld;
     const std::vector<double> lam = c->modal.lambda;
     const double density = c->modal.density;
-    if (correct) {
-        require(masked, MFH_ERR_UNSUPPORTED, "mfh_modal_harmonic: the static correction needs fixed variables (K alone is singular)");
-        for (int j = 0; j < m; ++j) require(lam[(size_t)j] > 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: the static correction needs lambda_j > 0");
-    }
+    if (correct) check_correctable(c, "mfh_modal_harmonic");
     // the denominators: nModes x nFreq complex scalars, refused before any device work where one is zero
     std::vector<Cplx> dinv((size_t)std::max(nFreq, 1) * m);
     for (int k2 = 0; k2 < nFreq; ++k2) {
         const double w = omega[k2];
-        const Cplx zK{1.0, P.lossFactor + w * P.rayleighStiff};
         for (int j = 0; j < m; ++j) {
             const double l = lam[(size_t)j];
             require(w > 0.0 || l > 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: omega = 0 with a zero eigenvalue in the basis");
-            const Cplx d{l * zK.re - w * w, l * zK.im + w * P.rayleighMass + (modalDamping ? 2.0 * modalDamping[j] * std::sqrt(l) * w : 0.0)};
+            const Cplx d = modal_d(l, w, P.rayleighMass, P.rayleighStiff, P.lossFactor, modalDamping ? modalDamping[j] : 0.0);
             require(d.re != 0.0 || d.im != 0.0, MFH_ERR_INVALID, "mfh_modal_harmonic: an undamped frequency sits on an eigenfrequency of the basis (d_j = 0)");
-            dinv[(size_t)k2 * m + j] = cdivh(Cplx{1.0, 0.0}, d);
+            dinv[(size_t)k2 * m + j] = crecip(d);
         }
     }
     hipStream_t s = c->stream;
     c->modalNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modalNote.empty()) c->modalNote += "; "; c->modalNote += t; };
     EventTimer tsetup(s);
 
     // ---- the static solves, as mfh_solve makes them (outside the WideGuard: the context's own storage, solver and preconditioner)
-    int staticSolves = 0, staticIts = 0;
-    std::vector<double> us[2];
-    bool planeNonZero[2] = {false, false};
-    const double *fPlane[2] = {fRe, fIm};
-    for (int pl = 0; pl < 2; ++pl) {
-        if (!fPlane[pl]) continue;
-        const uint8_t *hm = masked ? c->hFixedMask.data() : nullptr;
-        for (int64_t i = 0; i < n && !planeNonZero[pl]; ++i) planeNonZero[pl] = fPlane[pl][i] != 0.0 && !(hm && hm[i]);
-    }
-    if (correct)
-        correction_solves(c, "mfh_modal_harmonic", 2, fPlane, planeNonZero, us, P.rtol, P.maxit, staticSolves, staticIts, info ? &info->staticSolves : nullptr,
-                          info ? &info->staticIterations : nullptr);
+    ModalLoads L;
+    const double *const fPlane[2] = {fRe, fIm};
+    L.solve(c, "mfh_modal_harmonic", 2, fPlane, correct, P.rtol, P.maxit, info ? &info->staticSolves : nullptr, info ? &info->staticIterations : nullptr);
 
     std::optional<WideGuard> guard;        // (the operator product of the residuals alone needs both triangles: a sweep without them leaves the storage alone)
     if (wantRes) {
         guard.emplace(c);
-        if (guard->widened) note("the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
+        if (guard->widened) modal_note(c, "the pattern held the upper triangle only: symbolic phase re-run with both triangles (what option matrix_storage 0 does) for this call");
         prepare_pencil_state(c, "mfh_modal_harmonic", false);
-        if (c->harmTwoPass) note("mass product of the residuals: two real passes and a combine kernel (option harmonic_two_pass)");
+        if (c->harmTwoPass) modal_note(c, "mass product of the residuals: two real passes and a combine kernel (option harmonic_two_pass)");
     } else if (masked) ensure_fixed_uploaded(c);
-    require_basis(c, "mfh_modal_harmonic");
-    double *const B = c->modal.B.p;
 
     // ---- the load, its modal coordinates g = Phi^T f^ and its norm
-    DBuf<double> dF, dPart, dScal;
-    dF.alloc((size_t)ld * 2);
-    dF.zero(s);
-    upload(dF.p, fRe, n, s);
-    if (fIm) upload(dF.p + ld, fIm, n, s);
-    if (masked) { k::launch_mask(n, c->dFixedMask.p, dF.p, s); k::launch_mask(n, c->dFixedMask.p, dF.p + ld, s); }
+    L.stage(c, "mfh_modal_harmonic", fPlane);
+    const double *const B = c->modal.B.p;
+    const DBuf<double> &dF = L.dF;
+    DBuf<double> dPart, dScal;
     dPart.alloc((size_t)k::DYN_GRID_CAP * k::DYN_NV);
     dScal.alloc((size_t)std::max(nFreq, 1) + 1);
     dScal.zero(s);
@@ -1047,29 +1067,18 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
     MFH_HIP(hipMemcpyAsync(&hbb, dScal.p + nFreq, sizeof(double), hipMemcpyDeviceToHost, s));
     MFH_HIP(hipStreamSynchronize(s));
     require(std::isfinite(hbb), MFH_ERR_INVALID, "mfh_modal_harmonic: the load has an entry that is not finite");
-    std::vector<double> g((size_t)m * 2);
-    gram_against(c, B, ld, m, dF.p, ld, 2, 0.0, g.data());        // g[2 j + plane]
-
-    const int nb = staticSolves ? m + 2 : m;       // the two correction columns are streamed only where they hold something
-    // ---- the static correction r_s = u_s - sum_j phi_j g_j / lambda_j into the two reserved columns, through the expansion kernel itself
-    DBuf<double> dC, dTmp;
-    if (staticSolves) {
-        correction_columns(c, B, n, ld, m, 2, us, planeNonZero, g.data(), lam.data(), dC, dTmp, s);
-        note("static correction: " + std::to_string(staticSolves) + " solve(s) of K u = f, " + std::to_string(staticIts) + " iterations");
-    }
+    // ---- g[2 j + plane], and the static correction r_s = u_s - sum_j phi_j g_j / lambda_j in the two reserved columns, streamed (nb = m + 2) only
+    // where they hold something
+    L.project(c);
+    const std::vector<double> &g = L.g;
+    const int nb = L.nb;
+    if (L.corr) modal_note(c, "static correction: " + std::to_string(L.staticSolves) + " solve(s) of K u = f, " + std::to_string(L.staticIts) + " iterations");
 
     // ---- probes: the rows of B at the probe variables, gathered once
-    DBuf<double> dBp, dProbe;
-    DBuf<int64_t> dProbeVars;
+    DBuf<double> dBp, dProbe, dC;
     const int64_t ldp = ((int64_t)nProbe + 31) / 32 * 32;
     if (nProbe && nFreq) {
-        dProbeVars.alloc((size_t)nProbe);
-        MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        dBp.alloc((size_t)ldp * nb);
-        dBp.zero(s);
-        hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, (int)nProbe, nb, (const int64_t *)dProbeVars.p, (const double *)B, ld,
-                           dBp.p, ldp);
-        CHECK_LAUNCH();
+        gather_probe_rows(B, ld, nb, probeVars, nProbe, dBp, ldp, s);
         dProbe.alloc((size_t)nFreq * 2 * (size_t)nProbe);
     }
 
@@ -1088,7 +1097,7 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
             if (groupCap <= rowsIn256MB) throw;
             groupCap = (int)rowsIn256MB;
             dStage.alloc((size_t)std::min(groupCap, nFreq) * (size_t)rowLen);
-            note("no device memory for the staging rows of a full pass: groups of " + std::to_string(groupCap) + " frequency(ies)");
+            modal_note(c, "no device memory for the staging rows of a full pass: groups of " + std::to_string(groupCap) + " frequency(ies)");
         }
     }
     const int ldc = 2 * groupCap + k::MODAL_NP_MAX;
@@ -1112,8 +1121,8 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
                 hc[(size_t)j * ldc + 2 * kk + 1] = q.im;
                 if (modalCoords) { modalCoords[((size_t)k2 * m + j) * 2] = q.re; modalCoords[((size_t)k2 * m + j) * 2 + 1] = q.im; }
             }
-            if (staticSolves) {       // the real 2 x 2 form of 1 / zK on the two correction rows
-                const Cplx iz = cdivh(Cplx{1.0, 0.0}, Cplx{1.0, P.lossFactor + w * P.rayleighStiff});
+            if (L.corr) {       // the real 2 x 2 form of 1 / zK on the two correction rows
+                const Cplx iz = inv_zK(w, P.rayleighStiff, P.lossFactor);
                 hc[(size_t)m * ldc + 2 * kk] = iz.re;       hc[(size_t)(m + 1) * ldc + 2 * kk] = -iz.im;
                 hc[(size_t)m * ldc + 2 * kk + 1] = iz.im;   hc[(size_t)(m + 1) * ldc + 2 * kk + 1] = iz.re;
             }
@@ -1163,7 +1172,7 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
     }
     const double solveMs = tsolve.stop();
     if (info) {
-        info->staticSolves = staticSolves; info->staticIterations = staticIts;
+        info->staticSolves = L.staticSolves; info->staticIterations = L.staticIts;
         info->groups = groups; info->planesPerPass = k::MODAL_NP;
         info->worstTrueResidual = worst; info->setupMs = setupMs; info->solveMs = solveMs;
         info->note = c->modalNote.c_str();
@@ -1175,18 +1184,6 @@ mfh_status mfh_modal_harmonic(mfh_ctx *c, const mfh_modal_harmonic_params *prm, 
 }   // extern "C"
 
 namespace {
-
-// the probe rows of the nb columns of B, k_modal_gather_rows' layout; synchronises (probeVars is the caller's)
-void gather_probe_rows(const double *B, int64_t ld, int nb, const int64_t *probeVars, int nProbe, DBuf<double> &dBp, int64_t ldp, hipStream_t s) {
-    DBuf<int64_t> dProbeVars;
-    dProbeVars.alloc((size_t)nProbe);
-    MFH_HIP(hipMemcpyAsync(dProbeVars.p, probeVars, (size_t)nProbe * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    dBp.alloc((size_t)ldp * nb);
-    dBp.zero(s);
-    hipLaunchKernelGGL(k::k_modal_gather_rows, dim3(k::grid_for((int64_t)nProbe * nb)), dim3(256), 0, s, nProbe, nb, (const int64_t *)dProbeVars.p, B, ld, dBp.p, ldp);
-    CHECK_LAUNCH();
-    MFH_HIP(hipStreamSynchronize(s));
-}
 
 struct Factor {
     std::vector<double> F;
@@ -1214,9 +1211,7 @@ mfh_status mfh_modal_quadratic(mfh_ctx *c, int32_t nMat, const double *C, double
     require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_quadratic: null context");
     require(nMat >= 1 && nMat <= 4 && C != nullptr, MFH_ERR_INVALID, "mfh_modal_quadratic: 1 <= nMat <= 4 matrices");
     require(!std::isnan(tol), MFH_ERR_INVALID, "mfh_modal_quadratic: tol is not a number");
-    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeOut)), MFH_ERR_INVALID, "mfh_modal_quadratic: probes need their variables and their output");
-    const int64_t nv = (int64_t)c->bs() * c->nDoF;
-    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_quadratic: probe variable out of range");
+    check_probes(c, "mfh_modal_quadratic", probeVars, nProbe, probeOut);
     prepare_pencil(c, "mfh_modal_quadratic");
     require_basis(c, "mfh_modal_quadratic");
     const int m = c->modal.nModes;
@@ -1261,9 +1256,7 @@ mfh_status mfh_modal_random(mfh_ctx *c, const mfh_modal_random_params *prm, cons
     const mfh_modal_random_params P = *prm;
     require(P.nFreq >= 1 && P.maxit > 0, MFH_ERR_INVALID, "mfh_modal_random: nFreq >= 1, maxit > 0");
     require(P.nLoad >= 1 && P.nLoad <= 8, MFH_ERR_INVALID, "mfh_modal_random: 1 <= nLoad <= 8");
-    require(P.rayleighMass >= 0.0 && P.rayleighStiff >= 0.0 && std::isfinite(P.rayleighMass) && std::isfinite(P.rayleighStiff), MFH_ERR_INVALID,
-            "mfh_modal_random: the Rayleigh coefficients are not negative");
-    require(P.lossFactor >= 0.0 && std::isfinite(P.lossFactor), MFH_ERR_INVALID, "mfh_modal_random: the loss factor is not negative");
+    check_damping("mfh_modal_random", P.rayleighMass, P.rayleighStiff, P.lossFactor);
     require(P.rtol > 0.0 && P.rtol < 1.0, MFH_ERR_INVALID, "mfh_modal_random: 0 < rtol < 1");
     require(!std::isnan(P.tol), MFH_ERR_INVALID, "mfh_modal_random: tol is not a number");
     require((P.flags & ~(MFH_MODAL_RV_STATIC_CORRECTION | MFH_MODAL_RV_VELOCITY | MFH_MODAL_RV_ACCELERATION)) == 0, MFH_ERR_INVALID, "mfh_modal_random: unknown flag");
@@ -1276,66 +1269,31 @@ mfh_status mfh_modal_random(mfh_ctx *c, const mfh_modal_random_params *prm, cons
         require(k2 == 0 || omega[k2] > omega[k2 - 1], MFH_ERR_INVALID, "mfh_modal_random: the frequencies are not ascending");
         require(omega[k2] > 0.0 || !c->fixedVars.empty(), MFH_ERR_INVALID, "mfh_modal_random: omega = 0 needs fixed variables (K alone is singular)");
     }
-    require(nProbe >= 0 && (nProbe == 0 || (probeVars && probeRms)), MFH_ERR_INVALID, "mfh_modal_random: probes need their variables and their output");
+    check_probes(c, "mfh_modal_random", probeVars, nProbe, probeRms);
     require(nProbe > 0 || !probePsd, MFH_ERR_INVALID, "mfh_modal_random: the response spectra belong to probes");
-    const int64_t nv = (int64_t)c->bs() * c->nDoF;
-    for (int32_t j = 0; j < nProbe; ++j) require(probeVars[j] >= 0 && probeVars[j] < nv, MFH_ERR_INVALID, "mfh_modal_random: probe variable out of range");
-    if (modalDamping)
-        for (int j = 0; j < c->modal.nModes; ++j) require(std::isfinite(modalDamping[j]) && modalDamping[j] >= 0.0, MFH_ERR_INVALID, "mfh_modal_random: a damping ratio is negative or not finite");
+    check_modal_damping("mfh_modal_random", modalDamping, c->modal.nModes);
     prepare_pencil(c, "mfh_modal_random");
     require_basis(c, "mfh_modal_random");
-    const bool masked = !c->fixedVars.empty();
     const int m = c->modal.nModes;
     const int64_t n = c->modal.n, ld = c->modal.ld;
     const std::vector<double> lam = c->modal.lambda;
-    if (correct) {
-        require(masked, MFH_ERR_UNSUPPORTED, "mfh_modal_random: the static correction needs fixed variables (K alone is singular)");
-        for (int j = 0; j < m; ++j) require(lam[(size_t)j] > 0.0, MFH_ERR_INVALID, "mfh_modal_random: the static correction needs lambda_j > 0");
-    }
+    if (correct) check_correctable(c, "mfh_modal_random");
     require(all_finite(f, (int64_t)nl * n), MFH_ERR_INVALID, "mfh_modal_random: a load has an entry that is not finite");
     hipStream_t s = c->stream;
     c->modalNote.clear();
-    auto note = [&](const std::string &t) { if (!c->modalNote.empty()) c->modalNote += "; "; c->modalNote += t; };
 
-    // ---- the static solves, as mfh_modal_harmonic makes them: one per load that is not zero off the fixed variables
-    int staticSolves = 0, staticIts = 0;
-    std::vector<double> us[2];
-    bool loadNonZero[2] = {false, false};
-    if (correct) {
-        const uint8_t *hm = c->hFixedMask.data();
-        for (int a = 0; a < nl; ++a)
-            for (int64_t i = 0; i < n && !loadNonZero[a]; ++i) loadNonZero[a] = f[(size_t)a * n + i] != 0.0 && !hm[i];
-    }
-    if (correct) {
-        const double *fLoad[2] = {f, nl > 1 ? f + (size_t)n : nullptr};
-        correction_solves(c, "mfh_modal_random", nl, fLoad, loadNonZero, us, P.rtol, P.maxit, staticSolves, staticIts, info ? &info->staticSolves : nullptr,
-                          info ? &info->staticIterations : nullptr);
-    }
-    if (masked) ensure_fixed_uploaded(c);
-    require_basis(c, "mfh_modal_random");
-    double *const B = c->modal.B.p;
-
-    // ---- g = Phi^T f_a, m x nLoad
-    std::vector<double> g((size_t)m * nl);
-    {
-        DBuf<double> dF;
-        dF.alloc((size_t)ld * nl);
-        dF.zero(s);
-        for (int a = 0; a < nl; ++a) {
-            upload(dF.p + (int64_t)a * ld, f + (size_t)a * n, n, s);
-            if (masked) k::launch_mask(n, c->dFixedMask.p, dF.p + (int64_t)a * ld, s);
-        }
-        gram_against(c, B, ld, m, dF.p, ld, nl, 0.0, g.data());
-    }
-    // ---- r_a = u_a - sum_j phi_j g_ja / lambda_j into the two reserved columns, exactly as mfh_modal_harmonic writes r_re and r_im
-    const bool corr = staticSolves > 0;
-    const int nb = corr ? m + nl : m;
-    if (corr) {
-        DBuf<double> dC, dTmp;
-        correction_columns(c, B, n, ld, m, nl, us, loadNonZero, g.data(), lam.data(), dC, dTmp, s);
-        MFH_HIP(hipStreamSynchronize(s));
-        note("static correction: " + std::to_string(staticSolves) + " solve(s) of K u = f, " + std::to_string(staticIts) + " iterations");
-    } else if (correct) note("static correction: every load is zero off the fixed variables, nothing to correct");
+    // ---- the loads: g = Phi^T f_a (m x nLoad) and, with a correction, one static solve per load that is not zero off the fixed variables and
+    // r_a = u_a - sum_j phi_j g_ja / lambda_j in the two reserved columns
+    ModalLoads L;
+    std::vector<const double *> fLoad((size_t)nl);
+    for (int a = 0; a < nl; ++a) fLoad[(size_t)a] = f + (size_t)a * n;
+    prepare_modal_loads(c, "mfh_modal_random", L, nl, fLoad.data(), correct, P.rtol, P.maxit, info ? &info->staticSolves : nullptr, info ? &info->staticIterations : nullptr);
+    const double *const B = c->modal.B.p;
+    const std::vector<double> &g = L.g;
+    const bool corr = L.corr;
+    const int nb = L.nb;
+    if (corr) modal_note(c, "static correction: " + std::to_string(L.staticSolves) + " solve(s) of K u = f, " + std::to_string(L.staticIts) + " iterations");
+    else if (correct) modal_note(c, "static correction: every load is zero off the fixed variables, nothing to correct");
 
     // ---- the covariances of displacement, velocity and acceleration (host), and their factors
     auto tc = std::chrono::steady_clock::now();
@@ -1394,15 +1352,12 @@ mfh_status mfh_modal_random(mfh_ctx *c, const mfh_modal_random_params *prm, cons
         std::vector<Cplx> H((size_t)nb * nl), hp((size_t)nl);
         for (int k2 = 0; k2 < nFreq; ++k2) {
             const double w = omega[k2];
-            const Cplx zK{1.0, P.lossFactor + w * P.rayleighStiff};
             for (int j = 0; j < m; ++j) {
-                const double l = lam[(size_t)j];
-                const Cplx d{l * zK.re - w * w, l * zK.im + w * P.rayleighMass + (modalDamping ? 2.0 * modalDamping[j] * std::sqrt(l) * w : 0.0)};
-                const Cplx di = cdivh(Cplx{1.0, 0.0}, d);
+                const Cplx di = modal_dinv(lam[(size_t)j], w, P.rayleighMass, P.rayleighStiff, P.lossFactor, modalDamping ? modalDamping[j] : 0.0);
                 for (int a = 0; a < nl; ++a) H[(size_t)j * nl + a] = Cplx{g[(size_t)j * nl + a] * di.re, g[(size_t)j * nl + a] * di.im};
             }
             if (corr) {
-                const Cplx iz = cdivh(Cplx{1.0, 0.0}, zK);
+                const Cplx iz = inv_zK(w, P.rayleighStiff, P.lossFactor);
                 for (int a = 0; a < nl; ++a)
                     for (int b = 0; b < nl; ++b) H[(size_t)(m + a) * nl + b] = a == b ? iz : Cplx{0.0, 0.0};
             }
@@ -1426,7 +1381,7 @@ mfh_status mfh_modal_random(mfh_ctx *c, const mfh_modal_random_params *prm, cons
     }
     if (info) {
         info->nb = nb;
-        info->staticSolves = staticSolves; info->staticIterations = staticIts;
+        info->staticSolves = L.staticSolves; info->staticIterations = L.staticIts;
         info->covarianceMs = covarianceMs; info->factorMs = factorMs; info->solveMs = solveMs;
         info->note = c->modalNote.c_str();
     }
@@ -1456,8 +1411,7 @@ mfh_status mfh_debug_modal_sumsq(mfh_ctx *c, int64_t n, int32_t nb, const double
     if (rank > 0) {
         b.alloc((size_t)ld * nb);
         b.zero(s);
-        const size_t rowBytes = (size_t)n * sizeof(double);
-        MFH_HIP(hipMemcpy2DAsync(b.p, (size_t)ld * sizeof(double), Bh, rowBytes, rowBytes, (size_t)nb, hipMemcpyHostToDevice, s));
+        upload_columns(b.p, ld, Bh, n, nb, s);
     }
     k::SumsqPlan plan;
     plan.build(nb, Fh, rank, rank, piv, planesPerPass ? planesPerPass : k::MODAL_NP, s);
@@ -1534,9 +1488,8 @@ mfh_status mfh_debug_modal_gram(mfh_ctx *c, int64_t n, int32_t na, int32_t nv, c
     const int64_t ld = (n + 31) / 32 * 32;
     DBuf<double> a, v, part, g;
     a.alloc((size_t)ld * na); v.alloc((size_t)ld * nv); part.alloc((size_t)k::MG_GRID_CAP * na * nv); g.alloc((size_t)na * nv);
-    const size_t rowBytes = (size_t)n * sizeof(double), ldBytes = (size_t)ld * sizeof(double);
-    MFH_HIP(hipMemcpy2DAsync(a.p, ldBytes, A, rowBytes, rowBytes, (size_t)na, hipMemcpyHostToDevice, s));
-    MFH_HIP(hipMemcpy2DAsync(v.p, ldBytes, V, rowBytes, rowBytes, (size_t)nv, hipMemcpyHostToDevice, s));
+    upload_columns(a.p, ld, A, n, na, s);
+    upload_columns(v.p, ld, V, n, nv, s);
     k::launch_modal_gram(n, a.p, ld, na, v.p, ld, nv, part.p, g.p, s);
     g.download(G, (size_t)na * nv, s);
     MFH_CATCH(c)
@@ -1553,8 +1506,7 @@ mfh_status mfh_debug_modal_expand(mfh_ctx *c, int64_t n, int32_t nb, const doubl
     DBuf<double> b, cc, o;
     b.alloc((size_t)ld * nb); o.alloc((size_t)nPlanes * (size_t)n);
     b.zero(s);
-    const size_t rowBytes = (size_t)n * sizeof(double);
-    MFH_HIP(hipMemcpy2DAsync(b.p, (size_t)ld * sizeof(double), Bh, rowBytes, rowBytes, (size_t)nb, hipMemcpyHostToDevice, s));
+    upload_columns(b.p, ld, Bh, n, nb, s);
     std::vector<double> hc((size_t)nb * ldc, 0.0);
     for (int j = 0; j < nb; ++j)
         for (int p = 0; p < nPlanes; ++p) hc[(size_t)j * ldc + p] = Ch[(size_t)j * nPlanes + p];
