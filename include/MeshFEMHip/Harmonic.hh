@@ -403,4 +403,114 @@ responseSpectrum(const Sim &sim, int direction, SdFn Sd, const ResponseSpectrumO
     return r;
 }
 
+// ---- RMS stress (mfh_modal_random_stress, mfh_modal_quadratic_stress; docs/design/04_24_modal_stress.md). Per element corner, stressField's layout:
+// vonMises [nElem * NQ] = sqrt(E[sigma_vm^2]) (Segalman: the root of the mean square of the von Mises stress, not its mean), components
+// [nElem * NQ * flatLen] = sqrt(E[sigma_c^2]); NQ = 1 for degree 1 and N + 1 for degree 2.
+struct ModalStressOptions {
+    bool vonMises = true, components = false, strain = false;      // strain: strains instead of stresses
+    int32_t flags() const {
+        return (vonMises ? MFH_MODAL_STRESS_VON_MISES : 0) | (components ? MFH_MODAL_STRESS_COMPONENTS : 0) | (strain ? MFH_MODAL_STRESS_STRAIN : 0);
+    }
+};
+
+struct ModalStressResult {
+    std::vector<Real> vonMises, components;                   // empty where not asked for
+    Real peakVonMises = 0.0;
+    size_t peakElement = 0, peakCorner = 0;
+    std::vector<Real> cov;                                    // modalRandomStress: C^(0), nb x nb row-major
+    std::vector<Real> gamma, a;                               // responseSpectrumStress: participation factors, a_j = gamma_j Sd_j
+    std::vector<Real> lambda;
+    mfh_modal_basis_info basisInfo{};
+    mfh_modal_stress_info info{};
+};
+
+namespace detail {
+template <size_t N, size_t Deg>
+constexpr size_t stressNQ(const LinearElasticity::Simulator<N, Deg> &) { return Deg == 1 ? 1 : N + 1; }
+template <class Sim>
+size_t stressCorners(const Sim &sim) { return sim.numElements() * stressNQ(sim); }
+inline void setStressPeak(ModalStressResult &r, size_t nq) {
+    r.peakVonMises = r.info.peakVonMises[0];
+    r.peakElement = (size_t)r.info.peakCorner[0] / nq;
+    r.peakCorner = (size_t)r.info.peakCorner[0] % nq;
+}
+}   // namespace detail
+
+// the loads, spectrum, basis and damping of modalRandomResponse (its velocity / acceleration / probe options are not used)
+template <class Sim>
+ModalStressResult modalRandomStress(const Sim &sim, const std::vector<Real> &omegas, const std::vector<std::complex<Real>> &S,
+                                    const ModalRandomOptions<typename Sim::VField> &opt = ModalRandomOptions<typename Sim::VField>(),
+                                    const ModalStressOptions &sopt = ModalStressOptions()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value, FL = N * (N + 1) / 2;
+    mfh_ctx *c = sim.ctx();
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N, nFreq = omegas.size(), nLoad = std::max<size_t>(opt.loads.size(), 1);
+    if (S.size() != nFreq * nLoad * nLoad) throw std::runtime_error("modalRandomStress: S needs nFreq x nLoad x nLoad entries");
+    if (!opt.weights.empty() && opt.weights.size() != nFreq) throw std::runtime_error("modalRandomStress: one weight per frequency");
+    ModalStressResult r;
+    detail::setModalBasis(sim, opt, "modalRandomStress", r.lambda, r.basisInfo);
+    const size_t m = r.lambda.size();
+    if (!opt.modalDamping.empty() && opt.modalDamping.size() != m) throw std::runtime_error("modalRandomStress: one damping ratio per mode");
+    std::vector<Real> f(nLoad * n);
+    if (opt.loads.empty()) {
+        const VField l = sim.neumannLoad();
+        std::copy(&l[0][0], &l[0][0] + n, f.begin());
+    } else
+        for (size_t a = 0; a < nLoad; ++a) {
+            if (opt.loads[a].size() != nDoF) throw std::runtime_error("modalRandomStress: a load needs one entry per DoF");
+            std::copy(&opt.loads[a][0][0], &opt.loads[a][0][0] + n, f.begin() + (std::ptrdiff_t)(a * n));
+        }
+    const size_t corners = detail::stressCorners(sim), nbMax = m + 2;
+    r.vonMises.assign(sopt.vonMises ? corners : 0, 0.0);
+    r.components.assign(sopt.components ? corners * FL : 0, 0.0);
+    std::vector<Real> cov(nbMax * nbMax);
+    mfh_modal_random_params prm{};
+    prm.rayleighMass = opt.rayleighMass; prm.rayleighStiff = opt.rayleighStiff; prm.lossFactor = opt.lossFactor;
+    prm.rtol = opt.rtol; prm.tol = opt.tol; prm.maxit = opt.maxit; prm.nFreq = (int32_t)nFreq; prm.nLoad = (int32_t)nLoad;
+    prm.flags = opt.staticCorrection ? MFH_MODAL_RV_STATIC_CORRECTION : 0;
+    check(c, mfh_modal_random_stress(c, &prm, omegas.data(), opt.weights.empty() ? nullptr : opt.weights.data(),
+                                     opt.modalDamping.empty() ? nullptr : opt.modalDamping.data(), f.data(), reinterpret_cast<const Real *>(S.data()),
+                                     sopt.flags(), sopt.vonMises ? r.vonMises.data() : nullptr, sopt.components ? r.components.data() : nullptr, cov.data(),
+                                     &r.info));
+    const size_t nb = (size_t)r.info.nb;
+    r.cov.assign(cov.begin(), cov.begin() + (std::ptrdiff_t)(nb * nb));
+    detail::setStressPeak(r, detail::stressNQ(sim));
+    return r;
+}
+
+// the base motion, a_j = gamma_j Sd_j and the rules of responseSpectrum (its probe / fields options are not used)
+template <class Sim, class SdFn>
+ModalStressResult responseSpectrumStress(const Sim &sim, int direction, SdFn Sd,
+                                         const ResponseSpectrumOptions<typename Sim::VField> &opt = ResponseSpectrumOptions<typename Sim::VField>(),
+                                         const ModalStressOptions &sopt = ModalStressOptions()) {
+    using VField = typename Sim::VField;
+    constexpr size_t N = std::tuple_size<typename VField::value_type>::value, FL = N * (N + 1) / 2;
+    if (direction < 0 || direction >= (int)N) throw std::runtime_error("responseSpectrumStress: direction out of range");
+    mfh_ctx *c = sim.ctx();
+    const size_t nDoF = sim.numDoFs(), n = nDoF * N;
+    ModalStressResult r;
+    detail::setModalBasis(sim, opt, "responseSpectrumStress", r.lambda, r.basisInfo);
+    const size_t m = r.lambda.size();
+    if (!opt.modalDamping.empty() && opt.modalDamping.size() != m) throw std::runtime_error("responseSpectrumStress: one damping ratio per mode");
+    std::vector<Real> zeta = opt.modalDamping.empty() ? std::vector<Real>(m, opt.zeta) : opt.modalDamping;
+    std::vector<Real> rd(n, 0.0);
+    for (size_t i = 0; i < nDoF; ++i) rd[i * N + (size_t)direction] = 1.0;
+    r.gamma.assign(m, 0.0);
+    check(c, mfh_modal_coordinates(c, rd.data(), 1, r.gamma.data()));
+    r.a.assign(m, 0.0);
+    for (size_t j = 0; j < m; ++j) r.a[j] = r.gamma[j] * Sd(std::sqrt(r.lambda[j]), zeta[j]);
+    std::vector<Real> C(m * m, 0.0);
+    if (opt.cqc) check(c, mfh_cqc_matrix((int32_t)m, r.lambda.data(), zeta.data(), C.data()));
+    else for (size_t j = 0; j < m; ++j) C[j * m + j] = 1.0;
+    for (size_t j = 0; j < m; ++j)
+        for (size_t k = 0; k < m; ++k) C[j * m + k] *= r.a[j] * r.a[k];
+    const size_t corners = detail::stressCorners(sim);
+    r.vonMises.assign(sopt.vonMises ? corners : 0, 0.0);
+    r.components.assign(sopt.components ? corners * FL : 0, 0.0);
+    check(c, mfh_modal_quadratic_stress(c, 1, C.data(), opt.tol, sopt.flags(), sopt.vonMises ? r.vonMises.data() : nullptr,
+                                        sopt.components ? r.components.data() : nullptr, &r.info));
+    detail::setStressPeak(r, detail::stressNQ(sim));
+    return r;
+}
+
 } // namespace MeshFEMHip

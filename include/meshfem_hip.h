@@ -890,6 +890,41 @@ mfh_status mfh_modal_random(mfh_ctx* ctx, const mfh_modal_random_params* params,
                             double* cov,                              /* 3 x nb x nb, or NULL */
                             mfh_modal_random_info* info);
 
+/* ---------------------------------------------------------------- modal stress recovery (docs/design/04_24_modal_stress.md)
+ * RMS stress under the loads of mfh_modal_quadratic / mfh_modal_random, per element corner in mfh_stress_measures' layout: [nElem][NQ] (von Mises) and
+ * [nElem][NQ][flatLen] (components, tensor shear), NQ = 1 for degree 1 and dim + 1 for degree 2. With the covariance C = F F^T of the coordinates
+ * (mfh_psd_factor) and the factor fields u_t = B F[:, t], B = [Phi | r_1 | r_2]:
+ *     rmsComponents[c] = sqrt(E[sigma_c^2]) = sqrt(sum_t sigma_c(u_t)^2),
+ *     rmsVonMises      = sqrt(E[sigma_vm^2]) = sqrt(sum_t vm(sigma(u_t))^2)      (Segalman; the 2D value is mfh_stress_measures' plane-stress form).
+ * The von Mises figure is the root of the MEAN SQUARE of the von Mises stress, not the mean E[sigma_vm] (which is not a quadratic form and is smaller).
+ * MFH_MODAL_STRESS_STRAIN: strains instead of stresses. No stress basis is stored: the planes u_t are expanded 32 at a time and dropped.
+ * The squares are absolute (no scaling by the largest entry, unlike mfh_stress_measures): stresses whose squares leave the double range overflow or
+ * flush. What a truncated factorisation leaves out of a corner's variance is at most truncation * 3 * sum_j |s_j|^2, s_j the corner's stress of column
+ * j (3 = the largest eigenvalue of the von Mises form with tensor shear entries); info->truncation reports the trace, as for mfh_modal_quadratic.
+ *   mfh_modal_quadratic_stress   nMat <= 4 matrices over the modes (the SRSS / CQC primitive, C_jk = rho_jk a_j a_k); outputs nMat x ... one after the other.
+ *   mfh_modal_random_stress      sets up exactly as mfh_modal_random (loads, MFH_MODAL_RV_STATIC_CORRECTION in params->flags; the velocity and
+ *                                acceleration flags are MFH_ERR_INVALID), forms C^(0) only (cov: nb x nb, or NULL) and runs the passes over all nb columns.
+ * info->peakVonMises / peakCorner: the largest RMS von Mises value of each matrix and its flat corner index e NQ + q (ties: the lowest index; a NaN first).
+ * Validity, MFH_ERR_STATE on a stale basis and the refusals are those of mfh_modal_quadratic / mfh_modal_random; the elasticity operator on the mesh's
+ * own degree and an unpartitioned context are required (MFH_ERR_UNSUPPORTED); a requested output that is NULL, or flags without VON_MISES | COMPONENTS:
+ * MFH_ERR_INVALID. On any refusal nothing is written. */
+enum { MFH_MODAL_STRESS_VON_MISES = 1, MFH_MODAL_STRESS_COMPONENTS = 2, MFH_MODAL_STRESS_STRAIN = 4 /* strain instead of stress */ };
+typedef struct mfh_modal_stress_info {
+    int32_t ranks[4], passes[4];
+    double truncation[4];
+    double peakVonMises[4];
+    int64_t peakCorner[4];
+    int32_t staticSolves, staticIterations, nb, reserved;
+    double covarianceMs, factorMs, solveMs;                                            /* solveMs: device events around the passes, the peak AND the copies of the outputs to the host */
+    const char* note;                                                                  /* owned by the context, valid until its next call */
+} mfh_modal_stress_info;
+mfh_status mfh_modal_quadratic_stress(mfh_ctx* ctx, int32_t nMat, const double* C /* nMat x nModes x nModes */, double tol, int32_t flags,
+                                      double* rmsVonMises /* nMat x nElem x NQ, or NULL */, double* rmsComponents /* nMat x nElem x NQ x flatLen, or NULL */,
+                                      mfh_modal_stress_info* info);
+mfh_status mfh_modal_random_stress(mfh_ctx* ctx, const mfh_modal_random_params* params, const double* omega, const double* weights,
+                                   const double* modalDamping, const double* f, const double* S, int32_t stressFlags,
+                                   double* rmsVonMises, double* rmsComponents, double* cov /* nb x nb = C^(0), or NULL */, mfh_modal_stress_info* info);
+
 /* ---------------------------------------------------------------- per-element density, the product with M, mass properties
  * (docs/design/04_15_density.md.) The mass matrix of mfh_modes and mfh_newmark is assembled from a density field of the context:
  *     M = sum_e rho_e int_e phi_i phi_j   on displacement vectors (kron with the identity of size dim),   rho = 1 until a field is set.

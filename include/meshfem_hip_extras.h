@@ -138,6 +138,17 @@ mfh_status mfh_debug_modal_sumsq(mfh_ctx* ctx, int64_t n, int32_t nb, const doub
  * nb <= NP) */
 mfh_status mfh_time_modal_sumsq(mfh_ctx* ctx, int64_t n, int32_t nb, int32_t planesPerPass, int32_t reps, double* sumsqMs, double* expandMs,
                                 double* laterMs);
+/* test hook: k_modal_stress_sumsq (mfh_modal_quadratic_stress / mfh_modal_random_stress) on a caller's planes over the context's mesh. U: nPlanes x
+ * dim*nDoF (host, VARIABLE numbering), taken planesPerPass (1 .. 32; 0 = the default) at a time; flags: MFH_MODAL_STRESS_*; vm: nElem x NQ, the sums
+ * over the planes of the squared von Mises value (always written), comp: nElem x NQ x flatLen with MFH_MODAL_STRESS_COMPONENTS; their roots with
+ * sqrtFlag. nPlanes = 0: the kernel's rank-0 launch (no plane) over a scratch filled with NaNs, which writes zeros */
+mfh_status mfh_debug_modal_stress_sumsq(mfh_ctx* ctx, int32_t nPlanes, const double* U, int32_t planesPerPass, int32_t flags, int32_t sqrtFlag,
+                                        double* vm, double* comp);
+/* test hook: k_peak_of_array + k_peak_finish on n host doubles: the largest value and its index (ties: the lowest index; a NaN before every number) */
+mfh_status mfh_debug_peak_of_array(mfh_ctx* ctx, int64_t n, const double* v, double* value, int64_t* index);
+/* device time (ms, one entry per repetition each) of one pass of k_modal_stress_sumsq over nPlanes <= 32 hashed planes and of nPlanes launches of
+ * k_stress_measures (von Mises only) on the same planes, the two taking turns; contexts without a DoF map */
+mfh_status mfh_time_modal_stress(mfh_ctx* ctx, int32_t nPlanes, int32_t reps, double* stressMs, double* measuresMs);
 
 /* test hooks: the step kernels of mfh_newmark (mfh_dynamics.hip) on host arrays of n doubles. mask: n bytes or NULL (non-zero = fixed variable).
  * predict: ut = u + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a (both 0 where masked), w = gamma / (beta dt) ut - vt,

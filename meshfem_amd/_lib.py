@@ -26,6 +26,7 @@ HARM_WARM_START = 1
 MODAL_STATIC_CORRECTION, MODAL_RESIDUALS = 1, 2
 MODAL_TR_STATIC_CORRECTION, MODAL_TR_ENERGIES = 1, 2
 MODAL_RV_STATIC_CORRECTION, MODAL_RV_VELOCITY, MODAL_RV_ACCELERATION = 1, 2, 4
+MODAL_STRESS_VON_MISES, MODAL_STRESS_COMPONENTS, MODAL_STRESS_STRAIN = 1, 2, 4
 
 
 class SamplerGridInfo(C.Structure):
@@ -187,6 +188,17 @@ class ModalQuadraticInfo(C.Structure):
         return {k: (list(getattr(self, k)) if k in ("ranks", "passes", "truncation") else getattr(self, k)) for k, _ in self._fields_}
 
 
+class ModalStressInfo(C.Structure):
+    _fields_ = [("ranks", C.c_int32 * 4), ("passes", C.c_int32 * 4), ("truncation", C.c_double * 4), ("peakVonMises", C.c_double * 4),
+                ("peakCorner", C.c_int64 * 4), ("staticSolves", C.c_int32), ("staticIterations", C.c_int32), ("nb", C.c_int32), ("reserved", C.c_int32),
+                ("covarianceMs", C.c_double), ("factorMs", C.c_double), ("solveMs", C.c_double), ("note", C.c_char_p)]
+
+    def as_dict(self):
+        d = {k: (list(getattr(self, k)) if k in ("ranks", "passes", "truncation", "peakVonMises", "peakCorner") else getattr(self, k)) for k, _ in self._fields_}
+        d["note"] = (d["note"] or b"").decode()
+        return d
+
+
 class ModalRandomParams(C.Structure):
     _fields_ = [("rayleighMass", C.c_double), ("rayleighStiff", C.c_double), ("lossFactor", C.c_double), ("rtol", C.c_double), ("tol", C.c_double),
                 ("maxit", C.c_int32), ("nFreq", C.c_int32), ("nLoad", C.c_int32), ("flags", C.c_int32)]
@@ -345,6 +357,8 @@ PROTOTYPES = {
     "mfh_cqc_matrix": (_i32, [_i32, _P, _P, _P]),
     "mfh_modal_quadratic": (_i32, [_P, _i32, _P, _f64, _P, _i32, _P, _P, C.POINTER(ModalQuadraticInfo)]),
     "mfh_modal_random": (_i32, [_P, C.POINTER(ModalRandomParams), _P, _P, _P, _P, _P, _P, _i32, _P, _P, _P, _P, C.POINTER(ModalRandomInfo)]),
+    "mfh_modal_quadratic_stress": (_i32, [_P, _i32, _P, _f64, _i32, _P, _P, C.POINTER(ModalStressInfo)]),
+    "mfh_modal_random_stress": (_i32, [_P, C.POINTER(ModalRandomParams), _P, _P, _P, _P, _P, _i32, _P, _P, _P, C.POINTER(ModalStressInfo)]),
     "mfh_apply_delta_K": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_constant_strain_load": (_i32, [_P, _P, _P, _P]),
     "mfh_delta_average_strain": (_i32, [_P, _P, _P, _P, _i32, _P]),
@@ -415,6 +429,9 @@ PROTOTYPES = {
     "mfh_time_modal_series": (_i32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
     "mfh_debug_modal_sumsq": (_i32, [_P, _i64, _i32, _P, _P, _i32, _P, _i32, _i32, _P]),
     "mfh_time_modal_sumsq": (_i32, [_P, _i64, _i32, _i32, _i32, _P, _P, _P]),
+    "mfh_debug_modal_stress_sumsq": (_i32, [_P, _i32, _P, _i32, _i32, _i32, _P, _P]),
+    "mfh_debug_peak_of_array": (_i32, [_P, _i64, _P, _P, _P]),
+    "mfh_time_modal_stress": (_i32, [_P, _i32, _i32, _P, _P]),
     "mfh_debug_newmark_predict": (_i32, [_P, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_rhs": (_i32, [_P, _i64, _f64, _P, _P, _P, _P, _P]),
     "mfh_debug_newmark_correct": (_i32, [_P, _i64, _f64, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _P]),

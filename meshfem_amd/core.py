@@ -937,6 +937,113 @@ class Context:
         self._ck(self.lib.mfh_time_modal_sumsq(self.h, int(n), int(nb), int(planes_per_pass), int(reps), ptr(a), ptr(b), ptr(l)))
         return a, b, l
 
+    # ---------------------------------------------------------------- modal stress recovery (docs/design/04_24_modal_stress.md)
+    def _stress_flags(self, von_mises, components, strain):
+        return ((L.MODAL_STRESS_VON_MISES if von_mises else 0) | (L.MODAL_STRESS_COMPONENTS if components else 0) | (L.MODAL_STRESS_STRAIN if strain else 0))
+
+    def _stress_result(self, n_mat, vm, comp, info, squeeze):
+        d = info.as_dict()
+        for k in ("ranks", "passes", "truncation", "peakVonMises", "peakCorner"):
+            d[k] = d[k][:n_mat]
+        nq = self._nq()
+        peak = [(d["peakVonMises"][a], int(d["peakCorner"][a] // nq), int(d["peakCorner"][a] % nq)) for a in range(n_mat)]
+        if squeeze:
+            vm, comp, peak = (None if vm is None else vm[0]), (None if comp is None else comp[0]), peak[0]
+        return {"von_mises": vm, "components": comp, "peak": peak, "info": d}
+
+    def modal_quadratic_stress(self, Cm, tol=-1.0, von_mises=True, components=False, strain=False):
+        """RMS stress per element corner for symmetric positive semi-definite matrices C over the modes of set_modal_basis
+        (mfh_modal_quadratic_stress): Cm [m, m] or [nMat <= 4, m, m]; the SRSS / CQC rules are C_jk = rho_jk a_j a_k. Returns a dict: "von_mises"
+        [nMat, nElem, NQ] = sqrt(E[sigma_vm^2]) (Segalman: the root of the mean square, not the mean), "components" [nMat, nElem, NQ, flatLen] =
+        sqrt(E[sigma_c^2]) (None where not asked for), "peak": per matrix (largest von Mises value, element, corner), "info". strain=True: strains
+        instead of stresses."""
+        m = self.modal_basis_state()[0]
+        Cm = as_f64(np.asarray(Cm, dtype=np.float64))
+        if Cm.ndim == 2:
+            Cm = Cm[None]
+        if Cm.ndim != 3 or (m > 0 and Cm.shape[1:] != (m, m)):          # (no basis: the library answers with ERR_STATE)
+            raise ValueError("modal_quadratic_stress: the matrices are %d x %d (the modes of the basis), got %s" % (m, m, Cm.shape))
+        Cm = np.ascontiguousarray(Cm)
+        n_mat = Cm.shape[0]
+        nq, fl = self._nq(), flat_len(self.dim)
+        vm = np.full((n_mat, self.n_elem, nq), np.nan) if von_mises else None
+        comp = np.full((n_mat, self.n_elem, nq, fl), np.nan) if components else None
+        info = L.ModalStressInfo()
+        st = self.lib.mfh_modal_quadratic_stress(self.h, n_mat, ptr(Cm), float(tol), self._stress_flags(von_mises, components, strain), ptr(vm), ptr(comp), C.byref(info))
+        self.last_modal_stress = {"von_mises": vm, "components": comp, "info": info.as_dict()}
+        self._ck(st)
+        self.last_modal_stress = self._stress_result(n_mat, vm, comp, info, False)
+        return self.last_modal_stress
+
+    def modal_random_stress(self, omega, S, f, weights=None, damping=(0.0, 0.0), loss_factor=0.0, modal_damping=None, static_correction=True, tol=-1.0,
+                            rtol=1e-8, maxit=10000, von_mises=True, components=False, strain=False, _rv_flags=0):
+        """RMS stress per element corner under the loads of modal_random (mfh_modal_random_stress; the same arguments, the displacement's
+        covariance only). Returns a dict: "von_mises" [nElem, NQ] = sqrt(E[sigma_vm^2]), "components" [nElem, NQ, flatLen], "peak" (value,
+        element, corner), "cov" [nb, nb] = C^(0), "info"."""
+        n = self.bs * self.n_dof
+        om = as_f64(np.asarray(omega, dtype=np.float64).reshape(-1))
+        nf = om.size
+        f = as_f64(np.asarray(f, dtype=np.float64))
+        f = f.reshape(1, -1) if f.ndim == 1 else f.reshape(f.shape[0], -1)
+        if f.shape[1] != n:
+            raise ValueError("modal_random_stress: a load needs dim * n_dof = %d entries, got %d" % (n, f.shape[1]))
+        nl = f.shape[0]
+        Sc = np.asarray(S, dtype=np.complex128)
+        if Sc.ndim == 1:
+            Sc = Sc.reshape(-1, 1, 1)
+        if Sc.shape != (nf, nl, nl):
+            raise ValueError("modal_random_stress: S needs the shape [nFreq, nLoad, nLoad] = %s, got %s" % ((nf, nl, nl), Sc.shape))
+        Sri = np.ascontiguousarray(np.stack([Sc.real, Sc.imag], axis=-1))
+        w = None if weights is None else as_f64(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w is not None and w.size != nf:
+            raise ValueError("modal_random_stress: %d weights for %d frequencies" % (w.size, nf))
+        m = self.modal_basis_state()[0]
+        zeta = _modal_zeta(modal_damping, m)
+        nq, fl = self._nq(), flat_len(self.dim)
+        vm = np.full((1, self.n_elem, nq), np.nan) if von_mises else None
+        comp = np.full((1, self.n_elem, nq, fl), np.nan) if components else None
+        nbmax = m + 2
+        cov = np.zeros(nbmax * nbmax)
+        flags = (L.MODAL_RV_STATIC_CORRECTION if static_correction else 0) | int(_rv_flags)
+        prm = L.ModalRandomParams(float(damping[0]), float(damping[1]), float(loss_factor), float(rtol), float(tol), int(maxit), nf, nl, flags)
+        info = L.ModalStressInfo()
+        st = self.lib.mfh_modal_random_stress(self.h, C.byref(prm), ptr(om), ptr(w), ptr(zeta), ptr(f), ptr(Sri), self._stress_flags(von_mises, components, strain),
+                                              ptr(vm), ptr(comp), ptr(cov), C.byref(info))
+        self.last_modal_stress = {"von_mises": vm, "components": comp, "info": info.as_dict()}
+        self._ck(st)
+        out = self._stress_result(1, vm, comp, info, True)
+        nb = out["info"]["nb"]
+        out["cov"] = cov[:nb * nb].reshape(nb, nb).copy()
+        self.last_modal_stress = out
+        return out
+
+    def debug_modal_stress_sumsq(self, U, planes_per_pass=0, components=True, strain=False, sqrt=False):
+        """(vm [nElem, NQ], comp [nElem, NQ, flatLen] or None): the sums over the planes U [nPlanes, dim * n_dof] (variable numbering) of the squared
+        von Mises value / the squared components of the corner stress, through k_modal_stress_sumsq planes_per_pass planes at a time (test hook
+        mfh_debug_modal_stress_sumsq); their roots with sqrt."""
+        n = self.bs * self.n_dof
+        U = as_f64(np.asarray(U, dtype=np.float64).reshape(-1, n))
+        nq, fl = self._nq(), flat_len(self.dim)
+        vm = np.full((self.n_elem, nq), np.nan)
+        comp = np.full((self.n_elem, nq, fl), np.nan) if components else None
+        self._ck(self.lib.mfh_debug_modal_stress_sumsq(self.h, U.shape[0], ptr(U) if U.shape[0] else None, int(planes_per_pass),
+                                                       self._stress_flags(True, components, strain), int(bool(sqrt)), ptr(vm), ptr(comp)))
+        return vm, comp
+
+    def debug_peak_of_array(self, v):
+        """(max, argmax) of a host array through k_peak_of_array and k_peak_finish: ties to the lowest index, a NaN before every number."""
+        v = as_f64(np.asarray(v, dtype=np.float64).reshape(-1))
+        val, idx = C.c_double(), C.c_int64()
+        self._ck(self.lib.mfh_debug_peak_of_array(self.h, v.size, ptr(v), C.byref(val), C.byref(idx)))
+        return val.value, idx.value
+
+    def time_modal_stress(self, n_planes=32, reps=5):
+        """(stress_ms, measures_ms), one entry per repetition: device time of one pass of k_modal_stress_sumsq over n_planes hashed planes and of
+        n_planes launches of k_stress_measures (von Mises only) on the same planes, the two taking turns (mfh_time_modal_stress)."""
+        a, b = np.zeros(int(reps)), np.zeros(int(reps))
+        self._ck(self.lib.mfh_time_modal_stress(self.h, int(n_planes), int(reps), ptr(a), ptr(b)))
+        return a, b
+
     # ---------------------------------------------------------------- per-element density (docs/design/04_15_density.md)
     def set_density(self, rho):
         """The density field of the mass matrix of modes() and newmark() (mfh_set_density): one strictly positive value per element, or

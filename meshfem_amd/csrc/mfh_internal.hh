@@ -469,6 +469,14 @@ void launch_stress_measures(const AsmArgs &a, const int32_t *elemNodes, const do
 constexpr int PEAK_GRID_CAP = 1024;
 void launch_peak_von_mises(const AsmArgs &a, const int32_t *elemNodes, const double *intGrad, const double *uNodes, int wantStress,
                            double *partV, int64_t *partI, double *outV, int64_t *outI, hipStream_t s);
+// the same over a plain array of n doubles (k_peak_of_array, then k_peak_finish); n >= 1
+void launch_peak_of_array(int64_t n, const double *v, double *partV, int64_t *partI, double *outV, int64_t *outI, hipStream_t s);
+// one pass of k_modal_stress_sumsq (docs/design/04_24_modal_stress.md): vm[nElem][NQ] (and comp[nElem][NQ][flatLen] unless null) take the sums over
+// the planes U[t ldu + variable], t < np <= 32, of v2 (of the squared components) of the corner strain / stress; first: the sums start from 0.0,
+// else from the outputs; root: the square roots are stored. dofForNode: the node -> DoF table, null for the identity.
+constexpr int MODAL_STRESS_GRID_CAP = 2048;
+void launch_modal_stress_sumsq(const AsmArgs &a, const int32_t *elemNodes, const int32_t *dofForNode, const double *intGrad, const double *U, int64_t ldu, int np,
+                               int wantStress, bool first, bool root, double *vm, double *comp, hipStream_t s);
 // out[v][c] = sum vol_e field[e][corner | 0][c] / sum vol_e over the (element, corner) pairs of vertex v (node-pair list of launch_divergence,
 // code = e npe + j); field: [nElem][nq = 1 | dim + 1][nComp]
 void launch_vertex_average(int dim, int npe, int64_t nVert, const int32_t *nodePtr, const int32_t *nodePair, const double *geo, int geoStride,

@@ -1734,6 +1734,96 @@ __global__ void __launch_bounds__(256) k_peak_finish(int nPart, const double *__
     if (threadIdx.x == 0) { outV[0] = best; outI[0] = bestI; }
 }
 
+// first stage over a plain array: the (value, index) pair of every workgroup by peak_before's order, for k_peak_finish
+__global__ void __launch_bounds__(256) k_peak_of_array(int64_t n, const double *__restrict__ v, double *__restrict__ partV, long long *__restrict__ partI) {
+    __shared__ double ldsV[4];
+    __shared__ long long ldsI[4];
+    double best = -HUGE_VAL;
+    int64_t bestI = PEAK_NO_INDEX;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double x = v[i];
+        if (peak_before(x, i, best, bestI)) { best = x; bestI = i; }
+    }
+    peak_block_reduce(best, bestI, ldsV, ldsI);
+    if (threadIdx.x == 0) { partV[blockIdx.x] = best; partI[blockIdx.x] = bestI; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Modal stress recovery (mfh_modal_quadratic_stress, mfh_modal_random_stress; docs/design/04_24_modal_stress.md): per element corner the
+// sums over np <= 32 displacement planes u_t (VARIABLE numbering, ldu apart; the node -> DoF table of a.dofForNode, identity if null) of
+//     comp[e][q][c] += s_c(u_t)^2,   vm[e][q] += v2(s(u_t)),   s = corner_tensor's strain or stress of plane t at corner q,
+// t ascending: accC = fma(s_c, s_c, accC), accV += v2. v2 is the square of sym_measures' von Mises scalar WITHOUT its division by the
+// largest entry (the sums over the planes must be absolute): half a sum of squares, every term >= 0, nothing cancels. So the squares
+// have to stay inside the double range, as for k_modal_sumsq. One lane per element; the element record (gradients, material) stays in
+// registers over the planes; the accumulators start from 0.0 (first) or from the outputs, and are stored as they are or, under root,
+// as their square roots: neither the pass boundaries nor the planes per pass change a bit. No LDS, no atomics; planes beyond np are
+// not read. comp may be null.
+template <int DIM>
+DEV double von_mises_sq(const double (&s)[DIM * (DIM + 1) / 2]) {
+    if constexpr (DIM == 3) {
+        const double d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
+        return 0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]);
+    } else {
+        const double dd = s[0] - s[1];
+        return 0.5 * (dd * dd + s[0] * s[0] + s[1] * s[1]) + 3.0 * s[2] * s[2];
+    }
+}
+
+template <int DIM, int DEG, int MAT>
+__global__ void __launch_bounds__(256) k_modal_stress_sumsq(LoadArgs a, const double *__restrict__ U, int64_t ldu, int np, int wantStress, int first, int root,
+                                                           double *__restrict__ vm, double *__restrict__ comp) {
+    constexpr int NV = DIM + 1;
+    constexpr int FL = DIM * (DIM + 1) / 2;
+    constexpr int NPE = (DIM == 3) ? (DEG == 1 ? 4 : 10) : (DEG == 1 ? 3 : 6);
+    constexpr int NQ = DEG == 1 ? 1 : NV;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.nElem; e += (int64_t)gridDim.x * 256) {
+        const double *g = a.geo + e * a.geoStride;
+        const int32_t *en = a.elemNodes + e * NPE;
+        double gl[NV][DIM];
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) gl[k][d] = g[k * DIM + d];
+        int64_t var[NPE];           // first variable of every node
+#pragma unroll
+        for (int j = 0; j < NPE; ++j) {
+            const int32_t node = en[j];
+            var[j] = (int64_t)(a.dofForNode ? a.dofForNode[node] : node) * DIM;
+        }
+        double accV[NQ], accC[NQ][FL];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            accV[q] = first ? 0.0 : vm[e * NQ + q];
+#pragma unroll
+            for (int c = 0; c < FL; ++c) accC[q][c] = (first || !comp) ? 0.0 : comp[(e * NQ + q) * FL + c];
+        }
+        for (int t = 0; t < np; ++t) {
+            const double *__restrict__ u = U + (int64_t)t * ldu;
+            double xl[NPE][DIM];
+#pragma unroll
+            for (int j = 0; j < NPE; ++j)
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) xl[j][d] = u[var[j] + d];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                double ef[FL];
+                corner_tensor<DIM, DEG, MAT>(g, xl, gl, q, wantStress, ef);
+#pragma unroll
+                for (int c = 0; c < FL; ++c) accC[q][c] = fma(ef[c], ef[c], accC[q][c]);
+                accV[q] += von_mises_sq<DIM>(ef);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            vm[e * NQ + q] = root ? sqrt(accV[q]) : accV[q];
+            if (comp) {
+#pragma unroll
+                for (int c = 0; c < FL; ++c) comp[(e * NQ + q) * FL + c] = root ? sqrt(accC[q][c]) : accC[q][c];
+            }
+        }
+    }
+}
+
 // C0 volume-weighted vertex average of per-element corner values (vertexAveragedField, FieldPostProcessing.hh:24-47): one lane per
 // vertex walks the vertex's (element, local node) pairs of the node-pair list (ascending by element, code = e npe + j) and accumulates
 // vol_e value and vol_e in that order; nothing is added atomically. field: [nElem][nq][C] with nq = 1 (every corner takes the element's
@@ -2743,6 +2833,25 @@ void launch_peak_von_mises(const AsmArgs &a, const int32_t *elemNodes, const dou
     long long *pI = reinterpret_cast<long long *>(partI), *oI = reinterpret_cast<long long *>(outI);
     with_elem(a, [&](auto D, auto G, auto M) { launch_k(k_peak_von_mises<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, uNodes, wantStress, partV, pI); });
     hipLaunchKernelGGL(k_peak_finish, dim3(1), dim3(256), 0, s, grid, (const double *)partV, (const long long *)pI, outV, oI);
+    CHECK_LAUNCH();
+}
+
+void launch_peak_of_array(int64_t n, const double *v, double *partV, int64_t *partI, double *outV, int64_t *outI, hipStream_t s) {
+    const int grid = grid_for(n, PEAK_GRID_CAP);
+    long long *pI = reinterpret_cast<long long *>(partI), *oI = reinterpret_cast<long long *>(outI);
+    hipLaunchKernelGGL(k_peak_of_array, dim3(grid), dim3(256), 0, s, n, v, partV, pI);
+    hipLaunchKernelGGL(k_peak_finish, dim3(1), dim3(256), 0, s, grid, (const double *)partV, (const long long *)pI, outV, oI);
+    CHECK_LAUNCH();
+}
+
+void launch_modal_stress_sumsq(const AsmArgs &a, const int32_t *elemNodes, const int32_t *dofForNode, const double *intGrad, const double *U, int64_t ldu, int np,
+                               int wantStress, bool first, bool root, double *vm, double *comp, hipStream_t s) {
+    if (a.nElem <= 0) return;
+    const LoadArgs l = make_load_args(a, elemNodes, dofForNode, intGrad, nullptr);
+    const int grid = grid_for(a.nElem, MODAL_STRESS_GRID_CAP);
+    with_elem(a, [&](auto D, auto G, auto M) {
+        launch_k(k_modal_stress_sumsq<D(), G(), M()>, dim3(grid), dim3(256), 0, s, l, U, ldu, np, wantStress, first ? 1 : 0, root ? 1 : 0, vm, comp);
+    });
     CHECK_LAUNCH();
 }
 

@@ -1388,6 +1388,269 @@ mfh_status mfh_modal_random(mfh_ctx *c, const mfh_modal_random_params *prm, cons
     MFH_CATCH(c)
 }
 
+// ---------------------------------------------------------------- modal stress recovery (docs/design/04_24_modal_stress.md)
+}   // extern "C"
+
+namespace {
+
+// The stress passes of one covariance C = F F^T over the nb columns of B: the factor fields u_t = B F[:, t] in groups of planesPerPass <= 32 through
+// k_modal_expand into `planes` (32 x ld doubles), then one launch of k_modal_stress_sumsq per group, which adds the squares of the group's corner
+// stresses to dVm (and dComp unless null) and takes the roots on the last group. F: nb x rank, rows ldFh apart. rank 0: one launch with no plane, which
+// writes zeros; B is not read.
+struct StressRun {
+    DBuf<double> planes, dC, partV, outV;
+    DBuf<int64_t> partI, outI;
+    int64_t corners = 0, flat = 0;
+    void setup(const mfh_ctx *c, int64_t ld) {
+        const HostMesh &m = c->mesh;
+        corners = m.nElem * (m.deg == 1 ? 1 : m.dim + 1);
+        flat = m.dim * (m.dim + 1) / 2;
+        planes.alloc((size_t)ld * k::MODAL_NP_MAX);
+        partV.alloc(k::PEAK_GRID_CAP); partI.alloc(k::PEAK_GRID_CAP);
+        outV.alloc(1); outI.alloc(1);
+    }
+    int run(mfh_ctx *c, const double *B, int64_t n, int64_t ld, int nb, const double *F, int ldFh, int rank, int planesPerPass, int wantStress, bool root, double *dVm,
+            double *dComp, hipStream_t s) {
+        if (rank <= 0) {          // the kernel's own path: no plane, accumulators from 0.0 -- zeros, and neither B nor the scratch is read
+            k::launch_modal_stress_sumsq(asm_args(c), c->dElemNodes.p, device_dof_map(c), c->tables.intGrad.data(), planes.p, ld, 0, wantStress, true, root, dVm, dComp, s);
+            return 0;
+        }
+        const int ldc = rank + k::MODAL_NP_MAX;
+        std::vector<double> hc((size_t)nb * ldc, 0.0);
+        for (int j = 0; j < nb; ++j)
+            for (int t = 0; t < rank; ++t) hc[(size_t)j * ldc + t] = F[(size_t)j * ldFh + t];
+        dC.upload(hc, s);
+        int passes = 0;
+        for (int t0 = 0; t0 < rank; t0 += planesPerPass, ++passes) {
+            const int np = std::min(planesPerPass, rank - t0);
+            k::launch_modal_expand(n, B, ld, nb, dC.p + t0, ldc, np, k::MODAL_NP_MAX, planes.p, ld, s);
+            k::launch_modal_stress_sumsq(asm_args(c), c->dElemNodes.p, device_dof_map(c), c->tables.intGrad.data(), planes.p, ld, np, wantStress, t0 == 0,
+                                         root && t0 + np >= rank, dVm, dComp, s);
+        }
+        MFH_HIP(hipStreamSynchronize(s));      // hc and dC are this call's
+        return passes;
+    }
+    // max / argmax of the n values of v by peak_before's order; synchronises
+    void peak(const double *v, int64_t n, double *value, int64_t *index, hipStream_t s) {
+        k::launch_peak_of_array(n, v, partV.p, partI.p, outV.p, outI.p, s);
+        outV.download(value, 1, s);
+        outI.download(index, 1, s);
+        MFH_HIP(hipStreamSynchronize(s));
+    }
+};
+
+void check_stress_outputs(const char *who, int32_t flags, const double *vm, const double *comp) {
+    require_for((flags & ~(MFH_MODAL_STRESS_VON_MISES | MFH_MODAL_STRESS_COMPONENTS | MFH_MODAL_STRESS_STRAIN)) == 0, MFH_ERR_INVALID, who, "unknown stress flag");
+    require_for((flags & (MFH_MODAL_STRESS_VON_MISES | MFH_MODAL_STRESS_COMPONENTS)) != 0, MFH_ERR_INVALID, who, "nothing asked for: MFH_MODAL_STRESS_VON_MISES | MFH_MODAL_STRESS_COMPONENTS");
+    require_for(!(flags & MFH_MODAL_STRESS_VON_MISES) || vm, MFH_ERR_INVALID, who, "the von Mises output was requested but its pointer is null");
+    require_for(!(flags & MFH_MODAL_STRESS_COMPONENTS) || comp, MFH_ERR_INVALID, who, "the components were requested but their pointer is null");
+}
+
+// the passes of nMat factors and their outputs; the von Mises sums are always formed (the peak is theirs)
+void stress_outputs(mfh_ctx *c, int nb, const Factor *fac, int nMat, int32_t flags, double *rmsVonMises, double *rmsComponents, mfh_modal_stress_info *info) {
+    hipStream_t s = c->stream;
+    const int64_t n = c->modal.n, ld = c->modal.ld;
+    StressRun R;
+    R.setup(c, ld);
+    DBuf<double> dVm, dComp;
+    dVm.alloc((size_t)R.corners);
+    const bool wantComp = (flags & MFH_MODAL_STRESS_COMPONENTS) != 0;
+    if (wantComp) dComp.alloc((size_t)(R.corners * R.flat));
+    for (int a = 0; a < nMat; ++a) {
+        const int passes = R.run(c, c->modal.B.p, n, ld, nb, fac[a].F.data(), nb, fac[a].rank, k::MODAL_NP, (flags & MFH_MODAL_STRESS_STRAIN) ? 0 : 1, true, dVm.p,
+                                 wantComp ? dComp.p : nullptr, s);
+        double pv = 0.0;
+        int64_t pi = 0;
+        R.peak(dVm.p, R.corners, &pv, &pi, s);
+        if (flags & MFH_MODAL_STRESS_VON_MISES) dVm.download(rmsVonMises + (size_t)a * (size_t)R.corners, (size_t)R.corners, s);
+        if (wantComp) dComp.download(rmsComponents + (size_t)a * (size_t)(R.corners * R.flat), (size_t)(R.corners * R.flat), s);
+        MFH_HIP(hipStreamSynchronize(s));
+        if (info) {
+            info->ranks[a] = fac[a].rank; info->passes[a] = passes; info->truncation[a] = fac[a].truncation;
+            info->peakVonMises[a] = pv; info->peakCorner[a] = pi;
+        }
+    }
+}
+
+}   // namespace
+
+extern "C" {
+
+mfh_status mfh_modal_quadratic_stress(mfh_ctx *c, int32_t nMat, const double *C, double tol, int32_t flags, double *rmsVonMises, double *rmsComponents,
+                                      mfh_modal_stress_info *info) {
+    if (info) { *info = mfh_modal_stress_info{}; info->note = ""; }
+    MFH_TRY(c)
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_quadratic_stress: null context");
+    require(nMat >= 1 && nMat <= 4 && C != nullptr, MFH_ERR_INVALID, "mfh_modal_quadratic_stress: 1 <= nMat <= 4 matrices");
+    require(!std::isnan(tol), MFH_ERR_INVALID, "mfh_modal_quadratic_stress: tol is not a number");
+    check_stress_outputs("mfh_modal_quadratic_stress", flags, rmsVonMises, rmsComponents);
+    prepare_pencil(c, "mfh_modal_quadratic_stress");
+    require_basis(c, "mfh_modal_quadratic_stress");
+    const int m = c->modal.nModes;
+    c->modalNote.clear();
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<Factor> fac;
+    for (int a = 0; a < nMat; ++a) fac.push_back(factor_or_throw(m, C + (size_t)a * m * m, tol, "mfh_modal_quadratic_stress"));
+    const double factorMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    EventTimer tsolve(c->stream);
+    stress_outputs(c, m, fac.data(), nMat, flags, rmsVonMises, rmsComponents, info);
+    const double solveMs = tsolve.stop();
+    if (info) { info->nb = m; info->factorMs = factorMs; info->solveMs = solveMs; info->note = c->modalNote.c_str(); }
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_modal_random_stress(mfh_ctx *c, const mfh_modal_random_params *prm, const double *omega, const double *weights, const double *modalDamping, const double *f,
+                                   const double *S, int32_t stressFlags, double *rmsVonMises, double *rmsComponents, double *cov, mfh_modal_stress_info *info) {
+    if (info) { *info = mfh_modal_stress_info{}; info->note = ""; }
+    MFH_TRY(c)
+    const char *who = "mfh_modal_random_stress";
+    require(c != nullptr, MFH_ERR_INVALID, "mfh_modal_random_stress: null context");
+    require(prm != nullptr, MFH_ERR_INVALID, "mfh_modal_random_stress: params is null");
+    const mfh_modal_random_params P = *prm;
+    require(P.nFreq >= 1 && P.maxit > 0, MFH_ERR_INVALID, "mfh_modal_random_stress: nFreq >= 1, maxit > 0");
+    require(P.nLoad >= 1 && P.nLoad <= 8, MFH_ERR_INVALID, "mfh_modal_random_stress: 1 <= nLoad <= 8");
+    check_damping(who, P.rayleighMass, P.rayleighStiff, P.lossFactor);
+    require(P.rtol > 0.0 && P.rtol < 1.0, MFH_ERR_INVALID, "mfh_modal_random_stress: 0 < rtol < 1");
+    require(!std::isnan(P.tol), MFH_ERR_INVALID, "mfh_modal_random_stress: tol is not a number");
+    require((P.flags & ~(MFH_MODAL_RV_STATIC_CORRECTION | MFH_MODAL_RV_VELOCITY | MFH_MODAL_RV_ACCELERATION)) == 0, MFH_ERR_INVALID, "mfh_modal_random_stress: unknown flag");
+    require((P.flags & (MFH_MODAL_RV_VELOCITY | MFH_MODAL_RV_ACCELERATION)) == 0, MFH_ERR_INVALID,
+            "mfh_modal_random_stress: the stress of the displacement only: no velocity or acceleration flag");
+    require(omega && f && S, MFH_ERR_INVALID, "mfh_modal_random_stress: omega, f and S are needed");
+    check_stress_outputs(who, stressFlags, rmsVonMises, rmsComponents);
+    const bool correct = (P.flags & MFH_MODAL_RV_STATIC_CORRECTION) != 0;
+    require(!(correct && P.nLoad > 2), MFH_ERR_UNSUPPORTED, "mfh_modal_random_stress: the static correction has two reserved columns: at most two loads with it");
+    const int nFreq = P.nFreq, nl = P.nLoad;
+    for (int32_t k2 = 0; k2 < nFreq; ++k2) {
+        require(std::isfinite(omega[k2]) && omega[k2] >= 0.0, MFH_ERR_INVALID, "mfh_modal_random_stress: a frequency is negative or not finite");
+        require(k2 == 0 || omega[k2] > omega[k2 - 1], MFH_ERR_INVALID, "mfh_modal_random_stress: the frequencies are not ascending");
+        require(omega[k2] > 0.0 || !c->fixedVars.empty(), MFH_ERR_INVALID, "mfh_modal_random_stress: omega = 0 needs fixed variables (K alone is singular)");
+    }
+    check_modal_damping(who, modalDamping, c->modal.nModes);
+    prepare_pencil(c, who);
+    require_basis(c, who);
+    const int m = c->modal.nModes;
+    const int64_t n = c->modal.n;
+    const std::vector<double> lam = c->modal.lambda;
+    if (correct) check_correctable(c, who);
+    require(all_finite(f, (int64_t)nl * n), MFH_ERR_INVALID, "mfh_modal_random_stress: a load has an entry that is not finite");
+    c->modalNote.clear();
+
+    // ---- the loads, as mfh_modal_random sets them up
+    ModalLoads L;
+    std::vector<const double *> fLoad((size_t)nl);
+    for (int a = 0; a < nl; ++a) fLoad[(size_t)a] = f + (size_t)a * n;
+    prepare_modal_loads(c, who, L, nl, fLoad.data(), correct, P.rtol, P.maxit, info ? &info->staticSolves : nullptr, info ? &info->staticIterations : nullptr);
+    const int nb = L.nb;
+    if (L.corr) modal_note(c, "static correction: " + std::to_string(L.staticSolves) + " solve(s) of K u = f, " + std::to_string(L.staticIts) + " iterations");
+    else if (correct) modal_note(c, "static correction: every load is zero off the fixed variables, nothing to correct");
+
+    // ---- the covariance of the displacement coordinates (host) and its factor
+    auto tc = std::chrono::steady_clock::now();
+    std::vector<double> C0((size_t)nb * nb, 0.0);
+    {
+        const mfh_status st = mfh_modal_covariance(m, lam.data(), L.g.data(), nl, P.rayleighMass, P.rayleighStiff, P.lossFactor, modalDamping, nFreq, omega, weights, S,
+                                                   L.corr ? 1 : 0, C0.data(), nullptr, nullptr);
+        if (st != MFH_OK)
+            throw Error(st, "mfh_modal_random_stress: mfh_modal_covariance refused the input (omega = 0 with a zero eigenvalue, d_j = 0, a spectrum that is not Hermitian or "
+                            "has a negative diagonal, an entry that is not finite, or sums that overflow)");
+    }
+    const double covarianceMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
+    tc = std::chrono::steady_clock::now();
+    const Factor fac = factor_or_throw(nb, C0.data(), P.tol, who);
+    const double factorMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
+    if (cov) std::copy(C0.begin(), C0.end(), cov);
+
+    EventTimer tsolve(c->stream);
+    stress_outputs(c, nb, &fac, 1, stressFlags, rmsVonMises, rmsComponents, info);
+    const double solveMs = tsolve.stop();
+    if (info) {
+        info->nb = nb;
+        info->staticSolves = L.staticSolves; info->staticIterations = L.staticIts;
+        info->covarianceMs = covarianceMs; info->factorMs = factorMs; info->solveMs = solveMs;
+        info->note = c->modalNote.c_str();
+    }
+    MFH_CATCH(c)
+}
+
+// ---- hooks (include/meshfem_hip_extras.h)
+mfh_status mfh_debug_modal_stress_sumsq(mfh_ctx *c, int32_t nPlanes, const double *U, int32_t planesPerPass, int32_t flags, int32_t sqrtFlag, double *vm, double *comp) {
+    MFH_TRY(c)
+    require(c && vm && nPlanes >= 0 && nPlanes <= 4096 && (nPlanes == 0 || U) && planesPerPass >= 0 && planesPerPass <= k::MODAL_NP_MAX && (sqrtFlag == 0 || sqrtFlag == 1) &&
+                (flags & ~(MFH_MODAL_STRESS_VON_MISES | MFH_MODAL_STRESS_COMPONENTS | MFH_MODAL_STRESS_STRAIN)) == 0 && (!(flags & MFH_MODAL_STRESS_COMPONENTS) || comp),
+            MFH_ERR_INVALID, "mfh_debug_modal_stress_sumsq: arguments");
+    prepare_pencil(c, "mfh_debug_modal_stress_sumsq");
+    ensure_geometry(c);
+    hipStream_t s = c->stream;
+    const int64_t n = (int64_t)c->bs() * c->nDoF, ld = (n + 31) / 32 * 32;
+    const int per = planesPerPass ? planesPerPass : k::MODAL_NP;
+    StressRun R;
+    R.setup(c, ld);
+    DBuf<double> dVm, dComp;
+    dVm.alloc((size_t)R.corners);
+    const bool wantComp = (flags & MFH_MODAL_STRESS_COMPONENTS) != 0;
+    if (wantComp) dComp.alloc((size_t)(R.corners * R.flat));
+    if (nPlanes == 0) {          // rank 0 as the drivers launch it, over a scratch of NaNs: the planes are not read
+        MFH_HIP(hipMemsetAsync(R.planes.p, 0xFF, R.planes.n * sizeof(double), s));
+        R.run(c, nullptr, n, ld, 0, nullptr, 0, 0, per, (flags & MFH_MODAL_STRESS_STRAIN) ? 0 : 1, sqrtFlag != 0, dVm.p, wantComp ? dComp.p : nullptr, s);
+    }
+    for (int t0 = 0; t0 < nPlanes; t0 += per) {
+        const int np = std::min(per, nPlanes - t0);
+        upload_columns(R.planes.p, ld, U + (size_t)t0 * (size_t)n, n, np, s);
+        k::launch_modal_stress_sumsq(asm_args(c), c->dElemNodes.p, device_dof_map(c), c->tables.intGrad.data(), R.planes.p, ld, np, (flags & MFH_MODAL_STRESS_STRAIN) ? 0 : 1,
+                                     t0 == 0, sqrtFlag != 0 && t0 + np >= nPlanes, dVm.p, wantComp ? dComp.p : nullptr, s);
+    }
+    dVm.download(vm, (size_t)R.corners, s);
+    if (wantComp) dComp.download(comp, (size_t)(R.corners * R.flat), s);
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+mfh_status mfh_debug_peak_of_array(mfh_ctx *c, int64_t n, const double *v, double *value, int64_t *index) {
+    MFH_TRY(c)
+    require(c && v && value && index && n >= 1, MFH_ERR_INVALID, "mfh_debug_peak_of_array: arguments");
+    require_device(c);
+    MFH_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DBuf<double> d, partV, outV;
+    DBuf<int64_t> partI, outI;
+    d.alloc((size_t)n); partV.alloc(k::PEAK_GRID_CAP); partI.alloc(k::PEAK_GRID_CAP); outV.alloc(1); outI.alloc(1);
+    upload(d.p, v, n, s);
+    k::launch_peak_of_array(n, d.p, partV.p, partI.p, outV.p, outI.p, s);
+    outV.download(value, 1, s);
+    outI.download(index, 1, s);
+    MFH_HIP(hipStreamSynchronize(s));
+    MFH_CATCH(c)
+}
+
+// ms per repetition of one pass of k_modal_stress_sumsq over nPlanes <= 32 hashed planes (von Mises only) and of nPlanes launches of k_stress_measures (von
+// Mises only) on the same planes, the two taking turns
+mfh_status mfh_time_modal_stress(mfh_ctx *c, int32_t nPlanes, int32_t reps, double *stressMs, double *measuresMs) {
+    MFH_TRY(c)
+    require(c && stressMs && measuresMs && nPlanes >= 1 && nPlanes <= k::MODAL_NP_MAX && reps >= 1, MFH_ERR_INVALID, "mfh_time_modal_stress: arguments");
+    prepare_pencil(c, "mfh_time_modal_stress");
+    ensure_geometry(c);
+    require(c->dofForNode.empty(), MFH_ERR_UNSUPPORTED, "mfh_time_modal_stress: contexts without a DoF map (k_stress_measures reads node-numbered planes)");
+    hipStream_t s = c->stream;
+    const int64_t n = (int64_t)c->bs() * c->nDoF, ld = (n + 31) / 32 * 32;
+    StressRun R;
+    R.setup(c, ld);
+    DBuf<double> dVm, dVm1;
+    dVm.alloc((size_t)R.corners); dVm1.alloc((size_t)R.corners);
+    k::launch_fill_hash((int64_t)R.planes.n, R.planes.p, s);
+    auto a = [&] { k::launch_modal_stress_sumsq(asm_args(c), c->dElemNodes.p, nullptr, c->tables.intGrad.data(), R.planes.p, ld, nPlanes, 1, true, true, dVm.p, nullptr, s); };
+    auto b = [&] {
+        for (int t = 0; t < nPlanes; ++t)
+            k::launch_stress_measures(asm_args(c), c->dElemNodes.p, c->tables.intGrad.data(), R.planes.p + (int64_t)t * ld, 1, 1, dVm1.p, nullptr, nullptr, s);
+    };
+    a(); b();          // warm-up
+    MFH_HIP(hipStreamSynchronize(s));
+    for (int r = 0; r < reps; ++r) {
+        { EventTimer t(s); a(); stressMs[r] = t.stop(); }
+        { EventTimer t(s); b(); measuresMs[r] = t.stop(); }
+    }
+    MFH_CATCH(c)
+}
+
 mfh_status mfh_debug_modal_sumsq(mfh_ctx *c, int64_t n, int32_t nb, const double *Bh, const double *Fh, int32_t rank, const int32_t *piv, int32_t planesPerPass,
                                  int32_t sqrtFlag, double *out) {
     MFH_TRY(c)

@@ -729,6 +729,58 @@ class Simulator:
             R = R[dof, :] if mapped else R
         return {"R": R, "probes": q["probes"][0]}
 
+    def randomStress(self, omegas, psd, load=None, n_modes=None, modes=None, weights=None, density=1.0, damping=(0, 0), loss_factor=0.0,
+                     modal_damping=None, static_correction=True, von_mises=True, components=False, strain=False, tol=-1.0, rtol=None, maxit=None,
+                     modes_rtol=1e-6, batch=0):
+        """The RMS stress under the stationary random load of randomResponse (mfh_modal_random_stress, docs/design/04_24_modal_stress.md): the
+        same loads, spectrum, basis, clamp and damping. Returns a dict: "von_mises" [nElem, NQ] = sqrt(E[sigma_vm^2]) (Segalman: the root of the mean
+        square of the von Mises stress, not its mean), "components" [nElem, NQ, flatLen] = sqrt(E[sigma_c^2]) (on request), "peak" (value, element,
+        corner), "cov" [nb, nb]; NQ = 1 for degree 1, N + 1 for degree 2 (stressField's layout). strain=True: strains instead.
+        self.random_stress_info holds the solver's record."""
+        ctx = self.ctx
+        density = self._density_scalar(density)
+        self._ensure_modal_basis(n_modes, modes, density, batch, modes_rtol)
+        f = self.neumannLoad().reshape(1, -1) if load is None else np.asarray(load, dtype=np.float64).reshape(-1, ctx.n_dof * self.N)
+        try:
+            r = ctx.modal_random_stress(omegas, psd, f, weights=weights, damping=damping, loss_factor=loss_factor, modal_damping=modal_damping,
+                                        static_correction=static_correction, tol=tol, rtol=self.rtol if rtol is None else rtol,
+                                        maxit=self.maxit if maxit is None else maxit, von_mises=von_mises, components=components, strain=strain)
+        finally:
+            self.random_stress_info = getattr(ctx, "last_modal_stress", {}).get("info")
+        out = dict(r)
+        del out["info"]
+        return out
+
+    def responseSpectrumStress(self, direction, Sd, modal_damping=0.05, rule="cqc", n_modes=None, modes=None, density=1.0, von_mises=True,
+                               components=False, strain=False, tol=-1.0, modes_rtol=1e-6, batch=0):
+        """The peak stress under the design spectrum of responseSpectrum (mfh_modal_quadratic_stress): the same a_j = Gamma_j Sd_j and the same
+        rules "srss" / "cqc", C_jk = rho_jk a_j a_k. Returns a dict: "von_mises" [nElem, NQ], "components" [nElem, NQ, flatLen] (on request), "peak"
+        (value, element, corner). self.spectrum_stress_info: "gamma", "a", "rho" and the solver's record."""
+        ctx = self.ctx
+        if rule not in ("cqc", "srss"):
+            raise ValueError("responseSpectrumStress: rule is 'cqc' or 'srss'")
+        d = int(direction)
+        if not 0 <= d < self.N:
+            raise ValueError("responseSpectrumStress: direction in 0 .. %d" % (self.N - 1))
+        density = self._density_scalar(density)
+        self._ensure_modal_basis(n_modes, modes, density, batch, modes_rtol)
+        m = ctx.modal_basis_state()[0]
+        lam = getattr(self, "modal_eigenvalues", None)
+        if lam is None or len(lam) != m:
+            raise ValueError("responseSpectrumStress: the basis was not set through this Simulator (pass n_modes or modes)")
+        r = np.zeros((ctx.n_dof, self.N))
+        r[:, d] = 1.0
+        gamma = ctx.modal_coordinates(r.reshape(-1))
+        zeta = np.broadcast_to(np.asarray(modal_damping, dtype=np.float64), (m,))
+        sd = np.asarray(Sd(np.sqrt(lam), zeta), dtype=np.float64) if callable(Sd) else np.asarray(Sd, dtype=np.float64)
+        a = gamma * np.broadcast_to(sd, (m,))
+        from .core import cqc_matrix
+        rho = np.eye(m) if rule == "srss" else cqc_matrix(lam, zeta)
+        q = ctx.modal_quadratic_stress(rho * np.outer(a, a), tol=tol, von_mises=von_mises, components=components, strain=strain)
+        self.spectrum_stress_info = {"gamma": gamma, "a": a, "rho": rho, "info": q["info"]}
+        return {"von_mises": None if q["von_mises"] is None else q["von_mises"][0], "components": None if q["components"] is None else q["components"][0],
+                "peak": q["peak"][0]}
+
     def applyStiffnessMatrix(self, u_dofs):                             # :801-823
         return self.ctx.apply_K(np.asarray(u_dofs).ravel()).reshape(-1, self.N)
 
